@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- V-cycles/s + fine-level SpMV GB/s of libsmg on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 100 --warmup 10
+    python bench.py --gpus 1 --steps 100 --warmup 10 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one outer iteration of min_quad_with_fixed_mg_solve (reference src/min_quad_with_fixed_mg.cpp:108-125):
@@ -11,14 +11,19 @@ area, 3x mid-point subdivision -> 1 011 330 vertices, 5 levels, system M_bary + 
 N > 1: every rank owns one independent RHS column of the same mesh (weak scaling); the only communication is the
 8-byte all-reduce of the residual sum of squares per iteration (RCCL), exactly SURVEY.md section 8e.
 
-Timing: `--steps K` iterations are timed R = --repeats (default 9) times, each repeat bracketed by barrier + synchronize on both
-sides and measured with HIP events on the solve's stream (max over ranks per repeat); `ms_per_step` / `value` are the MEDIAN repeat
-(min / max alongside) -- a 20-step region is 6 ms, and one scheduling hiccup must not move the headline.
-The timed cycle is the REFERENCE's: V(2,2) with Gauss-Seidel on every level (`--smoother gs`, the library default); libsmg's
-Chebyshev-Jacobi hybrid is reported next to it in `smoothers` as an extension, with its own byte count.
+Timing: after --warmup W steps, exactly `--steps K` iterations are timed (R = --repeats times when R > 1, default 1), each repeat bracketed
+by barrier + synchronize on both sides and measured with HIP events on the solve's stream (max over ranks per repeat); `ms_per_step` /
+`value` are the MEDIAN repeat (min / max alongside).
+The timed cycle is the REFERENCE's: V(2,2) with Gauss-Seidel on every level (`--smoother gs`, the library default).
 
-Prints ONE compact JSON line (< 8 000 characters: `compact_line`) on rank 0 as the LAST line of stdout; the full record of every leg goes to
-bench_extra.json.
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` writes what the timed solve returned after its
+last step (rank 0's solution z and residual history, float64 .npy; the inputs are seeded, so two builds compare output for output).
+`--full` adds every other leg after the headline: the smoother comparison (libsmg's Chebyshev-Jacobi hybrid as an extension, with its
+own byte count), the fine-level SpMV / Gauss-Seidel rooflines, the memory budget, the CPU baselines, C5, C3 x 3 / x 64 columns, the
+re-precompute, the decimated hierarchy, C1, the block system, several meshes in one handle and C4.
+
+Prints ONE compact JSON line (< 8 000 characters: `compact_line`) on rank 0 as the LAST line of stdout; with --full the record of every
+leg goes to bench_extra.json.
 """
 import hashlib
 import argparse
@@ -1038,9 +1043,9 @@ def compact_line(out):
                                           "dtype", "data")}
     line["config"] = {k: _num(cfg.get(k)) for k in ("workload", "n_verts", "nnz", "levels", "level_rows", "cycle", "smoother", "rhs_columns_per_gpu", "parallelism")
                       if cfg.get(k) is not None}
-    rf = out.get("roofline") or {}
-    line["roofline"] = {k: _num(rf.get(k)) for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "bytes_per_launch", "us_per_launch", "traffic",
-                                                      "traffic_kind", "traffic_source", "infinity_cache_resident")}
+    rf = out.get("roofline")      # None: the kernel roofline is a --full leg
+    line["roofline"] = None if not rf else {k: _num(rf.get(k)) for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "bytes_per_launch", "us_per_launch", "traffic",
+                                                                         "traffic_kind", "traffic_source", "infinity_cache_resident")}
     cb = out.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = {k: _num(cb.get(k)) for k in ("value", "unit", "cores", "kind", "sample", "ms_per_cycle")}
@@ -1127,12 +1132,32 @@ def write_extra(out):
     return written
 
 
+DUMP_CAP_BYTES = 60 * 10 ** 6      # the outputs' budget is 64 MB: room for the .npy headers
+
+
+def dump_outputs(d, arrays):
+    """arrays (name -> float64 array) as d/<name>.npy, at most DUMP_CAP_BYTES in all: an array beyond its share of the cap is written as a
+    fixed, seeded sample of its entries (same indices from run to run for the same shape), so that two builds compare output for output."""
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if a.nbytes > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="C3")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg too (smoother comparison, kernel rooflines, memory budget, CPU baselines, C5, C3 x 3 / x 64, "
+                         "re-precompute, decimated hierarchy, C1, block, multi-mesh, C4) and the full record in bench_extra.json; the --no-* options skip single legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed solve returned after its last step (rank 0: solution z, residual history) to DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-c5", action="store_true", help="skip the out-of-cache roofline leg (C5, 4.19 M vertices)")
     ap.add_argument("--no-multi-mesh", action="store_true", help="skip the leg with M independent ogre.obj-size solves on one GPU")
@@ -1144,7 +1169,7 @@ def main():
     ap.add_argument("--no-c1", action="store_true", help="skip the C1 leg (03_mg_solver on bunny.obj / ogre.obj, GPU and oracle)")
     ap.add_argument("--no-c3k3", action="store_true", help="skip the C3 x 3 columns leg (the reference's own multi-RHS shape: 05_example_mean_curvature_flow)")
     ap.add_argument("--no-c3k64", action="store_true", help="skip the C3 x 64 columns column-sharded (strong scaling) leg")
-    ap.add_argument("--repeats", type=int, default=9, help="the --steps iterations are timed this many times; the line reports the median repeat")
+    ap.add_argument("--repeats", type=int, default=1, help="the --steps iterations are timed this many times; the line reports the median repeat")
     ap.add_argument("--spmv-reps", type=int, default=500)
     ap.add_argument("--smoother", default="gs", choices=["gs", "jacobi", "hybrid", "chebyshev", "hybrid_chebyshev"],
                     help="gs (default): the reference's Gauss-Seidel on every level = the cycle the metric is defined on; hybrid_chebyshev: "
@@ -1300,6 +1325,8 @@ def main():
     rep_ms = timed_repeats(torch, dist, world, dev, stream, run, K, NREP)
     dt = float(np.median(rep_ms)) * 1e-3           # the median repeat of K steps
     conv, r_his = mg.solve_end(z.data_ptr(), n, max_iter=HIS)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"z": z.cpu().numpy(), "residual_history": r_his})
     if state["his"] is not None and len(r_his) < 6:
         r_his = state["his"]   # the last segment was short: report the head of the previous one
 
@@ -1307,6 +1334,40 @@ def main():
     if rank == 0:
         ms_step = 1e3 * dt / K
         vcyc_bytes = mg.vcycle_bytes(1, 2, 2)      # of the cycle just timed (the handle still carries its smoother selection)
+        out = {
+            "metric": "V-cycles/sec + fine-level SpMV GB/s (% HBM peak), 1M-vert mesh fp64",
+            "value": world * K / dt, "unit": "V-cycles/s",
+            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": ms_step, "multi_gpu_preflight": preflight,
+            "timing": {"repeats": NREP, "what": "each repeat = --steps outer iterations between barrier + synchronize, HIP events on the solve stream, max over ranks; ms_per_step / value = the median repeat",
+                       "ms_per_step_min": min(rep_ms) / K, "ms_per_step_median": float(np.median(rep_ms)) / K, "ms_per_step_max": max(rep_ms) / K},
+            "higher_is_better": True, "scaling": "weak",
+            "scaling_note": "top-level value: one right-hand-side column per GPU, hierarchy replicated (fixed work per GPU as N grows); the c3_k64_sharded / c4_k64_sharded legs split a FIXED 64-column job over the ranks and say 'strong' themselves",
+            "vs_baseline": None, "host": host_info(),
+            # every SMG_* variable set in this run's environment (A/B knobs: DESIGN.md section 11): [] = the documented defaults
+            "env_overrides": sorted(k_ for k_ in os.environ if k_.startswith("SMG_") and k_ not in ("SMG_BENCH_EXTRA_DIR",)),
+            "dtype": "f64" if args.precision == "f64" else "f64 outer loop + f32 V-cycle (mixed)", "data": "synthetic",
+            "config": {"workload": label, "n_verts": n, "nnz": int(A.nnz), "levels": mg.n_levels,
+                       "level_rows": [mg.rows(l) for l in range(mg.n_levels)],
+                       "colors": [len(mg.colors(l)) - 1 for l in range(mg.n_levels - 1)],
+                       "rhs_columns_per_gpu": 1,
+                       "cycle": {"gs": "V(2,2), multi-colour Gauss-Seidel on every level (the reference's relax()), dense coarsest solve",
+                                 "hybrid": "V(2,2), multi-colour Gauss-Seidel on levels > %d rows, damped Jacobi (omega %.2f) below, dense coarsest solve" % (args.jacobi_max_rows, args.omega),
+                                 "jacobi": "V(2,2), damped Jacobi (omega %.2f) on every level, dense coarsest solve" % args.omega,
+                                 "chebyshev": "V(2,2), Chebyshev-Jacobi (degree 3) on every level, dense coarsest solve",
+                                 "hybrid_chebyshev": "V(2,2), multi-colour Gauss-Seidel on levels > %d rows, Chebyshev-Jacobi (degree 3) below, dense coarsest solve" % args.jacobi_max_rows}[args.smoother],
+                       "smoother": args.smoother,
+                       "relax_launches": "one launch per colour and sweep; on Gauss-Seidel levels of 2 048 - 100 000 rows the whole relax(2) is ONE launch (overlapped tiling, bit-identical; SMG_TILED=0 switches it off)",
+                       "parallelism": "1 RHS column per GPU, hierarchy replicated, all-reduce of residual sumsq" if world > 1 else "single GPU",
+                       "allreduce": ("RCCL on the solve stream (dist.StreamAllReduce)" if stream_ar is not None else "torch.distributed") if (world > 1 or force_split) else None},
+            "roofline_vcycle": {"bound": "hbm", "cycle": args.smoother, "bytes_per_step": int(vcyc_bytes),
+                                "achieved": vcyc_bytes / (ms_step * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": vcyc_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
+            "residual_history_head": [float(v) for v in r_his[:6]],
+            "setup_s": {"mesh_hierarchy_host": t_host, "precompute": t_pre,
+                        "precompute_note": "first (pattern-changing) smg_precompute of the process, HIP runtime already initialised; libsmg's own code object is loaded inside it"},
+        }
+    # ---- everything below measures beside the headline: --full only
+    if rank == 0 and args.full:
         # ---- smoother comparison: the reference's Gauss-Seidel everywhere vs the timed configuration.  What counts is the time
         # to the tolerance: cycles needed to 1e-10 (the drop-in solve on resident vectors, device-side break test, adaptive host
         # polling) x the steady-state time of an outer iteration.
@@ -1373,34 +1434,11 @@ def main():
         # the committed figure was measured on the kernel sources that are being timed (hash stamped by tools/make_traffic.py)
         traffic, traffic_note = committed_traffic(args.workload)
         ref = smoothers["timed"] if (smoothers and args.smoother == "gs") else (smoothers or {}).get("reference_gs")
-        out = {
-            "metric": "V-cycles/sec + fine-level SpMV GB/s (% HBM peak), 1M-vert mesh fp64",
-            "value": world * K / dt, "unit": "V-cycles/s",
-            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": ms_step, "multi_gpu_preflight": preflight,
-            "timing": {"repeats": NREP, "what": "each repeat = --steps outer iterations between barrier + synchronize, HIP events on the solve stream, max over ranks; ms_per_step / value = the median repeat",
-                       "ms_per_step_min": min(rep_ms) / K, "ms_per_step_median": float(np.median(rep_ms)) / K, "ms_per_step_max": max(rep_ms) / K},
+        out["setup_s"]["precompute_known"] = precompute_known_s(smg, mesh, mg, Vf, Ff) if args.workload == "C3" else None
+        out.update({
             # the reference's cycle -- V(2,2), Gauss-Seidel on every level (src/mg_VCycle.cpp) -- whatever --smoother timed
             "reference_cycle": {"v_cycles_per_s": ref["v_cycles_per_s"], "ms_per_step": ref["ms_per_step"], "cycles_to_1e-10": ref["cycles_to_tol"],
                                 "bytes_per_step": ref["bytes_per_step"], "frac_of_hbm_peak": ref["frac_of_hbm_peak"]} if ref else None,
-            "higher_is_better": True, "scaling": "weak",
-            "scaling_note": "top-level value: one right-hand-side column per GPU, hierarchy replicated (fixed work per GPU as N grows); the c3_k64_sharded / c4_k64_sharded legs split a FIXED 64-column job over the ranks and say 'strong' themselves",
-            "vs_baseline": None, "host": host_info(),
-            # every SMG_* variable set in this run's environment (A/B knobs: DESIGN.md section 11): [] = the documented defaults
-            "env_overrides": sorted(k_ for k_ in os.environ if k_.startswith("SMG_") and k_ not in ("SMG_BENCH_EXTRA_DIR",)),
-            "dtype": "f64" if args.precision == "f64" else "f64 outer loop + f32 V-cycle (mixed)", "data": "synthetic",
-            "config": {"workload": label, "n_verts": n, "nnz": int(nnz0), "levels": mg.n_levels,
-                       "level_rows": [mg.rows(l) for l in range(mg.n_levels)],
-                       "colors": [len(mg.colors(l)) - 1 for l in range(mg.n_levels - 1)],
-                       "rhs_columns_per_gpu": 1,
-                       "cycle": {"gs": "V(2,2), multi-colour Gauss-Seidel on every level (the reference's relax()), dense coarsest solve",
-                                 "hybrid": "V(2,2), multi-colour Gauss-Seidel on levels > %d rows, damped Jacobi (omega %.2f) below, dense coarsest solve" % (args.jacobi_max_rows, args.omega),
-                                 "jacobi": "V(2,2), damped Jacobi (omega %.2f) on every level, dense coarsest solve" % args.omega,
-                                 "chebyshev": "V(2,2), Chebyshev-Jacobi (degree 3) on every level, dense coarsest solve",
-                                 "hybrid_chebyshev": "V(2,2), multi-colour Gauss-Seidel on levels > %d rows, Chebyshev-Jacobi (degree 3) below, dense coarsest solve" % args.jacobi_max_rows}[args.smoother],
-                       "smoother": args.smoother,
-                       "relax_launches": "one launch per colour and sweep; on Gauss-Seidel levels of 2 048 - 100 000 rows the whole relax(2) is ONE launch (overlapped tiling, bit-identical; SMG_TILED=0 switches it off)",
-                       "parallelism": "1 RHS column per GPU, hierarchy replicated, all-reduce of residual sumsq" if world > 1 else "single GPU",
-                       "allreduce": ("RCCL on the solve stream (dist.StreamAllReduce)" if stream_ar is not None else "torch.distributed") if (world > 1 or force_split) else None},
             "roofline": {"kernel": "k_sell<SELL_AX,1> (fine-level y = A x)", "bound": "hbm",
                          "achieved": spmv_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": spmv_gbs / HBM_PEAK_GBS,
                          # the committed PMC figure of this kernel at this grid (rocprofv3 cannot run inside the benchmark): fabric-side
@@ -1421,16 +1459,10 @@ def main():
                                   "frac": gs_bytes / (gs_us * 1e-6) / 1e9 / HBM_PEAK_GBS, "us_per_sweep": gs_us, "us_per_sweep_repeats": gs_all,
                                   "timing": "median of 5 graph-replayed loops of 8 x relax(10) = 80 sweeps (smg_bench_relax, HIP events on the launch stream)",
                                   "bytes_per_sweep": int(gs_bytes)},
-            "roofline_vcycle": {"bound": "hbm", "cycle": args.smoother, "bytes_per_step": int(vcyc_bytes),
-                                "achieved": vcyc_bytes / (ms_step * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                "frac": vcyc_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
             "smoothers": smoothers,
             "time_to_tol_ms": smoothers["timed"]["time_to_tol_ms"] if smoothers else None,
             "cycles_to_tol": smoothers["timed"]["cycles_to_tol"] if smoothers else None,
             "profc": {k: {"count": v[0], "ms_total": v[1]} for k, v in prof.items()},
-            "residual_history_head": [float(v) for v in r_his[:6]],
-            "setup_s": {"mesh_hierarchy_host": t_host, "precompute": t_pre, "precompute_known": precompute_known_s(smg, mesh, mg, Vf, Ff) if args.workload == "C3" else None,
-                        "precompute_note": "first (pattern-changing) smg_precompute of the process, HIP runtime already initialised; libsmg's own code object is loaded inside it"},
             # memory budget: everything libsmg holds in HBM for this workload (operators in SELL incl. the fixed panel pitch, A^T images of the
             # Galerkin levels, dense coarse inverse, work vectors, graphs' buffers) against the algorithmic size of the hierarchy
             "device_bytes": {"libsmg_live": int(smg._lib.load().smg_device_bytes_live()), "hierarchy_algorithmic": algorithmic_bytes(mg),
@@ -1438,7 +1470,7 @@ def main():
                              "note": "by_purpose: what the C3 handle holds, entries >= 1 MiB (smg_debug_device_bytes): level0.A_sell carries the fixed panel pitch (12 columns of room for 7 used: "
                                      "addressing without a table, DESIGN.md section 2), the coarse inverse is kept whole for the k > 1 kernels, Galerkin levels keep an A^T image (the reference's sweep walks columns)",
                              "hbm_capacity": 288 * 10 ** 9},
-        }
+        })
         out["device_bytes"]["ratio_to_algorithmic"] = out["device_bytes"]["libsmg_live"] / max(out["device_bytes"]["hierarchy_algorithmic"], 1)
         if world == 1 and not force_split and args.workload == "C3":
             try:
@@ -1453,7 +1485,7 @@ def main():
             except Exception as e:  # the comparator is informational: never lose the bench line over it
                 out["cpu_allcore"] = {"error": str(e)}
     # ---- the same kernels beyond the Infinity Cache (BASELINE config C5), rank 0 at N = 1 only
-    if rank == 0 and world == 1 and not args.no_c5 and args.workload == "C3":
+    if args.full and rank == 0 and world == 1 and not args.no_c5 and args.workload == "C3":
         try:
             try:
                 del x, y, bvec, u
@@ -1463,13 +1495,13 @@ def main():
         except Exception as e:
             out["roofline_c5"] = {"error": repr(e)}
     # ---- the reference's own multi-RHS shape: three coordinate columns (05_example_mean_curvature_flow), rank 0 at N = 1 only
-    if rank == 0 and world == 1 and not args.no_c3k3 and args.workload == "C3":
+    if args.full and rank == 0 and world == 1 and not args.no_c3k3 and args.workload == "C3":
         try:
             out["c3_k3"] = c3_k3_leg(smg, mg, A, Mb, Vf, n, torch, dev, stream, with_cpu=not args.no_cpu)
         except Exception as e:
             out["c3_k3"] = {"error": repr(e)}
     # ---- a column-sharded job that shards usefully: the C3 mesh x 64 columns (strong scaling), through smg_solve_sharded
-    if not args.no_c3k64 and args.workload == "C3":
+    if args.full and not args.no_c3k64 and args.workload == "C3":
         try:
             if rank == 0 and world == 1:
                 try:
@@ -1484,40 +1516,40 @@ def main():
         if rank == 0:
             out["c3_k64_sharded"] = c3k
     # ---- row f-2: the value-only re-precompute of the time-stepping callers, rank 0 at N = 1 only (last use of the C3 handle)
-    if rank == 0 and world == 1 and not args.no_reprecompute and args.workload == "C3":
+    if args.full and rank == 0 and world == 1 and not args.no_reprecompute and args.workload == "C3":
         try:
             out["reprecompute"] = reprecompute_leg(smg, mg, A, torch)
         except Exception as e:
             out["reprecompute"] = {"error": repr(e)}
     # ---- the same mesh under the reference's own kind of hierarchy (mg_precompute: SSP decimation), rank 0 at N = 1 only
-    if rank == 0 and world == 1 and not args.no_c3dec and args.workload == "C3":
+    if args.full and rank == 0 and world == 1 and not args.no_c3dec and args.workload == "C3":
         try:
             out["c3_decimated"] = c3_decimated_leg(smg, mesh, torch, dev, stream, out["reference_cycle"]["ms_per_step"] if out.get("reference_cycle") else out["ms_per_step"],
                                                    out["reference_cycle"]["bytes_per_step"] if out.get("reference_cycle") else None)
         except Exception as e:
             out["c3_decimated"] = {"error": repr(e)}
     # ---- BASELINE config C1: the reference's 03_mg_solver on its own meshes, GPU and oracle side by side, rank 0 at N = 1 only
-    if rank == 0 and world == 1 and not args.no_c1:
+    if args.full and rank == 0 and world == 1 and not args.no_c1:
         try:
             out["c1_03_mg_solver"] = c1_leg(smg, mesh, torch, dev, stream)
         except Exception as e:
             out["c1_03_mg_solver"] = {"error": repr(e)}
     # ---- block (3-DOF) kernels, rank 0 at N = 1 only
-    if rank == 0 and world == 1 and not args.no_block3 and args.workload == "C3":
+    if args.full and rank == 0 and world == 1 and not args.no_block3 and args.workload == "C3":
         try:
             out["block3_c3"] = block3_leg(smg, mesh, torch, with_scalar=not args.no_block3_scalar)
             torch.cuda.set_stream(stream)
         except Exception as e:
             out["block3_c3"] = {"error": repr(e)}
     # ---- independent meshes on one GPU (north_star: "independent RHS columns / independent meshes shard"), rank 0 at N = 1 only
-    if rank == 0 and world == 1 and not args.no_multi_mesh:
+    if args.full and rank == 0 and world == 1 and not args.no_multi_mesh:
         try:
             out["multi_mesh"] = multi_mesh_leg(smg, mesh, torch, dev)
             torch.cuda.set_stream(stream)
         except Exception as e:
             out["multi_mesh"] = {"error": repr(e)}
     # ---- BASELINE config C4: k = 64 columns sharded over the ranks (strong scaling; N = 1 is the curve's first point)
-    if not args.no_c4:
+    if args.full and not args.no_c4:
         try:
             c4 = c4_k64_sharded(smg, mesh, torch, dist, rank, world, dev, stream, stream_ar, sm_kw, steps=max(args.steps, 1), warmup=max(args.warmup, 0))
         except Exception as e:   # never lose the bench line over the secondary measurement
@@ -1541,9 +1573,13 @@ def main():
         except Exception:
             pass
         sys.stdout.flush()
-        paths = write_extra(out)
-        print("bench: full record (%d legs) -> %s" % (len(out), ", ".join(paths) or "nowhere (not writable)"), file=sys.stderr)
-        print(json.dumps(compact_line(out), allow_nan=False), flush=True)
+        line = compact_line(out)
+        if args.full:
+            paths = write_extra(out)
+            print("bench: full record (%d legs) -> %s" % (len(out), ", ".join(paths) or "nowhere (not writable)"), file=sys.stderr)
+        else:
+            line.pop("extra_file", None)
+        print(json.dumps(line, allow_nan=False), flush=True)
 
 
 if __name__ == "__main__":

@@ -76,3 +76,25 @@ def test_full_record_is_written_as_strict_json(tmp_path, monkeypatch):
     assert len(paths) == 2
     back = json.load(open(paths[0]))
     assert back["x"] == {"nan": None, "arr": [0, 1, 2], "np": 1.5, "inf": None} and back["c3_decimated"] == full["c3_decimated"]
+
+
+def test_bench_line_of_a_plain_run_keeps_the_contract():
+    """a plain run (no --full) records the headline only: the contract keys stay, `roofline` is null, no CPU baseline, no extra file"""
+    full = _canned()
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "multi_gpu_preflight", "timing", "higher_is_better",
+                                  "scaling", "vs_baseline", "dtype", "data", "config", "roofline_vcycle", "residual_history_head", "setup_s")}
+    back = json.loads(json.dumps(B.compact_line(plain), allow_nan=False))
+    assert all(k in back for k in CONTRACT) and back["roofline"] is None and "cpu_baseline" not in back and "leg_errors" not in back
+    assert back["ms_per_step"] == float("%.6g" % full["ms_per_step"]) and back["extra"]["roofline_vcycle_frac"] > 0
+
+
+def test_dump_outputs_stays_under_its_cap_with_a_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(B, "DUMP_CAP_BYTES", 8000)
+    big, small = np.arange(10000, dtype=np.float64), np.linspace(0.0, 1.0, 7)
+    for d in ("a", "b"):
+        B.dump_outputs(str(tmp_path / d), {"z": big, "residual_history": small})
+    za, zb = np.load(str(tmp_path / "a" / "z.npy")), np.load(str(tmp_path / "b" / "z.npy"))
+    assert za.dtype == np.float64 and za.nbytes <= 4000 and np.array_equal(za, zb)            # the same sample from run to run ...
+    assert np.all(np.diff(za) > 0) and np.all(np.isin(za, big))                                # ... of distinct entries, in index order
+    assert np.array_equal(np.load(str(tmp_path / "a" / "residual_history.npy")), small)        # what fits is written whole

@@ -169,7 +169,7 @@ def _bench_n_ranks_on_one_gpu(tmp_path, n, port):
     import subprocess
     env = dict(os.environ, SMG_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", SMG_BENCH_EXTRA_DIR=str(tmp_path))
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "6", "--warmup", "2", "--no-c5", "--no-cpu"],
+                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "6", "--warmup", "2", "--full", "--no-c5", "--no-cpu"],
                          env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

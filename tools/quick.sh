@@ -1,7 +1,7 @@
 #!/bin/bash
 # quick perf line: tools/quick.sh [workload] [steps] [smoother]      (reads the FULL record, bench_extra.json: stdout's last line is the compact one)
 X=$(mktemp -d)
-SMG_BENCH_EXTRA_DIR=$X python bench.py --workload ${1:-C3} --steps ${2:-800} --warmup 100 --no-cpu --smoother ${3:-gs} --no-c5 --no-c4 --no-c3k3 --no-c3k64 --no-reprecompute --no-c3dec --no-c1 --no-block3 --no-multi-mesh >/dev/null 2>&1
+SMG_BENCH_EXTRA_DIR=$X python bench.py --workload ${1:-C3} --steps ${2:-800} --warmup 100 --full --no-cpu --smoother ${3:-gs} --no-c5 --no-c4 --no-c3k3 --no-c3k64 --no-reprecompute --no-c3dec --no-c1 --no-block3 --no-multi-mesh >/dev/null 2>&1
 python -c "
 import json,sys
 d=json.load(open('$X/bench_extra.json'))
