@@ -152,6 +152,7 @@ hipError_t SellBuf::upload(const Sell& S)
     view.n_rows = S.n_rows; view.n_cols = S.n_cols; view.n_slices = S.n_slices; view.C = S.C;
     view.order = S.region_order.empty() ? nullptr : order.p;
     view.slice_row = slice_row.p; view.slice_off = slice_off.p; view.slice_w = slice_w.p; view.col = col.p; view.val = val.p;
+    view.codes = 0;
     view.stride = S.stride; view.w_lo = S.w_lo;
     view.w_max = 0;
     for (int w : S.slice_w) view.w_max = std::max(view.w_max, w);
@@ -202,6 +203,36 @@ hipError_t SellBuf::upload_long(const std::vector<int>& rows, const std::vector<
     if ((e = long_col.upload(col)) != hipSuccess) return e;
     if ((e = long_val.upload(val)) != hipSuccess) return e;
     view.long_n = (int)rows.size(); view.long_row = long_row.p; view.long_ptr = long_ptr.p; view.long_col = long_col.p; view.long_val = long_val.p;
+    return hipSuccess;
+}
+
+hipError_t SellBuf::encode_codes(const double* vals, size_t n_vals, hipStream_t st)
+{
+    static const bool on = env_int("SMG_TRANSFER_CODES", 1) != 0;
+    if (!on || view.codes || view.long_n > 0 || padded == 0 || !view.val || view.n_cols >= (1 << 29)) return hipSuccess;
+    double tab[4] = {0.0, 0.0, 0.0, 0.0};
+    int n_tab = 0;
+    for (size_t p = 0; p < n_vals; p++) {     // distinct bit patterns, in order of first appearance
+        const double v = vals[p];
+        int i = 0;
+        while (i < n_tab && std::memcmp(&tab[i], &v, sizeof v) != 0) i++;
+        if (i == n_tab) { if (n_tab == 4) return hipSuccess; tab[n_tab++] = v; }
+    }
+    if (n_tab == 0) return hipSuccess;
+    DevBuf<int> ccol, d_bad;
+    hipError_t e = ccol.alloc((size_t)padded);
+    if (e == hipSuccess) e = d_bad.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_bad.p, 0, sizeof(int), st);
+    if (e == hipSuccess) e = launch_sell_encode(view, (size_t)padded, tab, n_tab, ccol.p, d_bad.p, st);
+    int bad = 1;
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess || bad) return e;   // some slot is not in the table: keep the values
+    col = std::move(ccol);
+    val.release();
+    view.col = col.p; view.val = nullptr; view.valf = nullptr;
+    view.codes = 1;
+    for (int i = 0; i < 4; i++) { view.tab[i] = tab[i]; view.tabf[i] = (float)tab[i]; }
     return hipSuccess;
 }
 

@@ -392,7 +392,7 @@ static int ensure_fp32(smg_hierarchy* h, int k)
                 src.view.long_valf = src.long_valf.p;
             }
             view = src.view;
-            if (src.padded == 0) { view.valf = nullptr; return SMG_OK; }
+            if (src.padded == 0 || src.view.codes) { view.valf = nullptr; return SMG_OK; }   // weight codes: the fp32 table is in the view
             HIPCHK(dst.ensure((size_t)src.padded));
             HIPCHK(launch_cvt_f64_f32(dst.p, src.view.val, (size_t)src.padded, h->stream));
             view.valf = dst.p;

@@ -39,7 +39,15 @@ const int* never_done()
 // u = 0 + d (omega = that step's coefficient), written to u and d.
 // SELL_CHEBY launches use d (the step's update vector, own row in / out), c1 (coefficient of the old update; 0 on the first step: d is
 // not read then) and omega (coefficient of the scaled residual).
-template <typename T> struct CoarseInit { T* u; const T* gs_val; const int* diag_slot; int n_first; int jacobi; T omega; T* d; T c1; };
+// codes / tab: the matrix of the launch holds weight codes instead of values (SellDev::codes; k_sell takes it as a template argument,
+// the other kernels test it at run time).
+template <typename T> struct CoarseInit { T* u; const T* gs_val; const int* diag_slot; int n_first; int jacobi; T omega; T* d; T c1; int codes; T tab[4]; };
+// the value behind a coded column word: tab[word & 3] as selects (an indexed read of the kernel-argument array would go through scratch)
+template <typename T> __device__ __forceinline__ T code_val(const CoarseInit<T>& z, int cw)
+{
+    const T lo = (cw & 1) ? z.tab[1] : z.tab[0], hi = (cw & 1) ? z.tab[3] : z.tab[2];
+    return (cw & 2) ? hi : lo;
+}
 
 // One wavefront per slice of 64 rows; lane l owns row row0 + l.
 // T = double: the reference arithmetic.  T = float: the fp32 V-cycle of the mixed-precision mode (values, vectors and
@@ -49,7 +57,9 @@ template <typename T> struct CoarseInit { T* u; const T* gs_val; const int* diag
 // for leading scalar / pointer arguments, hence no struct up front).  The rest is fetched in one batch.
 // W0C: the number of panel columns requested ahead, fixed at compile time (7: the one-ring of a regular mesh vertex plus the
 // diagonal, by far the most common slice width of A) -- straight-line loads, no branch per column; -1: taken from a_w_lo.
-template <int MODE, int KB, typename T, int W0C = -1, int WPB = 4>
+// CODED (SELL_AX / SELL_ADD on transfer operators): no value stream, the column words carry a weight code (SellDev::codes); the values are
+// decoded from z.tab when the columns arrive, and every sum runs as it does on the value array: the same bits.
+template <int MODE, int KB, typename T, int W0C = -1, int WPB = 4, bool CODED = false>
 __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_val, const int* a_order, const int* a_slice_off, int a_stride,
                                               int a_w_lo, int s_begin, int s_end, int n_blocks, int use_order, const T* x,
                                               const int* a_slice_row, const int* a_slice_w, const T* b, T* y, int ld, const int* done,
@@ -81,7 +91,7 @@ __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_
         const int W0 = W0C >= 0 ? W0C : (A.w_lo < 8 ? A.w_lo : 8);   // compile-time, or the kernel argument (0 for compact panels)
         const int off0 = (W0C >= 0 || A.stride) ? s * A.stride : A.slice_off[s];   // W0C >= 0: launched on fixed-pitch matrices only
         const int* cp = A.col + (size_t)off0 * C + lane;
-        const T* vp = a_val + (size_t)off0 * C + lane;
+        const T* vp = CODED ? nullptr : a_val + (size_t)off0 * C + lane;
         constexpr int U = W0C > 8 ? W0C : 8;   // W0C = 12: the whole pitch of the usual matrices in ONE batch (small launches only)
         int c0[U];
         T v0[U];
@@ -89,7 +99,7 @@ __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_
         for (int t = 0; t < U; t++) {
             // one wave-uniform branch per column, both loads behind it: as two selects this compiled to two branches per column
             // and the longer issue sequence cost 2.5 % of the V-cycle (every launch pays it before its loads are out)
-            if (t < W0) { c0[t] = cp[(size_t)t * C]; v0[t] = vp[(size_t)t * C]; }
+            if (t < W0) { c0[t] = cp[(size_t)t * C]; v0[t] = CODED ? (T)0 : vp[(size_t)t * C]; }
             else { c0[t] = -1; v0[t] = (T)0; }
         }
         // Now -- with the first panel loads in flight -- fetch the remaining kernel arguments in ONE batch of scalar loads
@@ -129,7 +139,14 @@ __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_
             if (CHEB && live && z.c1 != (T)0) dold[q] = z.d[(size_t)rowb * ld + q];
         }
         // one batch of U panel columns: gather x for all of them, then accumulate in ascending column order
-        auto consume = [&](const int (&c)[U], const T (&v)[U]) {
+        auto consume = [&](const int (&cw)[U], const T (&vw)[U]) {
+            int c[U];
+            T v[U];
+#pragma unroll
+            for (int t = 0; t < U; t++) {
+                if constexpr (CODED) { c[t] = cw[t] >> 2; v[t] = code_val<T>(z, cw[t]); }   // padding: -1 >> 2 == -1
+                else { c[t] = cw[t]; v[t] = vw[t]; }
+            }
             T xv[U][KB];
             T xo[MODE == SELL_GS_HEAD ? U : 1][KB];   // SELL_GS_HEAD: the OLD iterate at every stored column (xv holds the sweep's operand)
 #pragma unroll
@@ -173,7 +190,7 @@ __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_
             T v[U];
 #pragma unroll
             for (int t = 0; t < U; t++) {
-                if ((j0 + t) < w) { c[t] = cp[(size_t)(j0 + t) * C]; v[t] = vp[(size_t)(j0 + t) * C]; }   // wave-uniform
+                if ((j0 + t) < w) { c[t] = cp[(size_t)(j0 + t) * C]; v[t] = CODED ? (T)0 : vp[(size_t)(j0 + t) * C]; }   // wave-uniform
                 else { c[t] = -1; v[t] = (T)0; }
             }
             consume(c, v);
@@ -255,7 +272,7 @@ __global__ __launch_bounds__(256) void k_sell_deep(const int* a_col, const doubl
             for (int t = bt * 8; t < bt * 8 + 8; t++) {
                 const int tt = t < w ? t : w - 1;        // a column beyond the slice's width: its last one again (same line), dropped below
                 c[t] = cp[(size_t)tt * C];
-                v[t] = vp[(size_t)tt * C];
+                v[t] = z.codes ? 0.0 : vp[(size_t)tt * C];
             }
         } else {
 #pragma unroll
@@ -266,6 +283,10 @@ __global__ __launch_bounds__(256) void k_sell_deep(const int* a_col, const doubl
     if (MODE == SELL_AX && live && rowb < z.n_first) zd = z.gs_val[z.diag_slot[rowb]];
 #pragma unroll
     for (int q = 0; q < KB; q++) bv[q] = (MODE == SELL_RESID && live) ? b[(size_t)rowb * ld + q] : 0.0;
+    if (z.codes) {   // weight codes (SellDev::codes)
+#pragma unroll
+        for (int t = 0; t < S; t++) { v[t] = code_val<double>(z, c[t]); c[t] >>= 2; }
+    }
     double xv[S][KB];
 #pragma unroll
     for (int t = 0; t < S; t++) {
@@ -377,7 +398,7 @@ __global__ __launch_bounds__(256) void k_sell_wide(const int* a_col, const T* a_
                     const int e = q * 64 + lane, tt = e / RW, rr = e % RW;
                     const bool in2 = e < U * RW && (j0 + tt) < w;
                     cL[q] = in2 ? cp[(size_t)(j0 + tt) * 64 + sub * RW + rr] : -1;
-                    vL[q] = in2 ? vp[(size_t)(j0 + tt) * 64 + sub * RW + rr] : (T)0;
+                    vL[q] = (in2 && !z.codes) ? vp[(size_t)(j0 + tt) * 64 + sub * RW + rr] : (T)0;
                 }
             }
 #pragma unroll
@@ -388,7 +409,7 @@ __global__ __launch_bounds__(256) void k_sell_wide(const int* a_col, const T* a_
                     (void)in;
                     if constexpr (G == 1) {        // the row is the same for all lanes: the compiler fetches the entry through the scalar cache
                         cc[t][r] = in ? cp[(size_t)(j0 + t) * 64 + rl[r]] : -1;
-                        vv[t][r] = in ? vp[(size_t)(j0 + t) * 64 + rl[r]] : (T)0;
+                        vv[t][r] = (in && !z.codes) ? vp[(size_t)(j0 + t) * 64 + rl[r]] : (T)0;
                     } else {
                         // G rows per wave-instruction: as a load of its own every slot would have the 64 lanes ask for G distinct words, and
                         // these two loads per slot -- not the gathers -- bound the launch.  The batch's U x RW entries are fetched by
@@ -397,6 +418,7 @@ __global__ __launch_bounds__(256) void k_sell_wide(const int* a_col, const T* a_
                         cc[t][r] = __shfl(cL[(t * RW + r * G) / 64], src & 63, 64);
                         vv[t][r] = __shfl(vL[(t * RW + r * G) / 64], src & 63, 64);
                     }
+                    if (z.codes) { vv[t][r] = code_val<T>(z, cc[t][r]); cc[t][r] >>= 2; }   // weight codes (SellDev::codes)
                 }
 #pragma unroll
             for (int t = 0; t < U; t++)
@@ -564,6 +586,16 @@ template <typename T> static CoarseInit<T> coarse_init(T* zero_rows, int c0, con
 }
 template <> const double* host_vals<double>(const SellDev& A) { return A.val; }
 template <> const float* host_vals<float>(const SellDev& A) { return A.valf; }
+// coarse_init plus the weight-code table of A (SellDev::codes)
+template <typename T> static CoarseInit<T> coarse_codes(const SellDev& A, T* zero_rows, int c0, const FirstColour* first, double omega)
+{
+    CoarseInit<T> z = coarse_init<T>(zero_rows, c0, first, omega);
+    z.codes = A.codes;
+    for (int i = 0; i < 4; i++) {
+        if constexpr (std::is_same<T, double>::value) z.tab[i] = A.tab[i]; else z.tab[i] = A.tabf[i];
+    }
+    return z;
+}
 
 // one-row-per-lane variants (see k_sell_wide) up to this many waves
 static long wide_latency_max()
@@ -611,6 +643,44 @@ static constexpr int sell_wpb() { return 4; }
 static int gs_wpb() { static const int v = getenv("SMG_GS_WPB") ? atoi(getenv("SMG_GS_WPB")) : 4; return v; }   // A/B knob: waves per workgroup of the big colour launches
 int sell_blocks(int n_slices) { return (n_slices + sell_wpb() - 1) / sell_wpb(); }
 
+// the narrow launches (kb <= 4 columns per lane) of one group of columns; CODED: the matrix holds weight codes (SELL_AX / SELL_ADD only)
+template <int MODE, typename T, bool CODED>
+static void launch_narrow(const SellDev& A, int kb, int nb, int ns, int grid, int nbarg, bool one_xcd, int s_begin, int s_end, int use_order, const T* xx,
+                          const T* bb, T* yy, int k, const int* done, double* pp, const CoarseInit<T>& zz, hipStream_t st)
+{
+    switch (kb) {
+        case 1: {
+            // the usual widths get kernels with the look-ahead count fixed at compile time (no branch per panel column)
+            const int w0 = A.stride > 0 ? (A.w_lo < 8 ? A.w_lo : 8) : -1;
+            // whole-pitch look-ahead: colour sweeps of <= 32 workgroups, and the whole-matrix launches (Jacobi / Chebyshev sweeps,
+            // residual, transfer) of a level that small, <= 64 workgroups (C3 level 3: 37.3 -> 34.1 us per visit; colour sweeps of 62
+            // workgroups lose with it)
+            static const int pitch_env = getenv("SMG_PITCH_SPEC_MAX") ? atoi(getenv("SMG_PITCH_SPEC_MAX")) : -1;
+            const int pitch_max = pitch_env >= 0 ? pitch_env : (sell_is_gs(MODE) ? 32 : 64);
+            if (nb <= pitch_max && A.stride == 12 && w0 >= 7) hipLaunchKernelGGL((k_sell<MODE, 1, T, 12, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            else if (!CODED && w0 == 7 && MODE == SELL_GS && !one_xcd && gs_wpb() == 8) hipLaunchKernelGGL((k_sell<MODE == SELL_GS ? MODE : SELL_GS, 1, T, 7, 8>), dim3((ns + 7) / 8), dim3(512), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, (ns + 7) / 8, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            else if (!CODED && w0 == 7 && MODE == SELL_GS && !one_xcd && gs_wpb() == 2) hipLaunchKernelGGL((k_sell<MODE == SELL_GS ? MODE : SELL_GS, 1, T, 7, 2>), dim3((ns + 1) / 2), dim3(128), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, (ns + 1) / 2, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            else if (w0 == 7) hipLaunchKernelGGL((k_sell<MODE, 1, T, 7, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            else if (w0 == 8) hipLaunchKernelGGL((k_sell<MODE, 1, T, 8, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            else if (w0 == 2) hipLaunchKernelGGL((k_sell<MODE, 1, T, 2, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            else hipLaunchKernelGGL((k_sell<MODE, 1, T, -1, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            break;
+        }
+        case 2:
+            if (A.stride > 0 && A.w_lo == 7) hipLaunchKernelGGL((k_sell<MODE, 2, T, 7, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            else hipLaunchKernelGGL((k_sell<MODE, 2, T, -1, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            break;
+        case 3:
+            if (A.stride > 0 && A.w_lo == 7) hipLaunchKernelGGL((k_sell<MODE, 3, T, 7, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            else hipLaunchKernelGGL((k_sell<MODE, 3, T, -1, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            break;
+        default:
+            if (A.stride > 0 && A.w_lo == 7) hipLaunchKernelGGL((k_sell<MODE, 4, T, 7, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            else hipLaunchKernelGGL((k_sell<MODE, 4, T, -1, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            break;
+    }
+}
+
 template <int MODE, typename T>
 static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, const T* x, const T* b, T* y,
                                    int k, const Ctrl* ctrl, double* partials, int* n_blocks, hipStream_t st, T* zero_rows, const FirstColour* first,
@@ -637,7 +707,7 @@ static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, 
             const T* bb = b ? b + c0 : nullptr;
             T* yy = y ? y + c0 : nullptr;
             double* pp = partials ? partials + poff : nullptr;
-            const CoarseInit<T> zz = coarse_init<T>(zero_rows, c0, first, omega);
+            const CoarseInit<T> zz = coarse_codes<T>(A, zero_rows, c0, first, omega);
             int wnb = 0;
             switch (kw) {
                 case 64: launch_wide_one<MODE, 64, T>(A, s_begin, s_end, use_order, xx, bb, yy, k, done, pp, zz, st, &wnb); break;
@@ -659,7 +729,7 @@ static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, 
         const T* bb = b ? b + c0 : nullptr;
         T* yy = y ? y + c0 : nullptr;
         double* pp = partials ? partials + poff : nullptr;
-        const CoarseInit<T> zz = coarse_init<T>(zero_rows, c0, first, omega);
+        const CoarseInit<T> zz = coarse_codes<T>(A, zero_rows, c0, first, omega);
         poff += (size_t)nb;
         if constexpr (std::is_same<T, double>::value && (MODE == SELL_AX || MODE == SELL_RESID)) {
             // (k = 4 on a matrix the deep variant serves with 3 columns per lane: 3 + 1)
@@ -670,7 +740,7 @@ static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, 
                     int kk = kb - cc;
                     while (kk > 1 && !deep_wanted(MODE, A.w_max, kk)) kk--;
                     const int nbm = A.w_max <= 24 ? 3 : A.w_max <= 40 ? 5 : 8;
-                    const CoarseInit<T> zc = coarse_init<T>(zero_rows, c0 + cc, first, omega);
+                    const CoarseInit<T> zc = coarse_codes<T>(A, zero_rows, c0 + cc, first, omega);
 #define SMG_DEEP_LAUNCH(KB, NB) hipLaunchKernelGGL((k_sell_deep<MODE, KB, NB>), dim3(nb), dim3(256), 0, st, A.col, A.val, A.order, A.slice_off, A.stride, s_begin, s_end, nb, use_order, \
                                                    xx ? xx + cc : nullptr, A.slice_row, A.slice_w, bb ? bb + cc : nullptr, yy + cc, k, done, zc)
                     if (nbm == 3) { if (kk == 1) SMG_DEEP_LAUNCH(1, 3); else if (kk == 2) SMG_DEEP_LAUNCH(2, 3); else SMG_DEEP_LAUNCH(3, 3); }
@@ -682,41 +752,14 @@ static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, 
                 continue;
             }
         }
-        switch (kb) {
-            case 1: {
-                // the usual widths get kernels with the look-ahead count fixed at compile time (no branch per panel column)
-                const int w0 = A.stride > 0 ? (A.w_lo < 8 ? A.w_lo : 8) : -1;
-                // whole-pitch look-ahead: colour sweeps of <= 32 workgroups, and the whole-matrix launches (Jacobi / Chebyshev sweeps,
-                // residual, transfer) of a level that small, <= 64 workgroups (C3 level 3: 37.3 -> 34.1 us per visit; colour sweeps of 62
-                // workgroups lose with it)
-                static const int pitch_env = getenv("SMG_PITCH_SPEC_MAX") ? atoi(getenv("SMG_PITCH_SPEC_MAX")) : -1;
-                const int pitch_max = pitch_env >= 0 ? pitch_env : (sell_is_gs(MODE) ? 32 : 64);
-                if (nb <= pitch_max && A.stride == 12 && w0 >= 7) hipLaunchKernelGGL((k_sell<MODE, 1, T, 12>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                else if (w0 == 7 && MODE == SELL_GS && !one_xcd && gs_wpb() == 8) hipLaunchKernelGGL((k_sell<MODE == SELL_GS ? MODE : SELL_GS, 1, T, 7, 8>), dim3((ns + 7) / 8), dim3(512), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, (ns + 7) / 8, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                else if (w0 == 7 && MODE == SELL_GS && !one_xcd && gs_wpb() == 2) hipLaunchKernelGGL((k_sell<MODE == SELL_GS ? MODE : SELL_GS, 1, T, 7, 2>), dim3((ns + 1) / 2), dim3(128), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, (ns + 1) / 2, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                else if (w0 == 7) hipLaunchKernelGGL((k_sell<MODE, 1, T, 7>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                else if (w0 == 8) hipLaunchKernelGGL((k_sell<MODE, 1, T, 8>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                else if (w0 == 2) hipLaunchKernelGGL((k_sell<MODE, 1, T, 2>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                else hipLaunchKernelGGL((k_sell<MODE, 1, T>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                break;
-            }
-            case 2:
-                if (A.stride > 0 && A.w_lo == 7) hipLaunchKernelGGL((k_sell<MODE, 2, T, 7>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                else hipLaunchKernelGGL((k_sell<MODE, 2, T>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                break;
-            case 3:
-                if (A.stride > 0 && A.w_lo == 7) hipLaunchKernelGGL((k_sell<MODE, 3, T, 7>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                else hipLaunchKernelGGL((k_sell<MODE, 3, T>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                break;
-            default:
-                if (A.stride > 0 && A.w_lo == 7) hipLaunchKernelGGL((k_sell<MODE, 4, T, 7>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                else hipLaunchKernelGGL((k_sell<MODE, 4, T>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-                break;
+        if constexpr (MODE == SELL_AX || MODE == SELL_ADD) {
+            if (A.codes) { launch_narrow<MODE, T, true>(A, kb, nb, ns, grid, nbarg, one_xcd, s_begin, s_end, use_order, xx, bb, yy, k, done, pp, zz, st); continue; }
         }
+        launch_narrow<MODE, T, false>(A, kb, nb, ns, grid, nbarg, one_xcd, s_begin, s_end, use_order, xx, bb, yy, k, done, pp, zz, st);
     }
     if (MODE == SELL_AX && A.long_n > 0 && s_begin == 0 && s_end_in == A.n_slices && host_long_vals<T>(A)) {
         // the long rows of the matrix (their panel rows are empty: the launches above left zeros there), all k columns in one launch
-        const CoarseInit<T> zz = coarse_init<T>(zero_rows, 0, first, omega);
+        const CoarseInit<T> zz = coarse_codes<T>(A, zero_rows, 0, first, omega);
         if (k >= 8) {
             const long waves = (long)A.long_n * ((k + 63) / 64);
             hipLaunchKernelGGL((k_long_ax_cols<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, A.long_row, A.long_ptr, A.long_col, host_long_vals<T>(A), A.long_n, x, y,
@@ -773,11 +816,11 @@ hipError_t launch_sell(SellMode mode, const SellDev& A, int s_begin, int s_end, 
     return launch_sell_any<double>(mode, A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
 }
 
-// fp32 twin for the mixed-precision V-cycle (A.valf must be set; the norm modes are fp64-only)
+// fp32 twin for the mixed-precision V-cycle (A.valf must be set, or A hold weight codes; the norm modes are fp64-only)
 hipError_t launch_sell_f32(SellMode mode, const SellDev& A, int s_begin, int s_end, const float* x, const float* b,
                            float* y, int k, const Ctrl* ctrl, hipStream_t st, float* zero_rows, const FirstColour* first, double omega)
 {
-    if (!A.valf || mode == SELL_RESID_SS || mode == SELL_RESID_BOTH || mode >= SELL_GS_OOP) return hipErrorInvalidValue;
+    if ((!A.valf && !A.codes) || mode == SELL_RESID_SS || mode == SELL_RESID_BOTH || mode >= SELL_GS_OOP) return hipErrorInvalidValue;
     return launch_sell_any<float>(mode, A, s_begin, s_end, x, b, y, k, ctrl, nullptr, nullptr, st, zero_rows, first, omega);
 }
 
@@ -1930,6 +1973,27 @@ hipError_t launch_sell_fill_map(const int* ptr, const int* col, const int* perm,
     if (e != hipSuccess || S.n_slices <= 0) return e;
     hipLaunchKernelGGL(k_sell_fill<true>, dim3((S.n_slices + 3) / 4), dim3(256), 0, st, ptr, col, (const double*)nullptr, perm, iperm, S.slice_row, S.slice_off, S.stride,
                        S.n_slices, transposed ? 1 : 0, (int*)nullptr, (double*)nullptr, map);
+    return hipGetLastError();
+}
+
+// Weight codes of a filled image (SellDev::codes): the code of a slot is the index of its value's bit pattern in tab
+__global__ __launch_bounds__(256) void k_sell_encode(const int* __restrict__ s_col, const double* __restrict__ s_val, size_t n, double t0, double t1, double t2,
+                                                     double t3, int n_tab, int* __restrict__ out, int* bad)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = s_col[i];
+    if (c < 0) { out[i] = -1; return; }
+    const long long b = __double_as_longlong(s_val[i]);
+    const int code = b == __double_as_longlong(t0) ? 0 : (n_tab > 1 && b == __double_as_longlong(t1)) ? 1 : (n_tab > 2 && b == __double_as_longlong(t2)) ? 2
+                   : (n_tab > 3 && b == __double_as_longlong(t3)) ? 3 : -1;
+    if (code < 0 || c >= (1 << 29)) { atomicOr(bad, 1); out[i] = -1; return; }
+    out[i] = (c << 2) | code;
+}
+hipError_t launch_sell_encode(const SellDev& S, size_t padded, const double* tab, int n_tab, int* out_col, int* bad, hipStream_t st)
+{
+    if (padded == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_sell_encode, dim3(grid1d(padded, 256)), dim3(256), 0, st, S.col, S.val, padded, tab[0], tab[1], tab[2], tab[3], n_tab, out_col, bad);
     return hipGetLastError();
 }
 

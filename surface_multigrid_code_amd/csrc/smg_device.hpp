@@ -39,6 +39,12 @@ struct SellDev {
     const int* col = nullptr;
     const double* val = nullptr;
     const float* valf = nullptr;     // fp32 copy of val (same slots), only for the mixed-precision V-cycle
+    // Weight codes (transfer operators of subdivision hierarchies: P holds 1.0 and 0.5 only): codes != 0 means there is no value array
+    // (val / valf are null); every stored slot's column word is (column << 2) | code and its value is tab[code] (tabf: the fp32 image).
+    // Padding stays -1 (an arithmetic shift by 2 keeps it -1).  SellBuf::encode_codes builds it; smg_device.hip decodes it.
+    int codes = 0;
+    double tab[4] = {0.0, 0.0, 0.0, 0.0};
+    float tabf[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     // Long rows taken out of the panels (restriction operators of decimated hierarchies: a coarse vertex of the reference's construction
     // may gather from > 100 fine ones, and a panel row is one chain of dependent batches -- it set the launch's duration): in CSR,
     // ascending column order, served by launch_sell(SELL_AX) through a companion launch of one wave per (row, column); the panels hold
@@ -284,6 +290,9 @@ hipError_t launch_recipe(int n_out, const int* ptr, const int* idx, const double
 // transposed: the image of A(perm, perm)^T instead -- A structurally symmetric (launch_bit_symmetric), values looked up by bisection
 hipError_t launch_sell_fill(const int* ptr, const int* col, const double* val, const int* perm, const int* iperm, const SellDev& S, size_t padded, hipStream_t st,
                             bool transposed = false);
+// out_col[i] = S.col[i] < 0 ? -1 : (S.col[i] << 2) | code, where tab[code] is bit for bit S.val[i] (n_tab <= 4 entries); *bad (preset to 0 by
+// the caller) is raised when a stored slot's value is not in the table or its column does not fit in 29 bits
+hipError_t launch_sell_encode(const SellDev& S, size_t padded, const double* tab, int n_tab, int* out_col, int* bad, hipStream_t st);
 // slot[r] = index of a_rr in the value array of the filled square image S (-1: not stored); *first_missing (preset to n_rows by the caller) =
 // the smallest row without one
 hipError_t launch_sell_diag_slots(const SellDev& S, int* slot, int* first_missing, hipStream_t st);

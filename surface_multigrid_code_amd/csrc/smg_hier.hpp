@@ -99,6 +99,10 @@ struct SellBuf {  // device image of one SELL matrix
     DevBuf<double> long_val;
     DevBuf<float> long_valf;
     hipError_t upload_long(const std::vector<int>& rows, const std::vector<int>& ptr, const std::vector<int>& col, const std::vector<double>& val);
+    // transfer operators: when the n_vals CSR values `vals` the image was made from take at most 4 bit patterns, the panels have no long rows and
+    // SMG_TRANSFER_CODES is not 0, the column words take a 2-bit weight code and the value array is released (SellDev::codes).  Otherwise
+    // (and on any mismatch found while encoding) the image is left as it is.
+    hipError_t encode_codes(const double* vals, size_t n_vals, hipStream_t st);
 };
 
 struct Bsr3Buf {  // device image of one block (3 x 3) SELL matrix, smg_bsr3.hpp

@@ -964,12 +964,14 @@ static int level_images(smg_hierarchy* h, int lv, int sym0)
         const bool cut = tr_region && region && Of.color_ptr.size() > 2;
         if (!blk && Lp.P_device_filled) {
             eP = device_fill_sell(Lp.dP, Lp.P, Of.perm, Lp.ord.iperm, cut ? &Of.color_ptr : nullptr, cut, h->aux[1], h->mem_lean ? 0 : -1);
+            if (eP == hipSuccess) eP = Lp.dP.encode_codes(Lp.P.val.data(), Lp.P.val.size(), h->aux[1]);
             return;
         }
         Csr Pvi;
         if (blk) Pvi = permute(Lp.Pv, Of.perm, Lp.vord.perm);
         Sell S = build_sell(blk ? Pvi : Lp.P_int, cut ? &Of.color_ptr : nullptr, sellC, cut, h->mem_lean ? 0 : -1);
         eP = Lp.dP.upload(S);
+        if (eP == hipSuccess) eP = Lp.dP.encode_codes((blk ? Pvi : Lp.P_int).val.data(), (blk ? Pvi : Lp.P_int).val.size(), h->aux[1]);
     });
     tasks.push_back([&] {
         DeviceScope ds(h->device);
@@ -982,6 +984,7 @@ static int level_images(smg_hierarchy* h, int lv, int sym0)
         if (!blk && Lp.PT_device_filled) {
             eQ = device_fill_sell(Lp.dPT, Lp.PT, Oc.perm, Lw.ord.iperm, cut ? &Oc.color_ptr : nullptr, cut, h->aux[2], h->mem_lean ? 0 : -1);
             if (eQ == hipSuccess) eQ = Lp.dPT.upload_long({}, {0}, {}, {});
+            if (eQ == hipSuccess) eQ = Lp.dPT.encode_codes(Lp.PT.val.data(), Lp.PT.val.size(), h->aux[2]);
             return;
         }
         Csr PTvi;
@@ -1001,6 +1004,7 @@ static int level_images(smg_hierarchy* h, int lv, int sym0)
             Sell S = build_sell(M, cut ? &Oc.color_ptr : nullptr, sellC, cut, h->mem_lean ? 0 : -1);
             eQ = Lp.dPT.upload(S);
             if (eQ == hipSuccess) eQ = Lp.dPT.upload_long(lrow, lptr, lcol, lval);
+            if (eQ == hipSuccess) eQ = Lp.dPT.encode_codes(M.val.data(), M.val.size(), h->aux[2]);
             return;
         }
         Csr Ms;     // M with the long rows emptied
