@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 501
+#define SMG_VERSION 502
 
 enum {
     SMG_OK = 0,
@@ -339,6 +339,28 @@ int smg_assemble(smg_assembler *a, const double *d_V, int voronoi, double mass_c
 int smg_solve(smg_hierarchy *h, const double *RHS, int ld_rhs, const double *known_val, int ld_kv, const double *z0,
               int ld_z0, int k, int memspace, const smg_solve_opts *opts, double *z, int ld_z, double *r_his,
               int *n_his, int *converged);
+
+/* The same system solved by conjugate gradients with one V-cycle as the preconditioner (an addition: the reference has no Krylov solver).
+ * Flexible (Polak-Ribiere) PCG, one independent recurrence per column -- the V-cycle is not symmetric (pre- and post-smoothing sweep in the
+ * same order; the fp32 cycle of precision = 1 rounds), and the flexible beta tolerates that:
+ *     x = z0_u;  r = RHS_u - A x
+ *     loop entry i:  record |r|_F (all columns); if |r|_F < tol: break
+ *                    z = V(r, 0);  beta = -alpha_prev (z.q_prev) / rz_prev  (0 in the first iteration and after a restart);  p = z + beta p
+ *                    q = A p;  alpha = (z.r) / (p.q);  x += alpha p;  r -= alpha q
+ * Every division by an exact zero gives 0 (a zero column stays exactly zero).  V is what smg_solve's cycle is with the same opts (pre, post,
+ * smoother, precision); with precision = 1 the cycle runs in fp32 and everything else in fp64.
+ * Arguments, memspace, known_val, opts (tol, max_iter, check_every, use_graph, verbosity, ...), r_his, n_his and converged mean what they mean
+ * for smg_solve, and the history has its shape: one entry per loop entry, including the one that triggers the break; max_iter = 0 returns
+ * z = z0 and *n_his = 0.
+ *   r_his[0] is the true residual of z0, measured as smg_solve measures it (the same value as smg_solve's r_his[0]).  Later entries are the
+ *   norms of the recurrence's r.  When one of them passes the break test, the true residual of x is computed and replaces that entry; if it
+ *   is still >= tol and entries remain, the iteration restarts from x with r = the true residual (beta = 0).  So an entry that ended the loop
+ *   is always a true residual, and *converged = !(last entry > tol) as for smg_solve.  A non-finite norm ends the loop with SMG_ERR_NONFINITE.
+ * Union handles (smg_union_members > 0) are refused with SMG_ERR_INVALID, as is a call during a split-phase solve.  The Krylov vectors (five
+ * n x k blocks) are allocated by the first call; smg_debug_device_bytes lists them as "krylov". */
+int smg_solve_pcg(smg_hierarchy *h, const double *RHS, int ld_rhs, const double *known_val, int ld_kv, const double *z0,
+                  int ld_z0, int k, int memspace, const smg_solve_opts *opts, double *z, int ld_z, double *r_his,
+                  int *n_his, int *converged);
 
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.

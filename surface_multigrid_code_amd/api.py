@@ -164,6 +164,24 @@ class Hierarchy:
         _chk(rc, "smg_solve")
         return bool(conv.value), z, r_his[: n_his.value].copy()
 
+    def solve_pcg(self, RHS, z0, known_val=None, opts=None):
+        """The same system solved by conjugate gradients with one V-cycle as the preconditioner (include/smg.h: smg_solve_pcg):
+        flexible PCG, one recurrence per column, the history and the break test of solve().  Returns (converged, z, r_his)."""
+        opts = opts or SolveOpts()
+        RHS, z0 = _colmajor(RHS), _colmajor(z0)
+        n, k = RHS.shape
+        z = np.zeros((n, k), order="F")
+        r_his = np.zeros(max(opts.c.max_iter, 1))
+        n_his, conv = C.c_int(0), C.c_int(0)
+        kv_p, ld_kv = None, 0
+        if self.known is not None:
+            kv = _colmajor(known_val if known_val is not None else np.zeros((len(self.known), k)))
+            kv_p, ld_kv = kv.ctypes.data, kv.shape[0]
+        rc = self.L.smg_solve_pcg(self.h, RHS.ctypes.data, n, kv_p, ld_kv, z0.ctypes.data, n, k, SMG_HOST,
+                                  C.byref(opts.c), z.ctypes.data, n, _dp(r_his), C.byref(n_his), C.byref(conv))
+        _chk(rc, "smg_solve_pcg")
+        return bool(conv.value), z, r_his[: n_his.value].copy()
+
     def solve_device(self, rhs_ptr, z0_ptr, z_ptr, n, k=1, known_val_ptr=None, ld_kv=0, opts=None):
         """min_quad_with_fixed_mg_solve on column-major blocks already resident in HBM (device pointers, leading dimension n):
         the drop-in call, polling the device-side convergence flag every opts.check_every iterations."""
@@ -172,6 +190,15 @@ class Hierarchy:
         n_his, conv = C.c_int(0), C.c_int(0)
         _chk(self.L.smg_solve(self.h, rhs_ptr, n, known_val_ptr, ld_kv, z0_ptr, n, k, SMG_DEVICE, C.byref(opts.c), z_ptr, n,
                               _dp(r_his), C.byref(n_his), C.byref(conv)), "smg_solve")
+        return bool(conv.value), r_his[: n_his.value].copy()
+
+    def solve_pcg_device(self, rhs_ptr, z0_ptr, z_ptr, n, k=1, known_val_ptr=None, ld_kv=0, opts=None):
+        """solve_pcg on column-major blocks already resident in HBM (device pointers, leading dimension n).  Returns (converged, r_his)."""
+        opts = opts or SolveOpts()
+        r_his = np.zeros(max(opts.c.max_iter, 1))
+        n_his, conv = C.c_int(0), C.c_int(0)
+        _chk(self.L.smg_solve_pcg(self.h, rhs_ptr, n, known_val_ptr, ld_kv, z0_ptr, n, k, SMG_DEVICE, C.byref(opts.c), z_ptr, n,
+                                  _dp(r_his), C.byref(n_his), C.byref(conv)), "smg_solve_pcg")
         return bool(conv.value), r_his[: n_his.value].copy()
 
     def solve_sharded(self, rhs_ptr, z0_ptr, z_ptr, n, k_local, reduce, known_val_ptr=None, ld_kv=0, opts=None):

@@ -194,14 +194,18 @@ inline void min_quad_with_fixed_mg_precompute(const smgSparse& A, const smgDense
 // ---- min_quad_with_fixed_mg_solve ---------------------------------------------------------------------------------
 namespace smg_detail {
 inline bool solve_impl(const smgDense& RHS, const smgDense* known_val, const smgDense& z0, const smgCoarseSolver& solver,
-                       double tolerance, int maxIter, smgDense& z, std::vector<double>& r_his)
+                       double tolerance, int maxIter, smgDense& z, std::vector<double>& r_his, bool pcg = false)
 {
     smg_solve_opts o = solver.opts;
     o.tol = tolerance; o.max_iter = maxIter;
     z.resize(z0.rows, z0.cols);
     r_his.assign((size_t)(maxIter > 0 ? maxIter : 1), 0.0);
     int n_his = 0, conv = 0;
-    if (solver.reduce)   // this rank's columns of a column-sharded solve; the library runs the loop and calls the reduction
+    if (pcg)             // the V-cycle as the preconditioner of conjugate gradients (single GPU)
+        check(smg_solve_pcg(solver.h.get(), RHS.data.data(), RHS.rows, known_val ? known_val->data.data() : nullptr,
+                            known_val ? known_val->rows : 0, z0.data.data(), z0.rows, RHS.cols, SMG_HOST, &o, z.data.data(), z.rows,
+                            r_his.data(), &n_his, &conv), "min_quad_with_fixed_mg_solve_pcg");
+    else if (solver.reduce)   // this rank's columns of a column-sharded solve; the library runs the loop and calls the reduction
         check(smg_solve_sharded(solver.h.get(), RHS.data.data(), RHS.rows, known_val ? known_val->data.data() : nullptr,
                                 known_val ? known_val->rows : 0, z0.data.data(), z0.rows, RHS.cols, SMG_HOST, &o, solver.reduce, solver.reduce_ctx,
                                 z.data.data(), z.rows, r_his.data(), &n_his, &conv), "min_quad_with_fixed_mg_solve (sharded)");
@@ -251,6 +255,23 @@ inline bool min_quad_with_fixed_mg_solve(const min_quad_with_fixed_mg_data& d, c
                                          smgDense& z, std::vector<double>& r_his)
 {
     return min_quad_with_fixed_mg_solve(d, RHS, known_val, z0, solver, 1e-3, mg, z, r_his);  // .cpp:270
+}
+
+// ---- min_quad_with_fixed_mg_solve_pcg: an addition, not a reference interface -- the same arguments, the same system, solved by conjugate
+// gradients preconditioned by one V-cycle (include/smg.h: smg_solve_pcg).  Not available on a column-sharded solver.
+inline bool min_quad_with_fixed_mg_solve_pcg(const min_quad_with_fixed_mg_data&, const smgDense& RHS, const smgDense& z0,
+                                             const smgCoarseSolver& solver, const double& tolerance, const int& maxIter,
+                                             std::vector<mg_data>&, smgDense& z, std::vector<double>& r_his)
+{
+    if (solver.reduce) throw std::runtime_error("min_quad_with_fixed_mg_solve_pcg: no column-sharded form");
+    return smg_detail::solve_impl(RHS, nullptr, z0, solver, tolerance, maxIter, z, r_his, true);
+}
+inline bool min_quad_with_fixed_mg_solve_pcg(const min_quad_with_fixed_mg_data&, const smgDense& RHS, const smgDense& known_val,
+                                             const smgDense& z0, const smgCoarseSolver& solver, const double& tolerance,
+                                             const int& maxIter, std::vector<mg_data>&, smgDense& z, std::vector<double>& r_his)
+{
+    if (solver.reduce) throw std::runtime_error("min_quad_with_fixed_mg_solve_pcg: no column-sharded form");
+    return smg_detail::solve_impl(RHS, &known_val, z0, solver, tolerance, maxIter, z, r_his, true);
 }
 
 // ---- mg_VCycle (reference src/mg_VCycle.cpp:3-59) ----------------------------------------------------------------

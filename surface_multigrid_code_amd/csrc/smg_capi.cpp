@@ -73,6 +73,7 @@ extern "C" int smg_debug_device_bytes(const smg_hierarchy* h, char* buf, int cap
     line("maps_level0", B(h->d_map0) + B(h->d_perm0) + B(h->d_unknown) + B(h->d_known) + B(h->d_auk_ptr) + B(h->d_auk_col) + B(h->d_auk_val));
     line("reprecompute_bookkeeping", B(h->d_lhs_src) + B(h->d_auk_src) + B(h->d_diag_idx) + B(h->d_dense_pos) + B(h->d_Afull));
     line("early_upload", B(h->early0.ptr) + B(h->early0.col) + B(h->early0.val));
+    line("krylov", B(h->kry_x) + B(h->kry_r) + B(h->kry_p) + B(h->kry_q) + B(h->kry_b) + B(h->kry_part) + B(h->kry_s) + B(h->kry_restart));
     line("solve_state", B(h->d_ctrl) + B(h->d_rhis) + B(h->d_partials) + B(h->d_lam) + B(h->d_stage_rhs) + B(h->d_stage_z) + B(h->d_stage_kv) + B(h->d_tmp_cm) + B(h->d_zsave));
     out += "total " + std::to_string(tot) + "\n";
     std::snprintf(buf, (size_t)cap, "%s", out.c_str());
@@ -132,6 +133,10 @@ void smg::drop_graphs(smg_hierarchy* h)
     if (h->g_cyc) (void)hipGraphExecDestroy(h->g_cyc);
     h->g_iter = h->g_iter_n = h->g_resid = h->g_cycle = h->g_spec = h->g_rd = h->g_cyc = nullptr;
     h->g_key = smg::GraphKey();
+    if (h->g_pcg) (void)hipGraphExecDestroy(h->g_pcg);
+    if (h->g_pcg_n) (void)hipGraphExecDestroy(h->g_pcg_n);
+    h->g_pcg = h->g_pcg_n = nullptr;
+    h->g_pcg_key = smg::GraphKey();
 }
 
 hipError_t SellBuf::upload(const Sell& S)

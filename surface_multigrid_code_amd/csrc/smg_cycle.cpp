@@ -1328,16 +1328,18 @@ extern "C" int smg_solve_end(smg_hierarchy* h, double* z, int ld_z, int memspace
 // how many more cycles the tolerance needs and enqueues all but the last of them before the next look (the results do not depend
 // on this: an iteration enqueued after the break stores nothing).  The schedule is a function of the residual history alone, so the
 // ranks of a column-sharded solve -- who all see the same reduced residuals -- enqueue (and reduce) the same number of times.
+// budget >= 0: at most that many iterations instead of max_iter (smg_solve_pcg: the entries its first residual and its checks have used are not iterations).
 template <typename Iter>
-static int run_outer_loop(smg_hierarchy* h, Iter&& iterations, bool look_into_single_iterations = false)
+static int run_outer_loop(smg_hierarchy* h, Iter&& iterations, bool look_into_single_iterations = false, int budget = -1)
 {
     int it = 0;
     int chunk_next = 1;
     static const int look_env = env_int("SMG_LOOK_INTO", 1);      // A/B knob
     const bool look = look_into_single_iterations && look_env != 0;
-    while (it < h->max_iter) {
+    const int max_it = budget >= 0 ? budget : h->max_iter;
+    while (it < max_it) {
         const int want = h->check_every > 0 ? h->check_every : chunk_next;
-        const int chunk = std::min(want, h->max_iter - it);
+        const int chunk = std::min(want, max_it - it);
         Ctrl hc;
         if (look && chunk == 1) {
             // the look happens between the iteration's break test and its cycle; the cycle is enqueued behind it and the loop goes straight on
@@ -1348,7 +1350,7 @@ static int run_outer_loop(smg_hierarchy* h, Iter&& iterations, bool look_into_si
         } else {
             { int rc = iterations(chunk); if (rc) return rc; }
             it += chunk;
-            if (it >= h->max_iter) break;
+            if (it >= max_it) break;
             { int rc = read_ctrl(h, &hc); if (rc) return rc; }
             if (hc.done) break;
         }
@@ -1370,6 +1372,161 @@ extern "C" int smg_solve(smg_hierarchy* h, const double* RHS, int ld_rhs, const 
     rc = run_outer_loop(h, [&](int n) { return enqueue_outer_iterations(h, n); }, h->union_m == 0);
     if (rc) { h->in_solve = false; h->coarse_cols = 0; return rc; }
     return smg_solve_end(h, z, ld_z, memspace, r_his, n_his, converged);
+}
+
+// ---- conjugate gradients preconditioned by the V-cycle (include/smg.h: smg_solve_pcg) ------------------------------------------------
+// Flexible (Polak-Ribiere) PCG, one recurrence per column.  The vectors live in the handle's Krylov buffers; the V-cycle
+// keeps its own: its input r goes into L0.b (L0.b32), it starts from L0.u = 0 and leaves z in L0.u.  One iteration:
+//   z = V(r, 0);  rz = z.r, beta = -alpha_prev z.q / rz_prev;  p = z + beta p;  q = A p;  alpha = rz / p.q;  x += alpha p, r -= alpha q;  |r|_F -> r_his
+// and every launch of it starts with `if (done) return`, so iterations enqueued after the break store nothing -- the schedule of the outer loop
+// (run_outer_loop) is smg_solve's.
+static int ensure_krylov(smg_hierarchy* h)
+{
+    const int n = h->lv[0].n, k = h->k;
+    const size_t cnt = (size_t)n * k;
+    const int groups = kry_groups(n, k);
+    const size_t npart = (size_t)2 * groups * k, ns = (size_t)KS_SLOTS * k;
+    if (h->kry_x.n < cnt || h->kry_part.n < npart || h->kry_s.n < ns || !h->kry_restart.p) {
+        drop_graphs(h);      // (the PCG graphs hold these pointers; the MG graphs are recaptured at their next use)
+        for (DevBuf<double>* b : {&h->kry_x, &h->kry_r, &h->kry_p, &h->kry_q, &h->kry_b}) {
+            HIPCHK(b->ensure(cnt));
+            HIPCHK(hipMemsetAsync(b->p, 0, b->n * sizeof(double), h->stream));
+        }
+        HIPCHK(h->kry_part.ensure(npart));
+        HIPCHK(h->kry_s.ensure(ns));
+        HIPCHK(hipMemsetAsync(h->kry_s.p, 0, h->kry_s.n * sizeof(double), h->stream));
+        HIPCHK(h->kry_restart.ensure(1));
+    }
+    KryDev& K = h->kry;
+    K.n = n; K.k = k; K.groups = groups;
+    K.part = h->kry_part.p; K.s = h->kry_s.p; K.restart = h->kry_restart.p;
+    return SMG_OK;
+}
+
+static int enqueue_pcg_iteration(smg_hierarchy* h)
+{
+    Level& L0 = h->lv[0];
+    const int k = h->k;
+    const size_t cnt = (size_t)L0.n * k;
+    Ctrl* ctrl = h->d_ctrl.p;
+    const KryDev& K = h->kry;
+    {
+        ProfGuard pg(h, "MG: total VCycle");
+        if (h->precision == 1) {     // the fp32 cycle: z = (double) V32((float) r, 0)
+            HIPCHK(launch_residual_to_f32(L0.b32.p, L0.u32.p, h->kry_r.p, cnt, ctrl, h->stream));
+            int rc = enqueue_vcycle32(h, 0, k, h->pre, h->post, ctrl);
+            if (rc) return rc;
+            HIPCHK(launch_kry_widen(L0.u32.p, L0.u.p, cnt, ctrl, h->stream));
+        } else {
+            HIPCHK(launch_kry_precond_in(h->kry_r.p, L0.b.p, L0.u.p, cnt, ctrl, h->stream));
+            int rc = enqueue_vcycle(h, 0, k, h->pre, h->post, ctrl, FIRST_NONE);
+            if (rc) return rc;
+        }
+    }
+    ProfGuard pg(h, "PCG: vectors");
+    HIPCHK(launch_kry_dots_zr_zq(K, L0.u.p, h->kry_r.p, h->kry_q.p, ctrl, h->stream));
+    HIPCHK(launch_kry_direction(K, L0.u.p, h->kry_p.p, ctrl, h->stream));
+    HIPCHK(Prec<double>::opA(h, L0, false, SELL_AX, 0, -1, h->kry_p.p, nullptr, h->kry_q.p, k, ctrl));
+    HIPCHK(launch_kry_dots_pq(K, h->kry_p.p, h->kry_q.p, ctrl, h->stream));
+    HIPCHK(launch_kry_step_decide(K, h->kry_x.p, h->kry_r.p, h->kry_p.p, h->kry_q.p, ctrl, h->stream));
+    return SMG_OK;
+}
+
+// one iteration and graph_iters() of them, each a linear chain; kept apart from the MG graphs (own handles, own key)
+static int ensure_pcg_graphs(smg_hierarchy* h)
+{
+    const GraphKey key = current_graph_key(h);
+    if (h->g_pcg && h->g_pcg_key == key) return SMG_OK;
+    if (h->g_pcg) { (void)hipGraphExecDestroy(h->g_pcg); h->g_pcg = nullptr; }
+    if (h->g_pcg_n) { (void)hipGraphExecDestroy(h->g_pcg_n); h->g_pcg_n = nullptr; }
+    int rc = capture_graph(h, &h->g_pcg, [&]() { return enqueue_pcg_iteration(h); });
+    if (rc) return rc;
+    if (graph_iters() > 1) {
+        rc = capture_graph(h, &h->g_pcg_n, [&]() {
+            for (int i = 0; i < graph_iters(); i++) { int r = enqueue_pcg_iteration(h); if (r) return r; }
+            return (int)SMG_OK;
+        });
+        if (rc) return rc;
+    }
+    h->g_pcg_key = key;
+    return SMG_OK;
+}
+
+static int enqueue_pcg_iterations(smg_hierarchy* h, int n)
+{
+    if (graphs_usable(h)) {
+        int rc = ensure_pcg_graphs(h);
+        if (rc) return rc;
+        if (graph_iters() > 1)
+            for (; n >= graph_iters(); n -= graph_iters()) { HIPCHK(hipGraphLaunch(h->g_pcg_n, h->stream)); h->iters_enqueued += graph_iters(); }
+        for (; n > 0; n--) { HIPCHK(hipGraphLaunch(h->g_pcg, h->stream)); h->iters_enqueued++; }
+        return SMG_OK;
+    }
+    for (; n > 0; n--) { int rc = enqueue_pcg_iteration(h); if (rc) return rc; h->iters_enqueued++; }
+    return SMG_OK;
+}
+
+// r_his[n_his] = |RHS_u - A x| of the iterate in the Krylov buffer x, measured as smg_solve measures it, with the break test.  reopen: it replaces
+// the last entry (a recurrence norm that passed the test) and the restart flag is raised.
+static int enqueue_pcg_true_residual(smg_hierarchy* h, bool head, bool reopen)
+{
+    Level& L0 = h->lv[0];
+    const size_t bytes = (size_t)L0.n * h->k * sizeof(double);
+    HIPCHK(hipMemcpyAsync(L0.u.p, h->kry_x.p, bytes, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(L0.b.p, h->kry_b.p, bytes, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(launch_kry_arm(h->kry, h->d_ctrl.p, reopen, h->stream));
+    h->head_fuse = head;
+    int rc = enqueue_residual_ss(h, h->k, true);
+    h->head_fuse = false;
+    if (rc) return rc;
+    // r = RHS_u - A x: the recurrence (re)starts from the true residual
+    HIPCHK(Prec<double>::opA(h, L0, false, SELL_RESID, 0, -1, h->kry_x.p, h->kry_b.p, h->kry_r.p, h->k, h->d_ctrl.p));
+    return SMG_OK;
+}
+
+static int pcg_loop(smg_hierarchy* h)
+{
+    if (h->max_iter == 0) return SMG_OK;              // z = z0, no entries (as smg_solve)
+    int rc = ensure_krylov(h);
+    if (rc) return rc;
+    Level& L0 = h->lv[0];
+    const size_t bytes = (size_t)L0.n * h->k * sizeof(double);
+    const bool head = h->head_fuse;                   // entry 0 and the checks measure as smg_solve does; the iterations never fuse
+    h->head_fuse = false;
+    HIPCHK(hipMemcpyAsync(h->kry_x.p, L0.u.p, bytes, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->kry_b.p, L0.b.p, bytes, hipMemcpyDeviceToDevice, h->stream));
+    if ((rc = enqueue_pcg_true_residual(h, head, false))) return rc;
+    h->iters_enqueued = 1;
+    int n_true = 1;                                   // entries up to and including the last true residual
+    Ctrl hc;
+    for (;;) {
+        rc = run_outer_loop(h, [&](int n) { return enqueue_pcg_iterations(h, n); }, false, h->max_iter - n_true);
+        if (rc) return rc;
+        if ((rc = read_ctrl(h, &hc))) return rc;
+        // a recurrence norm passed the break test: verified on the true residual of x, which replaces it
+        if (!hc.done || hc.status != 0 || hc.n_his <= n_true) break;
+        if ((rc = enqueue_pcg_true_residual(h, head, true))) return rc;
+        if ((rc = read_ctrl(h, &hc))) return rc;
+        n_true = hc.n_his;
+        if (hc.done || n_true >= h->max_iter) break;  // converged (or non-finite) / no entries left; else restart from x
+    }
+    HIPCHK(hipMemcpyAsync(L0.u.p, h->kry_x.p, bytes, hipMemcpyDeviceToDevice, h->stream));
+    return SMG_OK;
+}
+
+extern "C" int smg_solve_pcg(smg_hierarchy* h, const double* RHS, int ld_rhs, const double* known_val, int ld_kv, const double* z0, int ld_z0, int k,
+                             int memspace, const smg_solve_opts* opts, double* z, int ld_z, double* r_his, int* n_his, int* converged)
+{
+    return guarded("smg_solve_pcg", [&]() -> int {
+        int rc = check_ready(h, "smg_solve_pcg");
+        if (rc) return rc;
+        if (h->union_m > 0) return fail(SMG_ERR_INVALID, "smg_solve_pcg: a union handle is not supported (its members stop one by one: use smg_solve)");
+        if ((rc = smg_solve_begin_impl(h, RHS, ld_rhs, known_val, ld_kv, z0, ld_z0, k, memspace, opts))) return rc;
+        DeviceScope dsc(h->device);
+        rc = pcg_loop(h);
+        if (rc) { h->in_solve = false; h->coarse_cols = 0; return rc; }
+        return smg_solve_end(h, z, ld_z, memspace, r_his, n_his, converged);
+    });
 }
 
 // ---- column-sharded solve (include/smg.h: smg_solve_sharded) ------------------------------------------------------------------------

@@ -873,18 +873,6 @@ __global__ __launch_bounds__(256) void k_ss_finalize(const double* partials, int
     if (threadIdx.x == 0) *out = red[0];
 }
 
-__device__ __forceinline__ void decide_body(Ctrl* ctrl, double sumsq)
-{
-    const double tol = ctrl->tol;
-    const double r = sqrt(sumsq);
-    const int i = ctrl->n_his;
-    if (i < ctrl->his_cap) ctrl->r_his[i] = r;
-    ctrl->n_his = i + 1;
-    ctrl->r_prev = ctrl->r_last; ctrl->r_last = r;
-    if (!(r == r) || r > 1.7e308) { ctrl->status = -1; ctrl->done = 1; }  // NaN / Inf
-    else if (r < tol) ctrl->done = 1;                                       // min_quad_with_fixed_mg.cpp:113-116
-}
-
 // single-GPU path: reduction of the partials and the break test in one launch
 __global__ __launch_bounds__(256) void k_ss_finalize_decide(const double* partials, int n, Ctrl* ctrl)
 {

@@ -264,6 +264,32 @@ hipError_t launch_restore_if_just_done(double* dst, const double* src, size_t n,
 // both of the above in one launch (single-GPU path, no all-reduce in between)
 hipError_t launch_ss_finalize_decide(const double* partials, int n, Ctrl* ctrl, hipStream_t st);
 
+// ---- conjugate gradients preconditioned by the V-cycle (smg_solve_pcg; kernels: smg_krylov_device.hip) --------------------------------
+// Per-column scalars of the recurrence: s[slot * k + c]
+enum { KS_RZ = 0, KS_RZ_PREV = 1, KS_ALPHA = 2, KS_BETA = 3, KS_SLOTS = 4 };
+constexpr int KRY_MAX_GROUPS = 512;
+struct KryDev {
+    int n = 0, k = 0;            // the internal blocks: row-major n x k
+    int groups = 0;              // row chunks of the reduction launches (kry_groups(n, k))
+    double* part = nullptr;      // 2 x groups x k partial sums
+    double* s = nullptr;         // KS_SLOTS x k
+    int* restart = nullptr;      // 1: the next direction is z itself (first iteration, or a restart from the true residual)
+};
+int kry_groups(int n, int k);
+// rz_c = z.r and beta_c = -alpha_c (z.q)_c / rz_prev_c (the flexible, Polak-Ribiere form: z.(r_new - r_old) / rz_prev, as r_old - r_new = alpha q)
+hipError_t launch_kry_dots_zr_zq(const KryDev& K, const double* z, const double* r, const double* q, const Ctrl* ctrl, hipStream_t st);
+// p = z + beta_c p
+hipError_t launch_kry_direction(const KryDev& K, const double* z, double* p, const Ctrl* ctrl, hipStream_t st);
+// alpha_c = rz_c / (p.q)_c, rz_prev_c = rz_c
+hipError_t launch_kry_dots_pq(const KryDev& K, const double* p, const double* q, const Ctrl* ctrl, hipStream_t st);
+// x += alpha_c p, r -= alpha_c q, then |r|_F -> the history and the break test (as launch_decide)
+hipError_t launch_kry_step_decide(const KryDev& K, double* x, double* r, const double* p, const double* q, Ctrl* ctrl, hipStream_t st);
+// b0 = r, u0 = 0: the fp64 preconditioner's input;  z = (double) e: the fp32 one's output
+hipError_t launch_kry_precond_in(const double* r, double* b0, double* u0, size_t cnt, const Ctrl* ctrl, hipStream_t st);
+hipError_t launch_kry_widen(const float* e, double* z, size_t cnt, const Ctrl* ctrl, hipStream_t st);
+// restart flag = 1; reopen: also lower `done` and drop the last history entry (the host's check of a recurrence norm replaces it by the true one)
+hipError_t launch_kry_arm(const KryDev& K, Ctrl* ctrl, bool reopen, hipStream_t st);
+
 // u[i,:] += sum_j Ainv[i,j] * b[j,:]   (mg_VCycle.cpp:199-200 with the factorisation pre-inverted)
 // sym_work (optional, (lda/64)^2 * 64 elements): with it, a single column (k = 1) is multiplied through the lower triangle of
 // tiles only (the inverse is symmetric): half the bytes, two launches, deterministic per-row summation in block order.

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "smg_device.hpp"
+
 namespace smg {
 
 __device__ __forceinline__ int xcd_remap(int bid, int nb)
@@ -43,6 +45,19 @@ __device__ __forceinline__ void gather_kb(const T* px, bool use, T (&out)[KB])
 #pragma unroll
         for (int q = 0; q < KB; q++) out[q] = g[q];
     }
+}
+
+// r = sqrt(sumsq) -> the history; the break test (min_quad_with_fixed_mg.cpp:113-116), non-finite -> status -1
+__device__ __forceinline__ void decide_body(Ctrl* ctrl, double sumsq)
+{
+    const double tol = ctrl->tol;
+    const double r = sqrt(sumsq);
+    const int i = ctrl->n_his;
+    if (i < ctrl->his_cap) ctrl->r_his[i] = r;
+    ctrl->n_his = i + 1;
+    ctrl->r_prev = ctrl->r_last; ctrl->r_last = r;
+    if (!(r == r) || r > 1.7e308) { ctrl->status = -1; ctrl->done = 1; }  // NaN / Inf
+    else if (r < tol) ctrl->done = 1;                                       // min_quad_with_fixed_mg.cpp:113-116
 }
 
 // the zero word launchers substitute for a null convergence flag (defined in smg_device.hip)

@@ -340,6 +340,13 @@ struct smg_hierarchy {
     double* g_sumsq_ptr = nullptr;   // the buffer g_resid writes / g_cycle reads (the caller's all-reduce buffer, or ctrl->sumsq)
     smg::GraphKey g_key;             // what the cached graphs were captured with (k == 0: nothing cached)
     bool head_fuse = false;          // this solve takes the outer residual out of the first sweep (latched at smg_solve_begin)
+    // ---- conjugate gradients preconditioned by the V-cycle (smg_solve_pcg): allocated by the first such solve, own graph cache ----
+    smg::DevBuf<double> kry_x, kry_r, kry_p, kry_q, kry_b;   // n_0 x k: iterate, residual, direction, A p, RHS_u (the cycle's input overwrites L0.b)
+    smg::DevBuf<double> kry_part, kry_s;                      // partial sums of the reductions, per-column scalars (smg_device.hpp: KryDev)
+    smg::DevBuf<int> kry_restart;
+    smg::KryDev kry;
+    hipGraphExec_t g_pcg = nullptr, g_pcg_n = nullptr;        // one / graph_iters() PCG iterations
+    smg::GraphKey g_pcg_key;                                  // what they were captured with (the MG graphs keep g_key)
     // ---- profc mirror ----
     bool prof_on = false;
     std::vector<smg::ProfScope> scopes;
