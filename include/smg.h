@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 502
+#define SMG_VERSION 503
 
 enum {
     SMG_OK = 0,
@@ -362,6 +362,35 @@ int smg_solve_pcg(smg_hierarchy *h, const double *RHS, int ld_rhs, const double 
                   int ld_z0, int k, int memspace, const smg_solve_opts *opts, double *z, int ld_z, double *r_his,
                   int *n_his, int *converged);
 
+/* The nev smallest eigenpairs of A_uu x = lambda M_uu x (an addition: the reference has no eigensolver).  A_uu is the unknown system the
+ * handle was precomputed with; it must be symmetric positive definite (known rows act as Dirichlet rows).  M = diag(mass_diag) restricted to
+ * the unknown rows: mass_diag holds n entries in the caller's numbering (block hierarchies: one per DOF), and every unknown row needs a finite
+ * mass > 0, else SMG_ERR_INVALID before anything of the handle changes.  Method: LOBPCG (Knyazev 2001) with the basis selection of
+ * Hetmaniuk and Lehoucq (2006), preconditioned by W = V(R, 0) -- one V-cycle with opts' pre / post / smoother; precision = 1 runs the cycle
+ * in fp32 and everything else in fp64.
+ *   block: m iterated columns, nev <= m <= 64 (the extra columns are guard vectors and are never tested).  0 selects the smallest of
+ *          8, 16, 32, 64 that is >= nev + max(2, nev / 4) (at most 64, at most the number of unknowns, at least nev).
+ *   X0:    n x m start (column-major, caller numbering, leading dimension ld_x0; all m = block columns are read -- with block = 0 that is
+ *          the default block, not nev), or NULL: start column c, row r = a counter-based hash of
+ *          (seed, r, c) (splitmix64 finaliser, uniform in [-1, 1)), the same for every memspace.
+ *   evals: the nev smallest Ritz values, ascending (host).  X: n x nev, leading dimension ld_x, caller numbering, M-orthonormal
+ *          (X^T M X = I), known rows exactly 0.  Within a cluster of equal eigenvalues any M-orthonormal basis of the eigenspace is correct.
+ *   res_his (host, NULL allowed): res_his[i * nev + j] = |A x_j - lambda_j M x_j|_{M^-1} / |lambda_j| (x_j^T M x_j = 1) at iteration i; row 0
+ *          is the Rayleigh-Ritz of the start.  It must hold (opts->max_iter + 1) * nev doubles; *n_iter = rows written.  Pair j is converged
+ *          when its residual <= opts->tol; the loop ends when pairs 0 .. nev-1 all are, or after opts->max_iter iterations.
+ *          *n_converged = the number of leading converged pairs.  Not converged is not an error (SMG_OK, as smg_solve).
+ *   memspace: where mass_diag, X0 and X live (SMG_HOST / SMG_DEVICE).
+ * A non-finite residual or Gram entry returns SMG_ERR_NONFINITE.  SMG_ERR_INVALID: a union handle, a call during a split-phase solve,
+ * nev < 1, block < nev or > 64, fewer unknowns than the block.  Every run with the same inputs returns the same bits (memspace, graphs on or
+ * off: the loop runs eagerly, one host synchronisation per iteration).  Nothing smg_solve / smg_solve_pcg compute afterwards changes.  The
+ * buffers (about ten n x m blocks) are allocated by the first call; smg_debug_device_bytes lists them as "eigs".
+ * Closed meshes (A = -L is singular): precompute a shifted matrix.  The mean-curvature-flow system A = M - delta L gives the Laplace-Beltrami
+ * eigenvalues of -L x = lambda_L M x as lambda_L = (mu - 1) / delta from its eigenvalues mu; for -L itself, precompute -L + sigma M and
+ * subtract sigma.  Not covered: a sparse (non-diagonal) mass matrix, union handles, a column-sharded form. */
+int smg_eigs(smg_hierarchy *h, const double *mass_diag, int nev, int block, const double *X0, int ld_x0, int memspace,
+             const smg_solve_opts *opts, unsigned long long seed, double *evals, double *X, int ld_x, double *res_his, int *n_iter,
+             int *n_converged);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -481,6 +510,12 @@ int smg_debug_schur_solve_host(int n, const int *ptr, const int *col, const doub
  * Returns SMG_ERR_INVALID when a pivot is not positive. */
 int smg_debug_check_sparse_cholesky(int n, const int *rowptr, const int *col, const double *val, long *factor_entries, int *dependency_depth,
                                     double *rel_residual);
+
+/* Test hook: the dense generalized symmetric eigensolver of smg_eigs' Rayleigh-Ritz step, on the host.  A (symmetric) and B (symmetric
+ * positive definite) are n x n column-major; out: the eigenvalues of A v = lambda B v ascending, V (n x n column-major) B-orthonormal.
+ * Cholesky of B, reduction to standard form, Householder tridiagonalisation and implicit QR steps; deterministic, no LAPACK.
+ * SMG_ERR_INVALID when B is not positive definite.  Needs no GPU. */
+int smg_debug_dense_geneig_host(int n, const double *A, const double *B, double *evals, double *V);
 
 /* ---- profc.h mirror: named scopes accumulated with hipEvents (src/profc.h:9-13; mg_VCycle.cpp:121) ------------- */
 int smg_prof_enable(smg_hierarchy *h, int on);     /* forces eager launches while on */

@@ -65,6 +65,8 @@ def load():
         "smg_assemble": (i, [vp, vp, i, d, d, vp, vp, vp, vp]),
         "smg_solve": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), vp, i, dp, ip, ip]),
         "smg_solve_pcg": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), vp, i, dp, ip, ip]),
+        "smg_eigs": (i, [vp, vp, i, i, vp, i, i, C.POINTER(SolveOptsC), C.c_ulonglong, dp, vp, i, dp, ip, ip]),
+        "smg_debug_dense_geneig_host": (i, [i, dp, dp, dp, dp]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

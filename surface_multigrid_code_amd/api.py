@@ -182,6 +182,44 @@ class Hierarchy:
         _chk(rc, "smg_solve_pcg")
         return bool(conv.value), z, r_his[: n_his.value].copy()
 
+    def eigs(self, mass, nev, block=0, X0=None, opts=None, seed=0):
+        """The nev smallest eigenpairs of A_uu x = lambda M_uu x, M = diag(mass) (include/smg.h: smg_eigs): LOBPCG preconditioned by one
+        V-cycle.  mass: n entries in the caller's numbering; X0: n x block start or None (a hash of seed) -- with X0 and block = 0 the block
+        is X0's column count (a warm start from a returned X iterates its nev columns); opts: tol (relative residual), max_iter (iterations)
+        and the cycle's settings.  Returns (evals, X, res_his, n_converged): X is n x nev, M-orthonormal, zero on the known rows; res_his is
+        (rows, nev)."""
+        opts = opts or SolveOpts(tol=1e-8, max_iter=200)
+        mass = np.ascontiguousarray(mass, dtype=np.float64).ravel()
+        n = mass.shape[0]
+        x0_p, ld_x0 = None, 0
+        if X0 is not None:
+            X0 = _colmajor(X0)
+            if block == 0:
+                block = X0.shape[1]
+            if X0.shape != (n, block):       # smg_eigs reads n x block doubles from X0
+                raise ValueError("X0 must be %d x %d (n x block), got %s" % (n, block, X0.shape))
+            x0_p, ld_x0 = X0.ctypes.data, X0.shape[0]
+        evals = np.zeros(nev)
+        X = np.zeros((n, nev), order="F")
+        res = np.zeros((opts.c.max_iter + 1) * nev)
+        n_iter, n_conv = C.c_int(0), C.c_int(0)
+        _chk(self.L.smg_eigs(self.h, mass.ctypes.data, nev, block, x0_p, ld_x0, SMG_HOST, C.byref(opts.c), seed, _dp(evals), X.ctypes.data, n,
+                             _dp(res), C.byref(n_iter), C.byref(n_conv)), "smg_eigs")
+        return evals, X, res[: n_iter.value * nev].reshape(n_iter.value, nev), n_conv.value
+
+    def eigs_device(self, mass_ptr, X_ptr, n, nev, block=0, X0_ptr=None, opts=None, seed=0):
+        """eigs on device memory: mass (n doubles), X0 (n x block or None) and X (n x nev) are column-major blocks resident in HBM
+        (leading dimension n).  With X0, block must be given: smg_eigs reads n x block doubles from it.  Returns (evals, res_his, n_converged)."""
+        if X0_ptr and block == 0:
+            raise ValueError("eigs_device: a start block X0 needs an explicit block (its column count)")
+        opts = opts or SolveOpts(tol=1e-8, max_iter=200)
+        evals = np.zeros(nev)
+        res = np.zeros((opts.c.max_iter + 1) * nev)
+        n_iter, n_conv = C.c_int(0), C.c_int(0)
+        _chk(self.L.smg_eigs(self.h, mass_ptr, nev, block, X0_ptr, n if X0_ptr else 0, SMG_DEVICE, C.byref(opts.c), seed, _dp(evals), X_ptr, n,
+                             _dp(res), C.byref(n_iter), C.byref(n_conv)), "smg_eigs")
+        return evals, res[: n_iter.value * nev].reshape(n_iter.value, nev), n_conv.value
+
     def solve_device(self, rhs_ptr, z0_ptr, z_ptr, n, k=1, known_val_ptr=None, ld_kv=0, opts=None):
         """min_quad_with_fixed_mg_solve on column-major blocks already resident in HBM (device pointers, leading dimension n):
         the drop-in call, polling the device-side convergence flag every opts.check_every iterations."""

@@ -74,6 +74,8 @@ extern "C" int smg_debug_device_bytes(const smg_hierarchy* h, char* buf, int cap
     line("reprecompute_bookkeeping", B(h->d_lhs_src) + B(h->d_auk_src) + B(h->d_diag_idx) + B(h->d_dense_pos) + B(h->d_Afull));
     line("early_upload", B(h->early0.ptr) + B(h->early0.col) + B(h->early0.val));
     line("krylov", B(h->kry_x) + B(h->kry_r) + B(h->kry_p) + B(h->kry_q) + B(h->kry_b) + B(h->kry_part) + B(h->kry_s) + B(h->kry_restart));
+    line("eigs", B(h->eig_x[0]) + B(h->eig_x[1]) + B(h->eig_ax[0]) + B(h->eig_ax[1]) + B(h->eig_p[0]) + B(h->eig_p[1]) + B(h->eig_ap[0]) + B(h->eig_ap[1]) +
+                 B(h->eig_w) + B(h->eig_aw) + B(h->eig_mass) + B(h->eig_part) + B(h->eig_small) + B(h->eig_stage));
     line("solve_state", B(h->d_ctrl) + B(h->d_rhis) + B(h->d_partials) + B(h->d_lam) + B(h->d_stage_rhs) + B(h->d_stage_z) + B(h->d_stage_kv) + B(h->d_tmp_cm) + B(h->d_zsave));
     out += "total " + std::to_string(tot) + "\n";
     std::snprintf(buf, (size_t)cap, "%s", out.c_str());

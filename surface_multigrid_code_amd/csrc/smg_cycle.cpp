@@ -1081,6 +1081,16 @@ static int internal_cols(const smg_hierarchy* h, int k)
 // host blocks of up to 1 MiB travel through page-locked staging (pin_vec): packed by the host, one DMA each way
 static bool small_host_block(int n, int k) { return (size_t)n * k * 8 <= ((size_t)1 << 20); }
 
+int smg::check_cycle_opts(const smg_solve_opts& o)
+{
+    if (o.precision != 0 && o.precision != 1) return fail(SMG_ERR_INVALID, "precision must be 0 (fp64) or 1 (mixed)");
+    if (o.pre < 0 || o.post < 0) return fail(SMG_ERR_INVALID, "pre / post must be >= 0");
+    if (o.smoother < SMG_SMOOTH_GS || o.smoother > SMG_SMOOTH_HYBRID_CHEBYSHEV) return fail(SMG_ERR_INVALID, "smoother must be one of SMG_SMOOTH_*");
+    if (o.omega > 2.0 || o.omega != o.omega) return fail(SMG_ERR_INVALID, "omega must be in (0, 2]");
+    if (o.cheby_fraction >= 1.0 || o.cheby_fraction != o.cheby_fraction) return fail(SMG_ERR_INVALID, "cheby_fraction must be in (0, 1)");
+    return SMG_OK;
+}
+
 static int smg_solve_begin_impl(smg_hierarchy* h, const double* RHS, int ld_rhs, const double* known_val, int ld_kv,
                                const double* z0, int ld_z0, int k, int memspace, const smg_solve_opts* opts)
 {
@@ -1094,11 +1104,7 @@ static int smg_solve_begin_impl(smg_hierarchy* h, const double* RHS, int ld_rhs,
     if (o.max_iter < 0) return fail(SMG_ERR_INVALID, "max_iter must be >= 0");
     if (h->has_known && (!known_val || ld_kv < (int)h->known.size())) return fail(SMG_ERR_INVALID, "known_val missing or ld_kv too small");
     // everything is validated before anything of the handle changes: a refused call leaves the handle as it was
-    if (o.precision != 0 && o.precision != 1) return fail(SMG_ERR_INVALID, "precision must be 0 (fp64) or 1 (mixed)");
-    if (o.pre < 0 || o.post < 0) return fail(SMG_ERR_INVALID, "pre / post must be >= 0");
-    if (o.smoother < SMG_SMOOTH_GS || o.smoother > SMG_SMOOTH_HYBRID_CHEBYSHEV) return fail(SMG_ERR_INVALID, "smoother must be one of SMG_SMOOTH_*");
-    if (o.omega > 2.0 || o.omega != o.omega) return fail(SMG_ERR_INVALID, "omega must be in (0, 2]");
-    if (o.cheby_fraction >= 1.0 || o.cheby_fraction != o.cheby_fraction) return fail(SMG_ERR_INVALID, "cheby_fraction must be in (0, 1)");
+    if ((rc = smg::check_cycle_opts(o))) return rc;
     if (h->in_solve) return fail(SMG_ERR_INVALID, "smg_solve_begin: a split-phase solve is already in progress (smg_solve_end)");
     if (h->union_m > 0 && o.precision != 0) return fail(SMG_ERR_INVALID, "a union handle solves in fp64 (no mixed-precision cycle)");
     h->tol = o.tol; h->max_iter = o.max_iter; h->pre = o.pre; h->post = o.post; h->verbosity = o.verbosity;
@@ -1527,6 +1533,35 @@ extern "C" int smg_solve_pcg(smg_hierarchy* h, const double* RHS, int ld_rhs, co
         if (rc) { h->in_solve = false; h->coarse_cols = 0; return rc; }
         return smg_solve_end(h, z, ld_z, memspace, r_his, n_his, converged);
     });
+}
+
+// ---- what the LOBPCG eigensolver (smg_eig.cpp) takes from the solve: the V-cycle and A on k unpadded internal columns ------------------
+int smg::eig_prepare(smg_hierarchy* h, const smg_solve_opts& o, int k)
+{
+    h->tol = o.tol; h->max_iter = o.max_iter; h->pre = o.pre; h->post = o.post; h->verbosity = o.verbosity;
+    h->check_every = std::max(0, o.check_every); h->use_graph = o.use_graph;
+    h->precision = o.precision;
+    int rc;
+    if ((rc = smg_hierarchy_set_smoother(h, o.smoother, o.omega, o.jacobi_max_rows))) return rc;
+    if ((rc = smg_hierarchy_set_chebyshev(h, o.cheby_fraction))) return rc;
+    if ((rc = ensure_work(h, k))) return rc;
+    if (h->precision == 1 && (rc = ensure_fp32(h, k))) return rc;
+    h->k = k; h->k_user = k; h->coarse_cols = 0;
+    h->head_fuse = false;
+    return SMG_OK;
+}
+
+int smg::eig_vcycle(smg_hierarchy* h, int k, const Ctrl* ctrl)
+{
+    ProfGuard pg(h, "MG: total VCycle");
+    if (h->precision == 1) return enqueue_vcycle32(h, 0, k, h->pre, h->post, ctrl);
+    return enqueue_vcycle(h, 0, k, h->pre, h->post, ctrl, FIRST_NONE);
+}
+
+int smg::eig_apply_A(smg_hierarchy* h, const double* x, double* y, int k, const Ctrl* ctrl)
+{
+    HIPCHK(Prec<double>::opA(h, h->lv[0], false, SELL_AX, 0, -1, x, nullptr, y, k, ctrl));
+    return SMG_OK;
 }
 
 // ---- column-sharded solve (include/smg.h: smg_solve_sharded) ------------------------------------------------------------------------

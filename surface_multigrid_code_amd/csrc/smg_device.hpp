@@ -290,6 +290,31 @@ hipError_t launch_kry_widen(const float* e, double* z, size_t cnt, const Ctrl* c
 // restart flag = 1; reopen: also lower `done` and drop the last history entry (the host's check of a recurrence norm replaces it by the true one)
 hipError_t launch_kry_arm(const KryDev& K, Ctrl* ctrl, bool reopen, hipStream_t st);
 
+// ---- LOBPCG eigensolver (smg_eigs, host side smg_eig.cpp; kernels: smg_eig_device.hip) ------------------------------------------------
+// The basis S = [X W P] is up to three row-major n x m blocks (m <= 64 columns each), concatenated by columns: column i of S is column i % m
+// of block i / m.  Every kernel returns at once when ctrl->done is set, as the V-cycle's do.
+struct EigBlocks {
+    const double* p[3] = {nullptr, nullptr, nullptr};
+    int nb = 0;                  // blocks in use
+};
+constexpr int EIG_TILE = 64;            // Gram output tile (EIG_TILE x EIG_TILE entries per work-group)
+constexpr int EIG_MAX_GROUPS = 256;
+int eig_groups(int n);                  // row chunks of the reductions: a function of n alone (determinism)
+// the partial-sum room the Gram of an a x b product needs (doubles), for groups = eig_groups(n)
+size_t eig_gram_part_size(int a, int b, int groups);
+// G (row-major a x b, a = Sa.nb * m, b = Sb.nb * m) = Sa^T diag(w) Sb; w == nullptr: 1.  sym (Sa == Sb): only the tiles on and above the
+// diagonal are formed, the finalize mirrors them.  Fixed row chunks, one partial per chunk, summed in chunk order.
+hipError_t launch_eig_gram(const EigBlocks& Sa, const EigBlocks& Sb, int n, int m, const double* w, bool sym, double* part, int groups,
+                           double* G, const Ctrl* ctrl, hipStream_t st);
+// With C row-major q x 2m (q = S.nb * m; columns 0..m-1: Cx, m..2m-1: Cp):  X = S Cx, AX = AS Cx and, when P != nullptr, P = S' Cp,
+// AP = AS' Cp where S' leaves out block 0 (the X rows of Cp are not read).  Outputs must not alias the inputs.
+hipError_t launch_eig_combine(const EigBlocks& S, const EigBlocks& AS, int n, int m, const double* C, double* X, double* AX, double* P,
+                              double* AP, const Ctrl* ctrl, hipStream_t st);
+// R = AX - diag(mass) X diag(lam); res_c = sqrt(sum_i r_ic^2 / mass_i) / |lam_c|.  The preconditioner's input in the same pass:
+// b32 == nullptr: b0 = R, u0 = 0 (fp64 cycle); else b32 = (float) R, u32 = 0 (fp32 cycle).
+hipError_t launch_eig_residual(const double* X, const double* AX, const double* mass, const double* lam, int n, int m, double* b0, double* u0,
+                               float* b32, float* u32, double* part, int groups, double* res, const Ctrl* ctrl, hipStream_t st);
+
 // u[i,:] += sum_j Ainv[i,j] * b[j,:]   (mg_VCycle.cpp:199-200 with the factorisation pre-inverted)
 // sym_work (optional, (lda/64)^2 * 64 elements): with it, a single column (k = 1) is multiplied through the lower triangle of
 // tiles only (the inverse is symmetric): half the bytes, two launches, deterministic per-row summation in block order.

@@ -347,6 +347,13 @@ struct smg_hierarchy {
     smg::KryDev kry;
     hipGraphExec_t g_pcg = nullptr, g_pcg_n = nullptr;        // one / graph_iters() PCG iterations
     smg::GraphKey g_pcg_key;                                  // what they were captured with (the MG graphs keep g_key)
+    // ---- LOBPCG eigensolver (smg_eigs, smg_eig.cpp): allocated by the first call ----
+    smg::DevBuf<double> eig_x[2], eig_ax[2], eig_p[2], eig_ap[2];   // n_0 x m: iterate, A iterate, direction, A direction (current / next)
+    smg::DevBuf<double> eig_w, eig_aw;                               // the preconditioned residual (fp32 cycle; the fp64 one leaves it in L0.u), A W
+    smg::DevBuf<double> eig_mass;                                    // diag(M) in the internal numbering
+    smg::DevBuf<double> eig_part, eig_small;                         // partial sums; Grams, coefficients, Ritz values and residuals
+    smg::DevBuf<double> eig_stage;                                   // caller-numbered start / result blocks
+    smg::PinBuf<double> eig_pin;                                     // the host's side of eig_small
     // ---- profc mirror ----
     bool prof_on = false;
     std::vector<smg::ProfScope> scopes;

@@ -90,6 +90,12 @@ void drop_graphs(smg_hierarchy* h);             // the cached hipGraphs no longe
 // the sweep plans a small level would want for a default solve (one column, the handle's pre / post sweeps), built ahead of the first solve (smg_cycle.cpp)
 int prepare_level_plans(smg_hierarchy* h, int lv);
 int check_ready(const smg_hierarchy* h, const char* who);
+int check_cycle_opts(const smg_solve_opts& o);  // the option checks of smg_solve_begin (change nothing)
+// what smg_eigs (smg_eig.cpp) borrows from the solve (smg_cycle.cpp): latch the cycle's options and make the level vectors ready for k
+// unpadded internal columns; one V-cycle L0.u = V(L0.b, 0) (precision 1: L0.u32 = V32(L0.b32, 0)) with the caller-prepared input; y = A_uu x
+int eig_prepare(smg_hierarchy* h, const smg_solve_opts& o, int k);
+int eig_vcycle(smg_hierarchy* h, int k, const Ctrl* ctrl);
+int eig_apply_A(smg_hierarchy* h, const double* x, double* y, int k, const Ctrl* ctrl);
 
 // ---- profc mirror (PROFC_NODE, reference src/profc.h:9-13), timed on the GPU timeline -----------------------------------------
 int prof_scope_id(smg_hierarchy* h, const char* name);
