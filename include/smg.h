@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 503
+#define SMG_VERSION 504
 
 enum {
     SMG_OK = 0,
@@ -516,6 +516,39 @@ int smg_debug_check_sparse_cholesky(int n, const int *rowptr, const int *col, co
  * Cholesky of B, reduction to standard form, Householder tridiagonalisation and implicit QR steps; deterministic, no LAPACK.
  * SMG_ERR_INVALID when B is not positive definite.  Needs no GPU. */
 int smg_debug_dense_geneig_host(int n, const double *A, const double *B, double *evals, double *V);
+
+/* ---- test hooks of the LOBPCG and PCG block kernels (csrc/smg_eig_device.hip, csrc/smg_krylov_device.hip) ----------------------------
+ * Handle-free: each hook copies its host arrays to scratch device buffers, calls the kernels' launcher once on a private stream with a
+ * control block whose `done` flag the caller picks (done = 1: every kernel must return at once and leave every output as it was), and copies
+ * the outputs back.  Output arrays are in/out: their host contents are uploaded first.  Every device buffer lies between two guard regions of
+ * sentinel bytes; *guard_bad (NULL ok) is the number of buffers whose guards changed, 0 when nothing was written out of place.  Blocks are
+ * row-major n x m (column c of row i at i * m + c).  SMG_ERR_INVALID for a bad shape (n < 1, m outside 1..64, nb outside 1..3) or a missing
+ * array; SMG_ERR_NO_DEVICE without a GPU. */
+/* G (row-major a x b, a = nb_a m, b = nb_b m) = Sa^T diag(w) Sb, w == NULL: 1.  Sa, Sb: nb row-major n x m blocks back to back.
+ * sym: Sb is Sa (Sb ignored, nb_b must equal nb_a), only the tiles on and above the diagonal are formed and mirrored.  *groups: the row chunks. */
+int smg_debug_eig_gram(int n, int m, int nb_a, const double *Sa, int nb_b, const double *Sb, const double *w, int sym, int done, double *G,
+                       int *groups, int *guard_bad);
+/* With C row-major q x 2m (q = nb m):  X = S Cx, AX = AS Cx;  make_p: also P = S' Cp, AP = AS' Cp with S' the blocks 1.. of S (the rows of
+ * block 0 of Cp are not read).  make_p = 0: P, AP are not handed to the launcher and may be NULL. */
+int smg_debug_eig_combine(int n, int m, int nb, const double *S, const double *AS, const double *C, int make_p, int done, double *X, double *AX,
+                          double *P, double *AP, int *guard_bad);
+/* R = AX - diag(mass) X diag(lam); res_c = sqrt(sum_i r_ic^2 / mass_i) / |lam_c|.  f32 = 0: b0 = R, u0 = 0 (b32, u32 unused, NULL ok);
+ * f32 = 1: b32 = (float) R, u32 = 0, and b0, u0 are handed to the launcher too and must come back unchanged.  *groups: the row chunks. */
+int smg_debug_eig_residual(int n, int m, const double *X, const double *AX, const double *mass, const double *lam, int f32, int done, double *b0,
+                           double *u0, float *b32, float *u32, double *res, int *groups, int *guard_bad);
+/* One PCG launcher on n x k blocks.  v0..v3 (n x k each) are the op's operands in order, all copied back (inputs must come back unchanged):
+ *   SMG_KRY_DOTS_ZR_ZQ  z, r, q      rz = z.r; beta = -alpha (z.q) / rz_prev (0 after a restart or when rz_prev == 0); clears *restart
+ *   SMG_KRY_DIRECTION   z, p         p = z + beta p (p = z where beta == 0)
+ *   SMG_KRY_DOTS_PQ     p, q         alpha = rz / (p.q) (0 when p.q == 0), rz_prev = rz
+ *   SMG_KRY_STEP_DECIDE x, r, p, q   x += alpha p, r -= alpha q, |r|_F^2 -> the history and the break test (r < tol ends, non-finite: status -1)
+ *   SMG_KRY_PRECOND_IN  r, b0, u0    b0 = r, u0 = 0
+ *   SMG_KRY_WIDEN       z            z = (double) e, e: n x k floats
+ * s (KS slots x k: rz, rz_prev, alpha, beta; ops up to STEP_DECIDE) and *restart (NULL: 0) are in/out.  The control block starts with
+ * sumsq = -1, a one-entry history holding -1, n_his = status = 0; out: ctrl_d = {sumsq, r_his[0]}, ctrl_i = {n_his, done, status} (NULL ok).
+ * *groups: the row chunks of the reductions. */
+enum { SMG_KRY_DOTS_ZR_ZQ = 0, SMG_KRY_DIRECTION = 1, SMG_KRY_DOTS_PQ = 2, SMG_KRY_STEP_DECIDE = 3, SMG_KRY_PRECOND_IN = 4, SMG_KRY_WIDEN = 5 };
+int smg_debug_krylov(int op, int n, int k, double *v0, double *v1, double *v2, double *v3, float *e, double *s, int *restart, double tol, int done,
+                     double *ctrl_d, int *ctrl_i, int *groups, int *guard_bad);
 
 /* ---- profc.h mirror: named scopes accumulated with hipEvents (src/profc.h:9-13; mg_VCycle.cpp:121) ------------- */
 int smg_prof_enable(smg_hierarchy *h, int on);     /* forces eager launches while on */

@@ -29,7 +29,7 @@ def load():
         raise ImportError("libsmg.so not built: run `python -m surface_multigrid_code_amd.build` "
                           "(expected at %s); there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    ip, dp, vp, lp = C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_long)
+    ip, dp, vp, lp, fp = C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_float)
     i, d, f = C.c_int, C.c_double, C.c_float
     sig = {
         "smg_version": (i, []),
@@ -67,6 +67,10 @@ def load():
         "smg_solve_pcg": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), vp, i, dp, ip, ip]),
         "smg_eigs": (i, [vp, vp, i, i, vp, i, i, C.POINTER(SolveOptsC), C.c_ulonglong, dp, vp, i, dp, ip, ip]),
         "smg_debug_dense_geneig_host": (i, [i, dp, dp, dp, dp]),
+        "smg_debug_eig_gram": (i, [i, i, i, dp, i, dp, dp, i, i, dp, ip, ip]),
+        "smg_debug_eig_combine": (i, [i, i, i, dp, dp, dp, i, i, dp, dp, dp, dp, ip]),
+        "smg_debug_eig_residual": (i, [i, i, dp, dp, dp, dp, i, i, dp, dp, fp, fp, dp, ip, ip]),
+        "smg_debug_krylov": (i, [i, i, i, dp, dp, dp, dp, fp, dp, ip, d, i, dp, ip, ip, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

@@ -1,0 +1,263 @@
+// smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
+// smg_debug_eig_residual, smg_debug_krylov).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
+// changed is reported, so a stray write past either end of an output is seen by the caller.
+#include <hip/hip_runtime_api.h>
+
+#include <cstring>
+#include <vector>
+
+#include "smg_device.hpp"
+#include "smg_internal.hpp"
+
+using namespace smg;
+
+namespace {
+
+constexpr size_t GUARD = 4096;            // bytes of sentinel in front of and behind every buffer
+constexpr unsigned char SENTINEL = 0xA5;
+
+// the scratch buffers and the stream of one hook call; freed on scope exit
+class Scratch {
+public:
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch()
+    {
+        for (Buf& b : bufs_) (void)hipFree(b.base);
+        if (st_) (void)hipStreamDestroy(st_);
+    }
+    hipError_t init() { return hipStreamCreateWithFlags(&st_, hipStreamNonBlocking); }
+    hipStream_t stream() const { return st_; }
+
+    // a device copy of src[0 .. bytes) (src == nullptr: sentinel bytes) between two guards; back != nullptr: copied there by finish()
+    template <typename T>
+    hipError_t add(const void* src, void* back, size_t bytes, T** dev)
+    {
+        Buf b;
+        b.bytes = bytes;
+        b.back = back;
+        hipError_t e = hipMalloc((void**)&b.base, bytes + 2 * GUARD);
+        if (e != hipSuccess) return e;
+        bufs_.push_back(b);
+        if ((e = hipMemsetAsync(b.base, SENTINEL, bytes + 2 * GUARD, st_)) != hipSuccess) return e;
+        if (src && bytes && (e = hipMemcpyAsync(b.base + GUARD, src, bytes, hipMemcpyHostToDevice, st_)) != hipSuccess) return e;
+        *dev = reinterpret_cast<T*>(b.base + GUARD);
+        return hipSuccess;
+    }
+
+    // after the launches: the outputs back to the host; *bad = the buffers whose guards changed
+    hipError_t finish(int* bad)
+    {
+        hipError_t e = hipStreamSynchronize(st_);
+        if (e != hipSuccess) return e;
+        int nbad = 0;
+        std::vector<unsigned char> h;
+        for (const Buf& b : bufs_) {
+            h.resize(b.bytes + 2 * GUARD);
+            if ((e = hipMemcpyAsync(h.data(), b.base, h.size(), hipMemcpyDeviceToHost, st_)) != hipSuccess) return e;
+            if ((e = hipStreamSynchronize(st_)) != hipSuccess) return e;
+            bool ok = true;
+            for (size_t i = 0; i < GUARD && ok; i++) ok = h[i] == SENTINEL && h[GUARD + b.bytes + i] == SENTINEL;
+            nbad += ok ? 0 : 1;
+            if (b.back && b.bytes) std::memcpy(b.back, h.data() + GUARD, b.bytes);
+        }
+        *bad = nbad;
+        return hipSuccess;
+    }
+
+private:
+    struct Buf {
+        unsigned char* base = nullptr;
+        size_t bytes = 0;
+        void* back = nullptr;
+    };
+    std::vector<Buf> bufs_;
+    hipStream_t st_ = nullptr;
+};
+
+int need_device(const char* who)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(SMG_ERR_NO_DEVICE, "%s: no HIP device: libsmg has no CPU fallback", who);
+    return SMG_OK;
+}
+
+Ctrl make_ctrl(int done, double tol, double* r_his)
+{
+    Ctrl c;
+    std::memset(&c, 0, sizeof c);
+    c.done = done ? 1 : 0;
+    c.sumsq = -1.0;
+    c.tol = tol;
+    c.r_his = r_his;
+    c.his_cap = r_his ? 1 : 0;
+    c.r_last = c.r_prev = -1.0;
+    return c;
+}
+
+bool bad_block_shape(int n, int m, int nb) { return n < 1 || m < 1 || m > 64 || nb < 1 || nb > 3; }
+
+}  // namespace
+
+extern "C" int smg_debug_eig_gram(int n, int m, int nb_a, const double* Sa, int nb_b, const double* Sb, const double* w, int sym, int done,
+                                  double* G, int* groups, int* guard_bad)
+{
+    return guarded("smg_debug_eig_gram", [&]() -> int {
+        if (bad_block_shape(n, m, nb_a) || bad_block_shape(n, m, nb_b) || !Sa || !G || (sym ? nb_b != nb_a : !Sb))
+            return fail(SMG_ERR_INVALID, "smg_debug_eig_gram: bad arguments");
+        if (int rc = need_device("smg_debug_eig_gram")) return rc;
+        Scratch X;
+        HIPCHK(X.init());
+        const size_t blk = (size_t)n * m;
+        const int a = nb_a * m, b = nb_b * m, g = eig_groups(n);
+        double *dSa = nullptr, *dSb = nullptr, *dw = nullptr, *dpart = nullptr, *dG = nullptr;
+        Ctrl* dctrl = nullptr;
+        HIPCHK(X.add(Sa, nullptr, nb_a * blk * sizeof(double), &dSa));
+        if (sym) dSb = dSa;
+        else HIPCHK(X.add(Sb, nullptr, nb_b * blk * sizeof(double), &dSb));
+        if (w) HIPCHK(X.add(w, nullptr, (size_t)n * sizeof(double), &dw));
+        HIPCHK(X.add(nullptr, nullptr, eig_gram_part_size(a, b, g) * sizeof(double), &dpart));
+        HIPCHK(X.add(G, G, (size_t)a * b * sizeof(double), &dG));
+        const Ctrl c = make_ctrl(done, 0.0, nullptr);
+        HIPCHK(X.add(&c, nullptr, sizeof c, &dctrl));
+        EigBlocks A, B;
+        A.nb = nb_a;
+        B.nb = nb_b;
+        for (int i = 0; i < nb_a; i++) A.p[i] = dSa + i * blk;
+        for (int i = 0; i < nb_b; i++) B.p[i] = dSb + i * blk;
+        HIPCHK(launch_eig_gram(A, B, n, m, dw, sym != 0, dpart, g, dG, dctrl, X.stream()));
+        int bad = 0;
+        HIPCHK(X.finish(&bad));
+        if (groups) *groups = g;
+        if (guard_bad) *guard_bad = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_eig_combine(int n, int m, int nb, const double* S, const double* AS, const double* C, int make_p, int done, double* X,
+                                     double* AX, double* P, double* AP, int* guard_bad)
+{
+    return guarded("smg_debug_eig_combine", [&]() -> int {
+        if (bad_block_shape(n, m, nb) || !S || !AS || !C || !X || !AX || (make_p && (!P || !AP)))
+            return fail(SMG_ERR_INVALID, "smg_debug_eig_combine: bad arguments");
+        if (int rc = need_device("smg_debug_eig_combine")) return rc;
+        Scratch Z;
+        HIPCHK(Z.init());
+        const size_t blk = (size_t)n * m, bytes = blk * sizeof(double);
+        const int q = nb * m;
+        double *dS = nullptr, *dAS = nullptr, *dC = nullptr, *dX = nullptr, *dAX = nullptr, *dP = nullptr, *dAP = nullptr;
+        Ctrl* dctrl = nullptr;
+        HIPCHK(Z.add(S, nullptr, nb * bytes, &dS));
+        HIPCHK(Z.add(AS, nullptr, nb * bytes, &dAS));
+        HIPCHK(Z.add(C, nullptr, (size_t)q * 2 * m * sizeof(double), &dC));
+        HIPCHK(Z.add(X, X, bytes, &dX));
+        HIPCHK(Z.add(AX, AX, bytes, &dAX));
+        if (make_p) {
+            HIPCHK(Z.add(P, P, bytes, &dP));
+            HIPCHK(Z.add(AP, AP, bytes, &dAP));
+        }
+        const Ctrl c = make_ctrl(done, 0.0, nullptr);
+        HIPCHK(Z.add(&c, nullptr, sizeof c, &dctrl));
+        EigBlocks Sb, ASb;
+        Sb.nb = ASb.nb = nb;
+        for (int i = 0; i < nb; i++) { Sb.p[i] = dS + i * blk; ASb.p[i] = dAS + i * blk; }
+        HIPCHK(launch_eig_combine(Sb, ASb, n, m, dC, dX, dAX, dP, dAP, dctrl, Z.stream()));
+        int bad = 0;
+        HIPCHK(Z.finish(&bad));
+        if (guard_bad) *guard_bad = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_eig_residual(int n, int m, const double* X, const double* AX, const double* mass, const double* lam, int f32, int done,
+                                      double* b0, double* u0, float* b32, float* u32, double* res, int* groups, int* guard_bad)
+{
+    return guarded("smg_debug_eig_residual", [&]() -> int {
+        if (bad_block_shape(n, m, 1) || !X || !AX || !mass || !lam || !b0 || !u0 || !res || (f32 && (!b32 || !u32)))
+            return fail(SMG_ERR_INVALID, "smg_debug_eig_residual: bad arguments");
+        if (int rc = need_device("smg_debug_eig_residual")) return rc;
+        Scratch Z;
+        HIPCHK(Z.init());
+        const size_t cnt = (size_t)n * m;
+        const int g = eig_groups(n);
+        double *dX = nullptr, *dAX = nullptr, *dmass = nullptr, *dlam = nullptr, *db0 = nullptr, *du0 = nullptr, *dpart = nullptr, *dres = nullptr;
+        float *db32 = nullptr, *du32 = nullptr;
+        Ctrl* dctrl = nullptr;
+        HIPCHK(Z.add(X, nullptr, cnt * sizeof(double), &dX));
+        HIPCHK(Z.add(AX, nullptr, cnt * sizeof(double), &dAX));
+        HIPCHK(Z.add(mass, nullptr, (size_t)n * sizeof(double), &dmass));
+        HIPCHK(Z.add(lam, nullptr, (size_t)m * sizeof(double), &dlam));
+        // f32: the fp64 input buffers are handed to the launcher as well; it must leave them alone
+        HIPCHK(Z.add(b0, b0, cnt * sizeof(double), &db0));
+        HIPCHK(Z.add(u0, u0, cnt * sizeof(double), &du0));
+        if (f32) {
+            HIPCHK(Z.add(b32, b32, cnt * sizeof(float), &db32));
+            HIPCHK(Z.add(u32, u32, cnt * sizeof(float), &du32));
+        }
+        HIPCHK(Z.add(nullptr, nullptr, (size_t)g * m * sizeof(double), &dpart));
+        HIPCHK(Z.add(res, res, (size_t)m * sizeof(double), &dres));
+        const Ctrl c = make_ctrl(done, 0.0, nullptr);
+        HIPCHK(Z.add(&c, nullptr, sizeof c, &dctrl));
+        HIPCHK(launch_eig_residual(dX, dAX, dmass, dlam, n, m, db0, du0, db32, du32, dpart, g, dres, dctrl, Z.stream()));
+        int bad = 0;
+        HIPCHK(Z.finish(&bad));
+        if (groups) *groups = g;
+        if (guard_bad) *guard_bad = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_krylov(int op, int n, int k, double* v0, double* v1, double* v2, double* v3, float* e, double* s, int* restart, double tol,
+                                int done, double* ctrl_d, int* ctrl_i, int* groups, int* guard_bad)
+{
+    return guarded("smg_debug_krylov", [&]() -> int {
+        // the n x k operands each op reads or writes, in the order v0, v1, ...
+        static const int n_vec[] = {3, 2, 2, 4, 3, 1};
+        if (op < SMG_KRY_DOTS_ZR_ZQ || op > SMG_KRY_WIDEN || n < 1 || k < 1 || (long)n * k > (1L << 30))
+            return fail(SMG_ERR_INVALID, "smg_debug_krylov: bad arguments");
+        double* v[4] = {v0, v1, v2, v3};
+        for (int i = 0; i < n_vec[op]; i++)
+            if (!v[i]) return fail(SMG_ERR_INVALID, "smg_debug_krylov: operand v%d missing", i);
+        if ((op <= SMG_KRY_STEP_DECIDE && !s) || (op == SMG_KRY_WIDEN && !e)) return fail(SMG_ERR_INVALID, "smg_debug_krylov: bad arguments");
+        if (int rc = need_device("smg_debug_krylov")) return rc;
+        Scratch Z;
+        HIPCHK(Z.init());
+        const size_t cnt = (size_t)n * k;
+        double* dv[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int i = 0; i < n_vec[op]; i++) HIPCHK(Z.add(v[i], v[i], cnt * sizeof(double), &dv[i]));
+        float* de = nullptr;
+        if (op == SMG_KRY_WIDEN) HIPCHK(Z.add(e, e, cnt * sizeof(float), &de));
+        KryDev K;
+        K.n = n;
+        K.k = k;
+        K.groups = kry_groups(n, k);
+        const int rs0 = 0;
+        HIPCHK(Z.add(nullptr, nullptr, (size_t)2 * K.groups * k * sizeof(double), &K.part));
+        if (s) HIPCHK(Z.add(s, s, (size_t)KS_SLOTS * k * sizeof(double), &K.s));
+        HIPCHK(Z.add(restart ? restart : &rs0, restart, sizeof(int), &K.restart));
+        const double his0 = -1.0;
+        double* dhis = nullptr;
+        Ctrl* dctrl = nullptr;
+        HIPCHK(Z.add(&his0, ctrl_d ? ctrl_d + 1 : nullptr, sizeof(double), &dhis));
+        Ctrl c = make_ctrl(done, tol, dhis);
+        HIPCHK(Z.add(&c, &c, sizeof c, &dctrl));
+        hipStream_t st = Z.stream();
+        switch (op) {
+            case SMG_KRY_DOTS_ZR_ZQ: HIPCHK(launch_kry_dots_zr_zq(K, dv[0], dv[1], dv[2], dctrl, st)); break;
+            case SMG_KRY_DIRECTION: HIPCHK(launch_kry_direction(K, dv[0], dv[1], dctrl, st)); break;
+            case SMG_KRY_DOTS_PQ: HIPCHK(launch_kry_dots_pq(K, dv[0], dv[1], dctrl, st)); break;
+            case SMG_KRY_STEP_DECIDE: HIPCHK(launch_kry_step_decide(K, dv[0], dv[1], dv[2], dv[3], dctrl, st)); break;
+            case SMG_KRY_PRECOND_IN: HIPCHK(launch_kry_precond_in(dv[0], dv[1], dv[2], cnt, dctrl, st)); break;
+            default: HIPCHK(launch_kry_widen(de, dv[0], cnt, dctrl, st)); break;
+        }
+        int bad = 0;
+        HIPCHK(Z.finish(&bad));
+        if (ctrl_d) ctrl_d[0] = c.sumsq;
+        if (ctrl_i) { ctrl_i[0] = c.n_his; ctrl_i[1] = c.done; ctrl_i[2] = c.status; }
+        if (groups) *groups = K.groups;
+        if (guard_bad) *guard_bad = bad;
+        return SMG_OK;
+    });
+}

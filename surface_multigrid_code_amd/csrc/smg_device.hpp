@@ -303,7 +303,7 @@ int eig_groups(int n);                  // row chunks of the reductions: a funct
 // the partial-sum room the Gram of an a x b product needs (doubles), for groups = eig_groups(n)
 size_t eig_gram_part_size(int a, int b, int groups);
 // G (row-major a x b, a = Sa.nb * m, b = Sb.nb * m) = Sa^T diag(w) Sb; w == nullptr: 1.  sym (Sa == Sb): only the tiles on and above the
-// diagonal are formed, the finalize mirrors them.  Fixed row chunks, one partial per chunk, summed in chunk order.
+// diagonal are formed, the finalize mirrors them (G exactly symmetric).  Fixed row chunks, one partial per chunk, summed in chunk order.
 hipError_t launch_eig_gram(const EigBlocks& Sa, const EigBlocks& Sb, int n, int m, const double* w, bool sym, double* part, int groups,
                            double* G, const Ctrl* ctrl, hipStream_t st);
 // With C row-major q x 2m (q = S.nb * m; columns 0..m-1: Cx, m..2m-1: Cp):  X = S Cx, AX = AS Cx and, when P != nullptr, P = S' Cp,

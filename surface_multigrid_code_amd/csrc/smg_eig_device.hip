@@ -86,7 +86,8 @@ __global__ __launch_bounds__(EIG_THREADS) void k_eig_gram(EigBlocks Sa, EigBlock
         for (int q = 0; q < 4; q++) out[(pi + 16 * p) * EIG_TILE + pj + 16 * q] = acc[p][q];
 }
 
-// one thread per entry of a tile: the chunks in order; sym: the mirror entry too
+// one thread per entry of a tile: the chunks in order; sym: the mirror entry too.  A diagonal tile of the sym form keeps its lower triangle and
+// mirrors it (its two triangles differ in rounding: fl(w s_i) s_j against fl(w s_j) s_i), so G comes out exactly symmetric.
 __global__ __launch_bounds__(EIG_THREADS) void k_eig_gram_finalize(const double* __restrict__ part, int groups, int a, int b, int ta, int tb, int sym,
                                                                    double* __restrict__ G, const int* done)
 {
@@ -95,12 +96,13 @@ __global__ __launch_bounds__(EIG_THREADS) void k_eig_gram_finalize(const double*
     const int t = (int)(e / EIG_TT), l = (int)(e % EIG_TT);
     int ti, tj;
     eig_tile(t, ta, tb, sym != 0, &ti, &tj);
-    const int i = ti * EIG_TILE + l / EIG_TILE, j = tj * EIG_TILE + l % EIG_TILE;
-    if (i >= a || j >= b) return;
+    const int li = l / EIG_TILE, lj = l % EIG_TILE;
+    const int i = ti * EIG_TILE + li, j = tj * EIG_TILE + lj;
+    if (i >= a || j >= b || (sym && ti == tj && li < lj)) return;
     double s = 0.0;
     for (int g = 0; g < groups; g++) s += part[((size_t)t * groups + g) * EIG_TT + l];
     G[(size_t)i * b + j] = s;
-    if (sym && ti != tj) G[(size_t)j * b + i] = s;
+    if (sym && i != j) G[(size_t)j * b + i] = s;
 }
 
 // X = S Cx, AX = AS Cx, and P = S' Cp, AP = AS' Cp (blocks 1.. only).  Work-group: rpb rows x jc output columns (jc = min(m, 16)); blockIdx.y

@@ -1,0 +1,131 @@
+"""numpy wrappers of the handle-free kernel test hooks (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine, smg_debug_eig_residual,
+smg_debug_krylov) and the rounding-error bounds the tests hold them to.
+
+Every wrapper asserts that the hook succeeded and that no guard region around a device buffer changed (no write out of place)."""
+import ctypes as C
+import math
+
+import numpy as np
+
+U = 2.0 ** -53                     # unit roundoff of fp64
+KRY_OPS = dict(zr_zq=0, direction=1, pq=2, step=3, precond_in=4, widen=5)
+KRY_NVEC = dict(zr_zq=3, direction=2, pq=2, step=4, precond_in=3, widen=1)
+KS_RZ, KS_RZ_PREV, KS_ALPHA, KS_BETA = range(4)
+EIG_MAX_GROUPS, KRY_MAX_GROUPS = 256, 512
+
+
+def gamma(N):
+    """gamma_N = N u / (1 - N u): the relative bound of any summation order of N terms in fp64 (Higham, Accuracy and Stability, 3.1)"""
+    return N * U / (1.0 - N * U)
+
+
+def sentinel(shape, dtype=np.float64):
+    """an array of 0x5B bytes: a value no kernel computes from the tests' data"""
+    a = np.empty(shape, dtype=dtype)
+    a.view(np.uint8)[...] = 0x5B
+    return a
+
+
+def _p(a, t=C.c_double):
+    if a is None:
+        return None
+    assert a.flags.c_contiguous
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+def _c(a, dtype=np.float64):
+    return None if a is None else np.ascontiguousarray(a, dtype=dtype)
+
+
+def eig_groups(n):
+    return max(1, min((n + 1023) // 1024, EIG_MAX_GROUPS))
+
+
+def kry_groups(n, k):
+    ct = min(k, 64)
+    R = 256 // ct
+    return max(1, min((n + R * 8 - 1) // (R * 8), KRY_MAX_GROUPS))
+
+
+def gram(L, Sa, Sb=None, w=None, sym=False, done=0, G=None):
+    """G = Sa^T diag(w) Sb for Sa, Sb of shape (nb, n, m); sym: Sb = Sa.  G: the array uploaded as the output (default zeros)."""
+    Sa = _c(Sa)
+    nb_a, n, m = Sa.shape
+    Sb = None if sym else _c(Sb)
+    nb_b = nb_a if sym else Sb.shape[0]
+    G = np.zeros((nb_a * m, nb_b * m)) if G is None else _c(G).copy()
+    w = _c(w)
+    groups, bad = C.c_int(-1), C.c_int(-1)
+    rc = L.smg_debug_eig_gram(n, m, nb_a, _p(Sa), nb_b, _p(Sb), _p(w), int(sym), done, _p(G), C.byref(groups), C.byref(bad))
+    assert rc == 0, L.smg_last_error()
+    assert bad.value == 0, "a guard region around a device buffer was overwritten"
+    assert groups.value == eig_groups(n)
+    return G
+
+
+def combine(L, S, AS, Cm, make_p=True, done=0, outs=None):
+    """X, AX, P, AP for S, AS of shape (nb, n, m) and C of shape (nb m, 2m); P, AP are None without make_p"""
+    S, AS, Cm = _c(S), _c(AS), _c(Cm)
+    nb, n, m = S.shape
+    outs = [np.zeros((n, m)) for _ in range(4)] if outs is None else [_c(o).copy() for o in outs]
+    X, AX, P, AP = outs
+    bad = C.c_int(-1)
+    rc = L.smg_debug_eig_combine(n, m, nb, _p(S), _p(AS), _p(Cm), int(make_p), done, _p(X), _p(AX), _p(P) if make_p else None,
+                                 _p(AP) if make_p else None, C.byref(bad))
+    assert rc == 0, L.smg_last_error()
+    assert bad.value == 0, "a guard region around a device buffer was overwritten"
+    return X, AX, P, AP
+
+
+def residual(L, X, AX, mass, lam, f32=False, done=0, outs=None):
+    """(b0, u0, b32, u32, res): outs = the arrays uploaded as the outputs (default: sentinels)"""
+    X, AX, mass, lam = _c(X), _c(AX), _c(mass), _c(lam)
+    n, m = X.shape
+    if outs is None:
+        outs = [sentinel((n, m)), sentinel((n, m)), sentinel((n, m), np.float32), sentinel((n, m), np.float32), sentinel(m)]
+    b0, u0, b32, u32, res = [o.copy() for o in outs]
+    groups, bad = C.c_int(-1), C.c_int(-1)
+    rc = L.smg_debug_eig_residual(n, m, _p(X), _p(AX), _p(mass), _p(lam), int(f32), done, _p(b0), _p(u0), _p(b32, C.c_float), _p(u32, C.c_float),
+                                  _p(res), C.byref(groups), C.byref(bad))
+    assert rc == 0, L.smg_last_error()
+    assert bad.value == 0, "a guard region around a device buffer was overwritten"
+    assert groups.value == eig_groups(n)
+    return b0, u0, b32, u32, res
+
+
+def krylov(L, op, vecs, s=None, restart=None, e=None, tol=0.0, done=0):
+    """one PCG launcher (e: the float input of widen): returns (vecs after, s after, restart after, ctrl),
+    ctrl = dict(sumsq, r0 = r_his[0], n_his, done, status)"""
+    vecs = [_c(v).copy() for v in vecs]
+    assert len(vecs) == KRY_NVEC[op]
+    n, k = vecs[0].shape
+    v = vecs + [None] * (4 - len(vecs))
+    s = None if s is None else _c(s).copy()
+    e = None if e is None else _c(e, np.float32).copy()
+    rs = None if restart is None else C.c_int(restart)
+    cd = (C.c_double * 2)(7.0, 7.0)
+    ci = (C.c_int * 3)(7, 7, 7)
+    groups, bad = C.c_int(-1), C.c_int(-1)
+    rc = L.smg_debug_krylov(KRY_OPS[op], n, k, _p(v[0]), _p(v[1]), _p(v[2]), _p(v[3]), _p(e, C.c_float), _p(s),
+                            None if rs is None else C.byref(rs), tol, done, cd, ci, C.byref(groups), C.byref(bad))
+    assert rc == 0, L.smg_last_error()
+    assert bad.value == 0, "a guard region around a device buffer was overwritten"
+    assert groups.value == kry_groups(n, k)
+    ctrl = dict(sumsq=cd[0], r0=cd[1], n_his=ci[0], done=ci[1], status=ci[2])
+    return vecs, s, (None if rs is None else rs.value), ctrl
+
+
+def exact_dot(a, b):
+    """sum_i a_i b_i correctly rounded: every product split into four exact fp64 products (Veltkamp), summed by math.fsum"""
+    return math.fsum(_exact_products(a, b))
+
+
+def _exact_products(a, b):
+    # Veltkamp split: x = hi + lo with 26-bit halves, so hi*hi, hi*lo, lo*lo are exact
+    def split(x):
+        c = (2.0 ** 27 + 1.0) * x
+        hi = c - (c - x)
+        return hi, x - hi
+    ah, al = split(np.asarray(a, dtype=np.float64))
+    bh, bl = split(np.asarray(b, dtype=np.float64))
+    return np.concatenate([(ah * bh).ravel(), (ah * bl).ravel(), (al * bh).ravel(), (al * bl).ravel()])

@@ -65,3 +65,49 @@ def test_compute_fails_loudly_without_gpu(smg_mod):
         mg.solve(p["RHS"], p["z0"])
     with pytest.raises(smg.SmgError):
         mg.A(0, p["z0"])
+
+
+def _kernel_hook_calls(L, n=4, m=2, nb=1, op=0, k=2):
+    """one call of each handle-free kernel hook (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine, smg_debug_eig_residual,
+    smg_debug_krylov) on arrays large enough for the largest legal shape among the arguments"""
+    dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+    big = max(n, 1) * max(m, 1, k) * 3
+    D = [np.zeros(big * max(m, 1) * 6) for _ in range(8)]
+    Fs = [np.zeros(big, np.float32) for _ in range(2)]
+    d = [a.ctypes.data_as(dp) for a in D]
+    f = [a.ctypes.data_as(fp) for a in Fs]
+    gi, bad, rs = C.c_int(0), C.c_int(0), C.c_int(0)
+    ci, cd = (C.c_int * 3)(), (C.c_double * 2)()
+    return {
+        "gram": L.smg_debug_eig_gram(n, m, nb, d[0], nb, d[1], None, 0, 0, d[2], C.byref(gi), C.byref(bad)),
+        "combine": L.smg_debug_eig_combine(n, m, nb, d[0], d[1], d[2], 1, 0, d[3], d[4], d[5], d[6], C.byref(bad)),
+        "residual": L.smg_debug_eig_residual(n, m, d[0], d[1], d[2], d[3], 1, 0, d[4], d[5], f[0], f[1], d[6], C.byref(gi), C.byref(bad)),
+        "krylov": L.smg_debug_krylov(op, n, k, d[0], d[1], d[2], d[3], f[0], d[4], C.byref(rs), 0.0, 0, cd, ci, C.byref(gi), C.byref(bad)),
+    }
+
+
+def test_kernel_hooks_refuse_bad_shapes(smg_mod):
+    """SMG_ERR_INVALID before any device work: n < 1, m outside 1..64, nb outside 1..3, an unknown Krylov op, k < 1"""
+    L = smg_mod._lib.load()
+    hooks = dict(n=["gram", "combine", "residual", "krylov"], m=["gram", "combine", "residual"], nb=["gram", "combine"], op=["krylov"],
+                 k=["krylov"])
+    for arg, bad_values in (("n", (0, -3)), ("m", (0, 65)), ("nb", (0, 4)), ("op", (-1, 6)), ("k", (0,))):
+        for v in bad_values:
+            rcs = _kernel_hook_calls(L, **{arg: v})
+            for name in hooks[arg]:
+                assert rcs[name] == -1, (arg, v, name, rcs[name])
+    # a missing array is refused the same way
+    assert L.smg_debug_eig_gram(4, 2, 1, None, 1, None, None, 0, 0, None, None, None) == -1
+    assert L.smg_debug_krylov(0, 4, 2, None, None, None, None, None, None, None, 0.0, 0, None, None, None, None) == -1
+
+
+@pytest.mark.skipif(os.environ.get("SMG_EXPECT_GPU") == "1", reason="GPU box")
+def test_kernel_hooks_fail_loudly_without_gpu(smg_mod):
+    L = smg_mod._lib.load()
+    if L.smg_device_count() > 0:
+        pytest.skip("a GPU is present")
+    for op in range(6):
+        rcs = _kernel_hook_calls(L, op=op)
+        for name, rc in rcs.items():
+            assert rc == -2, (op, name, rc)
+    assert "no CPU fallback" in L.smg_last_error().decode()

@@ -88,6 +88,16 @@ def test_torus_mcf(smg):
     assert abs(lb[0]) <= 1e-6 * lb[1]
 
 
+@pytest.mark.parametrize("block", [22, 64])
+def test_torus_mcf_wide_blocks(smg, block):
+    """block = 22: the 3 m = 66 basis columns cross a 64-column Gram tile edge; block = 64: 3 x 3 Gram tiles and four combine column chunks"""
+    mg, A, mass = torus_mcf(smg)
+    evals, X, his, nconv = mg.eigs(mass, 8, block=block, opts=smg.SolveOpts(tol=1e-8, max_iter=100))
+    print("torus block %d: rows" % block, his.shape[0])
+    assert nconv == 8 and np.all(his[-1] <= 1e-8)
+    check(A, mass, mg, evals, X, 8, 1e-8)
+
+
 def test_mixed_precision_same_eigenvalues(smg):
     mg, A, mass = torus_mcf(smg)
     e64, _, _, _ = mg.eigs(mass, 8, opts=smg.SolveOpts(tol=1e-8, max_iter=100))

@@ -93,6 +93,15 @@ def test_pcg_matches_host_reference_and_direct_solve(smg, case):
     assert len(his) <= len(hm) + 1, (len(his), len(hm))
 
 
+@pytest.mark.parametrize("k", [65, 100, 1100])
+def test_pcg_wide_blocks_match_host_reference(smg, k):
+    """widths no other case reaches: the second 64-column group of the reduction launches, and past 1024 columns the other summation path of
+    the |r|^2 finalize"""
+    p, mg = setup(smg, mesh="torus", n_sub=1, kind="poisson", n_pins=12, k=k)
+    conv, z, his, unknown, Auu, b = check_against_host(smg, mg, p, 1e-10)
+    assert np.linalg.norm(b - Auu @ z[unknown]) <= 1e-10
+
+
 def test_pcg_fewer_cycles_on_ogre(smg):
     tol = 1e-10
     p, mg = setup(smg, mesh="ogre.smgm", n_sub=1, kind="poisson")
