@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 504
+#define SMG_VERSION 505
 
 enum {
     SMG_OK = 0,
@@ -391,6 +391,44 @@ int smg_eigs(smg_hierarchy *h, const double *mass_diag, int nev, int block, cons
              const smg_solve_opts *opts, unsigned long long seed, double *evals, double *X, int ld_x, double *res_his, int *n_iter,
              int *n_converged);
 
+/* ---- geodesic distance by the heat method (Crane, Weischedel, Wardetzky 2013; libigl's heat_geodesics_precompute / _solve) ----------
+ * An addition: the reference has no distance query.  One query, per column c of sources S_c:
+ *     (M - t L) u = 1_{S_c}                       heat step, Neumann on mesh boundaries
+ *     X_f = -grad u / |grad u| per face            (X_f = 0 where grad u == 0)
+ *     -L phi = -div X                              Poisson step, vertex 0 pinned at 0
+ *     D = phi - mean(phi over S_c)                 so a single source has D = 0 there
+ * with L the cotangent matrix (negative semi-definite) and M the lumped mass matrix (voronoi != 0: mixed Voronoi, else barycentric), both
+ * assembled on the device (smg_assemble).  Both systems are solved by the V-cycle of the hierarchy the object was created from.
+ *
+ * smg_geodesics_create: h gives the prolongations (any scalar hierarchy on this mesh: smg_mg_precompute, _subdiv, a file, ...).  They are
+ *   copied in memory into two internal handles -- the heat handle (M - tL, no pins) and the Poisson handle (-L, vertex 0 known) -- which are
+ *   precomputed here; h is not modified and may be destroyed afterwards.  V: nV x 3 row-major, F: nF x 3.
+ *   t > 0 is used as given; t == 0 selects the default t = (d / 12)^2 with d the diagonal of the bounding box of V (DESIGN.md section 18:
+ *   libigl's t = h^2 leaves u below the rounding of an iterative solve on the far side of the mesh).  SMG_ERR_INVALID, before any device
+ *   work: a null argument, t < 0 or not finite, a union handle, a block (3-DOF) hierarchy, nV != the rows of level 0, a face index out of
+ *   range, a face with zero double area, a mesh of more than one connected component.  SMG_ERR_NO_DEVICE without a GPU.
+ * smg_geodesics_time: the t in use.
+ * smg_geodesics_set_solver: heat_pcg / poisson_pcg = 1 solve that stage with smg_solve_pcg (the default for both: fewer cycles at the tight
+ *   tolerances below), 0 with smg_solve's stationary loop; < 0 keeps the current choice.
+ * smg_geodesics_device_bytes: the device memory held by the object -- both internal handles (as smg_debug_device_bytes counts them) and
+ *   the object's own buffers (gradient basis, corner lists, three n x k blocks, sized by the largest k queried so far).
+ * smg_geodesics_solve: k >= 1 source sets, set c = src[src_ptr[c] .. src_ptr[c + 1]) (host arrays; a set must not be empty, indices in
+ *   [0, nV), a repeated index counts once in the heat step and once per occurrence in the mean).  D: nV x k column-major, leading dimension
+ *   ld_d >= nV, in memspace (SMG_HOST / SMG_DEVICE); everything between the source lists and D stays on the device, on one stream.
+ *   heat_opts / poisson_opts: the options of the two solves (tol is absolute, as for smg_solve); NULL selects smg_solve_opts_default with
+ *   max_iter = 100 and tol = 1e-11 sqrt(number of source entries) for the heat step (the norm of its right-hand side), 1e-11 sqrt(k A) for
+ *   the Poisson step (A = the mesh's area; its right-hand side has that scale).  cycles (NULL ok): the loop entries of the two solves.
+ *   A stage that ends unconverged is not an error (as for smg_solve: cycles[i] == max_iter tells); a failing solve's error code (e.g.
+ *   SMG_ERR_NONFINITE) is returned unchanged.  Every call with the same inputs returns the same bits (graphs on or off). */
+typedef struct smg_geodesics smg_geodesics;
+int smg_geodesics_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, double t, int voronoi, smg_geodesics **out);
+void smg_geodesics_destroy(smg_geodesics *g);
+double smg_geodesics_time(const smg_geodesics *g);
+int smg_geodesics_set_solver(smg_geodesics *g, int heat_pcg, int poisson_pcg);
+long long smg_geodesics_device_bytes(const smg_geodesics *g);
+int smg_geodesics_solve(smg_geodesics *g, int k, const int *src_ptr, const int *src, int memspace, const smg_solve_opts *heat_opts,
+                        const smg_solve_opts *poisson_opts, double *D, int ld_d, int *cycles);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -549,6 +587,16 @@ int smg_debug_eig_residual(int n, int m, const double *X, const double *AX, cons
 enum { SMG_KRY_DOTS_ZR_ZQ = 0, SMG_KRY_DIRECTION = 1, SMG_KRY_DOTS_PQ = 2, SMG_KRY_STEP_DECIDE = 3, SMG_KRY_PRECOND_IN = 4, SMG_KRY_WIDEN = 5 };
 int smg_debug_krylov(int op, int n, int k, double *v0, double *v1, double *v2, double *v3, float *e, double *s, int *restart, double tol, int done,
                      double *ctrl_d, int *ctrl_i, int *groups, int *guard_bad);
+/* One launcher of the heat-method geodesics (csrc/smg_geodesics_device.hip), handle-free and guarded like the hooks above.  Blocks are
+ * column-major n x k; `in` has leading dimension n, `out` has ld_out >= n and is in/out.  Source lists: src_ptr[0] = 0, k non-empty sets.
+ *   SMG_GEO_BASIS       in = V (n x 3 row-major), F (nF x 3) -> W[9f + 3i + d] = ((N x e_i) / (2A))_d, Af[f] = A   (out unused)
+ *   SMG_GEO_SCATTER     src_ptr, src -> out = the indicator block (1 at column c's sources, 0 elsewhere)
+ *   SMG_GEO_DIVERGENCE  F, W, Af, m_ptr[n + 1], m_idx (the corner lists t = 3f + j of each vertex), in = u -> out = -div X, X = -grad u / |grad u|
+ *   SMG_GEO_SHIFT       src_ptr, src, in = phi -> out = phi - (the mean of phi over column c's sources, list order)
+ * SMG_ERR_INVALID for an unknown op, a bad shape, an index out of range or an empty source set; SMG_ERR_NO_DEVICE without a GPU. */
+enum { SMG_GEO_BASIS = 0, SMG_GEO_SCATTER = 1, SMG_GEO_DIVERGENCE = 2, SMG_GEO_SHIFT = 3 };
+int smg_debug_geodesics(int op, int n, int nF, int k, const int *F, const int *m_ptr, const int *m_idx, const int *src_ptr, const int *src,
+                        const double *in, double *W, double *Af, double *out, int ld_out, int *guard_bad);
 
 /* ---- profc.h mirror: named scopes accumulated with hipEvents (src/profc.h:9-13; mg_VCycle.cpp:121) ------------- */
 int smg_prof_enable(smg_hierarchy *h, int on);     /* forces eager launches while on */

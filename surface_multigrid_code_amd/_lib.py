@@ -71,6 +71,13 @@ def load():
         "smg_debug_eig_combine": (i, [i, i, i, dp, dp, dp, i, i, dp, dp, dp, dp, ip]),
         "smg_debug_eig_residual": (i, [i, i, dp, dp, dp, dp, i, i, dp, dp, fp, fp, dp, ip, ip]),
         "smg_debug_krylov": (i, [i, i, i, dp, dp, dp, dp, fp, dp, ip, d, i, dp, ip, ip, ip]),
+        "smg_debug_geodesics": (i, [i, i, i, i, ip, ip, ip, ip, ip, dp, dp, dp, dp, i, ip]),
+        "smg_geodesics_create": (i, [vp, dp, i, ip, i, d, i, C.POINTER(vp)]),
+        "smg_geodesics_destroy": (None, [vp]),
+        "smg_geodesics_time": (d, [vp]),
+        "smg_geodesics_set_solver": (i, [vp, i, i]),
+        "smg_geodesics_device_bytes": (C.c_longlong, [vp]),
+        "smg_geodesics_solve": (i, [vp, i, ip, ip, i, C.POINTER(SolveOptsC), C.POINTER(SolveOptsC), vp, i, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

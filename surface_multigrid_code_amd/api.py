@@ -566,6 +566,79 @@ class Hierarchy:
         _chk(self.L.smg_synchronize(self.h), "smg_synchronize")
 
 
+class HeatGeodesics:
+    """Geodesic distance by the heat method on the V-cycle (include/smg.h: smg_geodesics_*), libigl's heat_geodesics_precompute / _solve.
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  t: None (or 0) for
+    the default (bounding-box diagonal / 12)^2, else the heat step's time.  voronoi: the mass matrix of the heat step."""
+
+    def __init__(self, hierarchy, V, F, t=None, voronoi=False):
+        self.L = _lib.load()
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        F = np.ascontiguousarray(F, dtype=np.int32)
+        self.n = V.shape[0]
+        out = C.c_void_p()
+        _chk(self.L.smg_geodesics_create(hierarchy.h, _dp(V), V.shape[0], _ip(F), F.shape[0], float(t or 0.0), int(bool(voronoi)),
+                                         C.byref(out)), "smg_geodesics_create")
+        self.g = C.c_void_p(out.value)
+        self.cycles = (0, 0)
+
+    def __del__(self):
+        try:
+            if self.g:
+                self.L.smg_geodesics_destroy(self.g)
+                self.g = None
+        except Exception:
+            pass
+
+    @property
+    def t(self):
+        return self.L.smg_geodesics_time(self.g)
+
+    def set_solver(self, heat_pcg=-1, poisson_pcg=-1):
+        """1: solve the stage by smg_solve_pcg (default), 0: by smg_solve's stationary loop, -1: unchanged."""
+        _chk(self.L.smg_geodesics_set_solver(self.g, int(heat_pcg), int(poisson_pcg)), "smg_geodesics_set_solver")
+
+    def device_bytes(self):
+        return self.L.smg_geodesics_device_bytes(self.g)
+
+    @staticmethod
+    def _sources(sources):
+        """an int, or a list whose entries are ints or index lists -> (k, src_ptr, src)"""
+        if isinstance(sources, (int, np.integer)):
+            sources = [[int(sources)]]
+        sets = [[int(s)] if isinstance(s, (int, np.integer)) else [int(x) for x in s] for s in sources]
+        ptr = np.zeros(len(sets) + 1, dtype=np.int32)
+        ptr[1:] = np.cumsum([len(s) for s in sets])
+        src = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int32) for s in sets]) if sets else np.zeros(0), dtype=np.int32)
+        return len(sets), ptr, src
+
+    @staticmethod
+    def _opts(o):
+        return C.byref(o.c) if o is not None else None
+
+    def distance(self, sources, heat_opts=None, poisson_opts=None):
+        """Distances to each source set: sources = an int (one set of one vertex) or a list of sets (an int or a list of vertex indices
+        each).  Returns the n x k array, column c = the distance to set c; self.cycles = the loop entries of the two solves."""
+        k, ptr, src = self._sources(sources)
+        D = np.zeros((self.n, max(k, 1)), order="F")
+        cyc = (C.c_int * 2)()
+        _chk(self.L.smg_geodesics_solve(self.g, k, _ip(ptr), _ip(src) if len(src) else None, SMG_HOST, self._opts(heat_opts),
+                                        self._opts(poisson_opts), D.ctypes.data, self.n, cyc), "smg_geodesics_solve")
+        self.cycles = (cyc[0], cyc[1])
+        return D
+
+    def distance_device(self, sources, D_ptr, ld_d=None, heat_opts=None, poisson_opts=None):
+        """distance() into a column-major n x k block resident in HBM (device pointer, leading dimension ld_d, default n).  Returns the
+        loop entries of the two solves."""
+        k, ptr, src = self._sources(sources)
+        cyc = (C.c_int * 2)()
+        _chk(self.L.smg_geodesics_solve(self.g, k, _ip(ptr), _ip(src) if len(src) else None, SMG_DEVICE, self._opts(heat_opts),
+                                        self._opts(poisson_opts), D_ptr, ld_d or self.n, cyc), "smg_geodesics_solve")
+        self.cycles = (cyc[0], cyc[1])
+        return self.cycles
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the reference's free functions
 

@@ -274,6 +274,53 @@ inline bool min_quad_with_fixed_mg_solve_pcg(const min_quad_with_fixed_mg_data&,
     return smg_detail::solve_impl(RHS, &known_val, z0, solver, tolerance, maxIter, z, r_his, true);
 }
 
+// ---- heat_geodesics_mg_precompute / _solve: an addition, shaped like libigl's heat_geodesics_precompute(V, F, t, data) /
+// heat_geodesics_solve(data, gamma, D) -- geodesic distance by the heat method, both solves on the V-cycle of `mg` (include/smg.h:
+// smg_geodesics_*).  t <= 0 selects the default t = (bounding-box diagonal / 12)^2; data.voronoi picks the mass matrix (set it before the
+// precompute); data.heat_opts / data.poisson_opts (nullptr: the documented defaults) are the two solves' options.
+struct heat_geodesics_mg_data {
+    std::shared_ptr<smg_geodesics> g;
+    int voronoi = 0;
+    const smg_solve_opts* heat_opts = nullptr;
+    const smg_solve_opts* poisson_opts = nullptr;
+    double t = 0.0;          // the t in use (after the precompute)
+    int n = 0;               // #V
+    int cycles[2] = {0, 0};  // loop entries of the two solves of the last query
+};
+
+inline bool heat_geodesics_mg_precompute(const smgDense& V, const smgDenseI& F, double t, const std::vector<mg_data>& mg, heat_geodesics_mg_data& data)
+{
+    const int L = (int)mg.size();
+    std::shared_ptr<smg_hierarchy> h(smg_hierarchy_create(L), smg_hierarchy_destroy);   // carries the prolongations only: the object copies them
+    if (!h) throw std::runtime_error(smg_last_error());
+    for (int lv = 1; lv < L; lv++) {
+        const smgSparse& P = mg[lv].P_full;
+        smg_detail::check(smg_level_set_prolong_csc(h.get(), lv, P.rows, P.cols, P.outer.data(), P.inner.data(), P.values.data()), "smg_level_set_prolong_csc");
+    }
+    std::vector<double> Vr((size_t)V.rows * 3);
+    std::vector<int> Fr((size_t)F.rows * 3);
+    for (int i = 0; i < V.rows; i++) for (int c = 0; c < 3; c++) Vr[3 * (size_t)i + c] = V(i, c);
+    for (int i = 0; i < F.rows; i++) for (int c = 0; c < 3; c++) Fr[3 * (size_t)i + c] = F(i, c);
+    smg_geodesics* g = nullptr;
+    const int rc = smg_geodesics_create(h.get(), Vr.data(), V.rows, Fr.data(), F.rows, t > 0.0 ? t : 0.0, data.voronoi, &g);
+    if (rc == SMG_ERR_INVALID) return false;   // libigl returns false when the precompute fails
+    smg_detail::check(rc, "heat_geodesics_mg_precompute");
+    data.g.reset(g, smg_geodesics_destroy);
+    data.t = smg_geodesics_time(g);
+    data.n = V.rows;
+    return true;
+}
+
+// D (#V x 1) = the distance to the vertex set gamma (#gamma x 1); gamma with several columns is not a libigl form: use the C ABI for batches
+inline void heat_geodesics_mg_solve(heat_geodesics_mg_data& data, const smgDenseI& gamma, smgDense& D)
+{
+    if (!data.g) throw std::runtime_error("heat_geodesics_mg_solve: run heat_geodesics_mg_precompute first");
+    const int ptr[2] = {0, gamma.size()};
+    D.resize(data.n, 1);
+    smg_detail::check(smg_geodesics_solve(data.g.get(), 1, ptr, gamma.data.data(), SMG_HOST, data.heat_opts, data.poisson_opts, D.data.data(), data.n,
+                                          data.cycles), "heat_geodesics_mg_solve");
+}
+
 // ---- mg_VCycle (reference src/mg_VCycle.cpp:3-59) ----------------------------------------------------------------
 inline void mg_VCycle(const smgCoarseSolver& solver, const smgDense& B, const int& preRelaxIter, const int& postRelaxIter,
                       const int lv, smgDense& u, std::vector<mg_data>&)

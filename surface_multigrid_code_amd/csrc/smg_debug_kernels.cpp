@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov) and of the geodesics kernels (smg_debug_geodesics).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -257,6 +257,73 @@ extern "C" int smg_debug_krylov(int op, int n, int k, double* v0, double* v1, do
         if (ctrl_d) ctrl_d[0] = c.sumsq;
         if (ctrl_i) { ctrl_i[0] = c.n_his; ctrl_i[1] = c.done; ctrl_i[2] = c.status; }
         if (groups) *groups = K.groups;
+        if (guard_bad) *guard_bad = bad;
+        return SMG_OK;
+    });
+}
+
+namespace {
+
+// the corner lists and source lists a geodesics hook is handed: in range, monotone, every source set non-empty
+const char* check_geo_lists(int op, int n, int nF, int k, const int* F, const int* m_ptr, const int* m_idx, const int* src_ptr, const int* src)
+{
+    if (op == SMG_GEO_BASIS || op == SMG_GEO_DIVERGENCE) {
+        if (!F || nF < 1) return "missing faces";
+        for (size_t i = 0; i < (size_t)nF * 3; i++) if (F[i] < 0 || F[i] >= n) return "face index out of range";
+    }
+    if (op == SMG_GEO_DIVERGENCE) {
+        if (!m_ptr || !m_idx || m_ptr[0] != 0) return "missing or bad corner lists";
+        for (int v = 0; v < n; v++) if (m_ptr[v + 1] < m_ptr[v]) return "corner list pointers not monotone";
+        for (int p = 0; p < m_ptr[n]; p++) if (m_idx[p] < 0 || m_idx[p] >= 3 * nF) return "corner index out of range";
+    }
+    if (op == SMG_GEO_SCATTER || op == SMG_GEO_SHIFT) {
+        if (!src_ptr || !src || src_ptr[0] != 0) return "missing or bad source lists";
+        for (int c = 0; c < k; c++) if (src_ptr[c + 1] <= src_ptr[c]) return "empty source set";
+        for (int p = 0; p < src_ptr[k]; p++) if (src[p] < 0 || src[p] >= n) return "source index out of range";
+    }
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" int smg_debug_geodesics(int op, int n, int nF, int k, const int* F, const int* m_ptr, const int* m_idx, const int* src_ptr,
+                                   const int* src, const double* in, double* W, double* Af, double* out, int ld_out, int* guard_bad)
+{
+    return guarded("smg_debug_geodesics", [&]() -> int {
+        if (op < SMG_GEO_BASIS || op > SMG_GEO_SHIFT || n < 1 || k < 1 || !in) return fail(SMG_ERR_INVALID, "smg_debug_geodesics: bad arguments");
+        if (op == SMG_GEO_BASIS ? (!W || !Af) : (!out || ld_out < n || (op == SMG_GEO_DIVERGENCE && (!W || !Af))))
+            return fail(SMG_ERR_INVALID, "smg_debug_geodesics: bad arguments");
+        if (const char* why = check_geo_lists(op, n, nF, k, F, m_ptr, m_idx, src_ptr, src))
+            return fail(SMG_ERR_INVALID, "smg_debug_geodesics: %s", why);
+        if (int rc = need_device("smg_debug_geodesics")) return rc;
+        Scratch X;
+        HIPCHK(X.init());
+        const size_t blk = (size_t)n * k, oblk = (size_t)ld_out * k;
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr, *dsp = nullptr, *ds = nullptr;
+        double *din = nullptr, *dW = nullptr, *dAf = nullptr, *dout = nullptr, *dmean = nullptr;
+        if (op == SMG_GEO_BASIS || op == SMG_GEO_DIVERGENCE) {
+            HIPCHK(X.add(F, nullptr, (size_t)nF * 3 * sizeof(int), &dF));
+            const bool basis = op == SMG_GEO_BASIS;   // the basis is the output of BASIS, an input of DIVERGENCE
+            HIPCHK(X.add(W, basis ? W : nullptr, (size_t)nF * 9 * sizeof(double), &dW));
+            HIPCHK(X.add(Af, basis ? Af : nullptr, (size_t)nF * sizeof(double), &dAf));
+        }
+        if (op == SMG_GEO_DIVERGENCE) {
+            HIPCHK(X.add(m_ptr, nullptr, ((size_t)n + 1) * sizeof(int), &dmp));
+            HIPCHK(X.add(m_idx, nullptr, (size_t)m_ptr[n] * sizeof(int), &dmi));
+        }
+        if (op == SMG_GEO_SCATTER || op == SMG_GEO_SHIFT) {
+            HIPCHK(X.add(src_ptr, nullptr, ((size_t)k + 1) * sizeof(int), &dsp));
+            HIPCHK(X.add(src, nullptr, (size_t)src_ptr[k] * sizeof(int), &ds));
+        }
+        if (op != SMG_GEO_SCATTER) HIPCHK(X.add(in, nullptr, (op == SMG_GEO_BASIS ? (size_t)n * 3 : blk) * sizeof(double), &din));
+        if (op != SMG_GEO_BASIS) HIPCHK(X.add(out, out, oblk * sizeof(double), &dout));
+        if (op == SMG_GEO_SHIFT) HIPCHK(X.add(nullptr, nullptr, (size_t)k * sizeof(double), &dmean));
+        if (op == SMG_GEO_BASIS) HIPCHK(launch_geo_basis(din, dF, nF, dW, dAf, X.stream()));
+        else if (op == SMG_GEO_SCATTER) HIPCHK(launch_geo_scatter(n, k, dsp, ds, dout, ld_out, X.stream()));
+        else if (op == SMG_GEO_DIVERGENCE) HIPCHK(launch_geo_divergence(n, k, dF, dW, dAf, dmp, dmi, din, n, dout, ld_out, X.stream()));
+        else HIPCHK(launch_geo_shift(n, k, dsp, ds, din, n, dmean, dout, ld_out, X.stream()));
+        int bad = 0;
+        HIPCHK(X.finish(&bad));
         if (guard_bad) *guard_bad = bad;
         return SMG_OK;
     });

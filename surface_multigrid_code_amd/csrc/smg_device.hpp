@@ -385,4 +385,16 @@ hipError_t launch_gather_cm(double* dst, const double* src, const int* idx, int 
 hipError_t launch_csr_sub(int n_rows, const int* ptr, const int* col, const double* val, const double* x, int ldx,
                           double* y, int ld, int k, hipStream_t st);
 
+// heat-method geodesics (smg_geodesics_device.hip; column-major caller blocks, column c of vertex i at c * ld + i) -------------------
+// W[9f + 3i + d] = ((n x e_i) / (2A))_d, the gradient of corner i's hat function on face f; Af[f] = A (V: nV x 3 row-major)
+hipError_t launch_geo_basis(const double* V, const int* F, int nF, double* W, double* Af, hipStream_t st);
+// B = the n x k indicator block: 1 at the sources src[src_ptr[c] .. src_ptr[c + 1]) of column c, 0 elsewhere
+hipError_t launch_geo_scatter(int n, int k, const int* src_ptr, const int* src, double* B, int ldb, hipStream_t st);
+// out[c * ldo + v] = sum over v's corners (m_ptr / m_idx order) of A_f (W_fj . X_f), X_f = -grad u / |grad u| (0 where grad u == 0)
+hipError_t launch_geo_divergence(int n, int k, const int* F, const double* W, const double* Af, const int* m_ptr, const int* m_idx,
+                                 const double* U, int ldu, double* out, int ldo, hipStream_t st);
+// mean[c] = the mean of phi over column c's sources (list order); D[c * ldd + i] = phi[c * ldp + i] - mean[c]
+hipError_t launch_geo_shift(int n, int k, const int* src_ptr, const int* src, const double* phi, int ldp, double* mean, double* D, int ldd,
+                            hipStream_t st);
+
 }  // namespace smg

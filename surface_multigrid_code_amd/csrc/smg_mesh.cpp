@@ -323,13 +323,19 @@ AssemblyPlan make_assembly_plan(const std::vector<int>& F, int nV)
     P.l_ptr.push_back((int)P.l_idx.size());
     P.pattern.val.assign(P.pattern.col.size(), 0.0);
     // mass: massmatrix_diag() adds the corner terms in face order
-    P.m_ptr.assign(nV + 1, 0);
-    for (int f = 0; f < nF; f++) for (int c = 0; c < 3; c++) P.m_ptr[F[3 * f + c] + 1]++;
-    for (int i = 0; i < nV; i++) P.m_ptr[i + 1] += P.m_ptr[i];
-    P.m_idx.resize(P.m_ptr[nV]);
-    std::vector<int> mn(P.m_ptr.begin(), P.m_ptr.end() - 1);
-    for (int f = 0; f < nF; f++) for (int c = 0; c < 3; c++) P.m_idx[mn[F[3 * f + c]]++] = 3 * f + c;
+    vertex_corner_lists(F, nV, P.m_ptr, P.m_idx);
     return P;
+}
+
+void vertex_corner_lists(const std::vector<int>& F, int nV, std::vector<int>& m_ptr, std::vector<int>& m_idx)
+{
+    const int nF = (int)(F.size() / 3);
+    m_ptr.assign(nV + 1, 0);
+    for (int f = 0; f < nF; f++) for (int c = 0; c < 3; c++) m_ptr[F[3 * f + c] + 1]++;
+    for (int i = 0; i < nV; i++) m_ptr[i + 1] += m_ptr[i];
+    m_idx.resize(m_ptr[nV]);
+    std::vector<int> mn(m_ptr.begin(), m_ptr.end() - 1);
+    for (int f = 0; f < nF; f++) for (int c = 0; c < 3; c++) m_idx[mn[F[3 * f + c]]++] = 3 * f + c;
 }
 
 Mesh make_torus(int nu, int nv, double R, double r)

@@ -54,6 +54,8 @@ struct AssemblyPlan {
     std::vector<int> diag_of;     // per entry: the vertex whose diagonal it is, or -1
 };
 AssemblyPlan make_assembly_plan(const std::vector<int>& F, int nV);
+// per vertex the corners t = 3f + c that touch it, faces ascending (AssemblyPlan::m_ptr / m_idx; the heat-method divergence gathers in this order)
+void vertex_corner_lists(const std::vector<int>& F, int nV, std::vector<int>& m_ptr, std::vector<int>& m_idx);
 
 // What one coarsening step keeps about its collapses when asked to (the reference's decInfo / decIM, src/single_collapse_data.h and
 // src/SSP_collapse_edge.cpp:452-459): per successful collapse the faces of the pre-collapse one-ring with their flattened positions.
