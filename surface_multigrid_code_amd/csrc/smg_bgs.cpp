@@ -259,4 +259,33 @@ BgsPlan build_bgs(const Csr& G, const std::vector<int>& vcp, int block_rows)
     return R;
 }
 
+long bgs_sweep_host(const BgsPlan& P, const double* b, double* u)
+{
+    std::vector<double> xs((size_t)P.xrows);
+    for (int q = 0; q < P.n_blocks; q++) {
+        const int* H = P.hdr.data() + (size_t)q * BGS_HDR;
+        const int unit0 = H[0], nu = H[1], S = H[2] * BGS_BATCH, ent0 = H[3];
+        for (int l = 0; l < P.xrows; l++) xs[(size_t)l] = u[(size_t)P.xrow[(size_t)q * P.xrows + l]];
+        for (int un = 0; un < nu; un++) {
+            double out[BGS_UROWS];
+            for (int r = 0; r < BGS_UROWS; r++) {
+                const size_t w = ((size_t)unit0 + un) * BGS_UROWS + r, e = (size_t)ent0 + ((size_t)un * BGS_UROWS + r) * S;
+                double acc = 0.0;
+                for (int t = 0; t < S; t++) {
+                    const int l = P.eidx[e + t];
+                    if (l < 0 || l >= P.xrows) return (long)(e + t);
+                    acc += P.eval[e + t] * xs[(size_t)l];
+                }
+                out[r] = (b[(size_t)P.ugrow[w]] - acc) / P.udiag[w];
+            }
+            for (int r = 0; r < BGS_UROWS; r++) {
+                const size_t w = ((size_t)unit0 + un) * BGS_UROWS + r;
+                xs[(size_t)P.ulrow[w]] = out[r];
+                u[(size_t)P.ugrow[w]] = out[r];
+            }
+        }
+    }
+    return -1;
+}
+
 }  // namespace smg

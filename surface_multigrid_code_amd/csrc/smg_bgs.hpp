@@ -67,6 +67,10 @@ struct BgsPlan {
 // more than BGS_RIM_MAX rows of other blocks.
 BgsPlan build_bgs(const Csr& G, const std::vector<int>& color_ptr, int block_rows = BGS_ROWS);
 
+// The plan executed on the host the way k_bgs executes it (one column, in place on u: block after block, an image per block, units in place) -- the
+// checker of the plan's bookkeeping (tests, CPU lane).  Returns -1, or an entry slot whose local index lies outside the image.
+long bgs_sweep_host(const BgsPlan& P, const double* b, double* u);
+
 // compact parts of <= tile_rows rows (smg_tiled.cpp)
 std::vector<int> partition_tiles(const Csr& G, int tile_rows, int* n_tiles);
 

@@ -58,10 +58,10 @@ extern "C" int smg_debug_device_bytes(const smg_hierarchy* h, char* buf, int cap
         line(p + "refresh_maps", B(L.mapA) + B(L.mapAT));
         line(p + "galerkin_recipes", B(L.r1_ptr) + B(L.r1_idx) + B(L.r2_ptr) + B(L.r2_idx) + B(L.r1_coef) + B(L.r2_coef));
         long long t = 0;
-        for (const auto& T : L.tiled) t += B(T.hdr) + B(T.ext_rows) + B(T.pcol) + B(T.prow) + B(T.map) + B(T.mapd) + B(T.pval) + B(T.pdiag);
+        for (const auto& T : L.tiled) t += T.bytes();
         line(p + "tiled_plans", t);
-        line(p + "bgs_plan", B(L.bgs.hdr) + B(L.bgs.xrow) + B(L.bgs.ugrow) + B(L.bgs.ulrow) + B(L.bgs.eidx) + B(L.bgs.map) + B(L.bgs.mapd) + B(L.bgs.eval) + B(L.bgs.udiag));
-        line(p + "wgs_plan", B(L.wgs.hdr) + B(L.wgs.grow) + B(L.wgs.meta) + B(L.wgs.rim) + B(L.wgs.map) + B(L.wgs.mapd) + B(L.wgs.eoff) + B(L.wgs.eval) + B(L.wgs.diag));
+        line(p + "bgs_plan", L.bgs.bytes());
+        line(p + "wgs_plan", L.wgs.bytes());
         line(p + "fp32_images", B(L.a32) + B(L.at32) + B(L.p32) + B(L.pt32) + B(L.b32) + B(L.u32) + B(L.r32) + B(L.t32) + B(L.d32));
         line(p + "vectors", B(L.b) + B(L.u) + B(L.r) + B(L.t) + B(L.d));
     }
@@ -621,228 +621,6 @@ extern "C" long smg_level_spmv_bytes(const smg_hierarchy* h, int lv, int k)
 }
 
 // ------------------------------------------------------------------------------------------------ host-side self-checks
-extern "C" int smg_debug_check_tiling_plan(smg_hierarchy* h, int lv, int sweeps, int tile_rows, int* n_tiles, int* max_ext_rows, double* redundancy,
-                                           double* max_abs_diff)
-{
-    return guarded("smg_debug_check_tiling_plan", [&]() -> int {
-        if (!h || lv < 0 || lv >= h->n_levels - 1 || sweeps < 1 || tile_rows < 8) return fail(SMG_ERR_INVALID, "smg_debug_check_tiling_plan: bad arguments");
-        int rc = ensure_A_int(h, lv);
-        if (rc) return rc;
-        Level& Lv = h->lv[lv];
-        if (Lv.A_int.nr != Lv.n || Lv.n == 0 || h->bs != 1) return fail(SMG_ERR_INVALID, "smg_debug_check_tiling_plan: the host half of smg_precompute has not run (scalar hierarchies only)");
-        const Csr& G = Lv.A_int;
-        const int n = G.nr;
-        const TiledGs P = build_tiled_gs(G, Lv.ord.color_ptr, sweeps, tile_rows, 1 << 20, 1 << 20);
-        if (n_tiles) *n_tiles = P.n_tiles;
-        if (max_ext_rows) *max_ext_rows = P.max_ext;
-        if (redundancy) *redundancy = P.n_tiles ? (double)P.updates / ((double)sweeps * n) : 0.0;
-        if (max_abs_diff) *max_abs_diff = 0.0;
-        if (P.empty()) return SMG_OK;
-        std::vector<double> x((size_t)n), b((size_t)n), ref, y((size_t)n, 0.0), xs;
-        for (int i = 0; i < n; i++) { x[(size_t)i] = std::sin(0.37 * i) + 0.25 * std::cos(1.3 * i); b[(size_t)i] = std::cos(0.11 * i) - 0.5 * std::sin(2.1 * i); }
-        // reference: the colour-by-colour sweeps in place (what one launch per colour computes)
-        ref = x;
-        const std::vector<int>& cp = Lv.ord.color_ptr;
-        for (int s = 0; s < sweeps; s++)
-            for (size_t c = 0; c + 1 < cp.size(); c++)
-                for (int i = cp[c]; i < cp[c + 1]; i++) {
-                    double acc = 0.0, diag = 1.0;
-                    for (int p = G.ptr[(size_t)i]; p < G.ptr[(size_t)i + 1]; p++) {
-                        if (G.col[(size_t)p] == i) diag = G.val[(size_t)p];
-                        else acc += G.val[(size_t)p] * ref[(size_t)G.col[(size_t)p]];
-                    }
-                    ref[(size_t)i] = (b[(size_t)i] - acc) / diag;
-                }
-        // the plan, executed like k_tiled_gs: x -> y
-        const int nc = P.nc, PP = P.P;
-        for (int t = 0; t < P.n_tiles; t++) {
-            const int* H = P.hdr.data() + (size_t)t * TILED_HDR;
-            const int ext_off = H[0], n_ext = H[1], w = H[2];
-            xs.assign((size_t)n_ext, 0.0);
-            for (int i = 0; i < n_ext; i++) xs[(size_t)i] = x[(size_t)P.ext_rows[(size_t)ext_off + i]];
-            for (int p = 1; p <= PP; p++) {
-                const int* C = H + 4 + ((p - 1) % nc) * TILED_CSTRIDE;
-                const int pan = C[0], m = C[1], ro = C[2], lbase = C[3], cnt = C[4 + (PP - p)];
-                for (int i = 0; i < cnt; i++) {
-                    double acc = 0.0;      // exactly the kernel's loop: every slot, the diagonal's and the padding's hold +0.0 at the row's own index
-                    for (int j = 0; j < w; j++) {
-                        const int cl = P.pcol[(size_t)pan + (size_t)j * m + i];
-                        if (cl < 0 || cl >= n_ext) return fail(SMG_ERR_INVALID, "tiling plan: tile %d holds a column outside its image", t);
-                        acc += P.pval[(size_t)pan + (size_t)j * m + i] * xs[(size_t)cl];
-                    }
-                    xs[(size_t)lbase + i] = (b[(size_t)P.prow[(size_t)ro + i]] - acc) / P.pdiag[(size_t)ro + i];
-                }
-            }
-            for (int c = 0; c < nc; c++) {
-                const int* C = H + 4 + c * TILED_CSTRIDE;
-                for (int i = 0; i < C[4]; i++) y[(size_t)P.prow[(size_t)C[2] + i]] = xs[(size_t)C[3] + i];
-            }
-        }
-        double d = 0.0;
-        for (int i = 0; i < n; i++) d = std::max(d, std::fabs(y[(size_t)i] - ref[(size_t)i]));
-        if (max_abs_diff) *max_abs_diff = d;
-        return SMG_OK;
-    });
-}
-
-// The wave Gauss-Seidel plan of level lv (smg_wgs.hpp) built on the host and EXECUTED on the host the way k_wgs executes it (wgs_sweep_host: per piece an
-// image of its rows and its rim, phases in place, packed byte offsets) against the plain lexicographic sweep in the wgs order (the reference's relax(),
-// src/mg_VCycle.cpp:146-160, on that numbering): *max_abs_diff must be 0.  Checks the plan's invariants on the way.  Needs no GPU once the host half of
-// smg_precompute has run.  *n_pieces = 0: the level does not qualify.
-extern "C" int smg_debug_check_wave_gs_plan(smg_hierarchy* h, int lv, int piece_rows, int pieces_mode, int* n_pieces, int* n_colors, double* stats, double* max_abs_diff)
-{
-    return guarded("smg_debug_check_wave_gs_plan", [&]() -> int {
-        if (!h || lv < 0 || lv >= h->n_levels - 1 || piece_rows < 8) return fail(SMG_ERR_INVALID, "smg_debug_check_wave_gs_plan: bad arguments");
-        int rc = ensure_A_int(h, lv);
-        if (rc) return rc;
-        Level& Lv = h->lv[lv];
-        if (Lv.A_int.nr != Lv.n || Lv.n == 0 || h->bs != 1) return fail(SMG_ERR_INVALID, "smg_debug_check_wave_gs_plan: the host half of smg_precompute has not run (scalar hierarchies only)");
-        const Csr& G = Lv.A_int;
-        const int n = G.nr;
-        const WgsPlan P = build_wgs(G, std::min(piece_rows, (int)WGS_ROWS), pieces_mode);
-        if (n_pieces) *n_pieces = P.n_pieces;
-        if (n_colors) *n_colors = P.n_colors;
-        if (stats) { stats[0] = P.rim_ratio; stats[1] = P.phases_mean; stats[2] = (double)P.phases_max; }
-        if (max_abs_diff) *max_abs_diff = 0.0;
-        if (P.empty()) return SMG_OK;
-        // invariants: every row in exactly one piece of <= 64 rows; pieces of one colour share no entry
-        std::vector<int> pc_of((size_t)n, -1), col_of_pc((size_t)P.n_pieces, -1);
-        for (int c = 0; c < P.n_colors; c++) for (int q = P.color_ptr[(size_t)c]; q < P.color_ptr[(size_t)c + 1]; q++) col_of_pc[(size_t)q] = c;
-        for (int q = 0; q < P.n_pieces; q++) {
-            if (P.piece_ptr[(size_t)q + 1] - P.piece_ptr[(size_t)q] > WGS_ROWS) return fail(SMG_ERR_INVALID, "wave plan: piece %d has more than 64 rows", q);
-            for (int t = P.piece_ptr[(size_t)q]; t < P.piece_ptr[(size_t)q + 1]; t++) {
-                const int i = P.rows[(size_t)t];
-                if (i < 0 || i >= n || pc_of[(size_t)i] >= 0) return fail(SMG_ERR_INVALID, "wave plan: row %d is not in exactly one piece", i);
-                pc_of[(size_t)i] = q;
-            }
-        }
-        for (int i = 0; i < n; i++) {
-            if (pc_of[(size_t)i] < 0) return fail(SMG_ERR_INVALID, "wave plan: row %d is in no piece", i);
-            for (int p = G.ptr[(size_t)i]; p < G.ptr[(size_t)i + 1]; p++) {
-                const int j = G.col[(size_t)p];
-                if (pc_of[(size_t)j] != pc_of[(size_t)i] && col_of_pc[(size_t)pc_of[(size_t)j]] == col_of_pc[(size_t)pc_of[(size_t)i]])
-                    return fail(SMG_ERR_INVALID, "wave plan: pieces %d and %d share an entry and a colour", pc_of[(size_t)i], pc_of[(size_t)j]);
-            }
-        }
-        std::vector<double> x((size_t)n), b((size_t)n), ref, y;
-        for (int i = 0; i < n; i++) { x[(size_t)i] = std::sin(0.37 * i) + 0.25 * std::cos(1.3 * i); b[(size_t)i] = std::cos(0.11 * i) - 0.5 * std::sin(2.1 * i); }
-        // reference: rows one after the other in the wgs order, products in ascending column OF THAT ORDER
-        std::vector<int> pos((size_t)n);
-        for (int t = 0; t < n; t++) pos[(size_t)P.rows[(size_t)t]] = t;
-        ref = x;
-        std::vector<std::pair<int, int>> ent;
-        for (int t = 0; t < n; t++) {
-            const int i = P.rows[(size_t)t];
-            ent.clear();
-            double diag = 1.0;
-            for (int p = G.ptr[(size_t)i]; p < G.ptr[(size_t)i + 1]; p++) {
-                if (G.col[(size_t)p] == i) diag = G.val[(size_t)p]; else ent.emplace_back(pos[(size_t)G.col[(size_t)p]], p);
-            }
-            std::sort(ent.begin(), ent.end());
-            double acc = 0.0;
-            for (const auto& e : ent) acc += G.val[(size_t)e.second] * ref[(size_t)G.col[(size_t)e.second]];
-            ref[(size_t)i] = (b[(size_t)i] - acc) / diag;
-        }
-        y = x;
-        wgs_sweep_host(P, b.data(), y.data());
-        double d = 0.0;
-        for (int i = 0; i < n; i++) d = std::max(d, std::fabs(y[(size_t)i] - ref[(size_t)i]));
-        if (max_abs_diff) *max_abs_diff = d;
-        return SMG_OK;
-    });
-}
-
-// The block Gauss-Seidel plan of level lv (smg_bgs.hpp) built on the host and EXECUTED on the host the way k_bgs executes it -- per block an image
-// of its rows and its rim, units of <= 16 rows updated in place from local indices -- against the plain lexicographic sweep in the bgs order
-// (the reference's relax(), src/mg_VCycle.cpp:146-160, on that numbering): *max_abs_diff must be 0.  Also checks the plan's invariants (every row in
-// exactly one block, blocks of one colour share no entry, local indices inside the image).  Works without a GPU once the host half of
-// smg_precompute has run.  Returns SMG_OK with *n_blocks = 0 when the level does not qualify.
-extern "C" int smg_debug_check_block_gs_plan(smg_hierarchy* h, int lv, int block_rows, int* n_blocks, int* n_colors, double* rim, double* fill, double* max_abs_diff)
-{
-    return guarded("smg_debug_check_block_gs_plan", [&]() -> int {
-        if (!h || lv < 0 || lv >= h->n_levels - 1 || block_rows < 8) return fail(SMG_ERR_INVALID, "smg_debug_check_block_gs_plan: bad arguments");
-        int rc = ensure_A_int(h, lv);
-        if (rc) return rc;
-        Level& Lv = h->lv[lv];
-        if (Lv.A_int.nr != Lv.n || Lv.n == 0 || h->bs != 1) return fail(SMG_ERR_INVALID, "smg_debug_check_block_gs_plan: the host half of smg_precompute has not run (scalar hierarchies only)");
-        const Csr& G = Lv.A_int;
-        const int n = G.nr;
-        const BgsPlan P = build_bgs(G, Lv.ord.color_ptr, std::min(block_rows, (int)BGS_ROWS));
-        if (n_blocks) *n_blocks = P.n_blocks;
-        if (n_colors) *n_colors = P.n_colors;
-        if (rim) *rim = P.rim;
-        if (fill) *fill = P.fill;
-        if (max_abs_diff) *max_abs_diff = 0.0;
-        if (P.empty()) return SMG_OK;
-        // invariants
-        std::vector<int> blk_of((size_t)n, -1), col_of_blk((size_t)P.n_blocks, -1);
-        for (int c = 0; c < P.n_colors; c++) for (int q = P.color_ptr[(size_t)c]; q < P.color_ptr[(size_t)c + 1]; q++) col_of_blk[(size_t)q] = c;
-        for (int q = 0; q < P.n_blocks; q++)
-            for (int t = P.blk_ptr[(size_t)q]; t < P.blk_ptr[(size_t)q + 1]; t++) {
-                const int i = P.rows[(size_t)t];
-                if (i < 0 || i >= n || blk_of[(size_t)i] >= 0) return fail(SMG_ERR_INVALID, "block plan: row %d is not in exactly one block", i);
-                blk_of[(size_t)i] = q;
-            }
-        for (int i = 0; i < n; i++) {
-            if (blk_of[(size_t)i] < 0) return fail(SMG_ERR_INVALID, "block plan: row %d is in no block", i);
-            for (int p = G.ptr[(size_t)i]; p < G.ptr[(size_t)i + 1]; p++) {
-                const int j = G.col[(size_t)p];
-                if (blk_of[(size_t)j] != blk_of[(size_t)i] && col_of_blk[(size_t)blk_of[(size_t)j]] == col_of_blk[(size_t)blk_of[(size_t)i]])
-                    return fail(SMG_ERR_INVALID, "block plan: blocks %d and %d share an entry and a colour", blk_of[(size_t)i], blk_of[(size_t)j]);
-            }
-        }
-        std::vector<double> x((size_t)n), b((size_t)n), ref, y;
-        for (int i = 0; i < n; i++) { x[(size_t)i] = std::sin(0.37 * i) + 0.25 * std::cos(1.3 * i); b[(size_t)i] = std::cos(0.11 * i) - 0.5 * std::sin(2.1 * i); }
-        // reference: rows one after the other in the bgs order, products in ascending column OF THAT ORDER
-        std::vector<int> pos((size_t)n);
-        for (int t = 0; t < n; t++) pos[(size_t)P.rows[(size_t)t]] = t;
-        ref = x;
-        std::vector<std::pair<int, int>> ent;
-        for (int t = 0; t < n; t++) {
-            const int i = P.rows[(size_t)t];
-            ent.clear();
-            double diag = 1.0;
-            for (int p = G.ptr[(size_t)i]; p < G.ptr[(size_t)i + 1]; p++) {
-                if (G.col[(size_t)p] == i) diag = G.val[(size_t)p]; else ent.emplace_back(pos[(size_t)G.col[(size_t)p]], p);
-            }
-            std::sort(ent.begin(), ent.end());
-            double acc = 0.0;
-            for (const auto& e : ent) acc += G.val[(size_t)e.second] * ref[(size_t)G.col[(size_t)e.second]];
-            ref[(size_t)i] = (b[(size_t)i] - acc) / diag;
-        }
-        // the plan, executed like k_bgs (one column): block colour by block colour, an image per block, units in place
-        y = x;
-        std::vector<double> xs((size_t)P.xrows);
-        for (int q = 0; q < P.n_blocks; q++) {
-            const int* H = P.hdr.data() + (size_t)q * BGS_HDR;
-            const int unit0 = H[0], nu = H[1], S = H[2] * BGS_BATCH, ent0 = H[3];
-            for (int l = 0; l < P.xrows; l++) xs[(size_t)l] = y[(size_t)P.xrow[(size_t)q * P.xrows + l]];
-            for (int un = 0; un < nu; un++) {
-                double out[BGS_UROWS];
-                for (int r = 0; r < BGS_UROWS; r++) {
-                    const size_t w = ((size_t)unit0 + un) * BGS_UROWS + r, e = (size_t)ent0 + ((size_t)un * BGS_UROWS + r) * S;
-                    double acc = 0.0;
-                    for (int t = 0; t < S; t++) {
-                        const int l = P.eidx[e + t];
-                        if (l < 0 || l >= P.xrows) return fail(SMG_ERR_INVALID, "block plan: local index %d outside the image of %d rows", l, P.xrows);
-                        acc += P.eval[e + t] * xs[(size_t)l];
-                    }
-                    out[r] = (b[(size_t)P.ugrow[w]] - acc) / P.udiag[w];
-                }
-                for (int r = 0; r < BGS_UROWS; r++) {
-                    const size_t w = ((size_t)unit0 + un) * BGS_UROWS + r;
-                    xs[(size_t)P.ulrow[w]] = out[r];
-                    y[(size_t)P.ugrow[w]] = out[r];
-                }
-            }
-        }
-        double d = 0.0;
-        for (int i = 0; i < n; i++) d = std::max(d, std::fabs(y[(size_t)i] - ref[(size_t)i]));
-        if (max_abs_diff) *max_abs_diff = d;
-        return SMG_OK;
-    });
-}
-
 extern "C" int smg_debug_raise_coarse_stall(smg_hierarchy* h)
 {
     if (!h || !h->coarse_sparse || !h->c_err.p) return fail(SMG_ERR_INVALID, "smg_debug_raise_coarse_stall: no sparse coarse factorisation on this handle");

@@ -25,294 +25,6 @@ using namespace smg;
 
 // ------------------------------------------------------------------------------------------------ V-cycle
 
-// ---- overlapped tiling of the Gauss-Seidel sweeps of the latency-bound levels (smg_tiled.hpp): relax(sweeps) as ONE launch ----------
-// Which levels: scalar fp64 hierarchies, up to 7 columns (groups of 3 per launch; 8 and more take the wide colour kernels), Gauss-Seidel, SMG_TILED_MIN_ROWS <= rows <= SMG_TILED_MAX_ROWS (default 512 ..
-// 122880 = one round of 240 parts of 512 rows: above, the redundant halo work of the tiles costs more than the launches it saves -- measured at C3 level 1, 253 k rows, and again on a 160 k-row
-// union level; below 2 048 rows it pays as well: a 768-row level 37.5 -> 18.0 us per visit, tools/size_sweep.py), at most 5 colours and 12 entries per row.
-// SMG_TILED=0 switches it off (A/B knob; the results are bit-identical either way).
-// The plans of the one-launch / piece-wise / block-wise sweeps hold copies of the level's values; the maps that refresh them (value slot -> index into
-// Level::d_Aval) are only needed by a value-only re-precompute: they stay on the host until the first one (a quarter of a plan's bytes).
-static hipError_t ensure_map(DevBuf<int>& d, const std::vector<int>& host)
-{
-    if (d.n == host.size() && (d.p || host.empty())) return hipSuccess;
-    return d.upload(host);
-}
-static bool wgs_forced(const smg_hierarchy* h, int lv);
-static bool tiled_wanted(const smg_hierarchy* h, int lv, int k, int sweeps)
-{
-    static const int on = env_int("SMG_TILED", 1);
-    if (wgs_forced(h, lv)) return false;      // smg_hierarchy_set_wave_gs(h, 1): the level sweeps piece-wise for EVERY k (the one-launch relax exists for k <= 7 only,
-                                              // and the order of a level's sweep must not depend on the number of columns: column-sharded == fused)
-    static const int max_rows = env_int("SMG_TILED_MAX_ROWS", 122880), min_rows = env_int("SMG_TILED_MIN_ROWS", 512);
-    if (!on || h->bs != 1 || k < 1 || k > 7 || lv < 0 || lv >= h->n_levels - 1 || sweeps < 1 || sweeps > 3) return false;
-    if (level_kind(h, lv) != LV_GS) return false;
-    const int n = h->lv[lv].n;
-    return n >= min_rows && n <= max_rows;
-}
-// the plan of relax(sweeps) on level lv, or nullptr (not wanted / the level does not qualify / not built yet)
-static const TiledDev* tiled_plan(const smg_hierarchy* h, int lv, int k, int sweeps)
-{
-    if (!tiled_wanted(h, lv, k, sweeps)) return nullptr;
-    const TiledBuf& B = h->lv[lv].tiled[sweeps];
-    // k columns go through the tiles in groups of up to 3, whose iterates share the workgroup's 64 KB of LDS
-    return B.view.n_tiles > 0 && (size_t)B.view.max_ext * std::min(k, 3) * sizeof(double) + TILED_LDS_STATIC <= 64 * 1024 ? &B.view : nullptr;
-}
-static int ensure_tiled(smg_hierarchy* h, int lv, int sweeps)
-{
-    Level& Lv = h->lv[lv];
-    TiledBuf& B = Lv.tiled[sweeps];
-    if (B.tried) return SMG_OK;
-    B.tried = true;
-    // Tile size (measured at C3, tools/tiled_sweep.sh): parts of 128 .. 256 rows, 512 threads (one row of every colour per thread).
-    // Smaller tiles put more CUs to work but the halo of P rings then dominates (6x redundant row updates at 64 rows: slower);
-    // larger ones run too few workgroups.
-    // Beyond 65 536 rows parts of 256 rows are more workgroups than the part has compute units (a second round of them: tools/size_sweep.py, a
-    // 69 120-row level 45.8 us per visit against 28 us at 56 320 rows): the parts grow to 512 rows so that the level stays one round up to 122 880
-    // rows (69 120 rows: 34.2 us, 77 824: 43.4 -> 32.2, 101 376: 47.5 (colour launches) -> 36.7; at 30 720 rows parts of 512 rows lose: 25.1 -> 28.0).
-    static const int rows_env = env_int("SMG_TILED_ROWS", 0), nt_env = env_int("SMG_TILED_NT", 0);
-    const int tile_rows0 = rows_env > 0 ? rows_env : std::min(512, std::max(256, (Lv.n + 239) / 240));
-    constexpr int max_ext = (64 * 1024 - TILED_LDS_STATIC) / 8;    // 64 KB of LDS, the kernel's static header included
-    // the matrix the smoother streams, in the internal numbering; entry -> index into the level's values in the caller's CSR order
-    std::vector<int> tsrc;
-    Csr AT;
-    { int rc = ensure_A_int(h, lv); if (rc) return rc; }
-    if (Lv.gs_on_transpose) AT = transpose(Lv.A_int, &tsrc);
-    const Csr& G = Lv.gs_on_transpose ? AT : Lv.A_int;
-    // a tile whose halo makes a colour's panel longer than the workgroup gets smaller tiles
-    TiledGs P;
-    int threads = 512;
-    for (int tile_rows = tile_rows0, tries = 0; tries < 3 && P.empty(); tile_rows = tile_rows * 2 / 3, tries++) {
-        threads = nt_env > 0 ? nt_env : 512;
-        P = build_tiled_gs(G, Lv.ord.color_ptr, sweeps, tile_rows, max_ext, threads);
-    }
-    if (P.empty()) return SMG_OK;
-    auto to_level_value = [&](const std::vector<int>& entries) {
-        std::vector<int> m(entries.size());
-        for (size_t i = 0; i < m.size(); i++) {
-            const int e = entries[i];
-            m[i] = e < 0 ? -1 : Lv.A_int_src[(size_t)(Lv.gs_on_transpose ? tsrc[(size_t)e] : e)];
-        }
-        return m;
-    };
-    std::vector<int> map = to_level_value(P.pentry), mapd = to_level_value(P.pdentry);
-    HIPCHK(B.hdr.upload(P.hdr)); HIPCHK(B.ext_rows.upload(P.ext_rows)); HIPCHK(B.pcol.upload(P.pcol)); HIPCHK(B.pval.upload(P.pval));
-    HIPCHK(B.prow.upload(P.prow)); HIPCHK(B.pdiag.upload(P.pdiag));
-    B.host_map = std::move(map); B.host_mapd = std::move(mapd);      // (uploaded when a value-only re-precompute first needs them: ensure_map)
-    HIPCHK(tiled_gs_prepare(P.max_ext));
-    int wmax = 0;
-    for (int t = 0; t < P.n_tiles; t++) wmax = std::max(wmax, P.hdr[(size_t)t * TILED_HDR + 2]);
-    B.view.threads = threads;
-    B.view.n_tiles = P.n_tiles; B.view.nc = P.nc; B.view.P = P.P; B.view.sweeps = sweeps; B.view.max_ext = P.max_ext; B.view.w_max = wmax;
-    B.view.hdr = B.hdr.p; B.view.ext_rows = B.ext_rows.p; B.view.pcol = B.pcol.p; B.view.pval = B.pval.p; B.view.prow = B.prow.p; B.view.pdiag = B.pdiag.p;
-    B.updates = P.updates;
-    // after a value-only re-precompute the host copy of the values is stale: take them from the device copy
-    if (h->host_stale && Lv.d_Aval.p) {
-        HIPCHK(ensure_map(B.map, B.host_map)); HIPCHK(ensure_map(B.mapd, B.host_mapd));
-        HIPCHK(launch_gather_vals(B.pval.p, Lv.d_Aval.p, B.map.p, B.pval.n, h->stream));
-        HIPCHK(launch_gather_vals(B.pdiag.p, Lv.d_Aval.p, B.mapd.p, B.pdiag.n, h->stream));
-    }
-    if (env_int("SMG_DEBUG_TILED", 0))
-        std::fprintf(stderr, "tiled relax(%d) level %d: %d rows, %d tiles x %d threads, %d phases, extended tile <= %d rows, %.2fx row updates, entries per row <= %d\n", sweeps, lv, Lv.n,
-                     P.n_tiles, threads, P.P, P.max_ext, (double)P.updates / ((double)sweeps * Lv.n), wmax);
-    return SMG_OK;
-}
-int smg::refresh_tiled_values(smg_hierarchy* h)
-{
-    for (int lv = 0; lv < h->n_levels - 1; lv++) {
-        for (int s = 1; s <= 3; s++) {
-            TiledBuf& B = h->lv[lv].tiled[s];
-            if (B.view.n_tiles > 0) {
-                HIPCHK(ensure_map(B.map, B.host_map)); HIPCHK(ensure_map(B.mapd, B.host_mapd));
-                HIPCHK(launch_gather_vals(B.pval.p, h->lv[lv].d_Aval.p, B.map.p, B.pval.n, h->stream));
-                HIPCHK(launch_gather_vals(B.pdiag.p, h->lv[lv].d_Aval.p, B.mapd.p, B.pdiag.n, h->stream));
-            }
-        }
-        WgsBuf& W = h->lv[lv].wgs;
-        if (W.view.n_pieces > 0) {
-            HIPCHK(ensure_map(W.map, W.host_map)); HIPCHK(ensure_map(W.mapd, W.host_mapd));
-            HIPCHK(launch_gather_vals(W.eval.p, h->lv[lv].d_Aval.p, W.map.p, W.eval.n, h->stream));
-            HIPCHK(launch_gather_vals(W.diag.p, h->lv[lv].d_Aval.p, W.mapd.p, W.diag.n, h->stream));
-        }
-        BgsBuf& Q = h->lv[lv].bgs;
-        if (Q.view.n_blocks > 0) {
-            HIPCHK(ensure_map(Q.map, Q.host_map)); HIPCHK(ensure_map(Q.mapd, Q.host_mapd));
-            HIPCHK(launch_gather_vals(Q.eval.p, h->lv[lv].d_Aval.p, Q.map.p, Q.eval.n, h->stream));
-            HIPCHK(launch_gather_vals(Q.udiag.p, h->lv[lv].d_Aval.p, Q.mapd.p, Q.udiag.n, h->stream));
-        }
-    }
-    return SMG_OK;
-}
-void smg::drop_tiled(smg_hierarchy* h)
-{
-    for (auto& Lv : h->lv) { for (auto& B : Lv.tiled) B = TiledBuf(); Lv.bgs = BgsBuf(); Lv.wgs = WgsBuf(); }
-}
-
-// ---- block Gauss-Seidel for solves with a multiple of 16 columns (smg_bgs.hpp): one launch per BLOCK colour -----------------
-// Which levels: scalar fp64 hierarchies, Gauss-Seidel, k % 16 == 0, at least bgs_min_rows rows (smg_hierarchy_set_block_gs; default: never;
-// SMG_BGS_MIN_ROWS; SMG_BGS=0 switches it off).  Measured at C3 (tools/bgs_cycle.py): worth it from ~500 000 rows on.
-static bool bgs_wanted(const smg_hierarchy* h, int lv, int k)
-{
-    static const int on = env_int("SMG_BGS", 1);
-    if (!on || h->bs != 1 || h->precision != 0 || k < BGS_COLS || k % BGS_COLS != 0 || lv < 0 || lv >= h->n_levels - 1 || h->bgs_min_rows < 0) return false;
-    if (level_kind(h, lv) != LV_GS) return false;
-    return h->lv[lv].n >= h->bgs_min_rows;
-}
-static const BgsBuf* bgs_plan(const smg_hierarchy* h, int lv, int k)
-{
-    if (!bgs_wanted(h, lv, k)) return nullptr;
-    const BgsBuf& B = h->lv[lv].bgs;
-    return B.view.n_blocks > 0 ? &B : nullptr;
-}
-static int ensure_bgs(smg_hierarchy* h, int lv)
-{
-    Level& Lv = h->lv[lv];
-    BgsBuf& B = Lv.bgs;
-    if (B.tried) return SMG_OK;
-    B.tried = true;
-    static const int rows_env = env_int("SMG_BGS_ROWS", 64);
-    std::vector<int> tsrc;
-    Csr AT;
-    { int rc = ensure_A_int(h, lv); if (rc) return rc; }
-    if (Lv.gs_on_transpose) AT = transpose(Lv.A_int, &tsrc);
-    const Csr& G = Lv.gs_on_transpose ? AT : Lv.A_int;
-    const auto t_plan0 = std::chrono::steady_clock::now();
-    BgsPlan P = build_bgs(G, Lv.ord.color_ptr, std::min(std::max(rows_env, 8), (int)BGS_ROWS));
-    const double plan_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_plan0).count();
-    if (P.empty()) return SMG_OK;
-    auto to_level_value = [&](const std::vector<int>& entries) {
-        std::vector<int> m(entries.size());
-        for (size_t i = 0; i < m.size(); i++) {
-            const int e = entries[i];
-            m[i] = e < 0 ? -1 : Lv.A_int_src[(size_t)(Lv.gs_on_transpose ? tsrc[(size_t)e] : e)];
-        }
-        return m;
-    };
-    const std::vector<int> map = to_level_value(P.eentry), mapd = to_level_value(P.dentry);
-    HIPCHK(B.hdr.upload(P.hdr)); HIPCHK(B.xrow.upload(P.xrow)); HIPCHK(B.ugrow.upload(P.ugrow)); HIPCHK(B.ulrow.upload(P.ulrow)); HIPCHK(B.udiag.upload(P.udiag));
-    HIPCHK(B.eidx.upload(P.eidx)); HIPCHK(B.eval.upload(P.eval)); B.host_map = map; B.host_mapd = mapd;
-    B.view.n_blocks = P.n_blocks; B.view.n_colors = P.n_colors; B.view.xrows = P.xrows;
-    B.view.hdr = B.hdr.p; B.view.xrow = B.xrow.p; B.view.ugrow = B.ugrow.p; B.view.ulrow = B.ulrow.p; B.view.udiag = B.udiag.p; B.view.eidx = B.eidx.p; B.view.eval = B.eval.p;
-    B.color_ptr = P.color_ptr; B.host_rows = P.rows; B.host_blk_ptr = P.blk_ptr; B.rim = P.rim; B.fill = P.fill;
-    // after a value-only re-precompute the host copy of the values is stale: take them from the device copy
-    if (h->host_stale && Lv.d_Aval.p) {
-        HIPCHK(ensure_map(B.map, B.host_map)); HIPCHK(ensure_map(B.mapd, B.host_mapd));
-        HIPCHK(launch_gather_vals(B.eval.p, Lv.d_Aval.p, B.map.p, B.eval.n, h->stream));
-        HIPCHK(launch_gather_vals(B.udiag.p, Lv.d_Aval.p, B.mapd.p, B.udiag.n, h->stream));
-    }
-    if (env_int("SMG_DEBUG_BGS", 0))
-        std::fprintf(stderr, "block Gauss-Seidel level %d: %d rows, %d blocks in %d colours, %.0f %% of the units' row slots hold a row of their own, rim %.3f rows read per row beyond the iterate, LDS image of %d rows; plan built in %.0f ms\n",
-                     lv, Lv.n, P.n_blocks, P.n_colors, 100.0 * P.fill, P.rim, P.xrows, plan_ms);
-    return SMG_OK;
-}
-
-// ---- wave Gauss-Seidel on the Galerkin levels of decimated hierarchies (smg_wgs.hpp): one launch per PIECE colour ------------------
-// Which levels: scalar fp64 hierarchies, Gauss-Seidel, any number of columns, SMG_WGS_MIN_ROWS <= rows <= SMG_WGS_MAX_ROWS, no one-launch relax()
-// (overlapped tiling) available; automatic mode: only levels the colour launches serve badly -- more than TILED_NCMAX colours or rows of more
-// than TILED_WMAX entries, i.e. the Galerkin levels of the reference's own hierarchies (mg_precompute).  smg_hierarchy_set_wave_gs / SMG_WGS=0|1|2.
-static int wgs_mode_now(const smg_hierarchy* h)
-{
-    static const int env = env_int("SMG_WGS", -1);
-    return env >= 0 ? (env == 0 ? 0 : env == 1 ? -1 : 1) : h->wgs_mode;      // SMG_WGS: 0 off, 1 automatic, 2 every level in range
-}
-// mode 1 (every Gauss-Seidel level in range): what the level needs to sweep piece-wise, whatever k -- such a level takes no one-launch relax (tiled_wanted)
-static bool wgs_forced(const smg_hierarchy* h, int lv)
-{
-    static const int max_rows = env_int("SMG_WGS_MAX_ROWS", 600000), min_rows = env_int("SMG_WGS_MIN_ROWS", 512);
-    if (wgs_mode_now(h) != 1 || h->bs != 1 || h->precision != 0 || lv < 0 || lv >= h->n_levels - 1 || level_kind(h, lv) != LV_GS) return false;
-    return h->lv[lv].n >= min_rows && h->lv[lv].n <= max_rows;
-}
-static bool wgs_wanted(const smg_hierarchy* h, int lv, int k)
-{
-    static const int max_rows = env_int("SMG_WGS_MAX_ROWS", 600000), min_rows = env_int("SMG_WGS_MIN_ROWS", 512);
-    const int mode = wgs_mode_now(h);
-    if (mode == 0 || h->bs != 1 || h->precision != 0 || k < 1 || lv < 0 || lv >= h->n_levels - 1) return false;      // (every k: the order of a level's sweep must not depend on how the columns are sharded)
-    if (level_kind(h, lv) != LV_GS) return false;
-    const Level& Lv = h->lv[lv];
-    if (Lv.n < min_rows || Lv.n > max_rows) return false;
-    if (mode == 1) return true;
-    const SellBuf& Gs = Lv.gs_on_transpose ? Lv.dAT : Lv.dA;
-    return Lv.ord.n_colors() > TILED_NCMAX || Gs.view.w_max > TILED_WMAX;
-}
-static const WgsBuf* wgs_plan(const smg_hierarchy* h, int lv, int k)
-{
-    if (!wgs_wanted(h, lv, k)) return nullptr;
-    const WgsBuf& B = h->lv[lv].wgs;
-    return B.view.n_pieces > 0 ? &B : nullptr;
-}
-static int ensure_wgs(smg_hierarchy* h, int lv)
-{
-    Level& Lv = h->lv[lv];
-    WgsBuf& B = Lv.wgs;
-    if (B.tried) return SMG_OK;
-    B.tried = true;
-    static const int rows_env = env_int("SMG_WGS_ROWS", WGS_ROWS), mode_env = env_int("SMG_WGS_PIECES", 1);
-    std::vector<int> tsrc;
-    Csr AT;
-    { int rc = ensure_A_int(h, lv); if (rc) return rc; }
-    if (Lv.gs_on_transpose) AT = transpose(Lv.A_int, &tsrc);
-    const Csr& G = Lv.gs_on_transpose ? AT : Lv.A_int;
-    const auto t_plan0 = std::chrono::steady_clock::now();
-    WgsPlan P = build_wgs(G, std::min(std::max(rows_env, 8), (int)WGS_ROWS), mode_env);
-    const double plan_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_plan0).count();
-    if (P.empty()) return SMG_OK;
-    auto to_level_value = [&](const std::vector<int>& entries) {
-        std::vector<int> m(entries.size());
-        for (size_t i = 0; i < m.size(); i++) {
-            const int e = entries[i];
-            m[i] = e < 0 ? -1 : Lv.A_int_src[(size_t)(Lv.gs_on_transpose ? tsrc[(size_t)e] : e)];
-        }
-        return m;
-    };
-    const std::vector<int> map = to_level_value(P.eentry), mapd = to_level_value(P.dentry);
-    HIPCHK(B.hdr.upload(P.hdr)); HIPCHK(B.grow.upload(P.grow)); HIPCHK(B.meta.upload(P.meta)); HIPCHK(B.diag.upload(P.diag)); HIPCHK(B.rim.upload(P.rim));
-    HIPCHK(B.eoff.upload(P.eoff)); HIPCHK(B.eval.upload(P.eval)); B.host_map = map; B.host_mapd = mapd;
-    B.view.n_pieces = P.n_pieces; B.view.n_colors = P.n_colors; B.view.rim_pitch = P.rim_pitch; B.view.nb_max = P.nb_max;
-    B.view.hdr = B.hdr.p; B.view.grow = B.grow.p; B.view.meta = B.meta.p; B.view.diag = B.diag.p; B.view.rim = B.rim.p; B.view.eoff = B.eoff.p; B.view.eval = B.eval.p;
-    B.color_ptr = P.color_ptr; B.host_rows = P.rows; B.host_piece_ptr = P.piece_ptr; B.rim_ratio = P.rim_ratio; B.phases_mean = P.phases_mean; B.phases_max = P.phases_max;
-    // after a value-only re-precompute the host copy of the values is stale: take them from the device copy (padding slots keep their +0.0, lanes without a row their 1.0)
-    if (h->host_stale && Lv.d_Aval.p) {
-        HIPCHK(ensure_map(B.map, B.host_map)); HIPCHK(ensure_map(B.mapd, B.host_mapd));
-        HIPCHK(launch_gather_vals(B.eval.p, Lv.d_Aval.p, B.map.p, B.eval.n, h->stream));
-        HIPCHK(launch_gather_vals(B.diag.p, Lv.d_Aval.p, B.mapd.p, B.diag.n, h->stream));
-    }
-    if (env_int("SMG_DEBUG_WGS", 0))
-        std::fprintf(stderr, "wave Gauss-Seidel level %d: %d rows, %d pieces in %d colours, phases per piece %.1f (max %d), rim %.2f rows read per row beyond the iterate, rim pitch %d; plan built in %.0f ms\n",
-                     lv, Lv.n, P.n_pieces, P.n_colors, P.phases_mean, P.phases_max, P.rim_ratio, P.rim_pitch, plan_ms);
-    return SMG_OK;
-}
-
-// Called by the first precompute for a level whose images exist, while its device half would otherwise wait for the host half (smg_precompute.cpp):
-// the plans prepare_tiled() below would build at the first solve with the handle's present selection (smoother, pre / post sweeps), one column.
-// Small levels only (a plan of tens of milliseconds at most: the 63 210-row Galerkin level of decimated C3 64 ms, its 252 834-row level 220 ms -- building
-// that one here kept level 0's images waiting and cost the precompute more than it saved the first solve).  First smg_solve on a fresh handle:
-// bunny.obj 8.4 -> 4.2 ms, ogre.obj 17 -> 11 ms (tools/first_solve.py).
-int smg::prepare_level_plans(smg_hierarchy* h, int lv)
-{
-    static const int on = env_int("SMG_EARLY_PLANS", 1), max_rows = env_int("SMG_EARLY_PLANS_MAX_ROWS", 70000);      // A/B knobs
-    if (!on || lv <= 0 || lv >= h->n_levels - 1 || h->precision != 0 || h->lv[lv].n > max_rows) return SMG_OK;
-    const int sa = h->pre, sb = h->post;
-    for (int sw : {sa, sb}) if (sw > 0 && tiled_wanted(h, lv, 1, sw)) { int rc = ensure_tiled(h, lv, sw); if (rc) return rc; }
-    if (wgs_wanted(h, lv, 1) && !h->lv[lv].wgs.tried && !tiled_plan(h, lv, 1, sa) && !tiled_plan(h, lv, 1, sb)) { int rc = ensure_wgs(h, lv); if (rc) return rc; }
-    return SMG_OK;
-}
-
-// plans + second iterate for relax(sa) / relax(sb) wherever they are wanted (host work and uploads: never inside a graph capture)
-static int prepare_tiled(smg_hierarchy* h, int k, int sa, int sb)
-{
-    for (int lv = 0; lv < h->n_levels - 1; lv++) {
-        Level& Lv = h->lv[lv];
-        for (int sw : {sa, sb}) if (tiled_wanted(h, lv, k, sw)) { int rc = ensure_tiled(h, lv, sw); if (rc) return rc; }
-        if (bgs_wanted(h, lv, k) && !Lv.bgs.tried) { drop_graphs(h); int rc = ensure_bgs(h, lv); if (rc) return rc; }
-        if (wgs_wanted(h, lv, k) && !Lv.wgs.tried && !tiled_plan(h, lv, k, sa) && !tiled_plan(h, lv, k, sb)) { drop_graphs(h); int rc = ensure_wgs(h, lv); if (rc) return rc; }
-        if ((tiled_plan(h, lv, k, sa) || tiled_plan(h, lv, k, sb)) && Lv.t.n < (size_t)Lv.n * std::max(h->kcap, 1)) {
-            drop_graphs(h);
-            HIPCHK(Lv.t.alloc((size_t)Lv.n * std::max(h->kcap, 1)));
-            HIPCHK(hipMemsetAsync(Lv.t.p, 0, Lv.t.n * sizeof(double), h->stream));
-        }
-    }
-    return SMG_OK;
-}
-
 static int ensure_work(smg_hierarchy* h, int k)
 {
     const int L = h->n_levels;
@@ -372,7 +84,7 @@ static int ensure_work(smg_hierarchy* h, int k)
             h->c_view.work = h->c_work.p;
         }
     }
-    int rc = prepare_tiled(h, k, h->pre, h->post);
+    int rc = prepare_sweep_plans(h, k, h->pre, h->post);
     if (rc) return rc;
     return ensure_spectral_bounds(h);
 }
@@ -587,34 +299,25 @@ static const std::vector<int>& colour_slices(const smg_hierarchy* h, const Level
     return (Lv.gs_on_transpose ? Lv.dAT : Lv.dA).color_slice_ptr;
 }
 
-// what of a level's first pre-smoothing sweep exists when its V-cycle starts
-enum { FIRST_NONE = 0,
-       FIRST_LAUNCH = 1,   // its first launch, produced by the restriction launch of the finer level (FirstColour): the first colour
-                           // (Gauss-Seidel, in Lv.u) or the whole first sweep / step (Jacobi / Chebyshev, in Lv.t)
-       FIRST_SWEEP = 2 };  // level 0 inside an outer iteration: the whole first sweep / step, produced out of place into Lv.t by the
-                           // launches that also formed the outer residual (enqueue_head)
-
-// `iters` forward Gauss-Seidel sweeps in place: one launch per colour (reference relax(), src/mg_VCycle.cpp:113-178)
-// first = FIRST_LAUNCH: the first colour of the first sweep is already in u.  FIRST_SWEEP: the whole first sweep is in `t`: the second
-// sweep goes from t back into u (out-of-place colour launches: same values), the rest run in place on u; needs iters >= 2.
+// `iters` forward Gauss-Seidel sweeps in place, with the level's wave / block plan sp (sweep_plan) or one launch per colour (reference relax(),
+// src/mg_VCycle.cpp:113-178).  first = FIRST_LAUNCH: the first colour of the first sweep is already in u.  FIRST_SWEEP: the whole first sweep is in `t`:
+// the second sweep goes from t back into u (out-of-place colour launches: same values), the rest run in place on u; needs iters >= 2.
 template <typename T>
-static int enqueue_gs(smg_hierarchy* h, int lv, const T* b, T* u, int k, int iters, const Ctrl* ctrl, int first = FIRST_NONE, T* t = nullptr)
+static int enqueue_gs(smg_hierarchy* h, int lv, const SweepPlan& sp, const T* b, T* u, int k, int iters, const Ctrl* ctrl, int first = FIRST_NONE, T* t = nullptr)
 {
     Level& Lv = h->lv[lv];
     ProfGuard pg(h, "MG: relaxation");  // PROFC_NODE at src/mg_VCycle.cpp:121
-    if (std::is_same<T, double>::value && first == FIRST_NONE) {
-        if (const WgsBuf* W = wgs_plan(h, lv, k)) {      // Galerkin levels of decimated hierarchies: one launch per piece colour (smg_wgs.hpp)
-            for (int it = 0; it < iters; it++)
-                for (size_t c = 0; c + 1 < W->color_ptr.size(); c++)
-                    HIPCHK(launch_wgs(W->view, W->color_ptr[c], W->color_ptr[c + 1], (const double*)b, (double*)u, k, ctrl, h->stream));
-            return SMG_OK;
-        }
-        if (const BgsBuf* Q = bgs_plan(h, lv, k)) {      // many columns: one launch per block colour (smg_bgs.hpp)
-            for (int it = 0; it < iters; it++)
-                for (size_t c = 0; c + 1 < Q->color_ptr.size(); c++)
-                    HIPCHK(launch_bgs(Q->view, Q->color_ptr[c], Q->color_ptr[c + 1], (const double*)b, (double*)u, k, ctrl, h->stream));
-            return SMG_OK;
-        }
+    if (const WgsBuf* W = sp.wave) {      // Galerkin levels of decimated hierarchies: one launch per piece colour (fp64)
+        for (int it = 0; it < iters; it++)
+            for (size_t c = 0; c + 1 < W->color_ptr.size(); c++)
+                HIPCHK(launch_wgs(W->view, W->color_ptr[c], W->color_ptr[c + 1], (const double*)b, (double*)u, k, ctrl, h->stream));
+        return SMG_OK;
+    }
+    if (const BgsBuf* Q = sp.block) {     // many columns: one launch per block colour (fp64)
+        for (int it = 0; it < iters; it++)
+            for (size_t c = 0; c + 1 < Q->color_ptr.size(); c++)
+                HIPCHK(launch_bgs(Q->view, Q->color_ptr[c], Q->color_ptr[c + 1], (const double*)b, (double*)u, k, ctrl, h->stream));
+        return SMG_OK;
     }
     const std::vector<int>& cs = colour_slices(h, Lv);
     for (int it = first == FIRST_SWEEP ? 1 : 0; it < iters; it++)
@@ -625,25 +328,14 @@ static int enqueue_gs(smg_hierarchy* h, int lv, const T* b, T* u, int k, int ite
     return SMG_OK;
 }
 
-// relax(iters) as one launch (overlapped tiling): from buf[*cur] into the other buffer, flips *cur.  fp64 only.
-static int enqueue_gs_tiled(smg_hierarchy* h, int lv, const TiledDev& plan, const double* b, double* const buf[2], int* cur, int k, const Ctrl* ctrl)
+// relax(iters) as one launch (overlapped tiling, fp64): from buf[*cur] into the other buffer, flips *cur
+template <typename T>
+static int enqueue_gs_tiled(smg_hierarchy* h, const TiledDev& plan, const T* b, T* const buf[2], int* cur, int k, const Ctrl* ctrl)
 {
     ProfGuard pg(h, "MG: relaxation");
-    HIPCHK(launch_tiled_gs(plan, buf[*cur], b, buf[1 - *cur], k, ctrl, h->stream));
+    HIPCHK(launch_tiled_gs(plan, (const double*)buf[*cur], (const double*)b, (double*)buf[1 - *cur], k, ctrl, h->stream));
     *cur ^= 1;
     return SMG_OK;
-}
-template <typename T> static const TiledDev* tiled_for(const smg_hierarchy*, Level&, int, int, int) { return nullptr; }
-template <> const TiledDev* tiled_for<double>(const smg_hierarchy* h, Level& Lv, int lv, int k, int sweeps)
-{
-    const TiledDev* p = tiled_plan(h, lv, k, sweeps);
-    return (p && Lv.t.p) ? p : nullptr;
-}
-template <typename T> static int enqueue_gs_tiled_t(smg_hierarchy*, int, const TiledDev&, const T*, T* const*, int*, int, const Ctrl*) { return SMG_ERR_INVALID; }
-template <> int enqueue_gs_tiled_t<double>(smg_hierarchy* h, int lv, const TiledDev& plan, const double* b, double* const* buf, int* cur, int k, const Ctrl* ctrl)
-{
-    double* const two[2] = {buf[0], buf[1]};
-    return enqueue_gs_tiled(h, lv, plan, b, two, cur, k, ctrl);
 }
 
 // `iters` damped-Jacobi sweeps, ping-pong between buf[0] and buf[1]: sweep s reads buf[*cur], writes the other, flips *cur.
@@ -700,9 +392,8 @@ static int enqueue_vcycle_t(smg_hierarchy* h, int lv, int k, int pre, int post, 
     T* const buf[2] = {Prec<T>::u(Lv), Prec<T>::t(Lv)};   // Jacobi-type levels ping-pong; the level's result always ends in buf[0] = u
     int cur = 0;
     // Gauss-Seidel levels whose relax() runs as one out-of-place launch (overlapped tiling): they ping-pong like the Jacobi-type ones.
-    // (Not when the first sweep already exists: level 0 inside an outer iteration, FIRST_SWEEP.)
-    const TiledDev* tl_pre = (kind == LV_GS && pre > 0 && first != FIRST_SWEEP) ? tiled_for<T>(h, Lv, lv, k, pre) : nullptr;
-    const TiledDev* tl_post = (kind == LV_GS && post > 0) ? tiled_for<T>(h, Lv, lv, k, post) : nullptr;
+    const bool fp64 = std::is_same<T, double>::value;
+    const SweepPlan sp_pre = sweep_plan(h, lv, k, pre, fp64, first), sp_post = sweep_plan(h, lv, k, post, fp64, FIRST_NONE);
     int rc;
     if (kind == LV_JACOBI) {
         if (first_done) cur = 1;
@@ -710,8 +401,8 @@ static int enqueue_vcycle_t(smg_hierarchy* h, int lv, int k, int pre, int post, 
     } else if (kind == LV_CHEBY) {
         if (first_done) cur = 1;
         rc = enqueue_cheby<T>(h, lv, Prec<T>::b(Lv), buf, &cur, k, pre, ctrl, first_done);                         // :36
-    } else if (tl_pre) rc = enqueue_gs_tiled_t<T>(h, lv, *tl_pre, Prec<T>::b(Lv), buf, &cur, k, ctrl);               // :36, one launch
-    else rc = enqueue_gs<T>(h, lv, Prec<T>::b(Lv), buf[0], k, pre, ctrl, first, buf[1]);                          // :36
+    } else if (sp_pre.tiled) rc = enqueue_gs_tiled<T>(h, *sp_pre.tiled, Prec<T>::b(Lv), buf, &cur, k, ctrl);                    // :36, one launch
+    else rc = enqueue_gs<T>(h, lv, sp_pre, Prec<T>::b(Lv), buf[0], k, pre, ctrl, first, buf[1]);                  // :36
     if (rc) return rc;
     {   // r = B - A u  (:40-42)
         ProfGuard pg(h, "MG: residual");
@@ -723,9 +414,9 @@ static int enqueue_vcycle_t(smg_hierarchy* h, int lv, int k, int pre, int post, 
     const SellBuf& Gc = Lc.gs_on_transpose ? Lc.dAT : Lc.dA;
     const int kind_c = level_kind(h, lv + 1);
     const bool jac_c = kind_c != LV_GS;
-    // (block hierarchies: the first launch of a coarse sweep is not a plain division -- row 3v+1 of the first colour already reads 3v)
-    const bool tiled_c = level_kind(h, lv + 1) == LV_GS && pre > 0 && tiled_for<T>(h, Lc, lv + 1, k, pre) != nullptr;   // the coarse level runs all its phases itself
-    const bool fuse = h->bs == 1 && !tiled_c && !(std::is_same<T, double>::value && (bgs_plan(h, lv + 1, k) || wgs_plan(h, lv + 1, k))) && fuse_first_colour() && lv + 1 < L - 1 && pre > 0 && Prec<T>::has_vals(Prec<T>::G(Lc)) && (jac_c ? Gc.n_all > 0 : Gc.n_first > 0);
+    // (block hierarchies: the first launch of a coarse sweep is not a plain division -- row 3v+1 of the first colour already reads 3v; a coarse level with
+    // a sweep plan runs all its phases itself)
+    const bool fuse = h->bs == 1 && sweep_plan(h, lv + 1, k, pre, fp64, FIRST_NONE).colours() && fuse_first_colour() && lv + 1 < L - 1 && pre > 0 && Prec<T>::has_vals(Prec<T>::G(Lc)) && (jac_c ? Gc.n_all > 0 : Gc.n_first > 0);
     const int kt = k * h->bs;   // block hierarchies: dP / dPT hold the vertex-level factor of P (x) I_3, applied to 3 k columns
     {   // rc = PT r  (:43-44, :80) and uc = 0 (:46-47) in one launch: both are indexed by the coarse row
         ProfGuard pg(h, "MG: restrict");
@@ -752,16 +443,16 @@ static int enqueue_vcycle_t(smg_hierarchy* h, int lv, int k, int pre, int post, 
         // the last sweep lands in u.
         ProfGuard pg(h, "MG: prolong");
         int dst = cur;
-        const int flips = tl_post ? 1 : kind == LV_CHEBY ? (post > 0 ? post + 1 : 0) : post;   // buffer switches of the post-smoothing
-        if ((jac || tl_post) && ((cur + flips) & 1)) dst = 1 - cur;
-        if (!jac && !tl_post && cur == 1) dst = 0;      // in-place Gauss-Seidel sweeps follow: they work on u
+        const int flips = sp_post.tiled ? 1 : kind == LV_CHEBY ? (post > 0 ? post + 1 : 0) : post;   // buffer switches of the post-smoothing
+        if ((jac || sp_post.tiled) && ((cur + flips) & 1)) dst = 1 - cur;
+        if (!jac && !sp_post.tiled && cur == 1) dst = 0;      // in-place Gauss-Seidel sweeps follow: they work on u
         HIPCHK(Prec<T>::sell(SELL_ADD, Prec<T>::P(Lc), 0, Prec<T>::P(Lc).n_slices, Prec<T>::u(Lc), buf[cur], buf[dst], kt, ctrl, h->stream));
         cur = dst;
     }
     if (kind == LV_CHEBY) return enqueue_cheby<T>(h, lv, Prec<T>::b(Lv), buf, &cur, k, post, ctrl);   // :57  (ends with cur == 0)
     if (jac) return enqueue_jacobi<T>(h, lv, Prec<T>::b(Lv), buf, &cur, k, post, ctrl);   // :57  (ends with cur == 0)
-    if (tl_post) return enqueue_gs_tiled_t<T>(h, lv, *tl_post, Prec<T>::b(Lv), buf, &cur, k, ctrl);   // :57  (ends with cur == 0)
-    return enqueue_gs<T>(h, lv, Prec<T>::b(Lv), buf[0], k, post, ctrl);                    // :57
+    if (sp_post.tiled) return enqueue_gs_tiled<T>(h, *sp_post.tiled, Prec<T>::b(Lv), buf, &cur, k, ctrl);   // :57  (ends with cur == 0)
+    return enqueue_gs<T>(h, lv, sp_post, Prec<T>::b(Lv), buf[0], k, post, ctrl);          // :57
 }
 
 static int enqueue_vcycle(smg_hierarchy* h, int lv, int k, int pre, int post, const Ctrl* ctrl, int first = FIRST_NONE)
@@ -776,23 +467,14 @@ static int enqueue_vcycle32(smg_hierarchy* h, int lv, int k, int pre, int post, 
 // relax() on caller-provided device vectors (pieces, raw interface): the result always ends in u
 static int enqueue_relax(smg_hierarchy* h, int lv, const double* b, double* u, int k, int iters, const Ctrl* ctrl)
 {
-    if (!level_is_jacobi(h, lv)) {
-        Level& Lg = h->lv[lv];
-        if (const TiledDev* tl = tiled_for<double>(h, Lg, lv, k, iters)) {
-            double* const two[2] = {u, Lg.t.p};
-            int c2 = 0;
-            int rc = enqueue_gs_tiled(h, lv, *tl, b, two, &c2, k, ctrl);
-            if (rc) return rc;
-            HIPCHK(hipMemcpyAsync(u, Lg.t.p, (size_t)Lg.n * k * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            return SMG_OK;
-        }
-        return enqueue_gs<double>(h, lv, b, u, k, iters, ctrl);
-    }
     Level& Lv = h->lv[lv];
-    double* const buf[2] = {u, Lv.t.p};
+    const int kind = level_kind(h, lv);
+    const SweepPlan sp = sweep_plan(h, lv, k, iters, true, FIRST_NONE);
+    if (kind == LV_GS && !sp.tiled) return enqueue_gs<double>(h, lv, sp, b, u, k, iters, ctrl);
+    double* const buf[2] = {u, Lv.t.p};      // Jacobi-type levels and the one-launch relax() ping-pong
     int cur = 0;
-    int rc = level_kind(h, lv) == LV_CHEBY ? enqueue_cheby<double>(h, lv, b, buf, &cur, k, iters, ctrl)
-                                           : enqueue_jacobi<double>(h, lv, b, buf, &cur, k, iters, ctrl);
+    int rc = kind == LV_GS ? enqueue_gs_tiled<double>(h, *sp.tiled, b, buf, &cur, k, ctrl)
+             : kind == LV_CHEBY ? enqueue_cheby<double>(h, lv, b, buf, &cur, k, iters, ctrl) : enqueue_jacobi<double>(h, lv, b, buf, &cur, k, iters, ctrl);
     if (rc) return rc;
     if (cur == 1) HIPCHK(hipMemcpyAsync(u, Lv.t.p, (size_t)Lv.n * k * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return SMG_OK;
@@ -810,9 +492,9 @@ static bool head_fusable(smg_hierarchy* h, int k)
     if (!on || h->precision != 0 || h->n_levels < 2 || h->prof_on || h->bs != 1 || h->union_m > 0) return false;      // (a union needs the residual VECTOR: per-member norms)
     Level& L0 = h->lv[0];
     if (L0.gs_on_transpose) return false;
-    if (bgs_plan(h, 0, k) || wgs_plan(h, 0, k)) return false;   // block- / piece-sequential sweeps run in place; their head is the residual launch
-    // a level 0 whose relax(pre) is ONE launch (overlapped tiling): residual launch + one launch beat a head of (colours x 2) launches
-    if (level_kind(h, 0) == LV_GS && tiled_plan(h, 0, k, h->pre) && L0.t.p) return false;
+    // block- / piece-sequential sweeps run in place: their head is the residual launch; a level 0 whose relax(pre) is ONE launch (overlapped tiling):
+    // residual launch + one launch beat a head of (colours x 2) launches
+    if (!sweep_plan(h, 0, k, h->pre, true, FIRST_NONE).colours()) return false;
     const int kind = level_kind(h, 0);
     return kind == LV_GS ? h->pre >= 2 : h->pre >= 1;
 }
@@ -1646,16 +1328,9 @@ extern "C" int smg_raw_outer_iteration(smg_hierarchy* h, int n_iter)
 
 static int piece_prolog(smg_hierarchy* h, int lv, int k, const char* who, bool need_coarser);
 
-extern "C" int smg_bench_vcycle(smg_hierarchy* h, int lv, int k, int pre, int post, int reps, double* us_per_cycle)
+// replays of graph g (3 warm, then `reps` timed): microseconds per replay; destroys g
+static int time_graph(smg_hierarchy* h, hipGraphExec_t g, int reps, double* us)
 {
-    int rc = piece_prolog(h, lv, k, "smg_bench_vcycle", false);
-    if (rc) return rc;
-    DeviceScope dsc(h->device);
-    if (reps < 1 || !us_per_cycle) return fail(SMG_ERR_INVALID, "smg_bench_vcycle: bad arguments");
-    if ((rc = prepare_tiled(h, k, pre, post))) return rc;
-    hipGraphExec_t g = nullptr;
-    rc = capture_graph(h, &g, [&]() { return enqueue_vcycle(h, lv, k, pre, post, nullptr); });
-    if (rc) return rc;
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
@@ -1666,61 +1341,23 @@ extern "C" int smg_bench_vcycle(smg_hierarchy* h, int lv, int k, int pre, int po
     HIPCHK(hipStreamSynchronize(h->stream));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *us_per_cycle = 1e3 * ms / reps;
+    *us = 1e3 * ms / reps;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipGraphExecDestroy(g);
-    return coarse_stall_check(h);
-}
-
-extern "C" int smg_hierarchy_set_block_gs(smg_hierarchy* h, int min_rows)
-{
-    if (!h) return fail(SMG_ERR_INVALID, "smg_hierarchy_set_block_gs: null handle");
-    if (h->in_solve) return fail(SMG_ERR_INVALID, "smg_hierarchy_set_block_gs called during a split-phase solve");
-    if (min_rows != h->bgs_min_rows) { h->bgs_min_rows = min_rows; if (h->stream) drop_graphs(h); }
     return SMG_OK;
 }
-extern "C" int smg_level_get_block_gs_order(smg_hierarchy* h, int lv, int k, int* n_blocks, int* n_colors, int* color_ptr, int* blk_ptr, int* rows, double* stats)
-{
-    int rc = check_ready(h, "smg_level_get_block_gs_order");
-    if (rc) return rc;
-    if (lv < 0 || lv >= h->n_levels || k < 1) return fail(SMG_ERR_INVALID, "smg_level_get_block_gs_order: bad level / k");
-    if (!bgs_wanted(h, lv, k)) return 0;
-    if (!h->lv[lv].bgs.tried) { drop_graphs(h); if ((rc = ensure_bgs(h, lv))) return rc; }
-    const BgsBuf* Q = bgs_plan(h, lv, k);
-    if (!Q) return 0;
-    if (n_blocks) *n_blocks = Q->view.n_blocks;
-    if (n_colors) *n_colors = Q->view.n_colors;
-    if (color_ptr) std::copy(Q->color_ptr.begin(), Q->color_ptr.end(), color_ptr);
-    if (blk_ptr) std::copy(Q->host_blk_ptr.begin(), Q->host_blk_ptr.end(), blk_ptr);
-    if (rows) std::copy(Q->host_rows.begin(), Q->host_rows.end(), rows);
-    if (stats) { stats[0] = Q->rim; stats[1] = Q->fill; }
-    return 1;
-}
 
-extern "C" int smg_hierarchy_set_wave_gs(smg_hierarchy* h, int mode)
+extern "C" int smg_bench_vcycle(smg_hierarchy* h, int lv, int k, int pre, int post, int reps, double* us_per_cycle)
 {
-    if (!h) return fail(SMG_ERR_INVALID, "smg_hierarchy_set_wave_gs: null handle");
-    if (h->in_solve) return fail(SMG_ERR_INVALID, "smg_hierarchy_set_wave_gs called during a split-phase solve");
-    if (mode < -1 || mode > 1) return fail(SMG_ERR_INVALID, "smg_hierarchy_set_wave_gs: mode must be -1 (automatic), 0 (never) or 1 (every Gauss-Seidel level in range)");
-    if (mode != h->wgs_mode) { h->wgs_mode = mode; if (h->stream) drop_graphs(h); }
-    return SMG_OK;
-}
-extern "C" int smg_level_get_wave_gs_order(smg_hierarchy* h, int lv, int k, int* n_pieces, int* n_colors, int* color_ptr, int* piece_ptr, int* rows, double* stats)
-{
-    int rc = check_ready(h, "smg_level_get_wave_gs_order");
+    int rc = piece_prolog(h, lv, k, "smg_bench_vcycle", false);
     if (rc) return rc;
-    if (lv < 0 || lv >= h->n_levels || k < 1) return fail(SMG_ERR_INVALID, "smg_level_get_wave_gs_order: bad level / k");
-    if (!wgs_wanted(h, lv, k)) return 0;
     DeviceScope dsc(h->device);
-    if ((rc = prepare_tiled(h, k, h->pre, h->post))) return rc;      // the one-launch relax() has precedence where it exists: decided there
-    const WgsBuf* Q = wgs_plan(h, lv, k);
-    if (!Q || tiled_plan(h, lv, k, h->pre) || tiled_plan(h, lv, k, h->post)) return 0;
-    if (n_pieces) *n_pieces = Q->view.n_pieces;
-    if (n_colors) *n_colors = Q->view.n_colors;
-    if (color_ptr) std::copy(Q->color_ptr.begin(), Q->color_ptr.end(), color_ptr);
-    if (piece_ptr) std::copy(Q->host_piece_ptr.begin(), Q->host_piece_ptr.end(), piece_ptr);
-    if (rows) std::copy(Q->host_rows.begin(), Q->host_rows.end(), rows);
-    if (stats) { stats[0] = Q->rim_ratio; stats[1] = Q->phases_mean; stats[2] = (double)Q->phases_max; }
-    return 1;
+    if (reps < 1 || !us_per_cycle) return fail(SMG_ERR_INVALID, "smg_bench_vcycle: bad arguments");
+    if ((rc = prepare_sweep_plans(h, k, pre, post))) return rc;
+    hipGraphExec_t g = nullptr;
+    rc = capture_graph(h, &g, [&]() { return enqueue_vcycle(h, lv, k, pre, post, nullptr); });
+    if (rc) return rc;
+    if ((rc = time_graph(h, g, reps, us_per_cycle))) return rc;
+    return coarse_stall_check(h);
 }
 
 extern "C" int smg_bench_relax(smg_hierarchy* h, int lv, int k, int sweeps, int reps, double* us_per_call)
@@ -1729,24 +1366,12 @@ extern "C" int smg_bench_relax(smg_hierarchy* h, int lv, int k, int sweeps, int 
     if (rc) return rc;
     DeviceScope dsc(h->device);
     if (reps < 1 || sweeps < 1 || !us_per_call) return fail(SMG_ERR_INVALID, "smg_bench_relax: bad arguments");
-    if ((rc = prepare_tiled(h, k, sweeps, sweeps))) return rc;
+    if ((rc = prepare_sweep_plans(h, k, sweeps, sweeps))) return rc;
     Level& Lv = h->lv[lv];
     hipGraphExec_t g = nullptr;
     rc = capture_graph(h, &g, [&]() { return enqueue_relax(h, lv, Lv.b.p, Lv.u.p, k, sweeps, nullptr); });
     if (rc) return rc;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    for (int i = 0; i < 3; i++) HIPCHK(hipGraphLaunch(g, h->stream));
-    HIPCHK(hipEventRecord(e0, h->stream));
-    for (int i = 0; i < reps; i++) HIPCHK(hipGraphLaunch(g, h->stream));
-    HIPCHK(hipEventRecord(e1, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *us_per_call = 1e3 * ms / reps;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipGraphExecDestroy(g);
-    return SMG_OK;
+    return time_graph(h, g, reps, us_per_call);
 }
 
 extern "C" int smg_synchronize(smg_hierarchy* h)
@@ -1836,7 +1461,7 @@ extern "C" int smg_relax(smg_hierarchy* h, int lv, const double* B, int k, int i
     if (rc) return rc;
     DeviceScope dsc(h->device);
     Level& Lv = h->lv[lv];
-    if ((rc = prepare_tiled(h, k, iters, iters))) return rc;
+    if ((rc = prepare_sweep_plans(h, k, iters, iters))) return rc;
     if ((rc = put_block(h, lv, B, k, Lv.b.p))) return rc;
     if ((rc = put_block(h, lv, u, k, Lv.u.p))) return rc;
     if ((rc = enqueue_relax(h, lv, Lv.b.p, Lv.u.p, k, iters, nullptr))) return rc;
@@ -1862,7 +1487,7 @@ extern "C" int smg_vcycle(smg_hierarchy* h, const double* B, int pre, int post, 
     if (rc) return rc;
     DeviceScope dsc(h->device);
     Level& Lv = h->lv[lv];
-    if ((rc = prepare_tiled(h, k, pre, post))) return rc;
+    if ((rc = prepare_sweep_plans(h, k, pre, post))) return rc;
     if ((rc = put_block(h, lv, B, k, Lv.b.p))) return rc;
     if ((rc = put_block(h, lv, u, k, Lv.u.p))) return rc;
     if ((rc = enqueue_vcycle(h, lv, k, pre, post, nullptr))) return rc;
@@ -1930,7 +1555,7 @@ extern "C" int smg_raw_relax(smg_hierarchy* h, int lv, const double* b, double* 
     DeviceScope dsc(h->device);
     if (lv < 0 || lv >= h->n_levels - 1 || k < 1) return fail(SMG_ERR_INVALID, "smg_raw_relax: bad level");
     if ((rc = ensure_work(h, k))) return rc;   // second iterate / update vector / spectral bound of a Jacobi-type level
-    if ((rc = prepare_tiled(h, k, iters, iters))) return rc;
+    if ((rc = prepare_sweep_plans(h, k, iters, iters))) return rc;
     return enqueue_relax(h, lv, b, u, k, iters, nullptr);
 }
 

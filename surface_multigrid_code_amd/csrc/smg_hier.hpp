@@ -66,6 +66,7 @@ struct DevBuf {
         return e;
     }
     hipError_t ensure(size_t count) { return count <= n ? hipSuccess : alloc(count); }
+    long long bytes() const { return (long long)(n * sizeof(T)); }
     template <class Alloc>
     hipError_t upload(const std::vector<T, Alloc>& v)
     {
@@ -115,37 +116,46 @@ struct Bsr3Buf {  // device image of one block (3 x 3) SELL matrix, smg_bsr3.hpp
     hipError_t upload(const Bsr3Sell& S);
 };
 
-struct TiledBuf {  // device image of one overlapped-tiling plan (smg_tiled.hpp)
-    DevBuf<int> hdr, ext_rows, pcol, prow, map, mapd;   // map / mapd: value slot / diagonal of a panel row -> index into Level::d_Aval (value-only re-precompute), -1: leave
-    DevBuf<double> pval, pdiag;
-    TiledDev view;
-    long updates = 0;
-    std::vector<int> host_map, host_mapd;   // the maps before their first use (uploaded by the first value-only re-precompute)
-    bool tried = false;      // a plan was attempted for this (level, sweeps): empty view = the level does not qualify
+// The level values a sweep plan holds copies of -- its entry slots and its diagonals -- and the maps that refresh them from Level::d_Aval
+// (slot -> index there, -1: padding the builder wrote; smg_sweep_plans.cpp: refresh_plan_values).  The maps are only needed by a value-only
+// re-precompute: they stay on the host until the first one (a quarter of a plan's bytes).
+struct PlanValues {
+    DevBuf<double> val, diag;
+    DevBuf<int> map, mapd;
+    std::vector<int> host_map, host_mapd;
+    long long bytes() const { return val.bytes() + diag.bytes() + map.bytes() + mapd.bytes(); }
 };
 
-struct BgsBuf {  // device image of the block-sequential Gauss-Seidel plan of a level (smg_bgs.hpp)
-    DevBuf<int> hdr, xrow, ugrow, ulrow, eidx, map, mapd;   // map / mapd: value slot / diagonal slot -> index into Level::d_Aval (value-only re-precompute), -1 padding
-    DevBuf<double> eval, udiag;
+struct TiledBuf {  // device image of one overlapped-tiling plan (smg_tiled.hpp); values: pval / pdiag
+    DevBuf<int> hdr, ext_rows, pcol, prow;
+    PlanValues v;
+    TiledDev view;
+    bool tried = false;      // a plan was attempted for this (level, sweeps): empty view = the level does not qualify
+    long long bytes() const { return hdr.bytes() + ext_rows.bytes() + pcol.bytes() + prow.bytes() + v.bytes(); }
+};
+
+struct BgsBuf {  // device image of the block-sequential Gauss-Seidel plan of a level (smg_bgs.hpp); values: eval / udiag
+    DevBuf<int> hdr, xrow, ugrow, ulrow, eidx;
+    PlanValues v;
     BgsDev view;
     std::vector<int> color_ptr;      // blocks of colour c
-    std::vector<int> host_map, host_mapd;          // the maps before their first use (uploaded by the first value-only re-precompute)
     std::vector<int> host_rows, host_blk_ptr;      // the bgs order (position -> internal row), positions per block: introspection, tests
     double rim = 0.0, fill = 0.0;
     bool tried = false;
+    long long bytes() const { return hdr.bytes() + xrow.bytes() + ugrow.bytes() + ulrow.bytes() + eidx.bytes() + v.bytes(); }
 };
 
-struct WgsBuf {  // device image of the wave Gauss-Seidel plan of a level (smg_wgs.hpp)
-    DevBuf<int> hdr, grow, meta, rim, map, mapd;   // map / mapd: value slot / diagonal slot -> index into Level::d_Aval (value-only re-precompute), -1 padding
+struct WgsBuf {  // device image of the wave Gauss-Seidel plan of a level (smg_wgs.hpp); values: eval / diag
+    DevBuf<int> hdr, grow, meta, rim;
     DevBuf<unsigned> eoff;
-    DevBuf<double> eval, diag;
+    PlanValues v;
     WgsDev view;
     std::vector<int> color_ptr;      // pieces of colour c
-    std::vector<int> host_map, host_mapd;          // the maps before their first use (uploaded by the first value-only re-precompute)
     std::vector<int> host_rows, host_piece_ptr;    // the wgs order (position -> internal row), positions per piece: introspection, tests
     double rim_ratio = 0.0, phases_mean = 0.0;
     int phases_max = 0;
     bool tried = false;
+    long long bytes() const { return hdr.bytes() + grow.bytes() + meta.bytes() + rim.bytes() + eoff.bytes() + v.bytes(); }
 };
 
 // one element of std::vector<mg_data> (reference src/mg_data.h:11-27)

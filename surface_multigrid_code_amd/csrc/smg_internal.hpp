@@ -2,6 +2,7 @@
 //   smg_capi.cpp        errors, the handle (container, setters, introspection), profc mirror, mesh numerics shims
 //   smg_precompute.cpp  min_quad_with_fixed_mg_precompute: host sparse algebra, device images, value-only re-precompute, assembly
 //   smg_cycle.cpp       mg_VCycle / min_quad_with_fixed_mg_solve: launch sequence of a cycle, graph cache, outer loop, pieces
+//   smg_sweep_plans.cpp the plan-based Gauss-Seidel sweeps: which one a level uses, building, value refresh, introspection, self-checks
 //   smg_hierarchy_io.cpp mg_precompute / mg_precompute_block builders, point queries, .smgh files
 // Nothing here is part of the ABI.
 #pragma once
@@ -87,8 +88,6 @@ struct StageTimer {
 
 int ensure_device(smg_hierarchy* h);            // first use of the device by a handle: stream, control block
 void drop_graphs(smg_hierarchy* h);             // the cached hipGraphs no longer describe the handle
-// the sweep plans a small level would want for a default solve (one column, the handle's pre / post sweeps), built ahead of the first solve (smg_cycle.cpp)
-int prepare_level_plans(smg_hierarchy* h, int lv);
 int check_ready(const smg_hierarchy* h, const char* who);
 int check_cycle_opts(const smg_solve_opts& o);  // the option checks of smg_solve_begin (change nothing)
 // what smg_eigs (smg_eig.cpp) borrows from the solve (smg_cycle.cpp): latch the cycle's options and make the level vectors ready for k
@@ -136,7 +135,27 @@ enum { LV_GS = 0, LV_JACOBI = 1, LV_CHEBY = 2 };
 int level_kind(const smg_hierarchy* h, int lv);   // the smoother of a level under the handle's selection
 inline bool level_is_jacobi(const smg_hierarchy* h, int lv) { return level_kind(h, lv) != LV_GS; }   // needs the second iterate buffer
 
-int refresh_tiled_values(smg_hierarchy* h);     // the overlapped-tiling plans hold copies of the level values (value-only re-precompute)
-void drop_tiled(smg_hierarchy* h);              // ... and describe one matrix image: dropped when the images are rebuilt
+// what of a level's first pre-smoothing sweep exists when its V-cycle starts
+enum { FIRST_NONE = 0,
+       FIRST_LAUNCH = 1,   // its first launch, produced by the restriction launch of the finer level (FirstColour): the first colour
+                           // (Gauss-Seidel, in Lv.u) or the whole first sweep / step (Jacobi / Chebyshev, in Lv.t)
+       FIRST_SWEEP = 2 };  // level 0 inside an outer iteration: the whole first sweep / step, produced out of place into Lv.t by the
+                           // launches that also formed the outer residual (enqueue_head)
+
+// ---- Gauss-Seidel sweep plans (smg_sweep_plans.cpp) -------------------------------------------------------------------------------
+// How relax(sweeps) runs on a Gauss-Seidel level: at most one plan is set; none: one launch per colour.
+struct SweepPlan {
+    const TiledDev* tiled = nullptr;   // overlapped tiling: one out-of-place launch (smg_tiled.hpp)
+    const WgsBuf* wave = nullptr;      // wave Gauss-Seidel: one launch per piece colour (smg_wgs.hpp)
+    const BgsBuf* block = nullptr;     // block Gauss-Seidel: one launch per block colour (smg_bgs.hpp)
+    bool colours() const { return !tiled && !wave && !block; }
+};
+// level lv, k columns, fp64 or fp32 cycle, `first` (FIRST_*): the plan its relax(sweeps) runs with (built plans only: prepare_sweep_plans)
+SweepPlan sweep_plan(const smg_hierarchy* h, int lv, int k, int sweeps, bool fp64, int first);
+int prepare_sweep_plans(smg_hierarchy* h, int k, int sa, int sb);   // plans + second iterate for relax(sa) / relax(sb) (never inside a graph capture)
+// the sweep plans a small level would want for a default solve (one column, the handle's pre / post sweeps), built ahead of the first solve
+int prepare_level_plans(smg_hierarchy* h, int lv);
+int refresh_plan_values(smg_hierarchy* h);      // the plans hold copies of the level values (value-only re-precompute)
+void drop_sweep_plans(smg_hierarchy* h);        // ... and describe one matrix image: dropped when the images are rebuilt
 
 }  // namespace smg

@@ -721,7 +721,7 @@ static int device_begin(smg_hierarchy* h)
 {
     HIPCHK(hipStreamSynchronize(h->stream));
     drop_graphs(h);
-    drop_tiled(h);
+    drop_sweep_plans(h);
     for (Level& Lv : h->lv) {
         Lv.b.release(); Lv.u.release(); Lv.r.release(); Lv.t.release(); Lv.d.release();
         Lv.b32.release(); Lv.u32.release(); Lv.r32.release(); Lv.t32.release(); Lv.d32.release();
@@ -1073,7 +1073,7 @@ static int build_recipes(smg_hierarchy* h)
     if (h->bs == 3) for (int lv = 0; lv < L; lv++) { int rc = ensure_A_int(h, lv); if (rc) return rc; }     // (the block maps are built on the host)
     for (hipStream_t& a : h->aux) if (!a) HIPCHK(hipStreamCreateWithFlags(&a, hipStreamNonBlocking));
     drop_graphs(h);  // the GS launches move to the A^T images on every level
-    drop_tiled(h);   // ... and so do the overlapped-tiling plans (rebuilt on demand)
+    drop_sweep_plans(h);   // ... and so do the sweep plans (rebuilt on demand)
     // all levels concurrently (maps of the SELL slots; the two numeric Galerkin stages as recipes); every task uploads what it built
     std::vector<int> bad(L, 0);
     std::vector<hipError_t> errs((size_t)2 * L, hipSuccess);
@@ -1252,7 +1252,7 @@ static int precompute_values_device(smg_hierarchy* h, const double* d_val)
         HIPCHK(hipStreamSynchronize(st));
     }
     {
-        int rc = refresh_tiled_values(h);   // the tiling plans hold copies of the level values
+        int rc = refresh_plan_values(h);   // the sweep plans hold copies of the level values
         if (rc) return rc;
     }
     h->host_stale = true;
@@ -1454,7 +1454,7 @@ static int smg_precompute_impl(smg_hierarchy* h, int n, const int* rowptr, const
             rc = coarse_images(h);
             tmv.lap("precompute: coarse factorisation (beside the host half)");
             // While this thread would only wait for the next finer level's numbering, it builds the sweep plans (overlapped tiles, wave Gauss-Seidel
-            // pieces: host work + uploads, csrc/smg_cycle.cpp: prepare_level_plans) of the small levels whose images exist -- otherwise the first solve
+            // pieces: host work + uploads, csrc/smg_sweep_plans.cpp: prepare_level_plans) of the small levels whose images exist -- otherwise the first solve
             // pays for them.  A level that is ready is never kept waiting for more than the plan in hand.
             std::vector<int> plans_due;
             for (int lv = L - 2; lv >= 0 && rc == SMG_OK; lv--) {

@@ -215,4 +215,34 @@ TiledGs build_tiled_gs(const Csr& G, const std::vector<int>& cp, int sweeps, int
     return R;
 }
 
+int tiled_sweep_host(const TiledGs& P, const double* b, const double* x, double* y)
+{
+    const int nc = P.nc, PP = P.P;
+    std::vector<double> xs;
+    for (int t = 0; t < P.n_tiles; t++) {
+        const int* H = P.hdr.data() + (size_t)t * TILED_HDR;
+        const int ext_off = H[0], n_ext = H[1], w = H[2];
+        xs.assign((size_t)n_ext, 0.0);
+        for (int i = 0; i < n_ext; i++) xs[(size_t)i] = x[(size_t)P.ext_rows[(size_t)ext_off + i]];
+        for (int p = 1; p <= PP; p++) {
+            const int* C = H + 4 + ((p - 1) % nc) * TILED_CSTRIDE;
+            const int pan = C[0], m = C[1], ro = C[2], lbase = C[3], cnt = C[4 + (PP - p)];
+            for (int i = 0; i < cnt; i++) {
+                double acc = 0.0;      // exactly the kernel's loop: every slot, the diagonal's and the padding's hold +0.0 at the row's own index
+                for (int j = 0; j < w; j++) {
+                    const int cl = P.pcol[(size_t)pan + (size_t)j * m + i];
+                    if (cl < 0 || cl >= n_ext) return t;
+                    acc += P.pval[(size_t)pan + (size_t)j * m + i] * xs[(size_t)cl];
+                }
+                xs[(size_t)lbase + i] = (b[(size_t)P.prow[(size_t)ro + i]] - acc) / P.pdiag[(size_t)ro + i];
+            }
+        }
+        for (int c = 0; c < nc; c++) {
+            const int* C = H + 4 + c * TILED_CSTRIDE;
+            for (int i = 0; i < C[4]; i++) y[(size_t)P.prow[(size_t)C[2] + i]] = xs[(size_t)C[3] + i];
+        }
+    }
+    return -1;
+}
+
 }  // namespace smg

@@ -52,4 +52,8 @@ struct TiledGs {
 // for max_ext local rows or a colour's panel for max_panel_rows).
 TiledGs build_tiled_gs(const Csr& G, const std::vector<int>& color_ptr, int sweeps, int tile_rows, int max_ext, int max_panel_rows = TILED_THREADS);
 
+// The plan executed on the host the way k_tiled_gs executes it (one column, x -> y: every tile writes its owned rows) -- the checker of the plan's
+// bookkeeping (tests, CPU lane).  Returns -1, or a tile that holds a column outside its image.
+int tiled_sweep_host(const TiledGs& P, const double* b, const double* x, double* y);
+
 }  // namespace smg
