@@ -1,7 +1,8 @@
 // smg_capi.cpp -- the C ABI declared in include/smg.h: errors, the hierarchy handle (container, setters, introspection), the profc
-// mirror and the mesh numerics shims.  The three heavy parts live in their own translation units (smg_internal.hpp):
+// mirror and the mesh numerics shims.  The heavy parts live in their own translation units (smg_internal.hpp):
 //   min_quad_with_fixed_mg_precompute  (reference src/min_quad_with_fixed_mg.cpp:3-51, :137-257)  -> smg_precompute.cpp
-//   min_quad_with_fixed_mg_solve, mg_VCycle (reference src/min_quad_with_fixed_mg.cpp:80-135, :288-361, src/mg_VCycle.cpp:3-201) -> smg_cycle.cpp
+//   mg_VCycle  (reference src/mg_VCycle.cpp:3-201)  -> smg_cycle.cpp
+//   min_quad_with_fixed_mg_solve  (reference src/min_quad_with_fixed_mg.cpp:80-135, :288-361)  -> smg_solve.cpp
 //   mg_precompute / mg_precompute_block / .smgh files  (reference src/mg_precompute.cpp, src/mg_precompute_block.cpp) -> smg_hierarchy_io.cpp
 #include <hip/hip_runtime.h>
 
@@ -124,22 +125,7 @@ int smg::ensure_device(smg_hierarchy* h)
     return SMG_OK;
 }
 
-void smg::drop_graphs(smg_hierarchy* h)
-{
-    if (h->g_iter) (void)hipGraphExecDestroy(h->g_iter);
-    if (h->g_iter_n) (void)hipGraphExecDestroy(h->g_iter_n);
-    if (h->g_resid) (void)hipGraphExecDestroy(h->g_resid);
-    if (h->g_cycle) (void)hipGraphExecDestroy(h->g_cycle);
-    if (h->g_spec) (void)hipGraphExecDestroy(h->g_spec);
-    if (h->g_rd) (void)hipGraphExecDestroy(h->g_rd);
-    if (h->g_cyc) (void)hipGraphExecDestroy(h->g_cyc);
-    h->g_iter = h->g_iter_n = h->g_resid = h->g_cycle = h->g_spec = h->g_rd = h->g_cyc = nullptr;
-    h->g_key = smg::GraphKey();
-    if (h->g_pcg) (void)hipGraphExecDestroy(h->g_pcg);
-    if (h->g_pcg_n) (void)hipGraphExecDestroy(h->g_pcg_n);
-    h->g_pcg = h->g_pcg_n = nullptr;
-    h->g_pcg_key = smg::GraphKey();
-}
+void smg::drop_graphs(smg_hierarchy* h) { h->graphs.drop(); }
 
 hipError_t SellBuf::upload(const Sell& S)
 {

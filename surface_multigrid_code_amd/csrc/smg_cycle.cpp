@@ -1,8 +1,7 @@
-// smg_cycle.cpp -- mg_VCycle (reference src/mg_VCycle.cpp:3-201) and min_quad_with_fixed_mg_solve (reference
-// src/min_quad_with_fixed_mg.cpp:80-135, :288-361) behind smg_solve*: the launch sequence of a cycle, the hipGraph cache, the outer loop
-// with its device-side break test, the V-cycle pieces on host blocks and the raw device interface.
-// The V-cycle never leaves the GPU: every kernel is enqueued on the handle's stream, the outer loop's break test runs on the device
-// (Ctrl, smg_device.hpp) and one outer iteration is replayed as a hipGraph.
+// smg_cycle.cpp -- mg_VCycle (reference src/mg_VCycle.cpp:3-201): what a cycle is.  The level vectors, the smoothers, the launch sequence of a
+// V-cycle and of the outer residual that goes in front of it, and the entry points that use them on a handle that is NOT in a solve: the V-cycle
+// pieces on host blocks, the raw device interface, the cycle benchmarks.  The solve loops that replay these launches live in smg_solve.cpp.
+// The V-cycle never leaves the GPU: every kernel is enqueued on the handle's stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,7 +24,7 @@ using namespace smg;
 
 // ------------------------------------------------------------------------------------------------ V-cycle
 
-static int ensure_work(smg_hierarchy* h, int k)
+int smg::ensure_work(smg_hierarchy* h, int k)
 {
     const int L = h->n_levels;
     if (k > h->kcap) {
@@ -90,7 +89,7 @@ static int ensure_work(smg_hierarchy* h, int k)
 }
 
 // ---- mixed precision: fp32 images of the operators and an fp32 V-cycle ------------------------------------------------
-static int ensure_fp32(smg_hierarchy* h, int k)
+int smg::ensure_fp32(smg_hierarchy* h, int k)
 {
     const int L = h->n_levels;
     if (h->union_m > 0) return fail(SMG_ERR_INVALID, "a union handle solves in fp64 (its coarse inverses are per-member blocks: no fp32 image)");
@@ -455,14 +454,19 @@ static int enqueue_vcycle_t(smg_hierarchy* h, int lv, int k, int pre, int post, 
     return enqueue_gs<T>(h, lv, sp_post, Prec<T>::b(Lv), buf[0], k, post, ctrl);          // :57
 }
 
-static int enqueue_vcycle(smg_hierarchy* h, int lv, int k, int pre, int post, const Ctrl* ctrl, int first = FIRST_NONE)
+// the cycle of a solve: level 0, the handle's sweeps, in the handle's precision (the fp32 cycle starts from nothing: `first` is the fp64 one's)
+int smg::enqueue_vcycle(smg_hierarchy* h, int k, const Ctrl* ctrl, int first)
 {
-    return enqueue_vcycle_t<double>(h, lv, k, pre, post, ctrl, first);
+    if (h->precision == 1) return enqueue_vcycle_t<float>(h, 0, k, h->pre, h->post, ctrl);
+    return enqueue_vcycle_t<double>(h, 0, k, h->pre, h->post, ctrl, first);
 }
-static int enqueue_vcycle32(smg_hierarchy* h, int lv, int k, int pre, int post, const Ctrl* ctrl)
+
+int smg::apply_A(smg_hierarchy* h, int lv, SellMode mode, const double* x, const double* b, double* y, int k, const Ctrl* ctrl)
 {
-    return enqueue_vcycle_t<float>(h, lv, k, pre, post, ctrl);
+    HIPCHK(Prec<double>::opA(h, h->lv[lv], false, mode, 0, -1, x, b, y, k, ctrl));
+    return SMG_OK;
 }
+
 
 // relax() on caller-provided device vectors (pieces, raw interface): the result always ends in u
 static int enqueue_relax(smg_hierarchy* h, int lv, const double* b, double* u, int k, int iters, const Ctrl* ctrl)
@@ -486,7 +490,7 @@ static int enqueue_relax(smg_hierarchy* h, int lv, const double* b, double* u, i
 // second accumulator that repeats SELL_RESID_SS's additions (SELL_*_HEAD in smg_device.hpp) -- and the cycle starts with FIRST_SWEEP.
 // fp64 cycles only (the mixed mode's residual IS the right-hand side of its fp32 cycle); Gauss-Seidel needs a second sweep to come back
 // into u; a level 0 that smooths on A^T (non-symmetric storage) forms other sums than the residual.
-static bool head_fusable(smg_hierarchy* h, int k)
+bool smg::head_fusable(smg_hierarchy* h, int k)
 {
     static const int on = env_int("SMG_FUSE_HEAD", 1);
     if (!on || h->precision != 0 || h->n_levels < 2 || h->prof_on || h->bs != 1 || h->union_m > 0) return false;      // (a union needs the residual VECTOR: per-member norms)
@@ -500,7 +504,7 @@ static bool head_fusable(smg_hierarchy* h, int k)
 }
 
 // sum of squares of RHS_u - A_0 z_u into ctrl->sumsq  (min_quad_with_fixed_mg.cpp:110 / :332)
-static int enqueue_residual_ss(smg_hierarchy* h, int k, bool fuse_decide = false, double* sumsq_out = nullptr)
+int smg::enqueue_residual_ss(smg_hierarchy* h, int k, bool fuse_decide, double* sumsq_out)
 {
     Level& L0 = h->lv[0];
     int nb = 0;
@@ -551,7 +555,7 @@ static int enqueue_residual_ss(smg_hierarchy* h, int k, bool fuse_decide = false
 }
 
 // d_sumsq == nullptr: the break test already ran inside the residual launch (single-GPU path)
-static int enqueue_cycle_part(smg_hierarchy* h, int k, const double* d_sumsq)
+int smg::enqueue_cycle_part(smg_hierarchy* h, int k, const double* d_sumsq)
 {
     if (d_sumsq) HIPCHK(launch_decide(h->d_ctrl.p, d_sumsq, h->stream));
     {
@@ -561,11 +565,11 @@ static int enqueue_cycle_part(smg_hierarchy* h, int k, const double* d_sumsq)
             Level& L0 = h->lv[0];
             const size_t cnt = (size_t)L0.n * k;
             HIPCHK(launch_residual_to_f32(L0.b32.p, L0.u32.p, L0.r.p, cnt, h->d_ctrl.p, h->stream));
-            int rc = enqueue_vcycle32(h, 0, k, h->pre, h->post, h->d_ctrl.p);
+            int rc = enqueue_vcycle(h, k, h->d_ctrl.p, FIRST_NONE);
             if (rc) return rc;
             HIPCHK(launch_add_correction(L0.u.p, L0.u32.p, cnt, h->d_ctrl.p, h->stream));
         } else {
-            int rc = enqueue_vcycle(h, 0, k, h->pre, h->post, h->d_ctrl.p, h->head_fuse ? FIRST_SWEEP : FIRST_NONE);
+            int rc = enqueue_vcycle(h, k, h->d_ctrl.p, h->head_fuse ? FIRST_SWEEP : FIRST_NONE);
             if (rc) return rc;
             if (h->union_m > 0) HIPCHK(launch_union_restore(h->un.view, h->lv[0].u.p, k, h->d_ctrl.p, h->stream));   // members whose loop has ended keep their iterate
         }
@@ -573,156 +577,10 @@ static int enqueue_cycle_part(smg_hierarchy* h, int k, const double* d_sumsq)
     return SMG_OK;
 }
 
-template <typename Fn>
-static int capture_graph(smg_hierarchy* h, hipGraphExec_t* out, Fn&& body)
-{
-    hipGraph_t g = nullptr;
-    HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    int rc = body();
-    hipError_t e = hipStreamEndCapture(h->stream, &g);
-    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-    if (e != hipSuccess) return fail(SMG_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-    e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) return fail(SMG_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-    return SMG_OK;
-}
-
-// The two halves of a split-phase iteration work on ONE buffer that the caller all-reduces in between: the residual graph leaves
-// the local sum of squares there, the cycle graph's break test reads the reduced value from there (no staging copies: an 8-byte
-// device-to-device copy costs several microseconds of stream time).  Re-captured when the caller hands in another buffer.
-static int capture_split_graphs(smg_hierarchy* h, double* buf)
-{
-    if (h->g_resid) { (void)hipGraphExecDestroy(h->g_resid); h->g_resid = nullptr; }
-    if (h->g_cycle) { (void)hipGraphExecDestroy(h->g_cycle); h->g_cycle = nullptr; }
-    const int k = h->k;
-    int rc = capture_graph(h, &h->g_resid, [&]() { return enqueue_residual_ss(h, k, false, buf); });
-    if (rc) return rc;
-    rc = capture_graph(h, &h->g_cycle, [&]() { return enqueue_cycle_part(h, k, buf); });
-    if (rc) return rc;
-    h->g_sumsq_ptr = buf;
-    return SMG_OK;
-}
-
-static GraphKey current_graph_key(const smg_hierarchy* h)
-{
-    GraphKey key;
-    key.k = h->k; key.k_user = h->k_user; key.pre = h->pre; key.post = h->post; key.precision = h->precision; key.smoother = h->smoother;
-    key.jacobi_max_rows = h->jacobi_max_rows; key.omega = h->omega; key.cheby_fraction = h->cheby_fraction; key.head_fuse = h->head_fuse;
-    return key;
-}
-
-static int graph_iters() { static const int v = std::max(1, std::min(16, env_int("SMG_GRAPH_ITERS", 4))); return v; }
-static int ensure_graphs(smg_hierarchy* h)
-{
-    const GraphKey key = current_graph_key(h);
-    if (h->g_iter && h->g_key == key) return SMG_OK;
-    drop_graphs(h);
-    const int k = h->k;
-    int rc = capture_graph(h, &h->g_iter, [&]() {
-        int r = enqueue_residual_ss(h, k, true);
-        if (r) return r;
-        return enqueue_cycle_part(h, k, nullptr);
-    });
-    if (rc) return rc;
-    // Between two graph launches the stream idles for the runtime's hand-over (8.7 us in the rocprof timeline of a 316 us iteration); several iterations
-    // in one graph pay it once.  Semantics unchanged: every launch of an iteration after the one whose break test fired writes nothing (Ctrl::done), as
-    // for iterations enqueued ahead of the host's polling.  SMG_GRAPH_ITERS (default 4; 1 = off): C3 headline 3 168 (1) / 3 174 (2) / 3 194 (4) V-cycles/s, same box, alternating.
-    if (graph_iters() > 1) {
-        rc = capture_graph(h, &h->g_iter_n, [&]() {
-            for (int i = 0; i < graph_iters(); i++) {
-                int r = enqueue_residual_ss(h, k, true);
-                if (r) return r;
-                if ((r = enqueue_cycle_part(h, k, nullptr))) return r;
-            }
-            return (int)SMG_OK;
-        });
-        if (rc) return rc;
-    }
-    if (!h->union_m) {      // (a union has no split-phase iteration: its members stop one by one)
-        rc = capture_split_graphs(h, h->g_sumsq_ptr ? h->g_sumsq_ptr : &h->d_ctrl.p->sumsq);
-        if (rc) return rc;
-        // the two halves of an iteration the host looks into (enqueue_checked_iteration)
-        rc = capture_graph(h, &h->g_rd, [&]() { return enqueue_residual_ss(h, k, true); });
-        if (rc) return rc;
-        rc = capture_graph(h, &h->g_cyc, [&]() { return enqueue_cycle_part(h, k, nullptr); });
-        if (rc) return rc;
-    }
-    h->g_key = key;
-    return SMG_OK;
-}
-
-// hipStreamBeginCapture is not allowed on the legacy default stream (smg_hierarchy_set_stream(h, NULL)): eager launches there
-static bool graphs_usable(const smg_hierarchy* h) { return h->use_graph && !h->prof_on && h->stream != nullptr; }
-
-// n full outer iterations, single-GPU form
-static int enqueue_outer_iteration(smg_hierarchy* h);
-static int enqueue_outer_iterations(smg_hierarchy* h, int n)
-{
-    if (graphs_usable(h) && graph_iters() > 1 && n >= graph_iters()) {
-        int rc = ensure_graphs(h);
-        if (rc) return rc;
-        for (; n >= graph_iters(); n -= graph_iters()) { HIPCHK(hipGraphLaunch(h->g_iter_n, h->stream)); h->iters_enqueued += graph_iters(); }
-    }
-    for (; n > 0; n--) { int rc = enqueue_outer_iteration(h); if (rc) return rc; }
-    return SMG_OK;
-}
-// one full outer iteration, single-GPU form
-static int enqueue_outer_iteration(smg_hierarchy* h)
-{
-    if (graphs_usable(h)) {
-        int rc = ensure_graphs(h);
-        if (rc) return rc;
-        HIPCHK(hipGraphLaunch(h->g_iter, h->stream));
-    } else {
-        int rc = enqueue_residual_ss(h, h->k, true);
-        if (rc) return rc;
-        rc = enqueue_cycle_part(h, h->k, nullptr);
-        if (rc) return rc;
-    }
-    h->iters_enqueued++;
-    return SMG_OK;
-}
-
-// the control block as the stream has it now (one synchronisation); through page-locked memory
-static int read_ctrl(smg_hierarchy* h, Ctrl* out)
-{
-    HIPCHK(h->pin_ctrl.ensure(1));
-    HIPCHK(hipMemcpyAsync(h->pin_ctrl.p, h->d_ctrl.p, sizeof(Ctrl), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    *out = *h->pin_ctrl.p;
-    return SMG_OK;
-}
-
-// One outer iteration the host looks INTO: residual + break test, a look at the flag, and the V-cycle only if the loop goes on.  An iteration
-// enqueued whole runs its cycle even when its own break test has just fired (every launch after the break stores nothing, but does its work):
-// the last iteration of every solve -- 0.31 ms at C3, of a 3.6 ms solve; a whole cycle more than the one a tol = 1e-3 solve of a small mesh
-// needs.  The host looks at the flag after every chunk of iterations anyway; where the chunk is a single iteration (the end of every solve
-// under the adaptive schedule), the look moves in front of the cycle.  Same launches in the same order as the whole iteration.
-static int enqueue_checked_iteration(smg_hierarchy* h, Ctrl* seen)
-{
-    const bool graphs = graphs_usable(h);
-    if (graphs) {
-        int rc = ensure_graphs(h);
-        if (rc) return rc;
-        HIPCHK(hipGraphLaunch(h->g_rd, h->stream));
-    } else {
-        int rc = enqueue_residual_ss(h, h->k, true);
-        if (rc) return rc;
-    }
-    h->iters_enqueued++;      // (its residual is recorded whether or not the cycle follows)
-    { int rc = read_ctrl(h, seen); if (rc) return rc; }      // (the flag and what the adaptive schedule reads)
-    if (seen->done) return SMG_OK;
-    if (graphs) HIPCHK(hipGraphLaunch(h->g_cyc, h->stream));
-    else { int rc = enqueue_cycle_part(h, h->k, nullptr); if (rc) return rc; }
-    return SMG_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ solve
 // The sparse triangular solves raise c_err when a wait gave up (smg_coarse_device.hip): the values they then wrote are NaN.  Every entry point
 // that has just synchronised with work that may contain such a solve reads the flag, clears it (it is sticky on the device: later waits give
 // up at once while it is set) and fails with SMG_ERR_HIP.  The stream is idle when this runs.
-static int coarse_stall_check(smg_hierarchy* h)
+int smg::coarse_stall_check(smg_hierarchy* h)
 {
     if (!h->coarse_sparse || !h->c_err.p) return SMG_OK;
     int cerr = 0;
@@ -750,7 +608,7 @@ int smg::check_ready(const smg_hierarchy* h, const char* who)
 // column independently of how many others there are, and the dense coarse product is formed for the caller's columns only (coarse_cols
 // above), so the caller's columns come out bit for bit as without padding (the tool prints a checksum of z; SMG_PAD_COLS=0: A/B knob).
 // (Schur / sparse coarse solvers take the padded block as it is.)  Union handles keep their own per-member bookkeeping and are not padded.
-static int internal_cols(const smg_hierarchy* h, int k)
+int smg::internal_cols(const smg_hierarchy* h, int k)
 {
     static const int on = env_int("SMG_PAD_COLS", 1);
     if (!on || k <= 4 || k > 64 || h->union_m > 0) return k;
@@ -758,572 +616,6 @@ static int internal_cols(const smg_hierarchy* h, int k)
     int p = 8;
     while (p < k) p *= 2;
     return p;
-}
-
-// host blocks of up to 1 MiB travel through page-locked staging (pin_vec): packed by the host, one DMA each way
-static bool small_host_block(int n, int k) { return (size_t)n * k * 8 <= ((size_t)1 << 20); }
-
-int smg::check_cycle_opts(const smg_solve_opts& o)
-{
-    if (o.precision != 0 && o.precision != 1) return fail(SMG_ERR_INVALID, "precision must be 0 (fp64) or 1 (mixed)");
-    if (o.pre < 0 || o.post < 0) return fail(SMG_ERR_INVALID, "pre / post must be >= 0");
-    if (o.smoother < SMG_SMOOTH_GS || o.smoother > SMG_SMOOTH_HYBRID_CHEBYSHEV) return fail(SMG_ERR_INVALID, "smoother must be one of SMG_SMOOTH_*");
-    if (o.omega > 2.0 || o.omega != o.omega) return fail(SMG_ERR_INVALID, "omega must be in (0, 2]");
-    if (o.cheby_fraction >= 1.0 || o.cheby_fraction != o.cheby_fraction) return fail(SMG_ERR_INVALID, "cheby_fraction must be in (0, 1)");
-    return SMG_OK;
-}
-
-static int smg_solve_begin_impl(smg_hierarchy* h, const double* RHS, int ld_rhs, const double* known_val, int ld_kv,
-                               const double* z0, int ld_z0, int k, int memspace, const smg_solve_opts* opts)
-{
-    int rc = check_ready(h, "smg_solve_begin");
-    if (rc) return rc;
-    smg_solve_opts o;
-    smg_solve_opts_default(&o);
-    if (opts) o = *opts;
-    const int n = h->n_full;
-    if (!RHS || !z0 || k < 1 || ld_rhs < n || ld_z0 < n) return fail(SMG_ERR_INVALID, "smg_solve: bad RHS/z0/k/ld");
-    if (o.max_iter < 0) return fail(SMG_ERR_INVALID, "max_iter must be >= 0");
-    if (h->has_known && (!known_val || ld_kv < (int)h->known.size())) return fail(SMG_ERR_INVALID, "known_val missing or ld_kv too small");
-    // everything is validated before anything of the handle changes: a refused call leaves the handle as it was
-    if ((rc = smg::check_cycle_opts(o))) return rc;
-    if (h->in_solve) return fail(SMG_ERR_INVALID, "smg_solve_begin: a split-phase solve is already in progress (smg_solve_end)");
-    if (h->union_m > 0 && o.precision != 0) return fail(SMG_ERR_INVALID, "a union handle solves in fp64 (no mixed-precision cycle)");
-    h->tol = o.tol; h->max_iter = o.max_iter; h->pre = o.pre; h->post = o.post; h->verbosity = o.verbosity;
-    h->check_every = std::max(0, o.check_every); h->use_graph = o.use_graph;
-    h->precision = o.precision;
-    if ((rc = smg_hierarchy_set_smoother(h, o.smoother, o.omega, o.jacobi_max_rows))) return rc;
-    if ((rc = smg_hierarchy_set_chebyshev(h, o.cheby_fraction))) return rc;
-    DeviceScope dsc(h->device);
-    const int kin = internal_cols(h, k);
-    rc = ensure_work(h, kin);
-    if (rc) return rc;
-    if (h->precision == 1 && (rc = ensure_fp32(h, kin))) return rc;
-    h->k = kin; h->k_user = k;
-    h->coarse_cols = kin > k ? k : 0;
-    const int nk = (int)h->known.size();
-    // stage host inputs
-    const double *dR = RHS, *dZ = z0, *dK = known_val;
-    int ldR = ld_rhs, ldZ = ld_z0, ldK = ld_kv;
-    if (memspace == SMG_HOST) {
-        HIPCHK(h->d_stage_rhs.ensure((size_t)n * k));
-        HIPCHK(h->d_stage_z.ensure((size_t)n * k));
-        if (small_host_block(n, k)) {
-            // small blocks: packed into page-locked memory by the host, then ONE copy each
-            HIPCHK(h->pin_vec.ensure((size_t)2 * n * k));
-            for (int c = 0; c < k; c++) {
-                std::memcpy(h->pin_vec.p + (size_t)c * n, RHS + (size_t)c * ld_rhs, (size_t)n * 8);
-                std::memcpy(h->pin_vec.p + (size_t)(k + c) * n, z0 + (size_t)c * ld_z0, (size_t)n * 8);
-            }
-            HIPCHK(hipMemcpyAsync(h->d_stage_rhs.p, h->pin_vec.p, (size_t)n * k * 8, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_stage_z.p, h->pin_vec.p + (size_t)n * k, (size_t)n * k * 8, hipMemcpyHostToDevice, h->stream));
-        } else {
-            HIPCHK(hipMemcpy2DAsync(h->d_stage_rhs.p, (size_t)n * 8, RHS, (size_t)ld_rhs * 8, (size_t)n * 8, k, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpy2DAsync(h->d_stage_z.p, (size_t)n * 8, z0, (size_t)ld_z0 * 8, (size_t)n * 8, k, hipMemcpyHostToDevice, h->stream));
-        }
-        dR = h->d_stage_rhs.p; dZ = h->d_stage_z.p; ldR = n; ldZ = n;
-        if (h->has_known) {
-            HIPCHK(h->d_stage_kv.ensure((size_t)nk * k));
-            HIPCHK(hipMemcpy2DAsync(h->d_stage_kv.p, (size_t)nk * 8, known_val, (size_t)ld_kv * 8, (size_t)nk * 8, k, hipMemcpyHostToDevice, h->stream));
-            dK = h->d_stage_kv.p; ldK = nk;
-        }
-    } else if (h->has_known) {
-        // keep a private copy: the caller may reuse its buffer before smg_solve_end scatters z(known)
-        HIPCHK(h->d_stage_kv.ensure((size_t)nk * k));
-        HIPCHK(hipMemcpy2DAsync(h->d_stage_kv.p, (size_t)nk * 8, known_val, (size_t)ld_kv * 8, (size_t)nk * 8, k, hipMemcpyDeviceToDevice, h->stream));
-        dK = h->d_stage_kv.p; ldK = nk;
-    }
-    h->cur_kv = dK; h->cur_ld_kv = ldK;
-    Level& L0 = h->lv[0];
-    // z_u = z0(unknown)  (:310-311)  /  z = z0 (:97)
-    HIPCHK(launch_gather_in(L0.u.p, dZ, h->d_map0.p, L0.n, k, kin, ldZ, h->stream));
-    if (h->has_known) {
-        // RHS_u = RHS(unknown) - Auk * known_val  (:316-318)
-        const int nu = L0.n;
-        HIPCHK(h->d_tmp_cm.ensure((size_t)nu * k));
-        HIPCHK(launch_gather_cm(h->d_tmp_cm.p, dR, h->d_unknown.p, nu, k, ldR, nu, h->stream));
-        HIPCHK(launch_csr_sub(nu, h->d_auk_ptr.p, h->d_auk_col.p, h->d_auk_val.p, dK, ldK, h->d_tmp_cm.p, nu, k, h->stream));
-        HIPCHK(launch_gather_in(L0.b.p, h->d_tmp_cm.p, h->d_perm0.p, nu, k, kin, nu, h->stream));
-    } else {
-        HIPCHK(launch_gather_in(L0.b.p, dR, h->d_map0.p, L0.n, k, kin, ldR, h->stream));
-    }
-    // the residual history lives in HBM, sized from max_iter (the reference's r_his grows with the loop, .cpp:112)
-    HIPCHK(h->d_rhis.ensure((size_t)std::max(h->max_iter, 1)));
-    Ctrl& zero = h->host_ctrl;   // lives in the handle: the asynchronous copy may read it after this call returns
-    std::memset(&zero, 0, sizeof(zero));
-    zero.tol = h->tol;
-    zero.r_his = h->d_rhis.p;
-    zero.his_cap = (int)std::min<size_t>(h->d_rhis.n, (size_t)std::max(h->max_iter, 1));
-    HIPCHK(hipMemcpyAsync(h->d_ctrl.p, &zero, sizeof(Ctrl), hipMemcpyHostToDevice, h->stream));
-    if (memspace == SMG_HOST) HIPCHK(hipStreamSynchronize(h->stream));  // the caller's host blocks may change after this call
-    if (h->union_m > 0) {
-        if ((rc = union_begin_solve(h, k))) return rc;
-    }
-    h->head_fuse = head_fusable(h, kin);   // latched: both halves of every iteration of this solve follow it
-    h->iters_enqueued = 0;
-    h->in_solve = true;
-    return SMG_OK;
-}
-
-extern "C" int smg_solve_begin(smg_hierarchy* h, const double* RHS, int ld_rhs, const double* known_val, int ld_kv,
-                               const double* z0, int ld_z0, int k, int memspace, const smg_solve_opts* opts)
-{
-    return guarded("smg_solve_begin", [&]() { return smg_solve_begin_impl(h, RHS, ld_rhs, known_val, ld_kv, z0, ld_z0, k, memspace, opts); });
-}
-
-extern "C" int smg_solve_iter_residual(smg_hierarchy* h, double* d_sumsq)
-{
-    if (!h || !h->in_solve) return fail(SMG_ERR_INVALID, "smg_solve_iter_residual: no solve in progress");
-    DeviceScope dsc(h->device);
-    double* buf = d_sumsq ? d_sumsq : &h->d_ctrl.p->sumsq;
-    if (graphs_usable(h)) {
-        int rc = ensure_graphs(h);
-        if (rc) return rc;
-        if (h->g_sumsq_ptr != buf) { rc = capture_split_graphs(h, buf); if (rc) return rc; }
-        HIPCHK(hipGraphLaunch(h->g_resid, h->stream));
-    } else {
-        int rc = enqueue_residual_ss(h, h->k, false, buf);
-        if (rc) return rc;
-    }
-    return SMG_OK;
-}
-
-extern "C" int smg_solve_iter_cycle(smg_hierarchy* h, const double* d_sumsq)
-{
-    if (!h || !h->in_solve) return fail(SMG_ERR_INVALID, "smg_solve_iter_cycle: no solve in progress");
-    DeviceScope dsc(h->device);
-    double* buf = d_sumsq ? const_cast<double*>(d_sumsq) : &h->d_ctrl.p->sumsq;
-    if (graphs_usable(h)) {
-        int rc = ensure_graphs(h);
-        if (rc) return rc;
-        if (h->g_sumsq_ptr != buf) { rc = capture_split_graphs(h, buf); if (rc) return rc; }
-        HIPCHK(hipGraphLaunch(h->g_cycle, h->stream));
-    } else {
-        int rc = enqueue_cycle_part(h, h->k, buf);
-        if (rc) return rc;
-    }
-    h->iters_enqueued++;
-    return SMG_OK;
-}
-
-// save z, V-cycle in place -- nothing here reads the reduced residual
-static int enqueue_cycle_speculative(smg_hierarchy* h)
-{
-    Level& L0 = h->lv[0];
-    const size_t cnt = (size_t)L0.n * h->k;
-    HIPCHK(launch_copy_unless_done(h->d_zsave.p, L0.u.p, cnt, h->d_ctrl.p, h->stream));
-    return enqueue_cycle_part(h, h->k, nullptr);   // nullptr: no decide in front of the cycle
-}
-
-extern "C" int smg_solve_iter_cycle_speculative(smg_hierarchy* h)
-{
-    if (!h || !h->in_solve) return fail(SMG_ERR_INVALID, "smg_solve_iter_cycle_speculative: no solve in progress");
-    DeviceScope dsc(h->device);
-    HIPCHK(h->d_zsave.ensure((size_t)h->lv[0].n * h->k));
-    if (graphs_usable(h)) {
-        int rc = ensure_graphs(h);
-        if (rc) return rc;
-        if (!h->g_spec) { rc = capture_graph(h, &h->g_spec, [&]() { return enqueue_cycle_speculative(h); }); if (rc) return rc; }
-        HIPCHK(hipGraphLaunch(h->g_spec, h->stream));
-    } else {
-        int rc = enqueue_cycle_speculative(h);
-        if (rc) return rc;
-    }
-    h->iters_enqueued++;
-    return SMG_OK;
-}
-
-extern "C" int smg_solve_iter_commit(smg_hierarchy* h, const double* d_sumsq)
-{
-    if (!h || !h->in_solve) return fail(SMG_ERR_INVALID, "smg_solve_iter_commit: no solve in progress");
-    DeviceScope dsc(h->device);
-    Level& L0 = h->lv[0];
-    HIPCHK(launch_decide_spec(h->d_ctrl.p, d_sumsq ? d_sumsq : &h->d_ctrl.p->sumsq, h->stream));
-    HIPCHK(launch_restore_if_just_done(L0.u.p, h->d_zsave.p, (size_t)L0.n * h->k, h->d_ctrl.p, h->stream));
-    return SMG_OK;
-}
-
-extern "C" int smg_solve_poll(smg_hierarchy* h, int* done, int* n_his)
-{
-    if (!h || !h->in_solve) return fail(SMG_ERR_INVALID, "smg_solve_poll: no solve in progress");
-    DeviceScope dsc(h->device);
-    int hdr[4];
-    HIPCHK(hipMemcpyAsync(hdr, h->d_ctrl.p, sizeof(hdr), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (done) *done = hdr[0];
-    if (n_his) *n_his = hdr[1];
-    return SMG_OK;
-}
-
-extern "C" int smg_solve_end(smg_hierarchy* h, double* z, int ld_z, int memspace, double* r_his, int* n_his, int* converged)
-{
-    if (!h || !h->in_solve) return fail(SMG_ERR_INVALID, "smg_solve_end: no solve in progress");
-    DeviceScope dsc(h->device);
-    const int n = h->n_full, k = h->k_user;
-    if (!z || ld_z < n) return fail(SMG_ERR_INVALID, "smg_solve_end: bad z / ld_z");
-    Level& L0 = h->lv[0];
-    double* dz = z;
-    int ldz = ld_z;
-    if (memspace == SMG_HOST) {
-        HIPCHK(h->d_stage_z.ensure((size_t)n * k));
-        dz = h->d_stage_z.p; ldz = n;
-    }
-    // z(unknown) = z_u ; z(known) = known_val  (:353-355)
-    HIPCHK(launch_scatter_out(dz, L0.u.p, h->d_map0.p, L0.n, k, h->k, ldz, h->stream));
-    if (h->has_known)
-        HIPCHK(launch_scatter_cm(dz, h->cur_kv, h->d_known.p, (int)h->known.size(), k, h->cur_ld_kv, ldz, h->stream));
-    const bool z_pinned = memspace == SMG_HOST && small_host_block(n, k);
-    if (z_pinned) {
-        HIPCHK(h->pin_vec.ensure((size_t)2 * n * k));
-        HIPCHK(hipMemcpyAsync(h->pin_vec.p, dz, (size_t)n * k * 8, hipMemcpyDeviceToHost, h->stream));
-    } else if (memspace == SMG_HOST)
-        HIPCHK(hipMemcpy2DAsync(z, (size_t)ld_z * 8, dz, (size_t)n * 8, (size_t)n * 8, k, hipMemcpyDeviceToHost, h->stream));
-    Ctrl hc;
-    // the history can hold at most one entry per enqueued iteration: fetched together with the control block, one synchronisation
-    const int cap = (int)std::min<size_t>(h->d_rhis.n, (size_t)std::max(std::min(h->iters_enqueued, std::max(h->max_iter, 1)), 1));
-    HIPCHK(h->pin_his.ensure((size_t)cap));
-    HIPCHK(h->pin_ctrl.ensure(1));
-    const double* his = h->pin_his.p;
-    HIPCHK(hipMemcpyAsync(h->pin_ctrl.p, h->d_ctrl.p, sizeof(Ctrl), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(h->pin_his.p, h->d_rhis.p, (size_t)cap * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    hc = *h->pin_ctrl.p;
-    if (z_pinned) for (int c = 0; c < k; c++) std::memcpy(z + (size_t)c * ld_z, h->pin_vec.p + (size_t)c * n, (size_t)n * 8);
-    const int cnt = std::max(0, std::min(std::min(hc.n_his, hc.his_cap), cap));
-    h->in_solve = false; h->coarse_cols = 0;
-    prof_collect(h);
-    if (r_his) for (int i = 0; i < cnt; i++) r_his[i] = his[i];
-    if (n_his) *n_his = cnt;
-    const double last = cnt > 0 ? his[cnt - 1] : HUGE_VAL;
-    if (converged) *converged = (last > h->tol) ? 0 : 1;  // :131-134 / :357-360
-    if (h->union_m > 0 && converged) {      // every member's own loop ended below the tolerance (the handle's history holds the norm over all members)
-        std::vector<int> md((size_t)h->union_m, 0);
-        HIPCHK(hipMemcpy(md.data(), h->un.done.p, md.size() * sizeof(int), hipMemcpyDeviceToHost));
-        *converged = (hc.status == 0 && std::all_of(md.begin(), md.end(), [](int d) { return d == 1; })) ? 1 : 0;      // 2 = that member's residual went non-finite
-    }
-    if (h->verbosity > 0) {
-        for (int i = 0; i < cnt; i++) std::printf("MG iteration: %d, residual: %g\n", i, his[i]);  // :111
-        if (cnt) std::printf("residual norm: %g\n", his[cnt - 1]);                                    // :127
-    }
-    { int rc = coarse_stall_check(h); if (rc) return rc; }
-    if (hc.status != 0) return fail(SMG_ERR_NONFINITE, "non-finite residual at iteration %d", cnt - 1);
-    return SMG_OK;
-}
-
-// for (iter < maxIter) { residual; push; if (residual < tol) break; V-cycle }   (:108-125 / :330-347)
-// The break happens on the device; the host only decides how many iterations to enqueue before it looks at the flag again.
-// check_every >= 1: that many.  check_every == 0 (default): adaptive -- from the two most recent residuals the host extrapolates
-// how many more cycles the tolerance needs and enqueues all but the last of them before the next look (the results do not depend
-// on this: an iteration enqueued after the break stores nothing).  The schedule is a function of the residual history alone, so the
-// ranks of a column-sharded solve -- who all see the same reduced residuals -- enqueue (and reduce) the same number of times.
-// budget >= 0: at most that many iterations instead of max_iter (smg_solve_pcg: the entries its first residual and its checks have used are not iterations).
-template <typename Iter>
-static int run_outer_loop(smg_hierarchy* h, Iter&& iterations, bool look_into_single_iterations = false, int budget = -1)
-{
-    int it = 0;
-    int chunk_next = 1;
-    static const int look_env = env_int("SMG_LOOK_INTO", 1);      // A/B knob
-    const bool look = look_into_single_iterations && look_env != 0;
-    const int max_it = budget >= 0 ? budget : h->max_iter;
-    while (it < max_it) {
-        const int want = h->check_every > 0 ? h->check_every : chunk_next;
-        const int chunk = std::min(want, max_it - it);
-        Ctrl hc;
-        if (look && chunk == 1) {
-            // the look happens between the iteration's break test and its cycle; the cycle is enqueued behind it and the loop goes straight on
-            int rc = enqueue_checked_iteration(h, &hc);
-            if (rc) return rc;
-            if (hc.done) break;
-            it += 1;
-        } else {
-            { int rc = iterations(chunk); if (rc) return rc; }
-            it += chunk;
-            if (it >= max_it) break;
-            { int rc = read_ctrl(h, &hc); if (rc) return rc; }
-            if (hc.done) break;
-        }
-        chunk_next = 1;
-        if (h->check_every == 0 && hc.n_his >= 2 && hc.r_last > 0.0 && hc.r_last < hc.r_prev && h->tol > 0.0 && hc.r_last > h->tol) {
-            const double need = std::ceil(std::log(h->tol / hc.r_last) / std::log(hc.r_last / hc.r_prev));   // more residuals until < tol
-            if (need > 2.0) chunk_next = (int)std::min(need - 1.0, 64.0);
-        }
-    }
-    return SMG_OK;
-}
-
-extern "C" int smg_solve(smg_hierarchy* h, const double* RHS, int ld_rhs, const double* known_val, int ld_kv,
-                         const double* z0, int ld_z0, int k, int memspace, const smg_solve_opts* opts, double* z, int ld_z,
-                         double* r_his, int* n_his, int* converged)
-{
-    int rc = smg_solve_begin(h, RHS, ld_rhs, known_val, ld_kv, z0, ld_z0, k, memspace, opts);
-    if (rc) return rc;
-    rc = run_outer_loop(h, [&](int n) { return enqueue_outer_iterations(h, n); }, h->union_m == 0);
-    if (rc) { h->in_solve = false; h->coarse_cols = 0; return rc; }
-    return smg_solve_end(h, z, ld_z, memspace, r_his, n_his, converged);
-}
-
-// ---- conjugate gradients preconditioned by the V-cycle (include/smg.h: smg_solve_pcg) ------------------------------------------------
-// Flexible (Polak-Ribiere) PCG, one recurrence per column.  The vectors live in the handle's Krylov buffers; the V-cycle
-// keeps its own: its input r goes into L0.b (L0.b32), it starts from L0.u = 0 and leaves z in L0.u.  One iteration:
-//   z = V(r, 0);  rz = z.r, beta = -alpha_prev z.q / rz_prev;  p = z + beta p;  q = A p;  alpha = rz / p.q;  x += alpha p, r -= alpha q;  |r|_F -> r_his
-// and every launch of it starts with `if (done) return`, so iterations enqueued after the break store nothing -- the schedule of the outer loop
-// (run_outer_loop) is smg_solve's.
-static int ensure_krylov(smg_hierarchy* h)
-{
-    const int n = h->lv[0].n, k = h->k;
-    const size_t cnt = (size_t)n * k;
-    const int groups = kry_groups(n, k);
-    const size_t npart = (size_t)2 * groups * k, ns = (size_t)KS_SLOTS * k;
-    if (h->kry_x.n < cnt || h->kry_part.n < npart || h->kry_s.n < ns || !h->kry_restart.p) {
-        drop_graphs(h);      // (the PCG graphs hold these pointers; the MG graphs are recaptured at their next use)
-        for (DevBuf<double>* b : {&h->kry_x, &h->kry_r, &h->kry_p, &h->kry_q, &h->kry_b}) {
-            HIPCHK(b->ensure(cnt));
-            HIPCHK(hipMemsetAsync(b->p, 0, b->n * sizeof(double), h->stream));
-        }
-        HIPCHK(h->kry_part.ensure(npart));
-        HIPCHK(h->kry_s.ensure(ns));
-        HIPCHK(hipMemsetAsync(h->kry_s.p, 0, h->kry_s.n * sizeof(double), h->stream));
-        HIPCHK(h->kry_restart.ensure(1));
-    }
-    KryDev& K = h->kry;
-    K.n = n; K.k = k; K.groups = groups;
-    K.part = h->kry_part.p; K.s = h->kry_s.p; K.restart = h->kry_restart.p;
-    return SMG_OK;
-}
-
-static int enqueue_pcg_iteration(smg_hierarchy* h)
-{
-    Level& L0 = h->lv[0];
-    const int k = h->k;
-    const size_t cnt = (size_t)L0.n * k;
-    Ctrl* ctrl = h->d_ctrl.p;
-    const KryDev& K = h->kry;
-    {
-        ProfGuard pg(h, "MG: total VCycle");
-        if (h->precision == 1) {     // the fp32 cycle: z = (double) V32((float) r, 0)
-            HIPCHK(launch_residual_to_f32(L0.b32.p, L0.u32.p, h->kry_r.p, cnt, ctrl, h->stream));
-            int rc = enqueue_vcycle32(h, 0, k, h->pre, h->post, ctrl);
-            if (rc) return rc;
-            HIPCHK(launch_kry_widen(L0.u32.p, L0.u.p, cnt, ctrl, h->stream));
-        } else {
-            HIPCHK(launch_kry_precond_in(h->kry_r.p, L0.b.p, L0.u.p, cnt, ctrl, h->stream));
-            int rc = enqueue_vcycle(h, 0, k, h->pre, h->post, ctrl, FIRST_NONE);
-            if (rc) return rc;
-        }
-    }
-    ProfGuard pg(h, "PCG: vectors");
-    HIPCHK(launch_kry_dots_zr_zq(K, L0.u.p, h->kry_r.p, h->kry_q.p, ctrl, h->stream));
-    HIPCHK(launch_kry_direction(K, L0.u.p, h->kry_p.p, ctrl, h->stream));
-    HIPCHK(Prec<double>::opA(h, L0, false, SELL_AX, 0, -1, h->kry_p.p, nullptr, h->kry_q.p, k, ctrl));
-    HIPCHK(launch_kry_dots_pq(K, h->kry_p.p, h->kry_q.p, ctrl, h->stream));
-    HIPCHK(launch_kry_step_decide(K, h->kry_x.p, h->kry_r.p, h->kry_p.p, h->kry_q.p, ctrl, h->stream));
-    return SMG_OK;
-}
-
-// one iteration and graph_iters() of them, each a linear chain; kept apart from the MG graphs (own handles, own key)
-static int ensure_pcg_graphs(smg_hierarchy* h)
-{
-    const GraphKey key = current_graph_key(h);
-    if (h->g_pcg && h->g_pcg_key == key) return SMG_OK;
-    if (h->g_pcg) { (void)hipGraphExecDestroy(h->g_pcg); h->g_pcg = nullptr; }
-    if (h->g_pcg_n) { (void)hipGraphExecDestroy(h->g_pcg_n); h->g_pcg_n = nullptr; }
-    int rc = capture_graph(h, &h->g_pcg, [&]() { return enqueue_pcg_iteration(h); });
-    if (rc) return rc;
-    if (graph_iters() > 1) {
-        rc = capture_graph(h, &h->g_pcg_n, [&]() {
-            for (int i = 0; i < graph_iters(); i++) { int r = enqueue_pcg_iteration(h); if (r) return r; }
-            return (int)SMG_OK;
-        });
-        if (rc) return rc;
-    }
-    h->g_pcg_key = key;
-    return SMG_OK;
-}
-
-static int enqueue_pcg_iterations(smg_hierarchy* h, int n)
-{
-    if (graphs_usable(h)) {
-        int rc = ensure_pcg_graphs(h);
-        if (rc) return rc;
-        if (graph_iters() > 1)
-            for (; n >= graph_iters(); n -= graph_iters()) { HIPCHK(hipGraphLaunch(h->g_pcg_n, h->stream)); h->iters_enqueued += graph_iters(); }
-        for (; n > 0; n--) { HIPCHK(hipGraphLaunch(h->g_pcg, h->stream)); h->iters_enqueued++; }
-        return SMG_OK;
-    }
-    for (; n > 0; n--) { int rc = enqueue_pcg_iteration(h); if (rc) return rc; h->iters_enqueued++; }
-    return SMG_OK;
-}
-
-// r_his[n_his] = |RHS_u - A x| of the iterate in the Krylov buffer x, measured as smg_solve measures it, with the break test.  reopen: it replaces
-// the last entry (a recurrence norm that passed the test) and the restart flag is raised.
-static int enqueue_pcg_true_residual(smg_hierarchy* h, bool head, bool reopen)
-{
-    Level& L0 = h->lv[0];
-    const size_t bytes = (size_t)L0.n * h->k * sizeof(double);
-    HIPCHK(hipMemcpyAsync(L0.u.p, h->kry_x.p, bytes, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(L0.b.p, h->kry_b.p, bytes, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(launch_kry_arm(h->kry, h->d_ctrl.p, reopen, h->stream));
-    h->head_fuse = head;
-    int rc = enqueue_residual_ss(h, h->k, true);
-    h->head_fuse = false;
-    if (rc) return rc;
-    // r = RHS_u - A x: the recurrence (re)starts from the true residual
-    HIPCHK(Prec<double>::opA(h, L0, false, SELL_RESID, 0, -1, h->kry_x.p, h->kry_b.p, h->kry_r.p, h->k, h->d_ctrl.p));
-    return SMG_OK;
-}
-
-static int pcg_loop(smg_hierarchy* h)
-{
-    if (h->max_iter == 0) return SMG_OK;              // z = z0, no entries (as smg_solve)
-    int rc = ensure_krylov(h);
-    if (rc) return rc;
-    Level& L0 = h->lv[0];
-    const size_t bytes = (size_t)L0.n * h->k * sizeof(double);
-    const bool head = h->head_fuse;                   // entry 0 and the checks measure as smg_solve does; the iterations never fuse
-    h->head_fuse = false;
-    HIPCHK(hipMemcpyAsync(h->kry_x.p, L0.u.p, bytes, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->kry_b.p, L0.b.p, bytes, hipMemcpyDeviceToDevice, h->stream));
-    if ((rc = enqueue_pcg_true_residual(h, head, false))) return rc;
-    h->iters_enqueued = 1;
-    int n_true = 1;                                   // entries up to and including the last true residual
-    Ctrl hc;
-    for (;;) {
-        rc = run_outer_loop(h, [&](int n) { return enqueue_pcg_iterations(h, n); }, false, h->max_iter - n_true);
-        if (rc) return rc;
-        if ((rc = read_ctrl(h, &hc))) return rc;
-        // a recurrence norm passed the break test: verified on the true residual of x, which replaces it
-        if (!hc.done || hc.status != 0 || hc.n_his <= n_true) break;
-        if ((rc = enqueue_pcg_true_residual(h, head, true))) return rc;
-        if ((rc = read_ctrl(h, &hc))) return rc;
-        n_true = hc.n_his;
-        if (hc.done || n_true >= h->max_iter) break;  // converged (or non-finite) / no entries left; else restart from x
-    }
-    HIPCHK(hipMemcpyAsync(L0.u.p, h->kry_x.p, bytes, hipMemcpyDeviceToDevice, h->stream));
-    return SMG_OK;
-}
-
-extern "C" int smg_solve_pcg(smg_hierarchy* h, const double* RHS, int ld_rhs, const double* known_val, int ld_kv, const double* z0, int ld_z0, int k,
-                             int memspace, const smg_solve_opts* opts, double* z, int ld_z, double* r_his, int* n_his, int* converged)
-{
-    return guarded("smg_solve_pcg", [&]() -> int {
-        int rc = check_ready(h, "smg_solve_pcg");
-        if (rc) return rc;
-        if (h->union_m > 0) return fail(SMG_ERR_INVALID, "smg_solve_pcg: a union handle is not supported (its members stop one by one: use smg_solve)");
-        if ((rc = smg_solve_begin_impl(h, RHS, ld_rhs, known_val, ld_kv, z0, ld_z0, k, memspace, opts))) return rc;
-        DeviceScope dsc(h->device);
-        rc = pcg_loop(h);
-        if (rc) { h->in_solve = false; h->coarse_cols = 0; return rc; }
-        return smg_solve_end(h, z, ld_z, memspace, r_his, n_his, converged);
-    });
-}
-
-// ---- what the LOBPCG eigensolver (smg_eig.cpp) takes from the solve: the V-cycle and A on k unpadded internal columns ------------------
-int smg::eig_prepare(smg_hierarchy* h, const smg_solve_opts& o, int k)
-{
-    h->tol = o.tol; h->max_iter = o.max_iter; h->pre = o.pre; h->post = o.post; h->verbosity = o.verbosity;
-    h->check_every = std::max(0, o.check_every); h->use_graph = o.use_graph;
-    h->precision = o.precision;
-    int rc;
-    if ((rc = smg_hierarchy_set_smoother(h, o.smoother, o.omega, o.jacobi_max_rows))) return rc;
-    if ((rc = smg_hierarchy_set_chebyshev(h, o.cheby_fraction))) return rc;
-    if ((rc = ensure_work(h, k))) return rc;
-    if (h->precision == 1 && (rc = ensure_fp32(h, k))) return rc;
-    h->k = k; h->k_user = k; h->coarse_cols = 0;
-    h->head_fuse = false;
-    return SMG_OK;
-}
-
-int smg::eig_vcycle(smg_hierarchy* h, int k, const Ctrl* ctrl)
-{
-    ProfGuard pg(h, "MG: total VCycle");
-    if (h->precision == 1) return enqueue_vcycle32(h, 0, k, h->pre, h->post, ctrl);
-    return enqueue_vcycle(h, 0, k, h->pre, h->post, ctrl, FIRST_NONE);
-}
-
-int smg::eig_apply_A(smg_hierarchy* h, const double* x, double* y, int k, const Ctrl* ctrl)
-{
-    HIPCHK(Prec<double>::opA(h, h->lv[0], false, SELL_AX, 0, -1, x, nullptr, y, k, ctrl));
-    return SMG_OK;
-}
-
-// ---- column-sharded solve (include/smg.h: smg_solve_sharded) ------------------------------------------------------------------------
-// A rank without columns: no vectors, no cycle -- it adds 0 to every reduction and lets the device take the same decision from the
-// reduced value as everybody else (same control block, same launch_decide, same polling schedule).
-static int solve_sharded_empty(smg_hierarchy* h, const smg_solve_opts* opts, smg_reduce_fn reduce, void* ctx, double* r_his, int* n_his, int* converged)
-{
-    int rc = check_ready(h, "smg_solve_sharded");
-    if (rc) return rc;
-    if (h->in_solve) return fail(SMG_ERR_INVALID, "smg_solve_sharded: a split-phase solve is in progress");
-    smg_solve_opts o;
-    smg_solve_opts_default(&o);
-    if (opts) o = *opts;
-    if (o.max_iter < 0) return fail(SMG_ERR_INVALID, "max_iter must be >= 0");
-    DeviceScope dsc(h->device);
-    h->tol = o.tol; h->max_iter = o.max_iter; h->check_every = std::max(0, o.check_every); h->verbosity = o.verbosity;
-    HIPCHK(h->d_rhis.ensure((size_t)std::max(h->max_iter, 1)));
-    Ctrl& zero = h->host_ctrl;
-    std::memset(&zero, 0, sizeof(zero));
-    zero.tol = h->tol;
-    zero.r_his = h->d_rhis.p;
-    zero.his_cap = (int)std::min<size_t>(h->d_rhis.n, (size_t)std::max(h->max_iter, 1));
-    HIPCHK(hipMemcpyAsync(h->d_ctrl.p, &zero, sizeof(Ctrl), hipMemcpyHostToDevice, h->stream));
-    double* buf = &h->d_ctrl.p->sumsq;
-    int n_it = 0;
-    rc = run_outer_loop(h, [&](int n) -> int {
-        for (int i = 0; i < n; i++) {
-            HIPCHK(hipMemsetAsync(buf, 0, sizeof(double), h->stream));
-            if (reduce(buf, 1, (void*)h->stream, ctx) != 0) return fail(SMG_ERR_REDUCE, "smg_solve_sharded: the caller's reduction failed");
-            HIPCHK(launch_decide(h->d_ctrl.p, buf, h->stream));
-            n_it++;
-        }
-        return SMG_OK;
-    });
-    if (rc) return rc;
-    Ctrl hc;
-    std::vector<double> his((size_t)std::max(std::min(n_it, std::max(h->max_iter, 1)), 1));
-    HIPCHK(hipMemcpyAsync(&hc, h->d_ctrl.p, sizeof(Ctrl), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(his.data(), h->d_rhis.p, his.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const int cnt = std::max(0, std::min(std::min(hc.n_his, hc.his_cap), (int)his.size()));
-    if (r_his) for (int i = 0; i < cnt; i++) r_his[i] = his[(size_t)i];
-    if (n_his) *n_his = cnt;
-    const double last = cnt > 0 ? his[(size_t)cnt - 1] : HUGE_VAL;
-    if (converged) *converged = (last > h->tol) ? 0 : 1;
-    if (hc.status != 0) return fail(SMG_ERR_NONFINITE, "non-finite residual at iteration %d", cnt - 1);
-    return SMG_OK;
-}
-
-extern "C" int smg_solve_sharded(smg_hierarchy* h, const double* RHS, int ld_rhs, const double* known_val, int ld_kv, const double* z0,
-                                 int ld_z0, int k_local, int memspace, const smg_solve_opts* opts, smg_reduce_fn reduce, void* ctx,
-                                 double* z, int ld_z, double* r_his, int* n_his, int* converged)
-{
-    return guarded("smg_solve_sharded", [&]() -> int {
-        if (!reduce) return fail(SMG_ERR_INVALID, "smg_solve_sharded: no reduction given");
-        if (k_local < 0) return fail(SMG_ERR_INVALID, "smg_solve_sharded: k_local must be >= 0");
-        if (k_local == 0) return solve_sharded_empty(h, opts, reduce, ctx, r_his, n_his, converged);
-        int rc = smg_solve_begin(h, RHS, ld_rhs, known_val, ld_kv, z0, ld_z0, k_local, memspace, opts);
-        if (rc) return rc;
-        DeviceScope dsc(h->device);
-        double* buf = &h->d_ctrl.p->sumsq;   // the word both halves of an iteration work on in place; the reduction too
-        rc = run_outer_loop(h, [&](int n) -> int {
-            for (int i = 0; i < n; i++) {
-                int r = smg_solve_iter_residual(h, buf);
-                if (r) return r;
-                if (reduce(buf, 1, (void*)h->stream, ctx) != 0) return fail(SMG_ERR_REDUCE, "smg_solve_sharded: the caller's reduction failed");
-                if ((r = smg_solve_iter_cycle(h, buf))) return r;
-            }
-            return SMG_OK;
-        });
-        if (rc) { h->in_solve = false; h->coarse_cols = 0; return rc; }
-        return smg_solve_end(h, z, ld_z, memspace, r_his, n_his, converged);
-    });
-}
-
-extern "C" int smg_raw_outer_iteration(smg_hierarchy* h, int n_iter)
-{
-    if (!h || !h->in_solve) return fail(SMG_ERR_INVALID, "smg_raw_outer_iteration: call smg_solve_begin first");
-    DeviceScope dsc(h->device);
-    return enqueue_outer_iterations(h, n_iter);
 }
 
 static int piece_prolog(smg_hierarchy* h, int lv, int k, const char* who, bool need_coarser);
@@ -1354,7 +646,7 @@ extern "C" int smg_bench_vcycle(smg_hierarchy* h, int lv, int k, int pre, int po
     if (reps < 1 || !us_per_cycle) return fail(SMG_ERR_INVALID, "smg_bench_vcycle: bad arguments");
     if ((rc = prepare_sweep_plans(h, k, pre, post))) return rc;
     hipGraphExec_t g = nullptr;
-    rc = capture_graph(h, &g, [&]() { return enqueue_vcycle(h, lv, k, pre, post, nullptr); });
+    rc = capture_graph(h, &g, [&]() { return enqueue_vcycle_t<double>(h, lv, k, pre, post, nullptr); });
     if (rc) return rc;
     if ((rc = time_graph(h, g, reps, us_per_cycle))) return rc;
     return coarse_stall_check(h);
@@ -1490,7 +782,7 @@ extern "C" int smg_vcycle(smg_hierarchy* h, const double* B, int pre, int post, 
     if ((rc = prepare_sweep_plans(h, k, pre, post))) return rc;
     if ((rc = put_block(h, lv, B, k, Lv.b.p))) return rc;
     if ((rc = put_block(h, lv, u, k, Lv.u.p))) return rc;
-    if ((rc = enqueue_vcycle(h, lv, k, pre, post, nullptr))) return rc;
+    if ((rc = enqueue_vcycle_t<double>(h, lv, k, pre, post, nullptr))) return rc;
     return get_block(h, lv, Lv.u.p, k, u);
 }
 
@@ -1503,10 +795,7 @@ extern "C" int smg_residual_norm(smg_hierarchy* h, int lv, const double* B, cons
     if ((rc = put_block(h, lv, B, k, Lv.b.p))) return rc;
     if ((rc = put_block(h, lv, u, k, Lv.u.p))) return rc;
     int nb = 0;
-    Ctrl zero;
-    std::memset(&zero, 0, sizeof(zero));
-    zero.r_his = h->d_rhis.p; zero.his_cap = (int)h->d_rhis.n;
-    HIPCHK(hipMemcpyAsync(h->d_ctrl.p, &zero, sizeof(Ctrl), hipMemcpyHostToDevice, h->stream));
+    if ((rc = reset_ctrl(h, (int)h->d_rhis.n))) return rc;
     if (h->bs == 3) HIPCHK(launch_bsr3(SELL_RESID_SS, Lv.bA.view, 0, Lv.bA.view.n_slices, Lv.u.p, Lv.b.p, nullptr, k, nullptr, h->d_partials.p, &nb, h->stream));
     else HIPCHK(launch_sell(SELL_RESID_SS, Lv.dA.view, 0, Lv.dA.view.n_slices, Lv.u.p, Lv.b.p, nullptr, k, nullptr, h->d_partials.p, &nb, h->stream));
     HIPCHK(launch_ss_finalize(h->d_partials.p, nb, h->d_ctrl.p, h->stream));

@@ -289,6 +289,17 @@ struct EigRun {
     int groups = 0;
 };
 
+// the cycle's options become the handle's selection and the level vectors are ready for k unpadded internal columns; the cycle never fuses a head
+int eig_prepare(smg_hierarchy* h, const smg_solve_opts& o, int k)
+{
+    int rc = latch_solve_opts(h, o);
+    if (rc || (rc = ensure_work(h, k))) return rc;
+    if (h->precision == 1 && (rc = ensure_fp32(h, k))) return rc;
+    h->k = k; h->k_user = k; h->coarse_cols = 0;
+    h->head_fuse = false;
+    return SMG_OK;
+}
+
 int eig_buffers(smg_hierarchy* h, EigRun& R)
 {
     const size_t cnt = (size_t)R.n * R.m;
@@ -409,12 +420,7 @@ extern "C" int smg_eigs(smg_hierarchy* h, const double* mass_diag, int nev, int 
         if ((rc = eig_buffers(h, R))) return rc;
         Level& L0 = h->lv[0];
         HIPCHK(hipMemcpyAsync(h->eig_mass.p, mi.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        // the control block: not done (the kernels' early return), nothing else of it is used here
-        Ctrl& zero = h->host_ctrl;
-        std::memset(&zero, 0, sizeof(zero));
-        HIPCHK(h->d_rhis.ensure(1));
-        zero.r_his = h->d_rhis.p;
-        HIPCHK(hipMemcpyAsync(h->d_ctrl.p, &zero, sizeof(Ctrl), hipMemcpyHostToDevice, h->stream));
+        if ((rc = reset_ctrl(h, 0))) return rc;      // not done (the kernels' early return): nothing else of the control block is used here
         // the start block, gathered into the internal numbering
         const double* src = X0;
         int ld_src = ld_x0;
@@ -431,7 +437,7 @@ extern "C" int smg_eigs(smg_hierarchy* h, const double* mass_diag, int nev, int 
             src = h->eig_stage.p; ld_src = n_full;
         }
         HIPCHK(launch_gather_in(h->eig_x[0].p, src, h->d_map0.p, n, m, m, ld_src, h->stream));
-        if ((rc = eig_apply_A(h, h->eig_x[0].p, h->eig_ax[0].p, m, R.ctrl))) return rc;
+        if ((rc = apply_A(h, 0, SELL_AX, h->eig_x[0].p, nullptr, h->eig_ax[0].p, m, R.ctrl))) return rc;
         // Rayleigh-Ritz of the start: history row 0 is its residual
         EigBlocks S, AS;
         S.p[0] = h->eig_x[0].p; AS.p[0] = h->eig_ax[0].p; S.nb = AS.nb = 1;
@@ -446,12 +452,15 @@ extern "C" int smg_eigs(smg_hierarchy* h, const double* mass_diag, int nev, int 
         for (;; it++) {
             const bool more = it < o.max_iter;
             if (more) {
-                if ((rc = eig_vcycle(h, m, R.ctrl))) return rc;
+                {
+                    ProfGuard pg(h, "MG: total VCycle");
+                    if ((rc = enqueue_vcycle(h, m, R.ctrl, FIRST_NONE))) return rc;
+                }
                 const double* W = L0.u.p;
                 if (f32) { HIPCHK(launch_kry_widen(L0.u32.p, h->eig_w.p, cnt, R.ctrl, h->stream)); W = h->eig_w.p; }
                 {
                     ProfGuard pg(h, "EIG: SpMV");
-                    if ((rc = eig_apply_A(h, W, h->eig_aw.p, m, R.ctrl))) return rc;
+                    if ((rc = apply_A(h, 0, SELL_AX, W, nullptr, h->eig_aw.p, m, R.ctrl))) return rc;
                 }
                 S.p[0] = h->eig_x[R.cur].p; S.p[1] = W; S.p[2] = h->eig_p[R.cur].p;
                 AS.p[0] = h->eig_ax[R.cur].p; AS.p[1] = h->eig_aw.p; AS.p[2] = h->eig_ap[R.cur].p;

@@ -226,6 +226,33 @@ struct GraphKey {
     bool operator!=(const GraphKey& o) const { return !(*this == o); }
 };
 
+// The replayable steps of the solve loops; smg_solve.cpp: enqueue_step is the one place that says which launches each consists of.
+enum Step { STEP_ITER,           // one outer iteration: residual + break test, cycle
+            STEP_ITER_N,         // graph_iters() of them
+            STEP_HEAD,           // an iteration the host looks into: residual + break test ...
+            STEP_TAIL,           // ... and the cycle that follows the look
+            STEP_SPLIT_RESID,    // split-phase: the local sum of squares into the caller's reduction buffer
+            STEP_SPLIT_CYCLE,    // ... break test on the reduced value in that buffer, cycle
+            STEP_SPEC,           // speculative split-phase: save the iterate, cycle (no break test in front)
+            STEP_PCG,            // one PCG iteration
+            STEP_PCG_N,          // graph_iters() of them
+            STEP_COUNT };
+
+// The captured steps of a handle.  The stationary steps (STEP_ITER .. STEP_SPEC) and the PCG pair are each valid while the handle's
+// selection compares equal to their own key: alternating smg_solve and smg_solve_pcg re-captures nothing (their head_fuse differs).
+struct GraphCache {
+    hipGraphExec_t exec[STEP_COUNT] = {};
+    GraphKey mg_key, pcg_key;
+    double* sumsq = nullptr;     // the buffer the split pair was captured with (the caller's all-reduce buffer, or ctrl->sumsq); outlives drop(): the next capture starts from it
+    void drop(int s0 = 0, int s1 = STEP_COUNT)
+    {
+        for (int s = s0; s < s1; s++) if (exec[s]) { (void)hipGraphExecDestroy(exec[s]); exec[s] = nullptr; }
+        // a group that lost its first graph has no key either (a capture that fails half way must not leave the old key on new graphs)
+        if (s0 <= STEP_ITER && s1 > STEP_ITER) mg_key = GraphKey();
+        if (s0 <= STEP_PCG && s1 > STEP_PCG) pcg_key = GraphKey();
+    }
+};
+
 struct ProfScope { std::string name; long count = 0; double ms = 0.0; };
 struct ProfRec { int scope; hipEvent_t e0, e1; };
 
@@ -340,23 +367,15 @@ struct smg_hierarchy {
     int iters_enqueued = 0;
     smg::DevBuf<double> d_stage_rhs, d_stage_z, d_stage_kv, d_tmp_cm;
     smg::DevBuf<double> d_zsave;     // iterate saved by the speculative cycle
-    hipGraphExec_t g_spec = nullptr;  // save + V-cycle (no decide)
     const double* cur_kv = nullptr;  // device pointer to known_val (column-major) of the running solve
     int cur_ld_kv = 0;
-    // ---- hipGraph cache (one outer iteration; and its two halves for the split-phase API) ----
-    hipGraphExec_t g_iter = nullptr, g_resid = nullptr, g_cycle = nullptr;
-    hipGraphExec_t g_iter_n = nullptr;    // graph_iters() outer iterations in one graph (smg_cycle.cpp: enqueue_outer_iterations)
-    hipGraphExec_t g_rd = nullptr, g_cyc = nullptr;   // residual + break test | the cycle that follows it: an iteration the host looks into (enqueue_checked_iteration)
-    double* g_sumsq_ptr = nullptr;   // the buffer g_resid writes / g_cycle reads (the caller's all-reduce buffer, or ctrl->sumsq)
-    smg::GraphKey g_key;             // what the cached graphs were captured with (k == 0: nothing cached)
+    smg::GraphCache graphs;          // the captured steps of the solve loops (smg_solve.cpp: run_step)
     bool head_fuse = false;          // this solve takes the outer residual out of the first sweep (latched at smg_solve_begin)
-    // ---- conjugate gradients preconditioned by the V-cycle (smg_solve_pcg): allocated by the first such solve, own graph cache ----
+    // ---- conjugate gradients preconditioned by the V-cycle (smg_solve_pcg): allocated by the first such solve ----
     smg::DevBuf<double> kry_x, kry_r, kry_p, kry_q, kry_b;   // n_0 x k: iterate, residual, direction, A p, RHS_u (the cycle's input overwrites L0.b)
     smg::DevBuf<double> kry_part, kry_s;                      // partial sums of the reductions, per-column scalars (smg_device.hpp: KryDev)
     smg::DevBuf<int> kry_restart;
     smg::KryDev kry;
-    hipGraphExec_t g_pcg = nullptr, g_pcg_n = nullptr;        // one / graph_iters() PCG iterations
-    smg::GraphKey g_pcg_key;                                  // what they were captured with (the MG graphs keep g_key)
     // ---- LOBPCG eigensolver (smg_eigs, smg_eig.cpp): allocated by the first call ----
     smg::DevBuf<double> eig_x[2], eig_ax[2], eig_p[2], eig_ap[2];   // n_0 x m: iterate, A iterate, direction, A direction (current / next)
     smg::DevBuf<double> eig_w, eig_aw;                               // the preconditioned residual (fp32 cycle; the fp64 one leaves it in L0.u), A W

@@ -1,7 +1,8 @@
 // smg_internal.hpp -- what the translation units behind the C ABI (include/smg.h) share with each other:
 //   smg_capi.cpp        errors, the handle (container, setters, introspection), profc mirror, mesh numerics shims
 //   smg_precompute.cpp  min_quad_with_fixed_mg_precompute: host sparse algebra, device images, value-only re-precompute, assembly
-//   smg_cycle.cpp       mg_VCycle / min_quad_with_fixed_mg_solve: launch sequence of a cycle, graph cache, outer loop, pieces
+//   smg_cycle.cpp       mg_VCycle: level vectors, smoothers, launch sequence of a cycle and of the outer residual, pieces, raw interface
+//   smg_solve.cpp       min_quad_with_fixed_mg_solve: the steps of the solve loops and their graph cache, outer loops (stationary, split-phase, sharded, PCG)
 //   smg_sweep_plans.cpp the plan-based Gauss-Seidel sweeps: which one a level uses, building, value refresh, introspection, self-checks
 //   smg_hierarchy_io.cpp mg_precompute / mg_precompute_block builders, point queries, .smgh files
 // Nothing here is part of the ABI.
@@ -90,11 +91,6 @@ int ensure_device(smg_hierarchy* h);            // first use of the device by a 
 void drop_graphs(smg_hierarchy* h);             // the cached hipGraphs no longer describe the handle
 int check_ready(const smg_hierarchy* h, const char* who);
 int check_cycle_opts(const smg_solve_opts& o);  // the option checks of smg_solve_begin (change nothing)
-// what smg_eigs (smg_eig.cpp) borrows from the solve (smg_cycle.cpp): latch the cycle's options and make the level vectors ready for k
-// unpadded internal columns; one V-cycle L0.u = V(L0.b, 0) (precision 1: L0.u32 = V32(L0.b32, 0)) with the caller-prepared input; y = A_uu x
-int eig_prepare(smg_hierarchy* h, const smg_solve_opts& o, int k);
-int eig_vcycle(smg_hierarchy* h, int k, const Ctrl* ctrl);
-int eig_apply_A(smg_hierarchy* h, const double* x, double* y, int k, const Ctrl* ctrl);
 
 // ---- profc mirror (PROFC_NODE, reference src/profc.h:9-13), timed on the GPU timeline -----------------------------------------
 int prof_scope_id(smg_hierarchy* h, const char* name);
@@ -141,6 +137,36 @@ enum { FIRST_NONE = 0,
                            // (Gauss-Seidel, in Lv.u) or the whole first sweep / step (Jacobi / Chebyshev, in Lv.t)
        FIRST_SWEEP = 2 };  // level 0 inside an outer iteration: the whole first sweep / step, produced out of place into Lv.t by the
                            // launches that also formed the outer residual (enqueue_head)
+
+int ensure_work(smg_hierarchy* h, int k);         // the level vectors (and sweep plans, spectral bounds) for k internal columns
+int ensure_fp32(smg_hierarchy* h, int k);         // ... and the fp32 images and vectors of the mixed-precision cycle
+// one V-cycle on level 0 with the handle's sweeps and precision: L0.u = V(L0.b, L0.u) (precision 1: L0.u32 = V32(L0.b32, L0.u32)); first: FIRST_* of the fp64 cycle
+int enqueue_vcycle(smg_hierarchy* h, int k, const Ctrl* ctrl, int first);
+int enqueue_residual_ss(smg_hierarchy* h, int k, bool fuse_decide = false, double* sumsq_out = nullptr);   // |RHS_u - A_0 z_u|^2 (+ break test), head-fused or not
+int enqueue_cycle_part(smg_hierarchy* h, int k, const double* d_sumsq);                                     // (break test on *d_sumsq,) the cycle of an outer iteration
+int apply_A(smg_hierarchy* h, int lv, SellMode mode, const double* x, const double* b, double* y, int k, const Ctrl* ctrl);   // SELL_AX / SELL_RESID with the level's matrix
+bool head_fusable(smg_hierarchy* h, int k);
+int internal_cols(const smg_hierarchy* h, int k);
+int coarse_stall_check(smg_hierarchy* h);
+
+template <typename Fn>
+static int capture_graph(smg_hierarchy* h, hipGraphExec_t* out, Fn&& body)
+{
+    hipGraph_t g = nullptr;
+    HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    int rc = body();
+    hipError_t e = hipStreamEndCapture(h->stream, &g);
+    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+    if (e != hipSuccess) return fail(SMG_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+    e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (e != hipSuccess) return fail(SMG_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+    return SMG_OK;
+}
+
+// ---- solve bookkeeping (smg_solve.cpp) ------------------------------------------------------------------------------------------------
+int latch_solve_opts(smg_hierarchy* h, const smg_solve_opts& o);   // the (checked) options become the handle's selection
+int reset_ctrl(smg_hierarchy* h, int cap);                         // a fresh control block on the stream: not done, the handle's tol, room for `cap` history entries
 
 // ---- Gauss-Seidel sweep plans (smg_sweep_plans.cpp) -------------------------------------------------------------------------------
 // How relax(sweeps) runs on a Gauss-Seidel level: at most one plan is set; none: one launch per colour.

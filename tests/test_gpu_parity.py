@@ -486,6 +486,58 @@ def test_speculative_split_phase_is_bit_identical(smg, oracle_mod):
     mg.set_stream(None)
 
 
+def test_loop_forms_alternating_on_one_handle_replay_what_eager_launches_give(smg, oracle_mod):
+    """Every loop form and several option sets in sequence on ONE handle and one user stream -- what makes the graph cache re-capture, keep
+    and drop -- against the same calls with eager launches on a second, fresh handle: every z, r_his and converged bit for bit."""
+    import torch
+    from surface_multigrid_code_amd.dist import GpuEngine, sharded_solve, sharded_solve_overlapped
+    p = subdiv_problem(kind="poisson", k=3, n_sub=2)
+    dev = torch.device("cuda", 0)
+
+    def sequence(use_graph):
+        mg = smg.Hierarchy.from_prolongs(p["Ps"])
+        mg.precompute(p["A"], p["known"])
+        st = torch.cuda.Stream(device=dev)
+        out, engines = [], []      # (the engines stay alive: each owns the reduction buffer its split-phase graphs were captured with)
+
+        def opts(**kw):
+            return smg.SolveOpts(tol=1e-9, max_iter=30, use_graph=use_graph, **kw)
+
+        def host(fn, k, o):
+            conv, z, rh = fn(p["RHS"][:, :k], p["z0"][:, :k], p["known_val"][:, :k], o)
+            out.append((conv, z.copy(), rh.copy()))
+
+        def split(loop):
+            to = lambda a: torch.from_numpy(np.ascontiguousarray(a[:, :1].T)).to(dev)
+            eng = GpuEngine(mg, to(p["RHS"]), to(p["z0"]), to(p["known_val"]), opts())
+            engines.append(eng)
+            conv, z, rh = loop(eng, 30, lambda t: None, check_every=2)
+            out.append((conv, z.cpu().numpy().T.copy(), rh.copy()))
+
+        with torch.cuda.stream(st):
+            mg.set_stream(st.cuda_stream)
+            host(mg.solve, 1, opts())
+            host(mg.solve_pcg, 1, opts())
+            host(mg.solve, 1, opts())
+            split(sharded_solve)
+            split(sharded_solve)                         # another reduction buffer
+            split(sharded_solve_overlapped)
+            host(mg.solve, 3, opts())                    # a key change
+            host(mg.solve, 3, opts(precision="mixed"))
+            host(mg.solve, 3, opts(pre=1))               # no head fusion for Gauss-Seidel
+            host(mg.solve_pcg, 1, opts())
+            torch.cuda.synchronize()
+        assert engines[0].sumsq.data_ptr() != engines[1].sumsq.data_ptr()
+        mg.set_stream(None)
+        return out
+
+    replayed, eager = sequence(1), sequence(0)
+    assert len(replayed) == len(eager) == 10
+    for i, (a, b) in enumerate(zip(replayed, eager)):
+        assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]), "step %d differs between graph replay and eager launches" % i
+    assert all(len(r[2]) > 2 for r in replayed)      # (every call iterated: tol 1e-9 from a random start)
+
+
 # ----------------------------------------------------------------------------------------------- SELL panel layouts
 @pytest.mark.parametrize("kind,k", [("mcf", 1), ("poisson", 3), ("mcf", 8)])
 def test_compact_and_fixed_pitch_panels_give_the_same_bits(smg, oracle_mod, kind, k, monkeypatch):
