@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 505
+#define SMG_VERSION 506
 
 enum {
     SMG_OK = 0,
@@ -429,6 +429,52 @@ long long smg_geodesics_device_bytes(const smg_geodesics *g);
 int smg_geodesics_solve(smg_geodesics *g, int k, const int *src_ptr, const int *src, int memspace, const smg_solve_opts *heat_opts,
                         const smg_solve_opts *poisson_opts, double *D, int ld_d, int *cycles);
 
+/* ---- as-rigid-as-possible deformation (Sorkine and Alexa 2007, spokes energy; libigl's arap_precompute / arap_solve) --------------------
+ * An addition: the reference has no deformation.  Rest positions p, deformed positions p', w_ij = L_ij the off-diagonal entries of the
+ * cotangent matrix of the REST pose (as smg_assemble produces them), e_ij = p_i - p_j, e'_ij = p'_i - p'_j, N(i) = the off-diagonal
+ * entries of row i of L in stored order:
+ *     E(R, p') = sum_i sum_{j in N(i)} w_ij |e'_ij - R_i e_ij|^2
+ *     local :  S_i = sum_j w_ij e_ij e'_ij^T,  R_i = the rotation (det = +1) that maximises tr(R_i S_i)
+ *              = V D U^T for S_i = U Sigma V^T, D = diag(1, 1, det(V U^T)), the flip on the smallest singular value
+ *     global:  (-L) p' = b,  b_i = sum_j (w_ij / 2) (R_i + R_j) e_ij,  the rows of the handle vertices known = the handle positions
+ * Iteration t: rotations R_t from the iterate U_t, E_t = E(R_t, U_t), the right-hand side, one 3-column solve warm-started at U_t -> U_{t+1}.
+ * After the last iteration one more local step gives the last energy (and leaves the final rotations in the object).  With exact solves
+ * E_{t+1} <= E_t.  The matrix never changes while handles move: it is precomputed once, at create.
+ *
+ * smg_arap_create: h gives the prolongations (any scalar hierarchy on this mesh); they are copied in memory into one internal handle, which
+ *   is precomputed here with -L and known = handles; h is not modified and may be destroyed afterwards.  V: nV x 3 row-major (the rest
+ *   pose), F: nF x 3, handles: n_handles distinct vertices (their order is the row order of handle_pos).  SMG_ERR_INVALID, before any
+ *   device work: a null argument, n_handles < 1, a handle out of range or repeated, every vertex a handle, a union handle, a block (3-DOF)
+ *   hierarchy, nV != the rows of level 0, a face index out of range, a face with zero double area, a non-finite coordinate, a mesh of more
+ *   than one connected component.  SMG_ERR_NO_DEVICE without a GPU.  A rest pose whose -L_uu is not positive definite fails in
+ *   smg_precompute, with that call's code.
+ * smg_arap_set_solver: pcg = 1 the global step runs smg_solve_pcg (the default: at the default tolerance the warm-started solves of the
+ *   1 M-vertex benchmark mesh take 7 - 8 loop entries by PCG against 10 - 11 by the stationary loop, 4.5 against 5.1 ms per iteration;
+ *   DESIGN.md section 19), 0 smg_solve's stationary loop; < 0 keeps the choice.
+ * smg_arap_device_bytes: the device memory held by the object -- the internal handle (as smg_debug_device_bytes counts it) and the
+ *   object's own buffers (the CSR of L, positions, rotations, four n x 3 blocks).
+ * smg_arap_solve: handle_pos: n_handles x 3 column-major, leading dimension ld_hp.  U0: nV x 3 column-major, or NULL = the rest pose; its
+ *   handle rows are ignored (the handle rows of every iterate are handle_pos).  U: nV x 3 column-major, leading dimension ld_u >= nV (rows
+ *   past nV are left alone).  handle_pos, U0 and U live in memspace (SMG_HOST / SMG_DEVICE); energy_his, cycles and n_iter are host.
+ *   Runs max_iter iterations (>= 0; 0 returns the start and E_0).  rel_tol > 0 ends the loop before iteration t + 1 when
+ *   E_t - E_{t+1} <= rel_tol |E_t|; rel_tol == 0 disables that test.  energy_his (NULL ok) must hold max_iter + 1 doubles, *n_iter + 1 are
+ *   written; cycles (NULL ok) must hold max_iter ints: the loop entries of each inner solve; *n_iter (NULL ok): the iterations run.
+ *   opts: the options of the inner solves (tol is absolute, as for smg_solve); NULL selects smg_solve_opts_default with max_iter = 50 and
+ *   tol = 1e-8 s, s = sqrt(sum_i (sum_j |w_ij| |e_ij|)^2), computed once at create: |R e| = |e|, so s bounds |b|_F for every set of
+ *   rotations and the default does not depend on the deformation.  An inner solve that ends unconverged is not an error
+ *   (cycles[t] == opts->max_iter tells); a failing solve's code is returned unchanged; a non-finite energy returns SMG_ERR_NONFINITE.
+ *   Everything between handle_pos / U0 and U stays on the object's stream; per iteration the host reads one energy double beside the inner
+ *   solve's own history.  Every call with the same inputs returns the same bits (graphs on or off, SMG_HOST or SMG_DEVICE).
+ * Not covered: the spokes-and-rims and element energies, dynamics, a new handle SET without a new object, union / block / sharded forms;
+ * negative cotangent weights are used as they are. */
+typedef struct smg_arap smg_arap;
+int smg_arap_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const int *handles, int n_handles, smg_arap **out);
+void smg_arap_destroy(smg_arap *a);
+int smg_arap_set_solver(smg_arap *a, int pcg);
+long long smg_arap_device_bytes(const smg_arap *a);
+int smg_arap_solve(smg_arap *a, const double *handle_pos, int ld_hp, const double *U0, int ld_u0, int memspace, int max_iter, double rel_tol,
+                   const smg_solve_opts *opts, double *U, int ld_u, double *energy_his, int *cycles, int *n_iter);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -597,6 +643,18 @@ int smg_debug_krylov(int op, int n, int k, double *v0, double *v1, double *v2, d
 enum { SMG_GEO_BASIS = 0, SMG_GEO_SCATTER = 1, SMG_GEO_DIVERGENCE = 2, SMG_GEO_SHIFT = 3 };
 int smg_debug_geodesics(int op, int n, int nF, int k, const int *F, const int *m_ptr, const int *m_idx, const int *src_ptr, const int *src,
                         const double *in, double *W, double *Af, double *out, int ld_out, int *guard_bad);
+/* One launcher of the ARAP local step (csrc/smg_arap_device.hip), handle-free and guarded like the hooks above.  rowptr[n + 1], col, w: a CSR
+ * matrix with n rows and columns (rowptr[0] = 0; diagonal entries are skipped, N(i) = the other entries of row i in stored order); P0, P:
+ * rest and current positions, n x 3 row-major; R_in: n rotations, 9 doubles each, row-major.  out is in/out.
+ *   SMG_ARAP_COVARIANCE     P0, P        -> out[9i + 3a + c] = sum_j (w_ij e_ij,a) e'_ij,c, e_ij = p_i - p_j
+ *   SMG_ARAP_ROTATIONS      P0, P        -> out[9i ..] = the rotation R_i that maximises tr(R_i S_i)
+ *   SMG_ARAP_RHS            P0, R_in     -> out (n x 3 column-major) = b, b_i = sum_j (w_ij / 2) (R_i + R_j) e_ij     (P may be NULL)
+ *   SMG_ARAP_VERTEX_ENERGY  P0, P, R_in  -> out[i] = sum_j w_ij |e'_ij - R_i e_ij|^2
+ *   SMG_ARAP_ENERGY         P0, P, R_in  -> out[0] = the sum of those terms (fixed row chunks, fixed-order finalize)
+ * SMG_ERR_INVALID for an unknown op, a missing operand or a bad CSR structure; SMG_ERR_NO_DEVICE without a GPU. */
+enum { SMG_ARAP_COVARIANCE = 0, SMG_ARAP_ROTATIONS = 1, SMG_ARAP_RHS = 2, SMG_ARAP_VERTEX_ENERGY = 3, SMG_ARAP_ENERGY = 4 };
+int smg_debug_arap(int op, int n, const int *rowptr, const int *col, const double *w, const double *P0, const double *P, const double *R_in,
+                   double *out, int *guard_hits);
 
 /* ---- profc.h mirror: named scopes accumulated with hipEvents (src/profc.h:9-13; mg_VCycle.cpp:121) ------------- */
 int smg_prof_enable(smg_hierarchy *h, int on);     /* forces eager launches while on */

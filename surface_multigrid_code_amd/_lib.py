@@ -78,6 +78,12 @@ def load():
         "smg_geodesics_set_solver": (i, [vp, i, i]),
         "smg_geodesics_device_bytes": (C.c_longlong, [vp]),
         "smg_geodesics_solve": (i, [vp, i, ip, ip, i, C.POINTER(SolveOptsC), C.POINTER(SolveOptsC), vp, i, ip]),
+        "smg_debug_arap": (i, [i, i, ip, ip, dp, dp, dp, dp, dp, ip]),
+        "smg_arap_create": (i, [vp, dp, i, ip, i, ip, i, C.POINTER(vp)]),
+        "smg_arap_destroy": (None, [vp]),
+        "smg_arap_set_solver": (i, [vp, i]),
+        "smg_arap_device_bytes": (C.c_longlong, [vp]),
+        "smg_arap_solve": (i, [vp, vp, i, vp, i, i, i, d, C.POINTER(SolveOptsC), vp, i, dp, ip, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

@@ -639,6 +639,64 @@ class HeatGeodesics:
         return self.cycles
 
 
+class ArapDeformer:
+    """As-rigid-as-possible deformation on the V-cycle (include/smg.h: smg_arap_*), libigl's arap_precompute / arap_solve (spokes energy).
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  V: the rest pose,
+    handles: the vertices whose positions deform() is given; the system -L of the rest pose is precomputed here, once."""
+
+    def __init__(self, hierarchy, V, F, handles):
+        self.L = _lib.load()
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        F = np.ascontiguousarray(F, dtype=np.int32)
+        self.handles = np.ascontiguousarray(handles, dtype=np.int32).reshape(-1)
+        self.n = V.shape[0]
+        out = C.c_void_p()
+        _chk(self.L.smg_arap_create(hierarchy.h, _dp(V), V.shape[0], _ip(F), F.shape[0], _ip(self.handles), self.handles.shape[0], C.byref(out)),
+             "smg_arap_create")
+        self.a = C.c_void_p(out.value)
+
+    def __del__(self):
+        try:
+            if self.a:
+                self.L.smg_arap_destroy(self.a)
+                self.a = None
+        except Exception:
+            pass
+
+    def set_solver(self, pcg=-1):
+        """1: the global step runs smg_solve_pcg (default), 0: smg_solve's stationary loop, -1: unchanged."""
+        _chk(self.L.smg_arap_set_solver(self.a, int(pcg)), "smg_arap_set_solver")
+
+    def device_bytes(self):
+        return self.L.smg_arap_device_bytes(self.a)
+
+    def _run(self, hp_ptr, ld_hp, U0_ptr, ld_u0, memspace, max_iter, rel_tol, opts, U_ptr, ld_u):
+        E = np.zeros(max_iter + 1)
+        cyc = np.zeros(max(max_iter, 1), dtype=np.int32)
+        nit = C.c_int(0)
+        _chk(self.L.smg_arap_solve(self.a, hp_ptr, ld_hp, U0_ptr, ld_u0, memspace, int(max_iter), float(rel_tol),
+                                   C.byref(opts.c) if opts is not None else None, U_ptr, ld_u, _dp(E), _ip(cyc), C.byref(nit)), "smg_arap_solve")
+        return E[:nit.value + 1].copy(), cyc[:nit.value].copy()
+
+    def deform(self, handle_pos, U0=None, max_iter=10, rel_tol=0.0, opts=None):
+        """handle_pos: n_handles x 3 (row r = the position of handles[r]); U0: the n x 3 start, None = the rest pose.  Returns
+        (U, energy_his, cycles): the n x 3 positions after the iterations run, E_0 .. E_n_iter, the loop entries of each inner solve."""
+        hp = _colmajor(handle_pos)
+        assert hp.shape == (self.handles.shape[0], 3)
+        U0 = None if U0 is None else _colmajor(U0)
+        assert U0 is None or U0.shape == (self.n, 3)
+        U = np.zeros((self.n, 3), order="F")
+        E, cyc = self._run(hp.ctypes.data, hp.shape[0], U0.ctypes.data if U0 is not None else None, self.n, SMG_HOST, max_iter, rel_tol, opts,
+                           U.ctypes.data, self.n)
+        return U, E, cyc
+
+    def deform_device(self, hp_ptr, U_ptr, ld_u=None, U0_ptr=None, ld_u0=None, ld_hp=None, max_iter=10, rel_tol=0.0, opts=None):
+        """deform() between column-major blocks resident in HBM (device pointers; leading dimensions default to n_handles and n).
+        Returns (energy_his, cycles)."""
+        return self._run(hp_ptr, ld_hp or self.handles.shape[0], U0_ptr, ld_u0 or self.n, SMG_DEVICE, max_iter, rel_tol, opts, U_ptr, ld_u or self.n)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the reference's free functions
 

@@ -1,0 +1,223 @@
+// smg_arap.cpp -- as-rigid-as-possible deformation on the V-cycle (include/smg.h: smg_arap_*).
+// The object owns one handle built from the caller's prolongations and precomputed with -L of the rest pose, the handle vertices known; the
+// CSR of L on the device (the weights of the local step are the system's own values), the rest positions and the buffers of an iteration.
+// One iteration: rotations + energy terms (k_arap_rotations), the energy (fixed-order reduction), the right-hand side (k_arap_rhs), one
+// 3-column solve warm-started at the iterate, the new iterate as xyz rows.  All of it is enqueued on the object's stream, which the handle
+// uses too; per iteration the host reads one energy double beside the solve's own history.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <vector>
+
+#include "smg_bsr3.hpp"
+#include "smg_device.hpp"
+#include "smg_internal.hpp"
+
+using namespace smg;
+
+struct smg_arap {
+    smg_hierarchy* h = nullptr;
+    hipStream_t stream = nullptr;
+    int device = -1;
+    int nV = 0, nh = 0;
+    int pcg = 1;                          // the inner solver: 1 smg_solve_pcg (7 - 8 loop entries per solve on C3 against 10 - 11), 0 smg_solve
+    double scale = 0.0;                   // s = sqrt(sum_i (sum_j |w_ij| |e_ij|)^2) >= |b|_F for every set of rotations
+    DevBuf<int> rowptr, col, handles;     // the CSR pattern of L, the handle vertices in the caller's order
+    DevBuf<double> w, P0;                 // the values of L (smg_assemble's d_Lval), rest positions (xyz rows)
+    DevBuf<double> P, R, eterm, part, E;  // current positions (xyz rows), rotations (9 per vertex), energy terms, their chunk sums, E_t
+    DevBuf<double> B, Ua, Ub, hp;         // column-major n x 3: right-hand side, the iterate and the solve's result; handle positions (nh x 3)
+    ~smg_arap()
+    {
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (h) smg_hierarchy_destroy(h);
+        rowptr.release(); col.release(); handles.release(); w.release(); P0.release(); P.release(); R.release(); eterm.release();
+        part.release(); E.release(); B.release(); Ua.release(); Ub.release(); hp.release();
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+
+int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, int nF, const int* handles, int n_handles, smg_arap** out)
+{
+    if (out) *out = nullptr;
+    if (!h || !V || !F || !handles || !out || nV <= 0 || nF <= 0) return fail(SMG_ERR_INVALID, "smg_arap_create: bad arguments");
+    if (n_handles < 1) return fail(SMG_ERR_INVALID, "smg_arap_create: n_handles = %d, at least one handle vertex is needed", n_handles);
+    if (h->union_m > 0) return fail(SMG_ERR_INVALID, "smg_arap_create: union handles are not supported");
+    Csr Pv;
+    if (h->bs == 3 || h->block_mode == 3 || (h->n_levels >= 2 && h->lv[1].P_full.nr > 0 && kron3_factor(h->lv[1].P_full, Pv)))
+        return fail(SMG_ERR_INVALID, "smg_arap_create: block (3-DOF) hierarchies are not supported");
+    const int rows = level0_rows(h);
+    if (rows != nV) return fail(SMG_ERR_INVALID, "smg_arap_create: nV = %d, but level 0 of the hierarchy has %d rows", nV, rows);
+    {
+        std::vector<char> seen((size_t)nV, 0);
+        for (int r = 0; r < n_handles; r++) {
+            if (handles[r] < 0 || handles[r] >= nV) return fail(SMG_ERR_INVALID, "smg_arap_create: handle %d out of range", handles[r]);
+            if (seen[handles[r]]) return fail(SMG_ERR_INVALID, "smg_arap_create: handle %d is repeated", handles[r]);
+            seen[handles[r]] = 1;
+        }
+    }
+    if (n_handles >= nV) return fail(SMG_ERR_INVALID, "smg_arap_create: every vertex is a handle: nothing to solve");
+    for (size_t i = 0; i < (size_t)nF * 3; i++)
+        if (F[i] < 0 || F[i] >= nV) return fail(SMG_ERR_INVALID, "smg_arap_create: face index out of range");
+    for (int f = 0; f < nF; f++)
+        if (!(double_area(V, F, f) > 0.0)) return fail(SMG_ERR_INVALID, "smg_arap_create: face %d has zero double area", f);
+    for (size_t i = 0; i < (size_t)nV * 3; i++)
+        if (!std::isfinite(V[i])) return fail(SMG_ERR_INVALID, "smg_arap_create: non-finite vertex coordinate");
+    if (const int nc = components(F, nF, nV); nc != 1)
+        return fail(SMG_ERR_INVALID, "smg_arap_create: the mesh has %d connected components (vertices in no face count)", nc);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SMG_ERR_NO_DEVICE, "smg_arap_create: no HIP device: libsmg has no CPU fallback");
+
+    std::unique_ptr<smg_arap> a(new smg_arap());
+    a->nV = nV; a->nh = n_handles;
+    HIPCHK(hipGetDevice(&a->device));
+    HIPCHK(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
+    a->h = smg_hierarchy_create(h->n_levels);
+    if (!a->h) return fail(SMG_ERR_ALLOC, "smg_arap_create: out of memory");
+    if (int rc = copy_prolongations(h, a->h)) return rc;
+    if (int rc = smg_hierarchy_set_stream(a->h, a->stream)) return rc;
+
+    // L of the rest pose on the device (smg_assemble): its values stay there as the weights, their negatives are the system
+    smg_assembler* as = nullptr;
+    if (int rc = smg_assembler_create(F, nF, nV, &as)) return rc;
+    struct AsmOwner { smg_assembler* a; ~AsmOwner() { smg_assembler_destroy(a); } } own_a{as};
+    int nnz = 0;
+    smg_assembler_pattern(as, &nnz, nullptr, nullptr);
+    std::vector<int> ptr((size_t)nV + 1), col((size_t)nnz);
+    smg_assembler_pattern(as, nullptr, ptr.data(), col.data());
+    std::vector<double> lval((size_t)nnz);
+    {
+        DevBuf<double> dval;
+        std::vector<double> Vh(V, V + (size_t)nV * 3);
+        HIPCHK(a->P0.upload(Vh));
+        HIPCHK(dval.alloc((size_t)nnz));
+        HIPCHK(a->w.alloc((size_t)nnz));
+        if (int rc = smg_assemble(as, a->P0.p, 0, 0.0, -1.0, dval.p, nullptr, a->w.p, a->stream)) return rc;
+        HIPCHK(hipStreamSynchronize(a->stream));
+        HIPCHK(hipMemcpy(lval.data(), a->w.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    double ss = 0.0;
+    for (int i = 0; i < nV; i++) {
+        double row = 0.0;
+        for (int q = ptr[i]; q < ptr[i + 1]; q++) {
+            const int j = col[q];
+            if (j == i) continue;
+            const double ex = V[3 * (size_t)i] - V[3 * (size_t)j], ey = V[3 * (size_t)i + 1] - V[3 * (size_t)j + 1], ez = V[3 * (size_t)i + 2] - V[3 * (size_t)j + 2];
+            row += std::fabs(lval[q]) * std::sqrt(ex * ex + ey * ey + ez * ez);
+        }
+        ss += row * row;
+    }
+    a->scale = std::sqrt(ss);
+    for (double& v : lval) v = -v;
+    if (int rc = smg_precompute(a->h, nV, ptr.data(), col.data(), lval.data(), handles, n_handles)) return rc;
+
+    HIPCHK(a->rowptr.upload(ptr));
+    HIPCHK(a->col.upload(col));
+    HIPCHK(a->handles.upload(std::vector<int>(handles, handles + n_handles)));
+    const size_t n = (size_t)nV;
+    HIPCHK(a->P.alloc(3 * n));
+    HIPCHK(a->R.alloc(9 * n));
+    HIPCHK(a->eterm.alloc(n));
+    HIPCHK(a->part.alloc((size_t)arap_groups(nV)));
+    HIPCHK(a->B.alloc(3 * n));
+    HIPCHK(a->Ua.alloc(3 * n));
+    HIPCHK(a->Ub.alloc(3 * n));
+    HIPCHK(a->hp.alloc(3 * (size_t)n_handles));
+    *out = a.release();
+    return SMG_OK;
+}
+
+int solve_impl(smg_arap* a, const double* handle_pos, int ld_hp, const double* U0, int ld_u0, int memspace, int max_iter, double rel_tol,
+               const smg_solve_opts* opts, double* U, int ld_u, double* energy_his, int* cycles, int* n_iter)
+{
+    if (!a || !handle_pos || !U || (memspace != SMG_HOST && memspace != SMG_DEVICE) || max_iter < 0 || !(rel_tol >= 0.0) || !std::isfinite(rel_tol))
+        return fail(SMG_ERR_INVALID, "smg_arap_solve: bad arguments");
+    const int n = a->nV, nh = a->nh;
+    if (ld_hp < nh || ld_u < n || (U0 && ld_u0 < n)) return fail(SMG_ERR_INVALID, "smg_arap_solve: a leading dimension is too small");
+    DeviceScope dsc(a->device);
+    hipStream_t st = a->stream;
+    const hipMemcpyKind in = memspace == SMG_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    const hipMemcpyKind back = memspace == SMG_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    const size_t col_n = (size_t)n * sizeof(double), col_h = (size_t)nh * sizeof(double);
+
+    smg_solve_opts so;
+    if (opts) so = *opts;
+    else { smg_solve_opts_default(&so); so.max_iter = 50; so.tol = 1e-8 * a->scale; }
+    std::vector<double> his((size_t)std::max(1, so.max_iter));
+    HIPCHK(a->E.ensure((size_t)max_iter + 1));
+
+    // the start: U0 or the rest pose, the handle rows from handle_pos; as the solve's column-major block (Ua) and as xyz rows (P)
+    HIPCHK(hipMemcpy2DAsync(a->hp.p, col_h, handle_pos, (size_t)ld_hp * sizeof(double), col_h, 3, in, st));
+    if (U0) HIPCHK(hipMemcpy2DAsync(a->Ua.p, col_n, U0, (size_t)ld_u0 * sizeof(double), col_n, 3, in, st));
+    else HIPCHK(launch_arap_columns(n, a->P0.p, a->Ua.p, n, st));
+    HIPCHK(launch_arap_set_handles(nh, a->handles.p, a->hp.p, nh, a->Ua.p, n, st));
+    HIPCHK(launch_arap_rows(n, a->Ua.p, n, a->P.p, st));
+
+    int t = 0;
+    double E_prev = 0.0;
+    for (;; t++) {
+        // local step: R_t from U_t, E_t = E(R_t, U_t); the right-hand side is enqueued ahead of the host's look at E_t
+        HIPCHK(launch_arap_rotations(n, a->rowptr.p, a->col.p, a->w.p, a->P0.p, a->P.p, a->R.p, a->eterm.p, st));
+        HIPCHK(launch_arap_energy(a->eterm.p, n, a->part.p, a->E.p + t, st));
+        double E_t = 0.0;
+        HIPCHK(hipMemcpyAsync(&E_t, a->E.p + t, sizeof(double), hipMemcpyDeviceToHost, st));
+        if (t < max_iter) HIPCHK(launch_arap_rhs(n, a->rowptr.p, a->col.p, a->w.p, a->P0.p, a->R.p, a->B.p, n, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (energy_his) energy_his[t] = E_t;
+        if (!std::isfinite(E_t)) {
+            if (n_iter) *n_iter = t;
+            return fail(SMG_ERR_NONFINITE, "smg_arap_solve: non-finite energy at iteration %d", t);
+        }
+        if (t == max_iter) break;
+        if (t > 0 && rel_tol > 0.0 && E_prev - E_t <= rel_tol * std::fabs(E_prev)) break;
+        E_prev = E_t;
+        // global step: (-L) U_{t+1} = b, handle rows known, from U_t
+        int nhis = 0, conv = 0;
+        if (int rc = (a->pcg ? smg_solve_pcg : smg_solve)(a->h, a->B.p, n, a->hp.p, nh, a->Ua.p, n, 3, SMG_DEVICE, &so, a->Ub.p, n, his.data(), &nhis, &conv)) {
+            if (n_iter) *n_iter = t;
+            return rc;
+        }
+        if (cycles) cycles[t] = nhis;
+        std::swap(a->Ua, a->Ub);
+        HIPCHK(launch_arap_rows(n, a->Ua.p, n, a->P.p, st));
+    }
+    if (n_iter) *n_iter = t;
+    HIPCHK(hipMemcpy2DAsync(U, (size_t)ld_u * sizeof(double), a->Ua.p, col_n, col_n, 3, back, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SMG_OK;
+}
+
+}  // namespace
+
+extern "C" int smg_arap_create(const smg_hierarchy* h, const double* V, int nV, const int* F, int nF, const int* handles, int n_handles, smg_arap** out)
+{
+    return guarded("smg_arap_create", [&]() { return create_impl(h, V, nV, F, nF, handles, n_handles, out); });
+}
+
+extern "C" void smg_arap_destroy(smg_arap* a) { delete a; }
+
+extern "C" int smg_arap_set_solver(smg_arap* a, int pcg)
+{
+    if (!a) return fail(SMG_ERR_INVALID, "null arap object");
+    if (pcg >= 0) a->pcg = pcg ? 1 : 0;
+    return SMG_OK;
+}
+
+extern "C" long long smg_arap_device_bytes(const smg_arap* a)
+{
+    if (!a) return 0;
+    auto B = [](const auto& d) { return (long long)(d.n * sizeof(*d.p)); };
+    return handle_bytes(a->h) + B(a->rowptr) + B(a->col) + B(a->handles) + B(a->w) + B(a->P0) + B(a->P) + B(a->R) + B(a->eterm) + B(a->part) +
+           B(a->E) + B(a->B) + B(a->Ua) + B(a->Ub) + B(a->hp);
+}
+
+extern "C" int smg_arap_solve(smg_arap* a, const double* handle_pos, int ld_hp, const double* U0, int ld_u0, int memspace, int max_iter,
+                              double rel_tol, const smg_solve_opts* opts, double* U, int ld_u, double* energy_his, int* cycles, int* n_iter)
+{
+    return guarded("smg_arap_solve", [&]() {
+        return solve_impl(a, handle_pos, ld_hp, U0, ld_u0, memspace, max_iter, rel_tol, opts, U, ld_u, energy_his, cycles, n_iter);
+    });
+}

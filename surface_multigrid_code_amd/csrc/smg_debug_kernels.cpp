@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov) and of the geodesics kernels (smg_debug_geodesics).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics) and of the ARAP kernels (smg_debug_arap).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -325,6 +325,49 @@ extern "C" int smg_debug_geodesics(int op, int n, int nF, int k, const int* F, c
         int bad = 0;
         HIPCHK(X.finish(&bad));
         if (guard_bad) *guard_bad = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_arap(int op, int n, const int* rowptr, const int* col, const double* w, const double* P0, const double* P,
+                              const double* R_in, double* out, int* guard_hits)
+{
+    return guarded("smg_debug_arap", [&]() -> int {
+        if (op < SMG_ARAP_COVARIANCE || op > SMG_ARAP_ENERGY || n < 1 || !rowptr || !col || !w || !P0 || !out)
+            return fail(SMG_ERR_INVALID, "smg_debug_arap: bad arguments");
+        if ((op != SMG_ARAP_RHS && !P) || (op >= SMG_ARAP_RHS && !R_in)) return fail(SMG_ERR_INVALID, "smg_debug_arap: op %d misses an operand", op);
+        if (rowptr[0] != 0) return fail(SMG_ERR_INVALID, "smg_debug_arap: rowptr[0] != 0");
+        if (const char* why = check_compressed(n, n, rowptr, col)) return fail(SMG_ERR_INVALID, "smg_debug_arap: %s", why);
+        if (int rc = need_device("smg_debug_arap")) return rc;
+        Scratch X;
+        HIPCHK(X.init());
+        const size_t nnz = (size_t)rowptr[n], vec = (size_t)n * sizeof(double);
+        const size_t out_bytes = op <= SMG_ARAP_ROTATIONS ? 9 * vec : op == SMG_ARAP_RHS ? 3 * vec : op == SMG_ARAP_VERTEX_ENERGY ? vec : sizeof(double);
+        int *dptr = nullptr, *dcol = nullptr;
+        double *dw = nullptr, *dP0 = nullptr, *dP = nullptr, *dR = nullptr, *dout = nullptr, *dterm = nullptr, *dpart = nullptr;
+        HIPCHK(X.add(rowptr, nullptr, ((size_t)n + 1) * sizeof(int), &dptr));
+        HIPCHK(X.add(col, nullptr, nnz * sizeof(int), &dcol));
+        HIPCHK(X.add(w, nullptr, nnz * sizeof(double), &dw));
+        HIPCHK(X.add(P0, nullptr, 3 * vec, &dP0));
+        if (P) HIPCHK(X.add(P, nullptr, 3 * vec, &dP));
+        if (op >= SMG_ARAP_RHS) HIPCHK(X.add(R_in, nullptr, 9 * vec, &dR));
+        HIPCHK(X.add(out, out, out_bytes, &dout));
+        if (op == SMG_ARAP_ROTATIONS || op == SMG_ARAP_ENERGY) HIPCHK(X.add(nullptr, nullptr, vec, &dterm));
+        if (op == SMG_ARAP_ENERGY) HIPCHK(X.add(nullptr, nullptr, (size_t)arap_groups(n) * sizeof(double), &dpart));
+        hipStream_t st = X.stream();
+        switch (op) {
+            case SMG_ARAP_COVARIANCE: HIPCHK(launch_arap_covariance(n, dptr, dcol, dw, dP0, dP, dout, st)); break;
+            case SMG_ARAP_ROTATIONS: HIPCHK(launch_arap_rotations(n, dptr, dcol, dw, dP0, dP, dout, dterm, st)); break;
+            case SMG_ARAP_RHS: HIPCHK(launch_arap_rhs(n, dptr, dcol, dw, dP0, dR, dout, n, st)); break;
+            case SMG_ARAP_VERTEX_ENERGY: HIPCHK(launch_arap_vertex_energy(n, dptr, dcol, dw, dP0, dP, dR, dout, st)); break;
+            default:
+                HIPCHK(launch_arap_vertex_energy(n, dptr, dcol, dw, dP0, dP, dR, dterm, st));
+                HIPCHK(launch_arap_energy(dterm, n, dpart, dout, st));
+                break;
+        }
+        int bad = 0;
+        HIPCHK(X.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
         return SMG_OK;
     });
 }

@@ -397,4 +397,24 @@ hipError_t launch_geo_divergence(int n, int k, const int* F, const double* W, co
 hipError_t launch_geo_shift(int n, int k, const int* src_ptr, const int* src, const double* phi, int ldp, double* mean, double* D, int ldd,
                             hipStream_t st);
 
+// as-rigid-as-possible deformation (smg_arap_device.hip).  rowptr / col / w: the CSR of the rest pose's cotangent matrix (diagonal entries
+// are skipped); P0, P: rest and current positions as xyz rows; S, R: 9 doubles per vertex, row-major; B, U: column-major n x 3 ----------
+// S_i = sum_j w_ij e_ij e'_ij^T in the row's stored order
+hipError_t launch_arap_covariance(int n, const int* rowptr, const int* col, const double* w, const double* P0, const double* P, double* S, hipStream_t st);
+// R_i = the closest rotation of S_i (smg_arap_inl.hpp), eterm[i] = sum_j w_ij |e'_ij - R_i e_ij|^2
+hipError_t launch_arap_rotations(int n, const int* rowptr, const int* col, const double* w, const double* P0, const double* P, double* R, double* eterm,
+                                 hipStream_t st);
+// eterm[i] with the given rotations
+hipError_t launch_arap_vertex_energy(int n, const int* rowptr, const int* col, const double* w, const double* P0, const double* P, const double* R,
+                                     double* eterm, hipStream_t st);
+// B[c * ldb + i] = (sum_j (w_ij / 2) (R_i + R_j) e_ij)_c
+hipError_t launch_arap_rhs(int n, const int* rowptr, const int* col, const double* w, const double* P0, const double* R, double* B, int ldb, hipStream_t st);
+// *E = sum_i eterm[i] by fixed row chunks (part: arap_groups(n) doubles of scratch) and a fixed-order finalize
+int arap_groups(int n);
+hipError_t launch_arap_energy(const double* eterm, int n, double* part, double* E, hipStream_t st);
+// P = U and U = P between xyz rows and a column-major block; the handle rows of U from hp (nh x 3 column-major, leading dimension ldh)
+hipError_t launch_arap_rows(int n, const double* U, int ldu, double* P, hipStream_t st);
+hipError_t launch_arap_columns(int n, const double* P, double* U, int ldu, hipStream_t st);
+hipError_t launch_arap_set_handles(int nh, const int* handles, const double* hp, int ldh, double* U, int ldu, hipStream_t st);
+
 }  // namespace smg

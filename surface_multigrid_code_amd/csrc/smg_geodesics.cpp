@@ -45,7 +45,8 @@ struct smg_geodesics {
     }
 };
 
-namespace {
+// ---- what every object built on a mesh and a caller's hierarchy checks and copies (smg_internal.hpp; smg_arap.cpp uses them too) ----
+namespace smg {
 
 // twice the area of face f, the expression of k_face_terms / k_geo_basis
 double double_area(const double* V, const int* F, int f)
@@ -98,6 +99,10 @@ int copy_prolongations(const smg_hierarchy* src, smg_hierarchy* dst)
     }
     return SMG_OK;
 }
+
+}  // namespace smg
+
+namespace {
 
 int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, int nF, double t, int voronoi, smg_geodesics** out)
 {

@@ -115,6 +115,13 @@ const char* check_compressed(int n_major, int n_minor, const int* ptr, const int
 int set_prolong(smg_hierarchy* h, int lv, Csr&& P);   // mg[lv].P = PT^T = P_full = P  (reference src/mg_precompute.cpp:74-76)
 Mesh wrap_mesh(const double* V, int nV, const int* F, int nF);
 
+// ---- objects built on a mesh and a caller's hierarchy: smg_geodesics, smg_arap (helpers in smg_geodesics.cpp) --------------------------
+double double_area(const double* V, const int* F, int f);          // twice the area of face f
+int components(const int* F, int nF, int nV);                      // connected components of the vertex graph (a vertex in no face is one)
+int level0_rows(const smg_hierarchy* h);                           // rows of level 0 of a hierarchy whose prolongations are set (-1: none set)
+long long handle_bytes(const smg_hierarchy* h);                    // the "total" of smg_debug_device_bytes
+int copy_prolongations(const smg_hierarchy* src, smg_hierarchy* dst);
+
 // ---- precompute (smg_precompute.cpp) ------------------------------------------------------------------------------------------------
 int spectral_bounds(smg_hierarchy* h);          // Gershgorin bounds of D^-1 A on every smoothed level (Chebyshev-Jacobi)
 int ensure_spectral_bounds(smg_hierarchy* h);   // ... only when a level is smoothed that way and the values changed
