@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 506
+#define SMG_VERSION 507
 
 enum {
     SMG_OK = 0,
@@ -475,6 +475,61 @@ long long smg_arap_device_bytes(const smg_arap *a);
 int smg_arap_solve(smg_arap *a, const double *handle_pos, int ld_hp, const double *U0, int ld_u0, int memspace, int max_iter, double rel_tol,
                    const smg_solve_opts *opts, double *U, int ld_u, double *energy_his, int *cycles, int *n_iter);
 
+/* ---- implicit-Euler steps of a pressurised neo-Hookean membrane (the reference's 06_example_balloon_sim: main.cpp:109-134,
+ * implicit_euler_mg_balloon.h:35-121, stretching energy only, no constraints) -- an application object on the BLOCK V-cycle -----------------
+ * Per face with corners q0, q1, q2 (order of F), e1 = q1 - q0, e2 = q2 - q0:  a = [[e1.e1, e1.e2], [e1.e2, e2.e2]], abar = a of the rest pose,
+ *     lnJ = log(det a / det abar) / 2,   W_f = coeff (beta (tr(abar^-1 a) - 2 - 2 lnJ) + alpha lnJ^2),   coeff = thickness sqrt(det abar) / 4,
+ *     alpha = young poisson / (1 - poisson^2),  beta = young / (2 (1 + poisson)).
+ * G_f (9) and H_f (9 x 9) are its derivatives with respect to (q0, q1, q2) (NeoHookeanMaterial.cpp:12-68); every eigenvalue of H_f below
+ * eig_floor is replaced by eig_value (ElasticShell.cpp:86-95), so H = M + dt^2 K is positive definite.  K and g sum the faces' blocks.
+ * A step from the state (pos, qdot), qdot0 = qdot, pos0 = pos:
+ *     fext_v = -pressure m_v(pos) n_v(pos)      m: lumped Voronoi mass of the CURRENT pose, n: unit vertex normal (area-weighted face normals)
+ *     M = mass_scale (Voronoi mass of the REST pose), three equal entries per vertex
+ *     newton_iters times:  (G, K) at pos;  H = M + dt^2 K;  b = -(M (qdot - qdot0) + dt G + dt fext)
+ *         value-only re-precompute with H;  dx = solve(H, b) from 0
+ *         f(t) = sum_v (pos0_v + dt t_v) . fext_v + (t - qdot0)^T M (t - qdot0) / 2 + W(pos0 + dt t)
+ *         s = f(qdot) + ls_c b . dx;  a = 1;  while a > ls_min_alpha: if f(qdot + a dx) <= s: qdot += a dx, stop;  else a *= ls_shrink
+ *         pos = pos0 + dt qdot
+ * The acceptance test is the reference's (b is the NEGATIVE gradient, so it is weaker than Armijo's); when the search gives up qdot is left
+ * alone.  When |b|_F is below the solve's tolerance the solve returns dx = 0 after one loop entry and a = 1 is accepted.
+ *
+ * smg_membrane_create: h must be a block hierarchy on this mesh (level 0 has 3 nV rows, every prolongation Pv (x) I_3: smg_mg_precompute_block,
+ *   smg_level_set_prolong, a file); its prolongations are copied into one internal handle, h is not modified.  The pattern is
+ *   (adjacency + I) (x) 1_3x3; the first precompute takes H of the rest pose (assembled on the device), every later one is
+ *   smg_precompute_values_device.  The state starts as (V, 0).  SMG_ERR_INVALID before any device work: a null argument, a scalar hierarchy, a
+ *   union handle, 3 nV != rows of level 0, a face index out of range, a face of zero double area, a non-finite coordinate, more than one
+ *   connected component, dt <= 0, |poisson| >= 1, young <= 0, thickness <= 0, mass_scale <= 0, newton_iters < 0, eig_value <= 0.
+ * smg_membrane_set_state / get_state: nV x 3 row-major blocks (host or device); set: NULL pos = the rest pose, NULL qdot = 0; get: NULL = skip.
+ * smg_membrane_set_solver: 0 (default) smg_solve, the reference's loop; 1 smg_solve_pcg.
+ * smg_membrane_step: opts == NULL selects smg_solve_opts_default with tol = 2e-1 (the reference's mg_tolerance; the tolerance is absolute).
+ *   Outputs (NULL ok): objective_his[i] = f(qdot) before Newton iteration i plus one final entry (newton_iters + 1 doubles), alpha[i] the
+ *   accepted step (0 when the search gave up), cycles[i] the loop entries of solve i, *n_newton the iterations completed.  A non-finite
+ *   objective at an accepted state (a face with det a <= 0 has W = +inf) returns SMG_ERR_NONFINITE; a trial state with one simply fails the
+ *   acceptance test.  A failing solve's code is returned unchanged.  The same inputs give the same bits.
+ * smg_membrane_lists: the block pattern and the contribution lists the matrix kernel sums in: bptr[nV + 1] / bcol[n_blocks] the block CSR
+ *   (columns ascending), c_ptr[n_blocks + 1] / c_src[9 nF] per block the sub-blocks 9 f + 3 a + b (corners a, b of face f), faces ascending.
+ *   Query the sizes with NULL arrays first.  Scalar row 3 i + l of H holds, for the blocks q of block row i in order, the columns
+ *   3 bcol[q] + m, m = 0 .. 2.
+ * smg_membrane_faces_host: the per-face maths of the device kernel compiled for the host (no device needed): W[nF], G (9 planes, entry e of
+ *   face f at G[e nF + f], may be NULL with H), H (the 45 entries of the upper triangle row by row, same planes, may be NULL), fixed when fix != 0. */
+typedef struct {
+    double young, poisson, thickness, mass_scale, dt, pressure;
+    int newton_iters;
+    double ls_c, ls_shrink, ls_min_alpha, eig_floor, eig_value;
+} smg_membrane_params;
+void smg_membrane_params_default(smg_membrane_params *p);   /* 6e6, .5, .1, 1000, 1e-3, 1e6, 10, 1e-8, .5, 1e-8, 1e-6, 1e-3 */
+typedef struct smg_membrane smg_membrane;
+int smg_membrane_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const smg_membrane_params *p, smg_membrane **out);
+void smg_membrane_destroy(smg_membrane *m);
+long long smg_membrane_device_bytes(const smg_membrane *m);
+int smg_membrane_set_state(smg_membrane *m, const double *pos, const double *qdot, int memspace);
+int smg_membrane_get_state(smg_membrane *m, double *pos, double *qdot, int memspace);
+int smg_membrane_set_solver(smg_membrane *m, int pcg);
+int smg_membrane_step(smg_membrane *m, const smg_solve_opts *opts, double *objective_his, double *alpha, int *cycles, int *n_newton);
+int smg_membrane_lists(const int *F, int nF, int nV, int *n_blocks, int *n_contrib, int *bptr, int *bcol, int *c_ptr, int *c_src);
+int smg_membrane_faces_host(const double *V0, const double *P, int nV, const int *F, int nF, const smg_membrane_params *p, int fix, double *W,
+                            double *G, double *H);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -655,6 +710,22 @@ int smg_debug_geodesics(int op, int n, int nF, int k, const int *F, const int *m
 enum { SMG_ARAP_COVARIANCE = 0, SMG_ARAP_ROTATIONS = 1, SMG_ARAP_RHS = 2, SMG_ARAP_VERTEX_ENERGY = 3, SMG_ARAP_ENERGY = 4 };
 int smg_debug_arap(int op, int n, const int *rowptr, const int *col, const double *w, const double *P0, const double *P, const double *R_in,
                    double *out, int *guard_hits);
+
+/* One launcher of the membrane step (csrc/smg_membrane_device.hip), handle-free and guarded like the hooks above.  V0: the rest pose, P: a pose,
+ * both nV x 3 row-major; per-face arrays are planes (entry e of face f at [e nF + f]); in / out are concatenations in the order given:
+ *   SMG_MEM_REST        V0                 -> out = rest constants (5 planes): (abar^-1)00, 01, 11, det abar, coeff
+ *   SMG_MEM_FACES_RAW   V0, P              -> out = W (nF), G (9 planes), the upper triangle of the UNFIXED H_f (45 planes)
+ *   SMG_MEM_FACES       V0, P              -> the same with the eigenvalue fix
+ *   SMG_MEM_ENERGY      V0, P              -> out = W (nF) by the energy-only kernel of the line search
+ *   SMG_MEM_PRESSURE    P                  -> out = e1 x e2 (3 planes), corner shares of the Voronoi mass (3 planes), m (nV), fext (3 nV)
+ *   SMG_MEM_MATRIX      in = H (45 planes), mass0 (nV)                                   -> out = the values of H = M + dt^2 K (9 n_blocks)
+ *   SMG_MEM_GRADIENT    in = G (9 planes), mass0 (nV), qdot, qdot0, fext (3 nV each)        -> out = g (3 nV), b (3 nV)
+ *   SMG_MEM_OBJECTIVE   V0, P = pos0, in = mass0 (nV), qdot, dx, qdot0, fext (3 nV each), step (1)
+ *                                          -> out = t (3 nV), pos0 + dt t (3 nV), the terms (nF faces, then nV vertices), f (1) */
+enum { SMG_MEM_REST = 0, SMG_MEM_FACES_RAW = 1, SMG_MEM_FACES = 2, SMG_MEM_ENERGY = 3, SMG_MEM_PRESSURE = 4, SMG_MEM_MATRIX = 5,
+       SMG_MEM_GRADIENT = 6, SMG_MEM_OBJECTIVE = 7 };
+int smg_debug_membrane(int op, int nV, int nF, const int *F, const double *V0, const double *P, const double *in, const smg_membrane_params *p,
+                       double *out, int *guard_hits);
 
 /* ---- profc.h mirror: named scopes accumulated with hipEvents (src/profc.h:9-13; mg_VCycle.cpp:121) ------------- */
 int smg_prof_enable(smg_hierarchy *h, int on);     /* forces eager launches while on */

@@ -14,6 +14,12 @@ class SolveOptsC(C.Structure):
                 ("smoother", C.c_int), ("omega", C.c_double), ("jacobi_max_rows", C.c_int), ("cheby_fraction", C.c_double)]
 
 
+class MembraneParamsC(C.Structure):
+    _fields_ = [("young", C.c_double), ("poisson", C.c_double), ("thickness", C.c_double), ("mass_scale", C.c_double), ("dt", C.c_double),
+                ("pressure", C.c_double), ("newton_iters", C.c_int), ("ls_c", C.c_double), ("ls_shrink", C.c_double),
+                ("ls_min_alpha", C.c_double), ("eig_floor", C.c_double), ("eig_value", C.c_double)]
+
+
 _lib = None
 
 
@@ -84,6 +90,17 @@ def load():
         "smg_arap_set_solver": (i, [vp, i]),
         "smg_arap_device_bytes": (C.c_longlong, [vp]),
         "smg_arap_solve": (i, [vp, vp, i, vp, i, i, i, d, C.POINTER(SolveOptsC), vp, i, dp, ip, ip]),
+        "smg_debug_membrane": (i, [i, i, i, ip, dp, dp, dp, C.POINTER(MembraneParamsC), dp, ip]),
+        "smg_membrane_params_default": (None, [C.POINTER(MembraneParamsC)]),
+        "smg_membrane_create": (i, [vp, dp, i, ip, i, C.POINTER(MembraneParamsC), C.POINTER(vp)]),
+        "smg_membrane_destroy": (None, [vp]),
+        "smg_membrane_device_bytes": (C.c_longlong, [vp]),
+        "smg_membrane_set_state": (i, [vp, vp, vp, i]),
+        "smg_membrane_get_state": (i, [vp, vp, vp, i]),
+        "smg_membrane_set_solver": (i, [vp, i]),
+        "smg_membrane_step": (i, [vp, C.POINTER(SolveOptsC), dp, dp, ip, ip]),
+        "smg_membrane_lists": (i, [ip, i, i, ip, ip, ip, ip, ip, ip]),
+        "smg_membrane_faces_host": (i, [dp, dp, i, ip, i, C.POINTER(MembraneParamsC), i, dp, dp, dp]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

@@ -697,6 +697,79 @@ class ArapDeformer:
         return self._run(hp_ptr, ld_hp or self.handles.shape[0], U0_ptr, ld_u0 or self.n, SMG_DEVICE, max_iter, rel_tol, opts, U_ptr, ld_u or self.n)
 
 
+class MembraneSim:
+    """Implicit-Euler steps of a pressurised neo-Hookean membrane on the block V-cycle (include/smg.h: smg_membrane_*), the time step of the
+    reference's 06_example_balloon_sim.
+
+    hierarchy: a block Hierarchy (mg_precompute_block) whose level 0 is the mesh (V, F) with 3 DOFs per vertex; its prolongations are copied, it
+    is not modified.  V: the rest pose.  params: the fields of smg_membrane_params (young, poisson, thickness, mass_scale, dt, pressure,
+    newton_iters, ls_c, ls_shrink, ls_min_alpha, eig_floor, eig_value); the state starts as (V, 0)."""
+
+    def __init__(self, hierarchy, V, F, **params):
+        self.L = _lib.load()
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        F = np.ascontiguousarray(F, dtype=np.int32)
+        self.n = V.shape[0]
+        self.params = membrane_params(**params)
+        out = C.c_void_p()
+        _chk(self.L.smg_membrane_create(hierarchy.h, _dp(V), V.shape[0], _ip(F), F.shape[0], C.byref(self.params), C.byref(out)), "smg_membrane_create")
+        self.m = C.c_void_p(out.value)
+
+    def __del__(self):
+        try:
+            if self.m:
+                self.L.smg_membrane_destroy(self.m)
+                self.m = None
+        except Exception:
+            pass
+
+    def set_solver(self, pcg=-1):
+        """0: smg_solve's stationary loop (default, the reference), 1: smg_solve_pcg, -1: unchanged."""
+        _chk(self.L.smg_membrane_set_solver(self.m, int(pcg)), "smg_membrane_set_solver")
+
+    def device_bytes(self):
+        return self.L.smg_membrane_device_bytes(self.m)
+
+    def set_state(self, pos=None, qdot=None):
+        """pos, qdot: n x 3 (None: the rest pose / zero)"""
+        pos = None if pos is None else np.ascontiguousarray(pos, dtype=np.float64).reshape(self.n, 3)
+        qdot = None if qdot is None else np.ascontiguousarray(qdot, dtype=np.float64).reshape(self.n, 3)
+        _chk(self.L.smg_membrane_set_state(self.m, None if pos is None else pos.ctypes.data, None if qdot is None else qdot.ctypes.data, SMG_HOST),
+             "smg_membrane_set_state")
+
+    def set_state_device(self, pos_ptr, qdot_ptr):
+        """the same from n x 3 row-major blocks resident in HBM (device pointers; 0 / None as above)"""
+        _chk(self.L.smg_membrane_set_state(self.m, pos_ptr or None, qdot_ptr or None, SMG_DEVICE), "smg_membrane_set_state")
+
+    def state(self):
+        """(pos, qdot), n x 3 each"""
+        pos, qdot = np.zeros((self.n, 3)), np.zeros((self.n, 3))
+        _chk(self.L.smg_membrane_get_state(self.m, pos.ctypes.data, qdot.ctypes.data, SMG_HOST), "smg_membrane_get_state")
+        return pos, qdot
+
+    def step(self, opts=None):
+        """One time step.  Returns a dict: objective (f(qdot) before every Newton iteration and after the last), alpha (the accepted steps, 0 where
+        the line search gave up), cycles (the loop entries of every solve)."""
+        n_it = self.params.newton_iters
+        obj, alpha = np.zeros(n_it + 1), np.zeros(max(n_it, 1))
+        cyc = np.zeros(max(n_it, 1), dtype=np.int32)
+        done = C.c_int(0)
+        _chk(self.L.smg_membrane_step(self.m, C.byref(opts.c) if opts is not None else None, _dp(obj), _dp(alpha), _ip(cyc), C.byref(done)),
+             "smg_membrane_step")
+        return {"objective": obj, "alpha": alpha[:n_it].copy(), "cycles": cyc[:n_it].copy()}
+
+
+def membrane_params(**params):
+    """smg_membrane_params with the library's defaults and the given fields"""
+    p = _lib.MembraneParamsC()
+    _lib.load().smg_membrane_params_default(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError("unknown membrane parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the reference's free functions
 

@@ -321,6 +321,73 @@ inline void heat_geodesics_mg_solve(heat_geodesics_mg_data& data, const smgDense
                                           data.cycles), "heat_geodesics_mg_solve");
 }
 
+// ---- mg_precompute_block (reference src/mg_precompute_block.cpp:23-95): the same hierarchy with P (x) I_3, DOF index 3 * vertex + d -------
+inline void mg_precompute_block(const smgDense& Vf, const smgDenseI& Ff, const float& ratio, const int& nVCoarsest, const int& dec_type,
+                                std::vector<mg_data>& mg)
+{
+    std::vector<double> V((size_t)Vf.rows * 3);
+    std::vector<int> F((size_t)Ff.rows * 3);
+    for (int i = 0; i < Vf.rows; i++) for (int c = 0; c < 3; c++) V[3 * (size_t)i + c] = Vf(i, c);
+    for (int i = 0; i < Ff.rows; i++) for (int c = 0; c < 3; c++) F[3 * (size_t)i + c] = Ff(i, c);
+    smg_hierarchy* h = nullptr;
+    smg_detail::check(smg_mg_precompute_block(V.data(), Vf.rows, F.data(), Ff.rows, ratio, nVCoarsest, dec_type, &h), "mg_precompute_block");
+    std::shared_ptr<smg_hierarchy> guard(h, smg_hierarchy_destroy);
+    mg.clear();
+    smg_detail::sync_levels(h, mg, false);
+}
+inline void mg_precompute_block(const smgDense& Vf, const smgDenseI& Ff, std::vector<mg_data>& mg) { mg_precompute_block(Vf, Ff, 0.25f, 500, 1, mg); }
+
+// ---- implicit_euler_mg_balloon (reference 06_example_balloon_sim/sim_utils/implicit_euler_mg_balloon.h:35-121, with the pressure force of
+// main.cpp:113-122): one time step of the neo-Hookean membrane on the block V-cycle of `mg` (include/smg.h: smg_membrane_*).  The state
+// lives on the device between steps; curPos / qdot are read back after every step as the reference's arguments are.
+struct balloon_sim_data {
+    std::shared_ptr<smg_membrane> m;
+    smg_membrane_params params;
+    int n = 0;                              // #V
+    std::vector<double> objective, alpha;   // of the last step: f(qdot) before every Newton iteration and after the last; the accepted steps
+    std::vector<int> cycles;                // ... and the loop entries of its solves
+    balloon_sim_data() { smg_membrane_params_default(&params); }
+};
+
+inline void balloon_sim_precompute(const smgDense& V, const smgDenseI& F, const std::vector<mg_data>& mg, balloon_sim_data& data)
+{
+    const int L = (int)mg.size();
+    std::shared_ptr<smg_hierarchy> h(smg_hierarchy_create(L), smg_hierarchy_destroy);   // carries the prolongations only: the object copies them
+    if (!h) throw std::runtime_error(smg_last_error());
+    for (int lv = 1; lv < L; lv++) {
+        const smgSparse& P = mg[lv].P_full;
+        smg_detail::check(smg_level_set_prolong_csc(h.get(), lv, P.rows, P.cols, P.outer.data(), P.inner.data(), P.values.data()), "smg_level_set_prolong_csc");
+    }
+    std::vector<double> Vr((size_t)V.rows * 3);
+    std::vector<int> Fr((size_t)F.rows * 3);
+    for (int i = 0; i < V.rows; i++) for (int c = 0; c < 3; c++) Vr[3 * (size_t)i + c] = V(i, c);
+    for (int i = 0; i < F.rows; i++) for (int c = 0; c < 3; c++) Fr[3 * (size_t)i + c] = F(i, c);
+    smg_membrane* m = nullptr;
+    smg_detail::check(smg_membrane_create(h.get(), Vr.data(), V.rows, Fr.data(), F.rows, &data.params, &m), "balloon_sim_precompute");
+    data.m.reset(m, smg_membrane_destroy);
+    data.n = V.rows;
+}
+
+// curPos (#V x 3) and qdot (3 #V, entry 3 v + d) are overwritten with the state after the step
+inline void implicit_euler_mg_balloon(balloon_sim_data& data, smgDense& curPos, std::vector<double>& qdot, const double& mg_tolerance)
+{
+    if (!data.m) throw std::runtime_error("implicit_euler_mg_balloon: run balloon_sim_precompute first");
+    smg_solve_opts opts;
+    smg_solve_opts_default(&opts);
+    opts.tol = mg_tolerance;
+    const int n_it = data.params.newton_iters;
+    data.objective.assign((size_t)n_it + 1, 0.0);
+    data.alpha.assign((size_t)(n_it > 0 ? n_it : 1), 0.0);
+    data.cycles.assign((size_t)(n_it > 0 ? n_it : 1), 0);
+    int done = 0;
+    smg_detail::check(smg_membrane_step(data.m.get(), &opts, data.objective.data(), data.alpha.data(), data.cycles.data(), &done), "implicit_euler_mg_balloon");
+    std::vector<double> pos((size_t)data.n * 3);
+    qdot.resize((size_t)data.n * 3);
+    smg_detail::check(smg_membrane_get_state(data.m.get(), pos.data(), qdot.data(), SMG_HOST), "smg_membrane_get_state");
+    curPos.resize(data.n, 3);
+    for (int i = 0; i < data.n; i++) for (int c = 0; c < 3; c++) curPos(i, c) = pos[3 * (size_t)i + c];
+}
+
 // ---- mg_VCycle (reference src/mg_VCycle.cpp:3-59) ----------------------------------------------------------------
 inline void mg_VCycle(const smgCoarseSolver& solver, const smgDense& B, const int& preRelaxIter, const int& postRelaxIter,
                       const int lv, smgDense& u, std::vector<mg_data>&)

@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics) and of the ARAP kernels (smg_debug_arap).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap) and of the membrane kernels (smg_debug_membrane).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -364,6 +364,87 @@ extern "C" int smg_debug_arap(int op, int n, const int* rowptr, const int* col, 
                 HIPCHK(launch_arap_vertex_energy(n, dptr, dcol, dw, dP0, dP, dR, dterm, st));
                 HIPCHK(launch_arap_energy(dterm, n, dpart, dout, st));
                 break;
+        }
+        int bad = 0;
+        HIPCHK(X.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_membrane(int op, int nV, int nF, const int* F, const double* V0, const double* P, const double* in,
+                                  const smg_membrane_params* p, double* out, int* guard_hits)
+{
+    return guarded("smg_debug_membrane", [&]() -> int {
+        if (op < SMG_MEM_REST || op > SMG_MEM_OBJECTIVE || nV < 1 || nF < 1 || !F || !p || !out) return fail(SMG_ERR_INVALID, "smg_debug_membrane: bad arguments");
+        const bool needs_rest = op <= SMG_MEM_ENERGY || op == SMG_MEM_OBJECTIVE, needs_pose = (op >= SMG_MEM_FACES_RAW && op <= SMG_MEM_PRESSURE) || op == SMG_MEM_OBJECTIVE;
+        if ((needs_rest && !V0) || (needs_pose && !P) || (op >= SMG_MEM_MATRIX && !in)) return fail(SMG_ERR_INVALID, "smg_debug_membrane: op %d misses an operand", op);
+        for (size_t i = 0; i < (size_t)nF * 3; i++)
+            if (F[i] < 0 || F[i] >= nV) return fail(SMG_ERR_INVALID, "smg_debug_membrane: face index out of range");
+        if (int rc = need_device("smg_debug_membrane")) return rc;
+        const double alpha = p->young * p->poisson / (1.0 - p->poisson * p->poisson), beta = p->young / 2.0 / (1.0 + p->poisson);
+        std::vector<int> Fv(F, F + 3 * (size_t)nF), mp, mi;
+        vertex_corner_lists(Fv, nV, mp, mi);
+        MembraneLists L;
+        membrane_lists(F, nF, nV, L);
+        const int nB = (int)L.bcol.size();
+        const size_t D = sizeof(double), nf = (size_t)nF, nv = (size_t)nV, n3 = 3 * nv;
+        const size_t out_n = op == SMG_MEM_REST ? 5 * nf : op <= SMG_MEM_FACES ? 55 * nf : op == SMG_MEM_ENERGY ? nf : op == SMG_MEM_PRESSURE ? 6 * nf + nv + n3
+                             : op == SMG_MEM_MATRIX ? 9 * (size_t)nB : op == SMG_MEM_GRADIENT ? 2 * n3 : 2 * n3 + nf + nv + 1;
+        const size_t in_n = op == SMG_MEM_MATRIX ? 45 * nf + nv : op == SMG_MEM_GRADIENT ? 9 * nf + nv + 3 * n3 : op == SMG_MEM_OBJECTIVE ? nv + 4 * n3 + 1 : 0;
+        Scratch X;
+        HIPCHK(X.init());
+        hipStream_t st = X.stream();
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr, *dbrow = nullptr, *dbcol = nullptr, *dbptr = nullptr, *dcp = nullptr, *dcs = nullptr;
+        double *dV0 = nullptr, *dP = nullptr, *din = nullptr, *dout = nullptr, *drest = nullptr, *dpart = nullptr;
+        HIPCHK(X.add(F, nullptr, 3 * nf * sizeof(int), &dF));
+        if (V0) HIPCHK(X.add(V0, nullptr, n3 * D, &dV0));
+        if (P) HIPCHK(X.add(P, nullptr, n3 * D, &dP));
+        if (in_n) HIPCHK(X.add(in, nullptr, in_n * D, &din));
+        HIPCHK(X.add(out, out, out_n * D, &dout));
+        if (needs_rest && op != SMG_MEM_REST) {
+            HIPCHK(X.add(nullptr, nullptr, 5 * nf * D, &drest));
+            HIPCHK(launch_membrane_rest(nF, dF, dV0, p->thickness, drest, st));
+        }
+        if (op == SMG_MEM_PRESSURE || op == SMG_MEM_GRADIENT) {
+            HIPCHK(X.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+            HIPCHK(X.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+        }
+        switch (op) {
+            case SMG_MEM_REST: HIPCHK(launch_membrane_rest(nF, dF, dV0, p->thickness, dout, st)); break;
+            case SMG_MEM_FACES_RAW:
+            case SMG_MEM_FACES:
+                HIPCHK(launch_membrane_faces(op == SMG_MEM_FACES ? 2 : 1, nF, dF, dP, drest, alpha, beta, p->eig_floor, p->eig_value, dout, dout + nf, dout + 10 * nf, st));
+                break;
+            case SMG_MEM_ENERGY:
+                HIPCHK(launch_membrane_faces(0, nF, dF, dP, drest, alpha, beta, p->eig_floor, p->eig_value, dout, nullptr, nullptr, st));
+                break;
+            case SMG_MEM_PRESSURE:
+                HIPCHK(launch_membrane_pressure(nV, nF, dF, dP, dmp, dmi, p->pressure, dout, dout + 6 * nf, dout + 6 * nf + nv, st));
+                break;
+            case SMG_MEM_MATRIX:
+                HIPCHK(X.add(L.brow.data(), nullptr, L.brow.size() * sizeof(int), &dbrow));
+                HIPCHK(X.add(L.bcol.data(), nullptr, L.bcol.size() * sizeof(int), &dbcol));
+                HIPCHK(X.add(L.bptr.data(), nullptr, L.bptr.size() * sizeof(int), &dbptr));
+                HIPCHK(X.add(L.c_ptr.data(), nullptr, L.c_ptr.size() * sizeof(int), &dcp));
+                HIPCHK(X.add(L.c_src.data(), nullptr, L.c_src.size() * sizeof(int), &dcs));
+                HIPCHK(launch_membrane_matrix(nB, dbrow, dbcol, dbptr, dcp, dcs, din, nF, p->dt * p->dt, din + 45 * nf, p->mass_scale, dout, st));
+                break;
+            case SMG_MEM_GRADIENT: {
+                const double* mass0 = din + 9 * nf;
+                HIPCHK(launch_membrane_gradient(nV, dmp, dmi, din, nF, mass0, p->mass_scale, p->dt, mass0 + nv, mass0 + nv + n3, mass0 + nv + 2 * n3, dout,
+                                                dout + n3, st));
+                break;
+            }
+            default: {
+                const double *qdot = din + nv, *dx = qdot + n3, *qdot0 = dx + n3, *fext = qdot0 + n3;
+                double* terms = dout + 2 * n3;
+                HIPCHK(X.add(nullptr, nullptr, (size_t)arap_groups(nF + nV) * D, &dpart));
+                HIPCHK(launch_membrane_trial(nV, qdot, dx, in[nv + 4 * n3], qdot0, dP, fext, din, p->mass_scale, p->dt, dout, dout + n3, terms + nf, st));
+                HIPCHK(launch_membrane_faces(0, nF, dF, dout + n3, drest, alpha, beta, p->eig_floor, p->eig_value, terms, nullptr, nullptr, st));
+                HIPCHK(launch_arap_energy(terms, nF + nV, dpart, terms + nf + nv, st));
+                break;
+            }
         }
         int bad = 0;
         HIPCHK(X.finish(&bad));

@@ -417,4 +417,29 @@ hipError_t launch_arap_rows(int n, const double* U, int ldu, double* P, hipStrea
 hipError_t launch_arap_columns(int n, const double* P, double* U, int ldu, hipStream_t st);
 hipError_t launch_arap_set_handles(int nh, const int* handles, const double* hp, int ldh, double* U, int ldu, hipStream_t st);
 
+// neo-Hookean membrane time step (smg_membrane_device.hip).  Vectors over the vertices are xyz rows (entry 3 v + l); per-face arrays are
+// face-major planes (plane e at [e * nF + f]); m_ptr / m_idx: the corner lists t = 3 f + j of every vertex, faces ascending -----------------
+// rest (5 planes): (abar^-1)00, 01, 11, det abar, thickness sqrt(det abar) / 4
+hipError_t launch_membrane_rest(int nF, const int* F, const double* V0, double thickness, double* rest, hipStream_t st);
+// mode 0: W (nF) alone; 1: W, G (9 planes), the upper triangle of the unfixed H (45 planes); 2: the same with the eigenvalue fix (smg_membrane_inl.hpp)
+hipError_t launch_membrane_faces(int mode, int nF, const int* F, const double* P, const double* rest, double alpha, double beta, double floor,
+                                 double value, double* W, double* G, double* H, hipStream_t st);
+// val = M + dt2 K in the scalar CSR of the pattern (adjacency + I) (x) 1_3x3: block q of block row brow[q] (bptr: block rows, bcol: block
+// columns) sums the face sub-blocks c_src[c_ptr[q] .. c_ptr[q + 1]) = 9 f + 3 a + b in list order; M = mass_scale mass0 on the diagonal
+hipError_t launch_membrane_matrix(int nB, const int* brow, const int* bcol, const int* bptr, const int* c_ptr, const int* c_src, const double* H,
+                                  int nF, double dt2, const double* mass0, double mass_scale, double* val, hipStream_t st);
+// Qn (6 planes of scratch): e1 x e2 and the corners' shares of the mixed Voronoi area; mass[v] (optional) their sum over the vertex's corners;
+// fext (optional) = (-(pressure mass_v)) (N / |N|), N the sum of e1 x e2 over the corners
+hipError_t launch_membrane_pressure(int nV, int nF, const int* F, const double* P, const int* m_ptr, const int* m_idx, double pressure, double* Qn,
+                                    double* mass, double* fext, hipStream_t st);
+// g (optional) = the corner sums of G; b = -((M (qdot - qdot0) + dt g) + dt fext)
+hipError_t launch_membrane_gradient(int nV, const int* m_ptr, const int* m_idx, const double* G, int nF, const double* mass0, double mass_scale,
+                                    double dt, const double* qdot, const double* qdot0, const double* fext, double* g, double* b, hipStream_t st);
+// t_out = qdot + step dx (dx == nullptr: qdot), p_out = pos0 + dt t_out, term[v] = p_v . fext_v + (M_v |t_v - qdot0_v|^2) / 2
+hipError_t launch_membrane_trial(int nV, const double* qdot, const double* dx, double step, const double* qdot0, const double* pos0,
+                                 const double* fext, const double* mass0, double mass_scale, double dt, double* t_out, double* p_out, double* term,
+                                 hipStream_t st);
+// term[v] = a_v . b_v
+hipError_t launch_membrane_dot3(int nV, const double* a, const double* b, double* term, hipStream_t st);
+
 }  // namespace smg

@@ -122,6 +122,11 @@ int level0_rows(const smg_hierarchy* h);                           // rows of le
 long long handle_bytes(const smg_hierarchy* h);                    // the "total" of smg_debug_device_bytes
 int copy_prolongations(const smg_hierarchy* src, smg_hierarchy* dst);
 
+// ---- the membrane's lists (smg_membrane.cpp): the block CSR of (adjacency + I), columns ascending, the block row of every block, and per block
+// the face sub-blocks 9 f + 3 a + b that k_membrane_matrix sums, faces ascending
+struct MembraneLists { std::vector<int> bptr, bcol, brow, c_ptr, c_src; };
+void membrane_lists(const int* F, int nF, int nV, MembraneLists& L);
+
 // ---- precompute (smg_precompute.cpp) ------------------------------------------------------------------------------------------------
 int spectral_bounds(smg_hierarchy* h);          // Gershgorin bounds of D^-1 A on every smoothed level (Chebyshev-Jacobi)
 int ensure_spectral_bounds(smg_hierarchy* h);   // ... only when a level is smoothed that way and the values changed

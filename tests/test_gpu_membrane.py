@@ -1,0 +1,323 @@
+"""GPU (-m gpu): the neo-Hookean membrane time step (include/smg.h: smg_membrane_*).
+
+The host reference is tests/test_membrane_host.py -- the same method with numpy.linalg.eigh for the per-face fix and direct solves.  The kernels
+are held launcher by launcher (smg_debug_membrane, guarded buffers): the per-face energy, gradient and unfixed Hessian to rounding against the
+restatement, the 6 x 6 Jacobi fix against LAPACK on the DEVICE's unfixed blocks, and every sum (matrix values, gradient, right-hand side,
+vertex masses, pressure force) bit for bit against a numpy sum of the device's own per-face outputs in the documented order.  Then one Newton
+system, whole steps against the restatement, the reference's configuration, and the reproducibility of the bits.
+
+Every bound below that is not bit-equality is 100 x the maximum measured on an MI355X, rounded up to a power of ten (the convention of
+DESIGN.md section 19); measured values are in DESIGN.md section 20 and in the comments beside the constants."""
+import math
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+from test_gpu_parity import smg  # noqa: F401  (fixture)
+from test_membrane_host import (MEM_ENERGY, MEM_FACES, MEM_FACES_RAW, MEM_GRADIENT, MEM_MATRIX, MEM_OBJECTIVE, MEM_PRESSURE, MEM_REST, MESHES,
+                                MembraneNp, corner_lists, eig_fix, fundamental_form, hook, lists, load_mesh, matrix_values_np, perturbed_pose,
+                                scalar_pattern, unpack_upper)
+
+pytestmark = pytest.mark.gpu
+
+EPS = np.finfo(np.float64).eps
+# per-face quantities against the restatement, max |x - x_np| / scale with scale = coeff beta |a| / sqrt(det abar) for W, that over |e| for G and
+# over |e|^2 for H:  measured 8.0e-18, 7.3e-16, 9.3e-15 (the rest pose agrees bit for bit)
+W_BOUND, G_BOUND, H_BOUND = 1e-15, 1e-13, 1e-12
+FIX_BOUND = 1e-12          # |H' - Q fix(Lambda) Q^T|_F / |.|_F against LAPACK on the device's unfixed blocks: measured 5.2e-15
+SOLVE_BOUND = {"ogre_sim.smgm": 1e-8, "bunny_15K_init.smgm": 1e-5}       # |dx - dx_np| / |dx_np|: measured 4.1e-11, 1.6e-8
+STEP_POS_BOUND = {"ogre_sim.smgm": 1e-7, "bunny_15K_init.smgm": 1e-6}    # max |pos - pos_np| / max |pos_np - rest|: measured 1.9e-10, 1.5e-9
+STEP_OBJ_BOUND = {"ogre_sim.smgm": 1e-13, "bunny_15K_init.smgm": 1e-13}  # relative difference of the objectives: measured 3.9e-16, 2.5e-16
+
+
+def call(smg, op, V0, F, P, inp, n_out, **params):
+    rc, bad, out = hook(smg, op, V0, F, P, inp, n_out, **params)
+    assert rc == 0 and bad == 0, (rc, bad, smg._lib.load().smg_last_error())
+    assert not np.any(np.isnan(out))
+    return out
+
+
+@pytest.fixture(scope="module")
+def cases():
+    """per mesh: the restatement, the three compared poses (rest, perturbed, the iterate after Newton iteration 1 of step 0) and that step's record"""
+    out = {}
+    for name in MESHES:
+        V, F = load_mesh(name)
+        mb = MembraneNp(V, F)
+        _, _, info = mb.step(V.copy(), np.zeros(3 * V.shape[0]), newton_iters=3, record=True)
+        out[name] = (V, F, mb, [V, perturbed_pose(V, F), info["poses"][2]], info)
+    return out
+
+
+def device_faces(smg, V, F, P, fixed):
+    nF = F.shape[0]
+    o = call(smg, MEM_FACES if fixed else MEM_FACES_RAW, V, F, P, None, 55 * nF)
+    return o[:nF], o[nF:10 * nF].reshape(9, nF), o[10 * nF:].reshape(45, nF)
+
+
+def device_mass(smg, V, F, P):
+    """(Qn planes, m, fext) of k_membrane_pressure_faces / k_membrane_pressure at P"""
+    nF, nV = F.shape[0], V.shape[0]
+    o = call(smg, MEM_PRESSURE, None, F, P, None, 6 * nF + 4 * nV)
+    return o[:6 * nF].reshape(6, nF), o[6 * nF:6 * nF + nV], o[6 * nF + nV:]
+
+
+# ---- 6: the kernels, launcher by launcher ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", MESHES)
+def test_face_kernels_against_the_restatement(smg, cases, name):
+    V, F, mb, poses, _ = cases[name]
+    nF = F.shape[0]
+    rest = call(smg, MEM_REST, V, F, None, None, 5 * nF).reshape(5, nF)
+    ref = np.stack([mb.abinv[:, 0], mb.abinv[:, 1], mb.abinv[:, 2], mb.detabar, mb.coeff])
+    assert np.abs(rest - ref).max() <= 4 * EPS * np.abs(ref).max() and np.all(np.abs(rest - ref) <= 4 * EPS * np.abs(ref))   # IEEE division and root
+    worst = np.zeros(4)
+    for P in poses:
+        W, G, H, _ = mb.faces(P, fix=False)
+        Wd, Gd, Hd = device_faces(smg, V, F, P, False)
+        assert np.array_equal(call(smg, MEM_ENERGY, V, F, P, None, nF), Wd)                  # the line search's kernel is the same text
+        _, _, a00, _, a11 = fundamental_form(P, F)
+        scale = mb.coeff * mb.beta * (a00 + a11) / np.sqrt(mb.detabar)
+        eW = np.abs(Wd - W).max() / scale.max()
+        eG = (np.abs(Gd.T - G).max(axis=1) / (scale / np.sqrt(a00 + a11))).max()
+        Hu = unpack_upper(Hd)
+        eH = (np.abs(Hu - H).max(axis=(1, 2)) / (scale / (a00 + a11))).max()
+        # the fix: only the eigen-solve is under test, so the reference is LAPACK on the DEVICE's unfixed blocks
+        ref_fix, lam = eig_fix(Hu, mb.p["eig_floor"], mb.p["eig_value"])
+        assert not np.any((lam >= 1e-8) & (lam <= 1e-4))                                      # the condition of the comparison
+        Wf, Gf, Hf = device_faces(smg, V, F, P, True)
+        assert np.array_equal(Wf, Wd) and np.array_equal(Gf, Gd)
+        Hfu = unpack_upper(Hf)
+        eF = (np.linalg.norm(Hfu - ref_fix, axis=(1, 2)) / np.linalg.norm(ref_fix, axis=(1, 2))).max()
+        lmin = np.linalg.eigvalsh(Hfu).min()
+        print(name, "W %.2e G %.2e H %.2e fix %.2e lambda_min %.6e" % (eW, eG, eH, eF, lmin))
+        worst = np.maximum(worst, [eW, eG, eH, eF])
+        assert lmin >= mb.p["eig_floor"] * (1 - 1e-9)
+    print(name, "worst W %.2e G %.2e H %.2e fix %.2e" % tuple(worst))
+    assert worst[0] <= W_BOUND and worst[1] <= G_BOUND and worst[2] <= H_BOUND and worst[3] <= FIX_BOUND
+
+
+@pytest.mark.parametrize("name", MESHES)
+def test_sums_are_bitwise_the_documented_ones(smg, cases, name):
+    V, F, mb, poses, info = cases[name]
+    nF, nV = F.shape[0], V.shape[0]
+    p = mb.p
+    lsts = lists(smg, F, nV)
+    slots = corner_lists(F, nV)
+    _, mass0, _ = device_mass(smg, V, F, V)
+    assert np.abs(mass0 - mb.mass0).max() <= 64 * EPS * mb.mass0.max()
+    rng = np.random.default_rng(3)
+    valence = int(np.diff(lsts[2]).max())
+    for P in poses:
+        _, Gd, Hd = device_faces(smg, V, F, P, True)
+        # matrix values: the sum of the device's own blocks in list order, times dt^2, the mass last
+        val = call(smg, MEM_MATRIX, None, F, None, np.concatenate([Hd.reshape(-1), mass0]), 9 * lsts[1].shape[0])
+        assert np.array_equal(val, matrix_values_np(Hd, mass0, lsts, p["dt"], p["mass_scale"]))
+        # ... and against scipy's assembly of the restatement's blocks
+        _, Hm, _, _ = mb.system(P, np.zeros(3 * nV), np.zeros(3 * nV), np.zeros(3 * nV))
+        rowptr, col = scalar_pattern(lsts[0], lsts[1])
+        assert np.array_equal(Hm.indptr, rowptr) and np.array_equal(Hm.indices, col)
+        hmax = np.linalg.norm(unpack_upper(Hd), axis=(1, 2)).max()
+        err = np.abs(val - Hm.data).max()
+        print(name, "matrix against scipy: %.2e, allowed %.2e" % (err, (FIX_BOUND + H_BOUND) * hmax * valence * p["dt"] ** 2 + 64 * EPS * p["mass_scale"] * mass0.max()))
+        assert err <= (FIX_BOUND + H_BOUND) * hmax * valence * p["dt"] ** 2 + 64 * EPS * p["mass_scale"] * mass0.max()
+        # pressure: masses and normals summed over the corner lists
+        Qn, m, fext = device_mass(smg, V, F, P)
+        m_np, N = np.zeros(nV), np.zeros((nV, 3))
+        for rows, ts in slots:
+            f, j = ts // 3, ts % 3
+            m_np[rows] += Qn[3 + j, f]
+            N[rows] += Qn[:3, f].T
+        ln = np.sqrt((N[:, 0] * N[:, 0] + N[:, 1] * N[:, 1]) + N[:, 2] * N[:, 2])
+        f_np = (-(p["pressure"] * m_np))[:, None] * (N / ln[:, None])
+        assert np.array_equal(m, m_np) and np.array_equal(fext, f_np.reshape(-1))
+        ref_f = mb.pressure_force(P)
+        assert np.abs(fext - ref_f).max() <= 1e-12 * np.abs(ref_f).max()
+        # gradient and right-hand side
+        qdot, qdot0 = rng.standard_normal(3 * nV), rng.standard_normal(3 * nV)
+        o = call(smg, MEM_GRADIENT, None, F, None, np.concatenate([Gd.reshape(-1), mass0, qdot, qdot0, fext]), 6 * nV)
+        g_np = np.zeros((nV, 3))
+        for rows, ts in slots:
+            f, j = ts // 3, ts % 3
+            for l in range(3):
+                g_np[rows, l] += Gd[3 * j + l, f]
+        g_np = g_np.reshape(-1)
+        mv = np.repeat(p["mass_scale"] * mass0, 3)
+        b_np = -((mv * (qdot - qdot0) + p["dt"] * g_np) + p["dt"] * fext)
+        assert np.array_equal(o[:3 * nV], g_np) and np.array_equal(o[3 * nV:], b_np)
+
+
+@pytest.mark.parametrize("name", MESHES)
+def test_objective_is_reproducible_and_accurate(smg, cases, name):
+    V, F, mb, poses, info = cases[name]
+    nF, nV = F.shape[0], V.shape[0]
+    p = mb.p
+    _, mass0, fext = device_mass(smg, V, F, V)
+    H, b, dx = info["systems"][0]
+    qdot0 = np.zeros(3 * nV)
+    for step in (0.0, 1.0, 0.25):
+        inp = np.concatenate([mass0, qdot0, dx, qdot0, fext, [step]])
+        o1 = call(smg, MEM_OBJECTIVE, V, F, V, inp, 6 * nV + nF + nV + 1)
+        o2 = call(smg, MEM_OBJECTIVE, V, F, V, inp, 6 * nV + nF + nV + 1)
+        assert np.array_equal(o1, o2)
+        t, pos, terms, f = o1[:3 * nV], o1[3 * nV:6 * nV], o1[6 * nV:-1], o1[-1]
+        assert np.array_equal(t, qdot0 + step * dx) and np.array_equal(pos, V.reshape(-1) + p["dt"] * t)
+        assert np.array_equal(terms[:nF], call(smg, MEM_ENERGY, V, F, pos.reshape(-1, 3), None, nF))
+        exact = math.fsum(terms)
+        n = terms.shape[0]
+        assert abs(f - exact) <= 2 * n * EPS * math.fsum(np.abs(terms))
+        ref = mb.objective(t, qdot0, V, mb.pressure_force(V))
+        print(name, "step %.2f f %.10e restatement %.10e" % (step, f, ref))
+        assert abs(f - ref) <= 1e-12 * abs(ref)
+
+
+# ---- 7: one Newton system end to end --------------------------------------------------------------------------------------------------------------
+def device_system(smg, V, F, mb, P, qdot, qdot0, fext_pose):
+    """H (CSR in the kernel's order) and b assembled by the device kernels at the pose P"""
+    nV = V.shape[0]
+    lsts = lists(smg, F, nV)
+    _, mass0, _ = device_mass(smg, V, F, V)
+    _, _, fext = device_mass(smg, V, F, fext_pose)
+    _, Gd, Hd = device_faces(smg, V, F, P, True)
+    val = call(smg, MEM_MATRIX, None, F, None, np.concatenate([Hd.reshape(-1), mass0]), 9 * lsts[1].shape[0])
+    o = call(smg, MEM_GRADIENT, None, F, None, np.concatenate([Gd.reshape(-1), mass0, qdot, qdot0, fext]), 6 * nV)
+    rowptr, col = scalar_pattern(lsts[0], lsts[1])
+    return sp.csr_matrix((val, col, rowptr), shape=(3 * nV, 3 * nV)), o[3 * nV:]
+
+
+def solver_settings(smg, name, bnorm):
+    """ogre_sim: the stationary loop contracts by 0.03 - 0.05 per entry; bunny_15K_init: by 0.6 late in the solve, so PCG there"""
+    if name == "ogre_sim.smgm":
+        return False, smg.SolveOpts(tol=1e-10 * bnorm, max_iter=40)
+    return True, smg.SolveOpts(tol=1e-8 * bnorm, max_iter=200)
+
+
+@pytest.mark.parametrize("name", MESHES)
+def test_one_newton_system(smg, cases, name):
+    V, F, mb, poses, info = cases[name]
+    nV = V.shape[0]
+    mg = smg.mg_precompute_block(V, F)
+    zero = np.zeros(3 * nV)
+    H0, _ = device_system(smg, V, F, mb, V, zero, zero, V)
+    mg.precompute(H0)                                                   # the pattern; the next precompute is the value-only path
+    assert mg.block_size() == 3
+    print(name, "rows per level", [mg.rows(l) for l in range(mg.n_levels)])
+    worst = 0.0
+    for it in (0, 1):
+        Hn, bn, dxn = info["systems"][it]
+        qdot = (info["poses"][it] - V).reshape(-1) / mb.p["dt"]
+        H, b = device_system(smg, V, F, mb, info["poses"][it], qdot, zero, V)
+        mg.precompute(H)
+        pcg, opts = solver_settings(smg, name, np.linalg.norm(b))
+        conv, z, his = (mg.solve_pcg if pcg else mg.solve)(b.reshape(-1, 1), zero.reshape(-1, 1), None, opts)
+        err = np.linalg.norm(z[:, 0] - dxn) / np.linalg.norm(dxn)
+        print(name, "Newton iteration %d: %s, %d loop entries, |dx - dx_np| / |dx_np| = %.2e; history %s"
+              % (it, "PCG" if pcg else "stationary", len(his), err, np.array2string(np.asarray(his) / np.linalg.norm(b), precision=2)))
+        assert conv
+        worst = max(worst, err)
+    assert worst <= SOLVE_BOUND[name]
+
+
+# ---- 8: a step against the restatement --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", MESHES)
+def test_step_against_the_restatement(smg, cases, name):
+    V, F, mb, poses, info = cases[name]
+    mg = smg.mg_precompute_block(V, F)
+    sim = smg.MembraneSim(mg, V, F, newton_iters=3)
+    sim.set_solver(1)
+    if name == "ogre_sim.smgm":
+        opts = smg.SolveOpts(tol=1e-10 * info["bnorm"][0], max_iter=60)
+    else:
+        opts = smg.SolveOpts(tol=1e-8 * info["bnorm"][2], max_iter=200)      # 1e-8 |b| of the smallest right-hand side of the three
+    r = sim.step(opts)
+    pos, qdot = sim.state()
+    ref = info["poses"][3]
+    e_pos = np.abs(pos - ref).max() / np.abs(ref - V).max()
+    obj = np.array(info["objective"])
+    e_obj = np.abs(r["objective"] - obj).max() / np.abs(obj).max()
+    print(name, "pos %.2e objective %.2e alpha %s cycles %s" % (e_pos, e_obj, r["alpha"], r["cycles"]))
+    assert np.array_equal(r["alpha"], info["alpha"]) and np.all(r["alpha"] == 1.0)
+    assert np.abs(qdot * mb.p["dt"] - (pos - V)).max() <= 4 * EPS * np.abs(pos).max()
+    assert e_pos <= STEP_POS_BOUND[name] and e_obj <= STEP_OBJ_BOUND[name]
+
+
+# ---- 9: the reference's own configuration -----------------------------------------------------------------------------------------------------------
+def test_reference_configuration_two_steps(smg, oracle_mod, cases):
+    name = "bunny_15K_init.smgm"
+    V, F, mb, poses, info = cases[name]
+    nV = V.shape[0]
+    mg = smg.mg_precompute_block(V, F)
+    sim = smg.MembraneSim(mg, V, F)
+    steps = [sim.step(), sim.step()]
+    for k, r in enumerate(steps):
+        print("step %d: cycles %s alpha %s objective %s" % (k, r["cycles"], r["alpha"], np.array2string(r["objective"], precision=10)))
+        acc = np.nonzero(r["alpha"] > 0)[0]
+        assert np.all(r["objective"][acc + 1] <= r["objective"][acc]) and np.all(np.diff(r["objective"]) <= 0)
+        assert np.all(r["cycles"] >= 1) and np.all(r["cycles"] <= 20)
+        one = np.nonzero(r["cycles"] == 1)[0]                            # |b| < tol: one loop entry, dx = 0, the search accepts 1 and nothing moves
+        assert np.all(r["alpha"][one] == 1.0) and np.array_equal(r["objective"][one + 1], r["objective"][one])
+    assert np.any(steps[0]["cycles"] == 1)
+    # the device's loop entries of the first two Newton iterations against the CPU oracle's loop on the device-assembled systems
+    Ps = [mg.matrix(l, "P_full") for l in range(1, mg.n_levels)]
+    one_it = smg.MembraneSim(mg, V, F, newton_iters=1)
+    r1 = one_it.step()
+    assert r1["cycles"][0] == steps[0]["cycles"][0] and r1["objective"][1] == steps[0]["objective"][1]
+    pos1, qdot1 = one_it.state()
+    zero = np.zeros(3 * nV)
+    for it, (P, qd) in enumerate(((V, zero), (pos1, qdot1.reshape(-1)))):
+        H, b = device_system(smg, V, F, mb, P, qd, zero, V)
+        orc = oracle_mod.OracleMG(Ps)
+        orc.precompute(H)
+        conv, z, his = orc.solve(b.reshape(-1, 1), zero.reshape(-1, 1), tol=2e-1, max_iter=20)
+        n, n_orc = int(steps[0]["cycles"][it]), len(his)
+        print("Newton iteration %d: |b| %.4f, device %d loop entries, oracle %d (%s)" % (it, np.linalg.norm(b), n, n_orc, np.array2string(np.asarray(his), precision=3)))
+        assert abs(n - n_orc) <= max(2, n_orc // 10)
+
+
+# ---- 10: the same bits ------------------------------------------------------------------------------------------------------------------------------
+def test_same_inputs_same_bits(smg, cases):
+    import torch
+    name = "ogre_sim.smgm"
+    V, F, mb, poses, info = cases[name]
+    nV = V.shape[0]
+    mg = smg.mg_precompute_block(V, F)
+    other = smg.mg_precompute_block(V, F)                                 # an unrelated handle
+    other.precompute(info["systems"][0][0])
+    rhs = info["systems"][0][1].reshape(-1, 1)
+    before = other.solve(rhs, np.zeros_like(rhs), None, smg.SolveOpts(tol=1e-8, max_iter=30))
+    sim = smg.MembraneSim(mg, V, F, newton_iters=4)
+
+    def run(opts=None, device=False):
+        P0, Q0 = perturbed_pose(V, F, seed=4, amount=0.002), 0.01 * np.random.default_rng(5).standard_normal(V.shape)
+        if device:
+            Pd, Qd = torch.from_numpy(P0).cuda(), torch.from_numpy(Q0).cuda()
+            torch.cuda.synchronize()
+            sim.set_state_device(Pd.data_ptr(), Qd.data_ptr())
+        else:
+            sim.set_state(P0, Q0)
+        a, b = sim.state()
+        assert np.array_equal(a, P0) and np.array_equal(b, Q0)              # get_state after set_state returns the input
+        r = sim.step(opts)
+        return r, sim.state()
+
+    def same(x, y):
+        return all(np.array_equal(x[0][k], y[0][k]) for k in ("objective", "alpha", "cycles")) and np.array_equal(x[1][0], y[1][0]) and np.array_equal(x[1][1], y[1][1])
+
+    first = run()
+    size = sim.device_bytes()
+    assert size > 0
+    second = run()
+    assert same(first, second)
+    assert same(first, run(device=True))
+    eager = run(smg.SolveOpts(tol=2e-1, max_iter=20, use_graph=0))
+    graph = run(smg.SolveOpts(tol=2e-1, max_iter=20, use_graph=1))
+    assert same(eager, graph) and same(first, graph)
+    assert sim.device_bytes() == size                                       # nothing grows after the first step
+    sim.set_state()                                                        # the rest pose, zero velocity
+    a, b = sim.state()
+    assert np.array_equal(a, V) and not b.any()
+    after = other.solve(rhs, np.zeros_like(rhs), None, smg.SolveOpts(tol=1e-8, max_iter=30))
+    assert np.array_equal(before[1], after[1]) and np.array_equal(before[2], after[2])
+    sim.set_solver(1)
+    assert same(run(), run())
