@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 507
+#define SMG_VERSION 508
 
 enum {
     SMG_OK = 0,
@@ -644,6 +644,10 @@ int smg_debug_raise_coarse_stall(smg_hierarchy *h);
 /* Test hook: the plan of the Schur-complement coarse solver built for the SPD matrix (ptr, col, val; lower triangle counts) and executed ON THE HOST
  * the way the kernels read it: x = A^-1 b.  *n_blocks = 0: no plan for this matrix (x untouched).  Needs no GPU. */
 int smg_debug_schur_solve_host(int n, const int *ptr, const int *col, const double *val, const double *b, double *x, int *n_blocks, int *n_sep);
+/* Test hook: the partition of the coarsest level's rows the handle's Schur-complement solver works with (csrc/smg_schur.hpp): block_of_row[r]
+ * (n_coarsest entries, the coarsest level's caller numbering; NULL ok) = the interior block of row r, or -1 for a separator row.  Fails unless
+ * the handle holds that solver (smg_hierarchy_coarse_solver == 2).  Needs no GPU beyond the precompute. */
+int smg_debug_schur_partition(const smg_hierarchy *h, int *n_blocks, int *n_sep, int *block_of_row);
 /* Sparse Cholesky of the coarse solver (csrc/smg_coarse.hpp) on an SPD matrix given in CSR (both triangles): nested-dissection order,
  * factorisation, and the relative residual |b - A x| / |b| of a host solve with the factor for a deterministic right-hand side.
  * Returns SMG_ERR_INVALID when a pivot is not positive. */
@@ -688,6 +692,37 @@ int smg_debug_eig_residual(int n, int m, const double *X, const double *AX, cons
 enum { SMG_KRY_DOTS_ZR_ZQ = 0, SMG_KRY_DIRECTION = 1, SMG_KRY_DOTS_PQ = 2, SMG_KRY_STEP_DECIDE = 3, SMG_KRY_PRECOND_IN = 4, SMG_KRY_WIDEN = 5 };
 int smg_debug_krylov(int op, int n, int k, double *v0, double *v1, double *v2, double *v3, float *e, double *s, int *restart, double tol, int done,
                      double *ctrl_d, int *ctrl_i, int *groups, int *guard_bad);
+/* ---- test hooks of the fp32 V-cycle (precision = 1: enqueue_vcycle_t<float>, csrc/smg_cycle.cpp), piece by piece ----------------------------
+ * Like the fp64 pieces (smg_apply_A ... smg_vcycle) these take host column-major blocks in the caller's numbering of the level (n_lv x k floats,
+ * leading dimension n_lv), refuse a handle in a split-phase solve, a union handle and a sparse coarse factorisation, and use the handle's
+ * current smoother (smg_hierarchy_set_smoother).  Each op launches what the fp32 cycle launches for that piece, on the handle's own fp32
+ * vectors (b32, u32, r32, t32, d32 of the levels) and with the handle's control block, whose `done` flag the caller picks: with done != 0
+ * every launch must return without writing.  `out` is in/out: its host contents are uploaded to every buffer the op writes and read back
+ * afterwards.  *inputs_changed (NULL ok): bit 0 is set when a buffer the op only reads no longer holds what was uploaded; bit 2 when, with
+ * done != 0, any fp32 vector of the cycle -- b32, u32, r32, the second iterate t32 and the update vector d32 of EVERY level, the Schur solver's
+ * separator vectors -- differs after the launches from what it held after the uploads.
+ *   SMG_F32_A            in0 = x (level lv)                  out = A x
+ *   SMG_F32_RESID        in0 = b, in1 = x                    out = b - A x
+ *   SMG_F32_RESTRICT     in0 = r (level lv)                  out = [PT r | uc], two n_{lv+1} x k blocks back to back: the restriction launch without
+ *                                                            a fused first launch writes the coarse right-hand side and zeroes the coarse iterate
+ *   SMG_F32_PROLONG_ADD  in0 = uc (level lv + 1)             out (level lv) += P uc
+ *   SMG_F32_RELAX        in0 = b                             out = relax(pre) of out: `pre` sweeps of Gauss-Seidel (one launch per colour) or damped
+ *                                                            Jacobi, or ONE Chebyshev polynomial of degree pre + 1 (pre = 0: nothing)
+ *   SMG_F32_COARSE       in0 = b (coarsest level, lv unused) out += A^-1 b, dense inverse or Schur complement, as the handle chose
+ *   SMG_F32_VCYCLE       in0 = b                             out = V(pre, post) from level lv: the launch sequence of the mixed-precision solve,
+ *                                                            with its fused first launches (SMG_FUSE_FIRST) and its buffer ping-pong
+ * Block (3-DOF) hierarchies: the same, on rows 3 v + d. */
+enum { SMG_F32_A = 0, SMG_F32_RESID = 1, SMG_F32_RESTRICT = 2, SMG_F32_PROLONG_ADD = 3, SMG_F32_RELAX = 4, SMG_F32_COARSE = 5, SMG_F32_VCYCLE = 6 };
+int smg_debug_cycle_f32(smg_hierarchy *h, int op, int lv, int k, int pre, int post, int done, const float *in0, const float *in1, float *out,
+                        int *inputs_changed);
+/* The two converters between the fp64 outer loop and the fp32 cycle, on level 0's vectors (n_0 x k blocks as above):
+ *   SMG_F32_RESIDUAL_TO_F32  in64 = r            out_b32 = (float) r, out_u32 = 0        (in32, out64 unused)
+ *   SMG_F32_ADD_CORRECTION   in32 = e            out64 (in/out) = z + (double) e          (in64, out_b32, out_u32 unused)
+ * *inputs_changed: bit 0 as above; bit 1 is set when the launch wrote behind the n_0 x k block (the room a handle that has served more
+ * columns keeps there is filled with sentinel bytes for the launch). */
+enum { SMG_F32_RESIDUAL_TO_F32 = 0, SMG_F32_ADD_CORRECTION = 1 };
+int smg_debug_convert_f32(smg_hierarchy *h, int op, int k, int done, const double *in64, const float *in32, double *out64, float *out_b32,
+                          float *out_u32, int *inputs_changed);
 /* One launcher of the heat-method geodesics (csrc/smg_geodesics_device.hip), handle-free and guarded like the hooks above.  Blocks are
  * column-major n x k; `in` has leading dimension n, `out` has ld_out >= n and is in/out.  Source lists: src_ptr[0] = 0, k non-empty sets.
  *   SMG_GEO_BASIS       in = V (n x 3 row-major), F (nF x 3) -> W[9f + 3i + d] = ((N x e_i) / (2A))_d, Af[f] = A   (out unused)

@@ -77,6 +77,8 @@ def load():
         "smg_debug_eig_combine": (i, [i, i, i, dp, dp, dp, i, i, dp, dp, dp, dp, ip]),
         "smg_debug_eig_residual": (i, [i, i, dp, dp, dp, dp, i, i, dp, dp, fp, fp, dp, ip, ip]),
         "smg_debug_krylov": (i, [i, i, i, dp, dp, dp, dp, fp, dp, ip, d, i, dp, ip, ip, ip]),
+        "smg_debug_cycle_f32": (i, [vp, i, i, i, i, i, i, fp, fp, fp, ip]),
+        "smg_debug_convert_f32": (i, [vp, i, i, i, dp, fp, dp, fp, fp, ip]),
         "smg_debug_geodesics": (i, [i, i, i, i, ip, ip, ip, ip, ip, dp, dp, dp, dp, i, ip]),
         "smg_geodesics_create": (i, [vp, dp, i, ip, i, d, i, C.POINTER(vp)]),
         "smg_geodesics_destroy": (None, [vp]),
@@ -136,6 +138,7 @@ def load():
         "smg_hierarchy_set_coarse_dense_max": (i, [vp, i]),
         "smg_hierarchy_set_coarse_schur": (i, [vp, i, i]),
         "smg_debug_schur_solve_host": (i, [i, ip, ip, dp, dp, dp, ip, ip]),
+        "smg_debug_schur_partition": (i, [vp, ip, ip, ip]),
         "smg_hierarchy_set_block_gs": (i, [vp, i]),
         "smg_hierarchy_set_wave_gs": (i, [vp, i]),
         "smg_hierarchy_set_memory_lean": (i, [vp, i]),

@@ -401,6 +401,20 @@ extern "C" int smg_hierarchy_coarse_solver(const smg_hierarchy* h, long* factor_
     } else if (factor_entries) *factor_entries = h->coarse_sparse ? h->chol.nnzL() : h->coarse_schur ? (long)h->schur.off_C : (long)h->nc_pad * h->nc_pad;
     return h->coarse_sparse ? 1 : h->coarse_schur ? 2 : 0;
 }
+extern "C" int smg_debug_schur_partition(const smg_hierarchy* h, int* n_blocks, int* n_sep, int* block_of_row)
+{
+    if (!h || !h->precomputed || !h->coarse_schur) return fail(SMG_ERR_INVALID, "smg_debug_schur_partition: the handle holds no Schur-complement coarse solver");
+    const smg::SchurPlan& S = h->schur;
+    if (n_blocks) *n_blocks = S.nb;
+    if (n_sep) *n_sep = S.ns;
+    if (block_of_row) {
+        for (int r = 0; r < S.n; r++) block_of_row[r] = -2;
+        for (int j = 0; j < S.ns; j++) block_of_row[S.srow[j]] = -1;
+        for (int i = 0; i < S.nb; i++)
+            for (int r = 0; r < S.bsize[i]; r++) block_of_row[S.irow[(size_t)i * 64 + r]] = i;
+    }
+    return SMG_OK;
+}
 extern "C" int smg_hierarchy_set_coarse_schur(smg_hierarchy* h, int when, int n_min)
 {
     if (!h || when < 0 || when > 2) return fail(SMG_ERR_INVALID, "smg_hierarchy_set_coarse_schur: bad arguments (when: 0 never, 1 always, 2 from the first value-only re-precompute on)");

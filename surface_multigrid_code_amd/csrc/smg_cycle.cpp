@@ -682,21 +682,23 @@ extern "C" int smg_level_rows(const smg_hierarchy* h, int lv)
 }
 
 // host column-major (caller numbering of level lv) -> device internal layout
-static int put_block(smg_hierarchy* h, int lv, const double* src, int k, double* dst)
+template <typename T>
+static int put_block(smg_hierarchy* h, int lv, const T* src, int k, T* dst)
 {
     const Level& Lv = h->lv[lv];
-    std::vector<double> tmp((size_t)Lv.n * k);
+    std::vector<T> tmp((size_t)Lv.n * k);
     for (int i = 0; i < Lv.n; i++)
         for (int c = 0; c < k; c++) tmp[(size_t)i * k + c] = src[(size_t)Lv.ord.perm[i] + (size_t)c * Lv.n];
-    HIPCHK(hipMemcpyAsync(dst, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dst, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return SMG_OK;
 }
-static int get_block(smg_hierarchy* h, int lv, const double* src, int k, double* dst)
+template <typename T>
+static int get_block(smg_hierarchy* h, int lv, const T* src, int k, T* dst)
 {
     const Level& Lv = h->lv[lv];
-    std::vector<double> tmp((size_t)Lv.n * k);
-    HIPCHK(hipMemcpyAsync(tmp.data(), src, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    std::vector<T> tmp((size_t)Lv.n * k);
+    HIPCHK(hipMemcpyAsync(tmp.data(), src, tmp.size() * sizeof(T), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int i = 0; i < Lv.n; i++)
         for (int c = 0; c < k; c++) dst[(size_t)Lv.ord.perm[i] + (size_t)c * Lv.n] = tmp[(size_t)i * k + c];
@@ -804,6 +806,235 @@ extern "C" int smg_residual_norm(smg_hierarchy* h, int lv, const double* B, cons
     HIPCHK(hipStreamSynchronize(h->stream));
     *norm = std::sqrt(ss);
     return SMG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the fp32 cycle, piece by piece (test hooks)
+// What enqueue_vcycle_t<float> launches for one piece, on the handle's own fp32 buffers, with the handle's control block (whose `done` flag the
+// caller picks) -- see include/smg.h, smg_debug_cycle_f32.
+
+// the control block the launches of a hook get: fresh, with the chosen flag
+static int hook_ctrl(smg_hierarchy* h, int done)
+{
+    int rc = reset_ctrl(h, 1);
+    if (rc) return rc;
+    if (done) {
+        static const int one = 1;
+        HIPCHK(hipMemcpyAsync(&h->d_ctrl.p->done, &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return SMG_OK;
+}
+
+// leaves the handle's control block fresh (not done) however the hook returns
+struct HookCtrlReset {
+    smg_hierarchy* h;
+    ~HookCtrlReset() { if (reset_ctrl(h, 1) == SMG_OK) (void)hipStreamSynchronize(h->stream); }
+};
+
+// Every fp32 vector a launch of the cycle may write -- b32, u32, r32, t32, d32 of every level, the Schur solver's g32 / xs32 -- whole
+// allocations, as bytes: with the done flag set none of them may change between the uploads and the end of the launches.
+static int snapshot_f32(smg_hierarchy* h, std::vector<float>& out)
+{
+    out.clear();
+    std::vector<const DevBuf<float>*> bufs;
+    for (Level& Lv : h->lv)
+        for (const DevBuf<float>* b : {&Lv.b32, &Lv.u32, &Lv.r32, &Lv.t32, &Lv.d32}) bufs.push_back(b);
+    bufs.push_back(&h->sch.g32); bufs.push_back(&h->sch.xs32);
+    size_t total = 0;
+    for (const DevBuf<float>* b : bufs) total += b->n;
+    out.resize(total);
+    size_t off = 0;
+    for (const DevBuf<float>* b : bufs) {
+        if (b->n) HIPCHK(hipMemcpyAsync(out.data() + off, b->p, b->n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        off += b->n;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return SMG_OK;
+}
+
+// the n x k head of a device buffer against the host block that was uploaded there (same permutation): 1 when a bit differs
+template <typename T>
+static int block_changed(smg_hierarchy* h, int lv, const T* dev, int k, const T* uploaded, int* changed)
+{
+    const Level& Lv = h->lv[lv];
+    std::vector<T> now((size_t)Lv.n * k);
+    int rc = get_block<T>(h, lv, dev, k, now.data());
+    if (rc) return rc;
+    if (std::memcmp(now.data(), uploaded, now.size() * sizeof(T)) != 0) *changed = 1;
+    return SMG_OK;
+}
+
+// relax(iters) of the fp32 cycle on Lv.b32 / Lv.u32: *res = the buffer the result is in (u32 or, after an odd number of Jacobi-type
+// launches, t32 -- the cycle itself arranges its prolongation so that the last sweep lands in u32, see enqueue_vcycle_t)
+static int enqueue_relax_f32(smg_hierarchy* h, int lv, int k, int iters, const Ctrl* ctrl, float** res)
+{
+    Level& Lv = h->lv[lv];
+    const int kind = level_kind(h, lv);
+    float* const buf[2] = {Lv.u32.p, Lv.t32.p};
+    int cur = 0, rc;
+    if (kind == LV_GS) rc = enqueue_gs<float>(h, lv, sweep_plan(h, lv, k, iters, false, FIRST_NONE), Lv.b32.p, Lv.u32.p, k, iters, ctrl);
+    else if (kind == LV_CHEBY) rc = enqueue_cheby<float>(h, lv, Lv.b32.p, buf, &cur, k, iters, ctrl);
+    else rc = enqueue_jacobi<float>(h, lv, Lv.b32.p, buf, &cur, k, iters, ctrl);
+    *res = buf[cur];
+    return rc;
+}
+
+extern "C" int smg_debug_cycle_f32(smg_hierarchy* h, int op, int lv, int k, int pre, int post, int done, const float* in0, const float* in1,
+                                   float* out, int* inputs_changed)
+{
+    return guarded("smg_debug_cycle_f32", [&]() -> int {
+        if (!h) return fail(SMG_ERR_INVALID, "smg_debug_cycle_f32: null handle");
+        if (op < SMG_F32_A || op > SMG_F32_VCYCLE) return fail(SMG_ERR_INVALID, "smg_debug_cycle_f32: unknown op %d", op);
+        if (op == SMG_F32_COARSE) lv = h->n_levels - 1;
+        const bool two_in = op == SMG_F32_RESID;
+        if (!in0 || !out || (two_in && !in1) || pre < 0 || post < 0) return fail(SMG_ERR_INVALID, "smg_debug_cycle_f32: missing array or negative sweep count");
+        int rc = piece_prolog(h, lv, k, "smg_debug_cycle_f32", op != SMG_F32_COARSE && op != SMG_F32_VCYCLE);
+        if (rc) return rc;
+        DeviceScope dsc(h->device);
+        if ((rc = ensure_fp32(h, k))) return rc;
+        if ((rc = prepare_sweep_plans(h, k, pre, post))) return rc;
+        HookCtrlReset reset_on_exit{h};
+        if ((rc = hook_ctrl(h, done))) return rc;
+        const Ctrl* ctrl = h->d_ctrl.p;
+        const int L = h->n_levels;
+        Level& Lv = h->lv[lv];
+        int changed = 0;
+        std::vector<float> before, after;
+        auto uploaded = [&]() -> int { return done ? snapshot_f32(h, before) : SMG_OK; };   // called between an op's uploads and its launches
+        switch (op) {
+            case SMG_F32_A:          // out = A in0
+                if ((rc = put_block<float>(h, lv, in0, k, Lv.u32.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, Lv.r32.p)) || (rc = uploaded())) return rc;
+                HIPCHK(Prec<float>::opA(h, Lv, false, SELL_AX, 0, -1, Lv.u32.p, nullptr, Lv.r32.p, k, ctrl));
+                if ((rc = block_changed<float>(h, lv, Lv.u32.p, k, in0, &changed))) return rc;
+                rc = get_block<float>(h, lv, Lv.r32.p, k, out);
+                break;
+            case SMG_F32_RESID:      // out = in0 - A in1: the residual launch of the cycle
+                if ((rc = put_block<float>(h, lv, in0, k, Lv.b32.p))) return rc;
+                if ((rc = put_block<float>(h, lv, in1, k, Lv.u32.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, Lv.r32.p)) || (rc = uploaded())) return rc;
+                HIPCHK(Prec<float>::opA(h, Lv, false, SELL_RESID, 0, -1, Lv.u32.p, Lv.b32.p, Lv.r32.p, k, ctrl));
+                if ((rc = block_changed<float>(h, lv, Lv.b32.p, k, in0, &changed))) return rc;
+                if ((rc = block_changed<float>(h, lv, Lv.u32.p, k, in1, &changed))) return rc;
+                rc = get_block<float>(h, lv, Lv.r32.p, k, out);
+                break;
+            case SMG_F32_RESTRICT: { // out = [PT in0 | the zeroed coarse iterate]: the restriction launch without a fused first launch
+                Level& Lc = h->lv[lv + 1];
+                const size_t cc = (size_t)Lc.n * k;
+                if ((rc = put_block<float>(h, lv, in0, k, Lv.r32.p))) return rc;
+                if ((rc = put_block<float>(h, lv + 1, out, k, Lc.b32.p))) return rc;
+                if ((rc = put_block<float>(h, lv + 1, out + cc, k, Lc.u32.p)) || (rc = uploaded())) return rc;
+                HIPCHK(Prec<float>::sell(SELL_AX, Prec<float>::PT(Lc), 0, Prec<float>::PT(Lc).n_slices, Lv.r32.p, nullptr, Lc.b32.p, k * h->bs, ctrl, h->stream, Lc.u32.p,
+                                         nullptr));
+                if ((rc = block_changed<float>(h, lv, Lv.r32.p, k, in0, &changed))) return rc;
+                if ((rc = get_block<float>(h, lv + 1, Lc.b32.p, k, out))) return rc;
+                rc = get_block<float>(h, lv + 1, Lc.u32.p, k, out + cc);
+                break;
+            }
+            case SMG_F32_PROLONG_ADD: { // out += P in0
+                Level& Lc = h->lv[lv + 1];
+                if ((rc = put_block<float>(h, lv + 1, in0, k, Lc.u32.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, Lv.u32.p)) || (rc = uploaded())) return rc;
+                HIPCHK(Prec<float>::sell(SELL_ADD, Prec<float>::P(Lc), 0, Prec<float>::P(Lc).n_slices, Lc.u32.p, Lv.u32.p, Lv.u32.p, k * h->bs, ctrl, h->stream));
+                if ((rc = block_changed<float>(h, lv + 1, Lc.u32.p, k, in0, &changed))) return rc;
+                rc = get_block<float>(h, lv, Lv.u32.p, k, out);
+                break;
+            }
+            case SMG_F32_RELAX: {    // out = relax(pre) of out with right-hand side in0
+                if ((rc = put_block<float>(h, lv, in0, k, Lv.b32.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, Lv.u32.p))) return rc;
+                if (level_is_jacobi(h, lv) && (rc = put_block<float>(h, lv, out, k, Lv.t32.p))) return rc;   // the second iterate: an output, too
+                float* res = nullptr;
+                if ((rc = uploaded())) return rc;
+                if ((rc = enqueue_relax_f32(h, lv, k, pre, ctrl, &res))) return rc;
+                if ((rc = block_changed<float>(h, lv, Lv.b32.p, k, in0, &changed))) return rc;
+                rc = get_block<float>(h, lv, res, k, out);
+                break;
+            }
+            case SMG_F32_COARSE:     // out += A^-1 in0 on the coarsest level
+                if ((rc = put_block<float>(h, lv, in0, k, Lv.b32.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, Lv.u32.p)) || (rc = uploaded())) return rc;
+                HIPCHK(Prec<float>::coarse(h, Lv, k, ctrl));
+                if ((rc = block_changed<float>(h, lv, Lv.b32.p, k, in0, &changed))) return rc;
+                rc = get_block<float>(h, lv, Lv.u32.p, k, out);
+                break;
+            case SMG_F32_VCYCLE:     // out = V(pre, post) from level lv with right-hand side in0
+                if ((rc = put_block<float>(h, lv, in0, k, Lv.b32.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, Lv.u32.p))) return rc;
+                if (lv < L - 1 && level_is_jacobi(h, lv) && (rc = put_block<float>(h, lv, out, k, Lv.t32.p))) return rc;
+                if ((rc = uploaded())) return rc;
+                if ((rc = enqueue_vcycle_t<float>(h, lv, k, pre, post, ctrl))) return rc;
+                if ((rc = block_changed<float>(h, lv, Lv.b32.p, k, in0, &changed))) return rc;
+                rc = get_block<float>(h, lv, Lv.u32.p, k, out);
+                break;
+        }
+        if (rc) return rc;
+        if (done) {      // nothing the cycle owns in fp32 may have moved: the second iterate, the update vector and the coarser levels included
+            if ((rc = snapshot_f32(h, after))) return rc;
+            if (before.size() != after.size() || std::memcmp(before.data(), after.data(), after.size() * sizeof(float)) != 0) changed |= 4;
+        }
+        if (inputs_changed) *inputs_changed = changed;
+        return SMG_OK;
+    });
+}
+
+// the two converters between the fp64 outer loop and the fp32 cycle, on level 0's own buffers.  The room of a buffer behind the n0 x k block
+// (a handle that has served more columns before) is filled with sentinel bytes first and must still hold them afterwards.
+extern "C" int smg_debug_convert_f32(smg_hierarchy* h, int op, int k, int done, const double* in64, const float* in32, double* out64, float* out_b32,
+                                     float* out_u32, int* inputs_changed)
+{
+    return guarded("smg_debug_convert_f32", [&]() -> int {
+        if (!h) return fail(SMG_ERR_INVALID, "smg_debug_convert_f32: null handle");
+        if (op != SMG_F32_RESIDUAL_TO_F32 && op != SMG_F32_ADD_CORRECTION) return fail(SMG_ERR_INVALID, "smg_debug_convert_f32: unknown op %d", op);
+        if (op == SMG_F32_RESIDUAL_TO_F32 ? (!in64 || !out_b32 || !out_u32) : (!in32 || !out64)) return fail(SMG_ERR_INVALID, "smg_debug_convert_f32: missing array");
+        int rc = piece_prolog(h, 0, k, "smg_debug_convert_f32", false);
+        if (rc) return rc;
+        DeviceScope dsc(h->device);
+        if ((rc = ensure_fp32(h, k))) return rc;
+        HookCtrlReset reset_on_exit{h};
+        if ((rc = hook_ctrl(h, done))) return rc;
+        const Ctrl* ctrl = h->d_ctrl.p;
+        Level& L0 = h->lv[0];
+        const size_t cnt = (size_t)L0.n * k;
+        int changed = 0;
+        // sentinel bytes behind the block, checked after the launch, then cleared again (the buffers start out as zeros)
+        auto tail_fill = [&](void* p, size_t have, size_t elem, int byte) -> int {
+            if (have > cnt) HIPCHK(hipMemsetAsync((char*)p + cnt * elem, byte, (have - cnt) * elem, h->stream));
+            return SMG_OK;
+        };
+        auto tail_check = [&](const void* p, size_t have, size_t elem) -> int {
+            if (have <= cnt) return SMG_OK;
+            std::vector<unsigned char> t((have - cnt) * elem);
+            HIPCHK(hipMemcpyAsync(t.data(), (const char*)p + cnt * elem, t.size(), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            for (unsigned char c : t) if (c != 0x5B) { changed |= 2; break; }
+            return SMG_OK;
+        };
+        if (op == SMG_F32_RESIDUAL_TO_F32) {      // b32 = (float) r, u32 = 0
+            if (h->n_levels < 2) return fail(SMG_ERR_INVALID, "smg_debug_convert_f32: a one-level handle has no residual vector");
+            if ((rc = put_block<double>(h, 0, in64, k, L0.r.p))) return rc;
+            if ((rc = put_block<float>(h, 0, out_b32, k, L0.b32.p))) return rc;
+            if ((rc = put_block<float>(h, 0, out_u32, k, L0.u32.p))) return rc;
+            if ((rc = tail_fill(L0.b32.p, L0.b32.n, sizeof(float), 0x5B)) || (rc = tail_fill(L0.u32.p, L0.u32.n, sizeof(float), 0x5B))) return rc;
+            HIPCHK(launch_residual_to_f32(L0.b32.p, L0.u32.p, L0.r.p, cnt, ctrl, h->stream));
+            if ((rc = tail_check(L0.b32.p, L0.b32.n, sizeof(float))) || (rc = tail_check(L0.u32.p, L0.u32.n, sizeof(float)))) return rc;
+            if ((rc = tail_fill(L0.b32.p, L0.b32.n, sizeof(float), 0)) || (rc = tail_fill(L0.u32.p, L0.u32.n, sizeof(float), 0))) return rc;
+            if ((rc = block_changed<double>(h, 0, L0.r.p, k, in64, &changed))) return rc;
+            if ((rc = get_block<float>(h, 0, L0.b32.p, k, out_b32))) return rc;
+            if ((rc = get_block<float>(h, 0, L0.u32.p, k, out_u32))) return rc;
+        } else {                                  // z += (double) e
+            if ((rc = put_block<double>(h, 0, out64, k, L0.u.p))) return rc;
+            if ((rc = put_block<float>(h, 0, in32, k, L0.u32.p))) return rc;
+            if ((rc = tail_fill(L0.u.p, L0.u.n, sizeof(double), 0x5B))) return rc;
+            HIPCHK(launch_add_correction(L0.u.p, L0.u32.p, cnt, ctrl, h->stream));
+            if ((rc = tail_check(L0.u.p, L0.u.n, sizeof(double)))) return rc;
+            if ((rc = tail_fill(L0.u.p, L0.u.n, sizeof(double), 0))) return rc;
+            if ((rc = block_changed<float>(h, 0, L0.u32.p, k, in32, &changed))) return rc;
+            if ((rc = get_block<double>(h, 0, L0.u.p, k, out64))) return rc;
+        }
+        if (inputs_changed) *inputs_changed = changed;
+        return SMG_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ raw device interface

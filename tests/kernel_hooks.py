@@ -1,5 +1,5 @@
-"""numpy wrappers of the handle-free kernel test hooks (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine, smg_debug_eig_residual,
-smg_debug_krylov) and the rounding-error bounds the tests hold them to.
+"""numpy wrappers of the kernel test hooks (include/smg.h: the handle-free smg_debug_eig_gram, smg_debug_eig_combine, smg_debug_eig_residual,
+smg_debug_krylov; on a handle smg_debug_cycle_f32, smg_debug_convert_f32) and the rounding-error bounds the tests hold them to.
 
 Every wrapper asserts that the hook succeeded and that no guard region around a device buffer changed (no write out of place)."""
 import ctypes as C
@@ -113,6 +113,88 @@ def krylov(L, op, vecs, s=None, restart=None, e=None, tol=0.0, done=0):
     assert groups.value == kry_groups(n, k)
     ctrl = dict(sumsq=cd[0], r0=cd[1], n_his=ci[0], done=ci[1], status=ci[2])
     return vecs, s, (None if rs is None else rs.value), ctrl
+
+
+F32_OPS = dict(A=0, RESID=1, RESTRICT=2, PROLONG_ADD=3, RELAX=4, COARSE=5, VCYCLE=6)
+F32_IN_LEVEL = dict(A=0, RESID=0, RESTRICT=0, PROLONG_ADD=1, RELAX=0, COARSE=0, VCYCLE=0)     # level of in0 relative to lv
+F32_OUT_LEVEL = dict(A=0, RESID=0, RESTRICT=1, PROLONG_ADD=0, RELAX=0, COARSE=0, VCYCLE=0)    # ... of out
+
+
+def _f32_block(a, rows, name):
+    a = np.asarray(a)
+    if a.ndim == 1:
+        a = a[:, None]
+    assert a.dtype == np.float32, "%s: the fp32 pieces take float32 blocks (round them where the cycle rounds them)" % name
+    assert a.shape[0] == rows, "%s: expected %d rows, got %d (the C ABI takes bare pointers)" % (name, rows, a.shape[0])
+    return np.asfortranarray(a)
+
+
+def _fp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def cycle_f32(mg, op, lv, in0, in1=None, out=None, pre=0, post=0, done=0, check=True):
+    """One piece of the fp32 V-cycle on hierarchy mg (smg_debug_cycle_f32), blocks in the caller's numbering of their level.
+    out: what is uploaded to the buffers the op writes (the iterate of PROLONG_ADD / RELAX / COARSE / VCYCLE; default zeros).
+    Returns the output block -- RESTRICT: the pair (PT r, the zeroed coarse iterate), `out` a pair likewise -- after asserting
+    (check) that no buffer the op only reads has changed and, with done = 1, that no fp32 vector of any level has (the second iterate and
+    the update vector of the Jacobi-type levels and the coarser levels of a cycle included)."""
+    L = mg.L
+    if op == "COARSE":
+        lv = mg.n_levels - 1
+    rows_in, rows_out = mg.rows(lv + F32_IN_LEVEL[op]), mg.rows(lv + F32_OUT_LEVEL[op])
+    in0 = _f32_block(in0, rows_in, op)
+    k = in0.shape[1]
+    in1 = None if in1 is None else _f32_block(in1, rows_in, op)
+    if op == "RESTRICT":
+        pair = (np.zeros((rows_out, k), np.float32),) * 2 if out is None else out
+        o = np.concatenate([_f32_block(x, rows_out, op).ravel(order="F") for x in pair])
+    else:
+        o = (np.zeros((rows_out, k), np.float32, order="F") if out is None else _f32_block(out, rows_out, op).copy(order="F"))
+        assert o.shape[1] == k
+    changed = C.c_int(-1)
+    rc = L.smg_debug_cycle_f32(mg.h, F32_OPS[op], lv, k, pre, post, done, _fp(in0), _fp(in1), _fp(o), C.byref(changed))
+    assert rc == 0, L.smg_last_error()
+    if check:
+        assert not changed.value & 1, "%s on level %d: a buffer the op only reads was written" % (op, lv)
+        assert not changed.value & 4, "%s on level %d with done = 1: an fp32 vector of the cycle (some level's b32 / u32 / r32 / t32 / d32) was written" % (op, lv)
+        assert changed.value == 0, changed.value
+    if op == "RESTRICT":
+        return o[:rows_out * k].reshape((rows_out, k), order="F"), o[rows_out * k:].reshape((rows_out, k), order="F")
+    return o
+
+
+def residual_to_f32(mg, r, done=0, outs=None):
+    """(b32, u32) = ((float) r, 0) on level 0 (smg_debug_convert_f32); outs: what is uploaded as b32, u32 (default: sentinels)"""
+    r = np.asfortranarray(np.asarray(r, dtype=np.float64).reshape(mg.rows(0), -1))
+    k = r.shape[1]
+    b32, u32 = [_f32_block(o, mg.rows(0), "RESIDUAL_TO_F32").copy(order="F") for o in (outs or (sentinel(r.shape, np.float32),) * 2)]
+    changed = C.c_int(-1)
+    rc = mg.L.smg_debug_convert_f32(mg.h, 0, k, done, _p(r.T), None, None, _fp(b32), _fp(u32), C.byref(changed))
+    assert rc == 0, mg.L.smg_last_error()
+    assert changed.value == 0, "RESIDUAL_TO_F32: the input changed or the launch wrote behind the block (inputs_changed = %d)" % changed.value
+    return b32, u32
+
+
+def add_correction(mg, z, e, done=0):
+    """z + (double) e on level 0 (smg_debug_convert_f32)"""
+    z = np.asfortranarray(np.asarray(z, dtype=np.float64).reshape(mg.rows(0), -1)).copy(order="F")
+    e = _f32_block(e, mg.rows(0), "ADD_CORRECTION")
+    changed = C.c_int(-1)
+    rc = mg.L.smg_debug_convert_f32(mg.h, 1, z.shape[1], done, None, _fp(e), _p(z.T), None, None, C.byref(changed))
+    assert rc == 0, mg.L.smg_last_error()
+    assert changed.value == 0, "ADD_CORRECTION: the input changed or the launch wrote behind the block (inputs_changed = %d)" % changed.value
+    return z
+
+
+def schur_partition(mg):
+    """block_of_row of the handle's Schur-complement coarse solver (smg_debug_schur_partition): interior block per coarsest-level row, -1 = separator"""
+    nb, ns = C.c_int(-1), C.c_int(-1)
+    out = np.full(mg.rows(mg.n_levels - 1), -3, np.int32)
+    rc = mg.L.smg_debug_schur_partition(mg.h, C.byref(nb), C.byref(ns), _p(out, C.c_int))
+    assert rc == 0, mg.L.smg_last_error()
+    assert out.min() >= -1 and (out == -1).sum() == ns.value and out.max() == nb.value - 1, "not a partition"
+    return out
 
 
 def exact_dot(a, b):

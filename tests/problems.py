@@ -42,3 +42,30 @@ def subdiv_problem(mesh="ogre_sim.smgm", n_sub=2, kind="mcf", k=1, seed=0, n_pin
         out.update(A=A, RHS=np.asfortranarray(B), z0=np.asfortranarray(z0), known=b, known_val=bval)
     A.sort_indices()
     return out
+
+
+def random_spd_hierarchy(rng, n, levels, hub):
+    """A random sparse SPD matrix (irregular degrees; optionally a few hub rows so that SELL slices get very wide and the
+    compact-panel fallback and > 4 colours are exercised) with a random aggregation-type prolongation hierarchy."""
+    deg = rng.integers(2, 9, n)
+    rows = np.repeat(np.arange(n), deg)
+    cols = rng.integers(0, n, rows.size)
+    if hub:
+        hubs = rng.choice(n, 3, replace=False)
+        extra = rng.choice(n, (3, min(n - 1, 120)))
+        rows = np.concatenate([rows, np.repeat(hubs, extra.shape[1])]); cols = np.concatenate([cols, extra.ravel()])
+    W = sp.coo_matrix((-rng.uniform(0.1, 1.0, rows.size), (rows, cols)), shape=(n, n)).tocsr()
+    W.setdiag(0); W.eliminate_zeros()
+    W = W + W.T
+    A = (W + sp.diags(np.asarray(-W.sum(axis=1)).ravel() + rng.uniform(0.05, 0.5, n))).tocsr()   # strictly diagonally dominant
+    A.sort_indices()
+    Ps, m = [], n
+    for _ in range(levels - 1):
+        mc = max(2, m // 3)
+        agg = rng.integers(0, mc, m); agg[:mc] = np.arange(mc)          # every coarse vertex has a child
+        second = rng.integers(0, mc, m)
+        w = rng.uniform(0.5, 1.0, m)
+        P = sp.coo_matrix((np.concatenate([w, 1 - w]), (np.concatenate([np.arange(m)] * 2), np.concatenate([agg, second]))), shape=(m, mc)).tocsr()
+        P.sum_duplicates(); P.sort_indices()
+        Ps.append(P); m = mc
+    return A, Ps

@@ -87,7 +87,8 @@ def _kernel_hook_calls(L, n=4, m=2, nb=1, op=0, k=2):
 
 
 def test_kernel_hooks_refuse_bad_shapes(smg_mod):
-    """SMG_ERR_INVALID before any device work: n < 1, m outside 1..64, nb outside 1..3, an unknown Krylov op, k < 1"""
+    """SMG_ERR_INVALID before any device work: n < 1, m outside 1..64, nb outside 1..3, an unknown Krylov op, k < 1; the fp32 cycle's hooks:
+    no handle, an unknown op, a missing array, a handle without a precomputed system"""
     L = smg_mod._lib.load()
     hooks = dict(n=["gram", "combine", "residual", "krylov"], m=["gram", "combine", "residual"], nb=["gram", "combine"], op=["krylov"],
                  k=["krylov"])
@@ -99,6 +100,27 @@ def test_kernel_hooks_refuse_bad_shapes(smg_mod):
     # a missing array is refused the same way
     assert L.smg_debug_eig_gram(4, 2, 1, None, 1, None, None, 0, 0, None, None, None) == -1
     assert L.smg_debug_krylov(0, 4, 2, None, None, None, None, None, None, None, 0.0, 0, None, None, None, None) == -1
+    # the hooks of the fp32 cycle work on a handle: no handle, an unknown op, a missing array and a handle that was never precomputed are refused
+    fp = C.POINTER(C.c_float)
+    f = [np.zeros(64, np.float32).ctypes.data_as(fp) for _ in range(3)]
+    d = np.zeros(64).ctypes.data_as(C.POINTER(C.c_double))
+    assert L.smg_debug_cycle_f32(None, 0, 0, 1, 0, 0, 0, f[0], f[1], f[2], None) == -1
+    assert L.smg_debug_convert_f32(None, 0, 1, 0, d, f[0], d, f[1], f[2], None) == -1
+    h = L.smg_hierarchy_create(2)
+    try:
+        for op in (-1, 7):
+            assert L.smg_debug_cycle_f32(h, op, 0, 1, 0, 0, 0, f[0], f[1], f[2], None) == -1 and b"unknown op" in L.smg_last_error()
+        assert L.smg_debug_convert_f32(h, 2, 1, 0, d, f[0], d, f[1], f[2], None) == -1 and b"unknown op" in L.smg_last_error()
+        assert L.smg_debug_cycle_f32(h, 1, 0, 1, 0, 0, 0, f[0], None, f[2], None) == -1 and b"missing" in L.smg_last_error()
+        assert L.smg_debug_cycle_f32(h, 4, 0, 1, -1, 0, 0, f[0], None, f[2], None) == -1
+        assert L.smg_debug_convert_f32(h, 0, 1, 0, None, None, None, f[1], f[2], None) == -1 and b"missing" in L.smg_last_error()
+        assert L.smg_debug_convert_f32(h, 1, 1, 0, None, f[0], None, None, None, None) == -1 and b"missing" in L.smg_last_error()
+        for op in range(7):
+            assert L.smg_debug_cycle_f32(h, op, 0, 1, 1, 1, 0, f[0], f[1], f[2], None) == -1 and b"smg_precompute first" in L.smg_last_error()
+        for op in range(2):
+            assert L.smg_debug_convert_f32(h, op, 1, 0, d, f[0], d, f[1], f[2], None) == -1 and b"smg_precompute first" in L.smg_last_error()
+    finally:
+        L.smg_hierarchy_destroy(h)
 
 
 @pytest.mark.skipif(os.environ.get("SMG_EXPECT_GPU") == "1", reason="GPU box")

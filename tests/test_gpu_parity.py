@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from problems import subdiv_problem
+from problems import random_spd_hierarchy as _random_spd_hierarchy, subdiv_problem
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -441,11 +441,30 @@ def test_value_only_reprecompute_on_device_is_bit_exact(smg, oracle_mod, kind, c
     assert mg.solve(pm["RHS"], pm["z0"], None, o)[0]
 
 
-@pytest.mark.parametrize("kind,k,tol", [("mcf", 3, 1e-10), ("poisson", 1, 1e-10), ("mcf", 16, 5e-7)])
+def _decimated_bunny_poisson(smg, k):
+    """bunny.obj Poisson with the boundary loop pinned on the library's own decimated hierarchy (Galerkin levels, long restriction rows), k columns"""
+    from oracle import mesh_np as M
+    V, F = M.read_smgm("bunny.smgm")
+    V = M.normalize_unit_area(V, F)
+    mg = smg.mg_precompute(V, F, 0.25, 500, 1)
+    b = M.boundary_loop(F)
+    n = V.shape[0]
+    rng = np.random.default_rng(0)
+    B = np.repeat((M.massmatrix(V, F, "voronoi") @ np.ones(n))[:, None], k, axis=1) * rng.uniform(0.5, 1.5, (1, k))
+    B[b, :] = 0.0
+    mg.precompute((-M.cotmatrix(V, F)).tocsr(), b)
+    return dict(RHS=np.asfortranarray(B), z0=np.asfortranarray(rng.uniform(-1, 1, (n, k))), known=b, known_val=np.zeros((len(b), k))), mg
+
+
+@pytest.mark.parametrize("kind,k,tol", [("mcf", 3, 1e-10), ("poisson", 1, 1e-10), ("mcf", 16, 5e-7), ("mcf", 7, 5e-7), ("mcf", 13, 5e-7), ("mcf", 64, 5e-7),
+                                        ("decimated", 2, 5e-7)])
 def test_mixed_precision_reaches_fp64_accuracy(smg, oracle_mod, kind, k, tol):
     """BASELINE config 5 (fp32 vs fp64): fp32 V-cycle inside an fp64 outer loop.  r_his is measured in fp64, so the same
     tolerance is reached; the solution agrees with the all-fp64 run (and the oracle) at solver precision."""
-    p, mg, orc = build(smg, oracle_mod, kind=kind, k=k, n_sub=2)
+    if kind == "decimated":
+        p, mg = _decimated_bunny_poisson(smg, k)
+    else:
+        p, mg, orc = build(smg, oracle_mod, kind=kind, k=k, n_sub=2)
     c64, z64, r64 = mg.solve(p["RHS"], p["z0"], p["known_val"], smg.SolveOpts(tol=tol, max_iter=40))
     cmx, zmx, rmx = mg.solve(p["RHS"], p["z0"], p["known_val"], smg.SolveOpts(tol=tol, max_iter=40, precision="mixed"))
     assert c64 and cmx and rmx[-1] < tol
@@ -607,33 +626,6 @@ def test_tiny_and_ragged_systems(smg, oracle_mod, n, levels, k, known):
 
 
 # ----------------------------------------------------------------------------------------------- random non-mesh systems
-def _random_spd_hierarchy(rng, n, levels, hub):
-    """A random sparse SPD matrix (irregular degrees; optionally a few hub rows so that SELL slices get very wide and the
-    compact-panel fallback and > 4 colours are exercised) with a random aggregation-type prolongation hierarchy."""
-    deg = rng.integers(2, 9, n)
-    rows = np.repeat(np.arange(n), deg)
-    cols = rng.integers(0, n, rows.size)
-    if hub:
-        hubs = rng.choice(n, 3, replace=False)
-        extra = rng.choice(n, (3, min(n - 1, 120)))
-        rows = np.concatenate([rows, np.repeat(hubs, extra.shape[1])]); cols = np.concatenate([cols, extra.ravel()])
-    W = sp.coo_matrix((-rng.uniform(0.1, 1.0, rows.size), (rows, cols)), shape=(n, n)).tocsr()
-    W.setdiag(0); W.eliminate_zeros()
-    W = W + W.T
-    A = (W + sp.diags(np.asarray(-W.sum(axis=1)).ravel() + rng.uniform(0.05, 0.5, n))).tocsr()   # strictly diagonally dominant
-    A.sort_indices()
-    Ps, m = [], n
-    for _ in range(levels - 1):
-        mc = max(2, m // 3)
-        agg = rng.integers(0, mc, m); agg[:mc] = np.arange(mc)          # every coarse vertex has a child
-        second = rng.integers(0, mc, m)
-        w = rng.uniform(0.5, 1.0, m)
-        P = sp.coo_matrix((np.concatenate([w, 1 - w]), (np.concatenate([np.arange(m)] * 2), np.concatenate([agg, second]))), shape=(m, mc)).tocsr()
-        P.sum_duplicates(); P.sort_indices()
-        Ps.append(P); m = mc
-    return A, Ps
-
-
 @pytest.mark.parametrize("seed,n,levels,k,hub", [(1, 200, 2, 1, False), (2, 777, 3, 2, False), (3, 1500, 3, 1, True), (4, 4000, 4, 3, True),
                                                 (5, 65, 2, 9, False), (6, 2600, 3, 1, False)])
 def test_random_non_mesh_systems_match_the_oracle(smg, oracle_mod, seed, n, levels, k, hub):
