@@ -3,24 +3,20 @@
 // CSR of L on the device (the weights of the local step are the system's own values), the rest positions and the buffers of an iteration.
 // One iteration: rotations + energy terms (k_arap_rotations), the energy (fixed-order reduction), the right-hand side (k_arap_rhs), one
 // 3-column solve warm-started at the iterate, the new iterate as xyz rows.  All of it is enqueued on the object's stream, which the handle
-// uses too; per iteration the host reads one energy double beside the solve's own history.
+// uses too; per iteration the host reads one energy double beside the solve's own history.  Checks, stream, handle, the cotangent system and
+// the inner solve: smg_mesh_object.hpp; the energy's sum: launch_fixed_sum.
 #include <hip/hip_runtime_api.h>
 
-#include <algorithm>
 #include <cmath>
 #include <memory>
 #include <vector>
 
-#include "smg_bsr3.hpp"
 #include "smg_device.hpp"
-#include "smg_internal.hpp"
+#include "smg_mesh_object.hpp"
 
 using namespace smg;
 
-struct smg_arap {
-    smg_hierarchy* h = nullptr;
-    hipStream_t stream = nullptr;
-    int device = -1;
+struct smg_arap : MeshObject {            // handle[0]: -L of the rest pose, the handle vertices known
     int nV = 0, nh = 0;
     int pcg = 1;                          // the inner solver: 1 smg_solve_pcg (7 - 8 loop entries per solve on C3 against 10 - 11), 0 smg_solve
     double scale = 0.0;                   // s = sqrt(sum_i (sum_j |w_ij| |e_ij|)^2) >= |b|_F for every set of rotations
@@ -28,14 +24,7 @@ struct smg_arap {
     DevBuf<double> w, P0;                 // the values of L (smg_assemble's d_Lval), rest positions (xyz rows)
     DevBuf<double> P, R, eterm, part, E;  // current positions (xyz rows), rotations (9 per vertex), energy terms, their chunk sums, E_t
     DevBuf<double> B, Ua, Ub, hp;         // column-major n x 3: right-hand side, the iterate and the solve's result; handle positions (nh x 3)
-    ~smg_arap()
-    {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (h) smg_hierarchy_destroy(h);
-        rowptr.release(); col.release(); handles.release(); w.release(); P0.release(); P.release(); R.release(); eterm.release();
-        part.release(); E.release(); B.release(); Ua.release(); Ub.release(); hp.release();
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~smg_arap() { quiesce(); }
 };
 
 namespace {
@@ -43,85 +32,53 @@ namespace {
 int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, int nF, const int* handles, int n_handles, smg_arap** out)
 {
     if (out) *out = nullptr;
-    if (!h || !V || !F || !handles || !out || nV <= 0 || nF <= 0) return fail(SMG_ERR_INVALID, "smg_arap_create: bad arguments");
-    if (n_handles < 1) return fail(SMG_ERR_INVALID, "smg_arap_create: n_handles = %d, at least one handle vertex is needed", n_handles);
-    if (h->union_m > 0) return fail(SMG_ERR_INVALID, "smg_arap_create: union handles are not supported");
-    Csr Pv;
-    if (h->bs == 3 || h->block_mode == 3 || (h->n_levels >= 2 && h->lv[1].P_full.nr > 0 && kron3_factor(h->lv[1].P_full, Pv)))
-        return fail(SMG_ERR_INVALID, "smg_arap_create: block (3-DOF) hierarchies are not supported");
-    const int rows = level0_rows(h);
-    if (rows != nV) return fail(SMG_ERR_INVALID, "smg_arap_create: nV = %d, but level 0 of the hierarchy has %d rows", nV, rows);
+    const char* who = "smg_arap_create";
+    if (!h || !V || !F || !handles || !out || nV <= 0 || nF <= 0) return fail(SMG_ERR_INVALID, "%s: bad arguments", who);
+    if (int rc = check_hierarchy(who, h, 1, nV)) return rc;
+    if (int rc = check_mesh(who, V, nV, F, nF, true)) return rc;
+    if (n_handles < 1) return fail(SMG_ERR_INVALID, "%s: n_handles = %d, at least one handle vertex is needed", who, n_handles);
     {
         std::vector<char> seen((size_t)nV, 0);
         for (int r = 0; r < n_handles; r++) {
-            if (handles[r] < 0 || handles[r] >= nV) return fail(SMG_ERR_INVALID, "smg_arap_create: handle %d out of range", handles[r]);
-            if (seen[handles[r]]) return fail(SMG_ERR_INVALID, "smg_arap_create: handle %d is repeated", handles[r]);
+            if (handles[r] < 0 || handles[r] >= nV) return fail(SMG_ERR_INVALID, "%s: handle %d out of range", who, handles[r]);
+            if (seen[handles[r]]) return fail(SMG_ERR_INVALID, "%s: handle %d is repeated", who, handles[r]);
             seen[handles[r]] = 1;
         }
     }
-    if (n_handles >= nV) return fail(SMG_ERR_INVALID, "smg_arap_create: every vertex is a handle: nothing to solve");
-    for (size_t i = 0; i < (size_t)nF * 3; i++)
-        if (F[i] < 0 || F[i] >= nV) return fail(SMG_ERR_INVALID, "smg_arap_create: face index out of range");
-    for (int f = 0; f < nF; f++)
-        if (!(double_area(V, F, f) > 0.0)) return fail(SMG_ERR_INVALID, "smg_arap_create: face %d has zero double area", f);
-    for (size_t i = 0; i < (size_t)nV * 3; i++)
-        if (!std::isfinite(V[i])) return fail(SMG_ERR_INVALID, "smg_arap_create: non-finite vertex coordinate");
-    if (const int nc = components(F, nF, nV); nc != 1)
-        return fail(SMG_ERR_INVALID, "smg_arap_create: the mesh has %d connected components (vertices in no face count)", nc);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SMG_ERR_NO_DEVICE, "smg_arap_create: no HIP device: libsmg has no CPU fallback");
+    if (n_handles >= nV) return fail(SMG_ERR_INVALID, "%s: every vertex is a handle: nothing to solve", who);
 
     std::unique_ptr<smg_arap> a(new smg_arap());
     a->nV = nV; a->nh = n_handles;
-    HIPCHK(hipGetDevice(&a->device));
-    HIPCHK(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
-    a->h = smg_hierarchy_create(h->n_levels);
-    if (!a->h) return fail(SMG_ERR_ALLOC, "smg_arap_create: out of memory");
-    if (int rc = copy_prolongations(h, a->h)) return rc;
-    if (int rc = smg_hierarchy_set_stream(a->h, a->stream)) return rc;
+    if (int rc = a->open(who)) return rc;
+    if (int rc = a->clone(who, h, 0)) return rc;
 
-    // L of the rest pose on the device (smg_assemble): its values stay there as the weights, their negatives are the system
-    smg_assembler* as = nullptr;
-    if (int rc = smg_assembler_create(F, nF, nV, &as)) return rc;
-    struct AsmOwner { smg_assembler* a; ~AsmOwner() { smg_assembler_destroy(a); } } own_a{as};
-    int nnz = 0;
-    smg_assembler_pattern(as, &nnz, nullptr, nullptr);
-    std::vector<int> ptr((size_t)nV + 1), col((size_t)nnz);
-    smg_assembler_pattern(as, nullptr, ptr.data(), col.data());
-    std::vector<double> lval((size_t)nnz);
-    {
-        DevBuf<double> dval;
-        std::vector<double> Vh(V, V + (size_t)nV * 3);
-        HIPCHK(a->P0.upload(Vh));
-        HIPCHK(dval.alloc((size_t)nnz));
-        HIPCHK(a->w.alloc((size_t)nnz));
-        if (int rc = smg_assemble(as, a->P0.p, 0, 0.0, -1.0, dval.p, nullptr, a->w.p, a->stream)) return rc;
-        HIPCHK(hipStreamSynchronize(a->stream));
-        HIPCHK(hipMemcpy(lval.data(), a->w.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
-    }
+    // L of the rest pose on the device: its values stay there as the weights, their negatives are the system
+    HIPCHK(a->P0.upload(std::vector<double>(V, V + (size_t)nV * 3)));
+    CotanSystem S;
+    if (int rc = cotan_system(F, nF, nV, a->P0.p, 0, 0.0, -1.0, a->stream, S, false, &a->w)) return rc;
     double ss = 0.0;
     for (int i = 0; i < nV; i++) {
         double row = 0.0;
-        for (int q = ptr[i]; q < ptr[i + 1]; q++) {
-            const int j = col[q];
+        for (int q = S.ptr[i]; q < S.ptr[i + 1]; q++) {
+            const int j = S.col[q];
             if (j == i) continue;
             const double ex = V[3 * (size_t)i] - V[3 * (size_t)j], ey = V[3 * (size_t)i + 1] - V[3 * (size_t)j + 1], ez = V[3 * (size_t)i + 2] - V[3 * (size_t)j + 2];
-            row += std::fabs(lval[q]) * std::sqrt(ex * ex + ey * ey + ez * ez);
+            row += std::fabs(S.L[q]) * std::sqrt(ex * ex + ey * ey + ez * ez);
         }
         ss += row * row;
     }
     a->scale = std::sqrt(ss);
-    for (double& v : lval) v = -v;
-    if (int rc = smg_precompute(a->h, nV, ptr.data(), col.data(), lval.data(), handles, n_handles)) return rc;
+    for (double& v : S.L) v = -v;
+    if (int rc = smg_precompute(a->handle[0], nV, S.ptr.data(), S.col.data(), S.L.data(), handles, n_handles)) return rc;
 
-    HIPCHK(a->rowptr.upload(ptr));
-    HIPCHK(a->col.upload(col));
+    HIPCHK(a->rowptr.upload(S.ptr));
+    HIPCHK(a->col.upload(S.col));
     HIPCHK(a->handles.upload(std::vector<int>(handles, handles + n_handles)));
     const size_t n = (size_t)nV;
     HIPCHK(a->P.alloc(3 * n));
     HIPCHK(a->R.alloc(9 * n));
     HIPCHK(a->eterm.alloc(n));
-    HIPCHK(a->part.alloc((size_t)arap_groups(nV)));
+    HIPCHK(a->part.alloc((size_t)fixed_sum_groups(nV)));
     HIPCHK(a->B.alloc(3 * n));
     HIPCHK(a->Ua.alloc(3 * n));
     HIPCHK(a->Ub.alloc(3 * n));
@@ -146,7 +103,6 @@ int solve_impl(smg_arap* a, const double* handle_pos, int ld_hp, const double* U
     smg_solve_opts so;
     if (opts) so = *opts;
     else { smg_solve_opts_default(&so); so.max_iter = 50; so.tol = 1e-8 * a->scale; }
-    std::vector<double> his((size_t)std::max(1, so.max_iter));
     HIPCHK(a->E.ensure((size_t)max_iter + 1));
 
     // the start: U0 or the rest pose, the handle rows from handle_pos; as the solve's column-major block (Ua) and as xyz rows (P)
@@ -161,7 +117,7 @@ int solve_impl(smg_arap* a, const double* handle_pos, int ld_hp, const double* U
     for (;; t++) {
         // local step: R_t from U_t, E_t = E(R_t, U_t); the right-hand side is enqueued ahead of the host's look at E_t
         HIPCHK(launch_arap_rotations(n, a->rowptr.p, a->col.p, a->w.p, a->P0.p, a->P.p, a->R.p, a->eterm.p, st));
-        HIPCHK(launch_arap_energy(a->eterm.p, n, a->part.p, a->E.p + t, st));
+        HIPCHK(launch_fixed_sum(a->eterm.p, n, a->part.p, a->E.p + t, st));
         double E_t = 0.0;
         HIPCHK(hipMemcpyAsync(&E_t, a->E.p + t, sizeof(double), hipMemcpyDeviceToHost, st));
         if (t < max_iter) HIPCHK(launch_arap_rhs(n, a->rowptr.p, a->col.p, a->w.p, a->P0.p, a->R.p, a->B.p, n, st));
@@ -175,12 +131,10 @@ int solve_impl(smg_arap* a, const double* handle_pos, int ld_hp, const double* U
         if (t > 0 && rel_tol > 0.0 && E_prev - E_t <= rel_tol * std::fabs(E_prev)) break;
         E_prev = E_t;
         // global step: (-L) U_{t+1} = b, handle rows known, from U_t
-        int nhis = 0, conv = 0;
-        if (int rc = (a->pcg ? smg_solve_pcg : smg_solve)(a->h, a->B.p, n, a->hp.p, nh, a->Ua.p, n, 3, SMG_DEVICE, &so, a->Ub.p, n, his.data(), &nhis, &conv)) {
+        if (int rc = inner_solve(a->handle[0], a->pcg, a->B.p, n, a->hp.p, nh, a->Ua.p, n, 3, so, a->Ub.p, n, cycles ? cycles + t : nullptr)) {
             if (n_iter) *n_iter = t;
             return rc;
         }
-        if (cycles) cycles[t] = nhis;
         std::swap(a->Ua, a->Ub);
         HIPCHK(launch_arap_rows(n, a->Ua.p, n, a->P.p, st));
     }
@@ -202,16 +156,13 @@ extern "C" void smg_arap_destroy(smg_arap* a) { delete a; }
 extern "C" int smg_arap_set_solver(smg_arap* a, int pcg)
 {
     if (!a) return fail(SMG_ERR_INVALID, "null arap object");
-    if (pcg >= 0) a->pcg = pcg ? 1 : 0;
+    latch_solver(a->pcg, pcg);
     return SMG_OK;
 }
 
 extern "C" long long smg_arap_device_bytes(const smg_arap* a)
 {
-    if (!a) return 0;
-    auto B = [](const auto& d) { return (long long)(d.n * sizeof(*d.p)); };
-    return handle_bytes(a->h) + B(a->rowptr) + B(a->col) + B(a->handles) + B(a->w) + B(a->P0) + B(a->P) + B(a->R) + B(a->eterm) + B(a->part) +
-           B(a->E) + B(a->B) + B(a->Ua) + B(a->Ub) + B(a->hp);
+    return a ? device_bytes(*a, a->rowptr, a->col, a->handles, a->w, a->P0, a->P, a->R, a->eterm, a->part, a->E, a->B, a->Ua, a->Ub, a->hp) : 0;
 }
 
 extern "C" int smg_arap_solve(smg_arap* a, const double* handle_pos, int ld_hp, const double* U0, int ld_u0, int memspace, int max_iter,

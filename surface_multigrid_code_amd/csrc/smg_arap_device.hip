@@ -6,12 +6,10 @@
 // (row-major), so a neighbour costs one gather per array.  The solver's blocks are column-major n x 3 (column c of vertex i at c * ld + i);
 // k_arap_rhs writes one, k_arap_rows / k_arap_columns convert between the two as plain streams.
 //
-// Determinism: no atomics.  Every per-vertex sum is one lane's sequential loop in the row's stored order; the energy is reduced over fixed
-// row chunks by a fixed tree and finalised by one wave in a fixed order (the scheme of smg_krylov_device.hip).  Expressions are written
+// Determinism: no atomics.  Every per-vertex sum is one lane's sequential loop in the row's stored order; the energy is the fixed-order sum
+// of the vertices' terms (launch_fixed_sum, smg_fixed_sum_device.hip).  Expressions are written
 // operation by operation (-ffp-contract=off): tests/test_arap_host.py restates them in numpy in the same order.
 #include <hip/hip_runtime.h>
-
-#include <algorithm>
 
 #include "smg_arap_inl.hpp"
 #include "smg_device.hpp"
@@ -21,7 +19,6 @@ namespace smg {
 namespace {
 
 constexpr int ARAP_THREADS = 256;
-constexpr int ARAP_MAX_GROUPS = 1024;
 
 inline int arap_grid(long long n) { return (int)((n + ARAP_THREADS - 1) / ARAP_THREADS); }
 
@@ -133,33 +130,6 @@ __global__ __launch_bounds__(ARAP_THREADS) void k_arap_rhs(int n, const int* __r
     B[2 * (size_t)ldb + i] = bz;
 }
 
-// part[g] = the sum of eterm over row chunk g: rows split over the block's threads with a fixed stride, combined by a fixed halving tree
-__global__ __launch_bounds__(ARAP_THREADS) void k_arap_energy_part(const double* __restrict__ eterm, int n, int groups, double* __restrict__ part)
-{
-    __shared__ double red[ARAP_THREADS];
-    const int g = blockIdx.x, rpc = (n + groups - 1) / groups;
-    const int r0 = g * rpc, r1 = min(n, r0 + rpc);
-    double acc = 0.0;
-    for (int r = r0 + (int)threadIdx.x; r < r1; r += ARAP_THREADS) acc += eterm[r];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int half = ARAP_THREADS / 2; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half) red[threadIdx.x] += red[threadIdx.x + half];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[g] = red[0];
-}
-
-// *E = the sum of the chunks: fixed lane shares, fixed shuffle tree (one wave)
-__global__ __launch_bounds__(64) void k_arap_energy_final(const double* __restrict__ part, int groups, double* __restrict__ E)
-{
-    double v = 0.0;
-    for (int g = threadIdx.x; g < groups; g += 64) v += part[g];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if (threadIdx.x == 0) *E = v;
-}
-
 // P (xyz rows) = U (column-major n x 3)
 __global__ __launch_bounds__(ARAP_THREADS) void k_arap_rows(int n, const double* __restrict__ U, int ldu, double* __restrict__ P)
 {
@@ -190,12 +160,6 @@ __global__ __launch_bounds__(ARAP_THREADS) void k_arap_set_handles(int nh, const
     U[(size_t)c * ldu + handles[r]] = hp[(size_t)c * ldh + r];
 }
 
-int arap_groups(int n)
-{
-    const long want = ((long)n + (long)ARAP_THREADS * 8 - 1) / ((long)ARAP_THREADS * 8);     // at least 8 rows per thread
-    return (int)std::max(1L, std::min(want, (long)ARAP_MAX_GROUPS));
-}
-
 hipError_t launch_arap_covariance(int n, const int* rowptr, const int* col, const double* w, const double* P0, const double* P, double* S, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
@@ -223,15 +187,6 @@ hipError_t launch_arap_rhs(int n, const int* rowptr, const int* col, const doubl
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_arap_rhs, dim3(arap_grid(n)), dim3(ARAP_THREADS), 0, st, n, rowptr, col, w, P0, R, B, ldb);
-    return hipGetLastError();
-}
-
-hipError_t launch_arap_energy(const double* eterm, int n, double* part, double* E, hipStream_t st)
-{
-    if (n <= 0) return hipSuccess;
-    const int groups = arap_groups(n);
-    hipLaunchKernelGGL(k_arap_energy_part, dim3(groups), dim3(ARAP_THREADS), 0, st, eterm, n, groups, part);
-    hipLaunchKernelGGL(k_arap_energy_final, dim3(1), dim3(64), 0, st, part, groups, E);
     return hipGetLastError();
 }
 

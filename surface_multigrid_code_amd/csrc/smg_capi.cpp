@@ -41,15 +41,13 @@ int smg::fail(int code, const char* fmt, ...)
 extern "C" const char* smg_last_error(void) { return g_err.c_str(); }
 extern "C" int smg_version(void) { return SMG_VERSION; }
 extern "C" long long smg_device_bytes_live(void) { return (long long)smg::devbuf_live_bytes().load(); }
-// What one handle holds in HBM, by purpose (memory budget reporting; bench.py's device_bytes, tools/mem_probe.py): text into buf, one "name bytes" line each.
-extern "C" int smg_debug_device_bytes(const smg_hierarchy* h, char* buf, int cap)
+// What one handle holds in HBM, by purpose: the entries that are not zero
+std::vector<std::pair<std::string, long long>> smg::device_byte_entries(const smg_hierarchy* h)
 {
-    if (!h || !buf || cap < 1) return SMG_ERR_INVALID;
-    std::string out;
+    std::vector<std::pair<std::string, long long>> out;
     auto B = [](const auto& d) { return (long long)(d.n * sizeof(*d.p)); };
     auto sell = [&](const smg::SellBuf& S) { return B(S.slice_row) + B(S.slice_off) + B(S.slice_w) + B(S.col) + B(S.order) + B(S.val) + B(S.diag_slot) + B(S.long_row) + B(S.long_ptr) + B(S.long_col) + B(S.long_val) + B(S.long_valf); };
-    long long tot = 0;
-    auto line = [&](const std::string& nm, long long v) { if (v) { out += nm + " " + std::to_string(v) + "\n"; tot += v; } };
+    auto line = [&](const std::string& nm, long long v) { if (v) out.emplace_back(nm, v); };
     for (int lv = 0; lv < h->n_levels; lv++) {
         const smg::Level& L = h->lv[lv];
         const std::string p = "level" + std::to_string(lv) + ".";
@@ -78,6 +76,18 @@ extern "C" int smg_debug_device_bytes(const smg_hierarchy* h, char* buf, int cap
     line("eigs", B(h->eig_x[0]) + B(h->eig_x[1]) + B(h->eig_ax[0]) + B(h->eig_ax[1]) + B(h->eig_p[0]) + B(h->eig_p[1]) + B(h->eig_ap[0]) + B(h->eig_ap[1]) +
                  B(h->eig_w) + B(h->eig_aw) + B(h->eig_mass) + B(h->eig_part) + B(h->eig_small) + B(h->eig_stage));
     line("solve_state", B(h->d_ctrl) + B(h->d_rhis) + B(h->d_partials) + B(h->d_lam) + B(h->d_stage_rhs) + B(h->d_stage_z) + B(h->d_stage_kv) + B(h->d_tmp_cm) + B(h->d_zsave));
+    return out;
+}
+// Memory budget reporting (bench.py's device_bytes, tools/mem_probe.py): text into buf, one "name bytes" line per entry, then "total bytes".
+extern "C" int smg_debug_device_bytes(const smg_hierarchy* h, char* buf, int cap)
+{
+    if (!h || !buf || cap < 1) return SMG_ERR_INVALID;
+    std::string out;
+    long long tot = 0;
+    for (const auto& e : device_byte_entries(h)) {
+        out += e.first + " " + std::to_string(e.second) + "\n";
+        tot += e.second;
+    }
     out += "total " + std::to_string(tot) + "\n";
     std::snprintf(buf, (size_t)cap, "%s", out.c_str());
     return SMG_OK;

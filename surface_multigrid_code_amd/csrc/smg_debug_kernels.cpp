@@ -9,6 +9,8 @@
 
 #include "smg_device.hpp"
 #include "smg_internal.hpp"
+#include "smg_membrane_inl.hpp"
+#include "smg_mesh_object.hpp"
 
 using namespace smg;
 
@@ -353,7 +355,7 @@ extern "C" int smg_debug_arap(int op, int n, const int* rowptr, const int* col, 
         if (op >= SMG_ARAP_RHS) HIPCHK(X.add(R_in, nullptr, 9 * vec, &dR));
         HIPCHK(X.add(out, out, out_bytes, &dout));
         if (op == SMG_ARAP_ROTATIONS || op == SMG_ARAP_ENERGY) HIPCHK(X.add(nullptr, nullptr, vec, &dterm));
-        if (op == SMG_ARAP_ENERGY) HIPCHK(X.add(nullptr, nullptr, (size_t)arap_groups(n) * sizeof(double), &dpart));
+        if (op == SMG_ARAP_ENERGY) HIPCHK(X.add(nullptr, nullptr, (size_t)fixed_sum_groups(n) * sizeof(double), &dpart));
         hipStream_t st = X.stream();
         switch (op) {
             case SMG_ARAP_COVARIANCE: HIPCHK(launch_arap_covariance(n, dptr, dcol, dw, dP0, dP, dout, st)); break;
@@ -362,7 +364,7 @@ extern "C" int smg_debug_arap(int op, int n, const int* rowptr, const int* col, 
             case SMG_ARAP_VERTEX_ENERGY: HIPCHK(launch_arap_vertex_energy(n, dptr, dcol, dw, dP0, dP, dR, dout, st)); break;
             default:
                 HIPCHK(launch_arap_vertex_energy(n, dptr, dcol, dw, dP0, dP, dR, dterm, st));
-                HIPCHK(launch_arap_energy(dterm, n, dpart, dout, st));
+                HIPCHK(launch_fixed_sum(dterm, n, dpart, dout, st));
                 break;
         }
         int bad = 0;
@@ -379,10 +381,10 @@ extern "C" int smg_debug_membrane(int op, int nV, int nF, const int* F, const do
         if (op < SMG_MEM_REST || op > SMG_MEM_OBJECTIVE || nV < 1 || nF < 1 || !F || !p || !out) return fail(SMG_ERR_INVALID, "smg_debug_membrane: bad arguments");
         const bool needs_rest = op <= SMG_MEM_ENERGY || op == SMG_MEM_OBJECTIVE, needs_pose = (op >= SMG_MEM_FACES_RAW && op <= SMG_MEM_PRESSURE) || op == SMG_MEM_OBJECTIVE;
         if ((needs_rest && !V0) || (needs_pose && !P) || (op >= SMG_MEM_MATRIX && !in)) return fail(SMG_ERR_INVALID, "smg_debug_membrane: op %d misses an operand", op);
-        for (size_t i = 0; i < (size_t)nF * 3; i++)
-            if (F[i] < 0 || F[i] >= nV) return fail(SMG_ERR_INVALID, "smg_debug_membrane: face index out of range");
+        if (int rc = check_faces("smg_debug_membrane", F, nF, nV)) return rc;
         if (int rc = need_device("smg_debug_membrane")) return rc;
-        const double alpha = p->young * p->poisson / (1.0 - p->poisson * p->poisson), beta = p->young / 2.0 / (1.0 + p->poisson);
+        double alpha, beta;
+        lame(*p, alpha, beta);
         std::vector<int> Fv(F, F + 3 * (size_t)nF), mp, mi;
         vertex_corner_lists(Fv, nV, mp, mi);
         MembraneLists L;
@@ -439,10 +441,10 @@ extern "C" int smg_debug_membrane(int op, int nV, int nF, const int* F, const do
             default: {
                 const double *qdot = din + nv, *dx = qdot + n3, *qdot0 = dx + n3, *fext = qdot0 + n3;
                 double* terms = dout + 2 * n3;
-                HIPCHK(X.add(nullptr, nullptr, (size_t)arap_groups(nF + nV) * D, &dpart));
+                HIPCHK(X.add(nullptr, nullptr, (size_t)fixed_sum_groups(nF + nV) * D, &dpart));
                 HIPCHK(launch_membrane_trial(nV, qdot, dx, in[nv + 4 * n3], qdot0, dP, fext, din, p->mass_scale, p->dt, dout, dout + n3, terms + nf, st));
                 HIPCHK(launch_membrane_faces(0, nF, dF, dout + n3, drest, alpha, beta, p->eig_floor, p->eig_value, terms, nullptr, nullptr, st));
-                HIPCHK(launch_arap_energy(terms, nF + nV, dpart, terms + nf + nv, st));
+                HIPCHK(launch_fixed_sum(terms, nF + nV, dpart, terms + nf + nv, st));
                 break;
             }
         }

@@ -409,13 +409,15 @@ hipError_t launch_arap_vertex_energy(int n, const int* rowptr, const int* col, c
                                      double* eterm, hipStream_t st);
 // B[c * ldb + i] = (sum_j (w_ij / 2) (R_i + R_j) e_ij)_c
 hipError_t launch_arap_rhs(int n, const int* rowptr, const int* col, const double* w, const double* P0, const double* R, double* B, int ldb, hipStream_t st);
-// *E = sum_i eterm[i] by fixed row chunks (part: arap_groups(n) doubles of scratch) and a fixed-order finalize
-int arap_groups(int n);
-hipError_t launch_arap_energy(const double* eterm, int n, double* part, double* E, hipStream_t st);
 // P = U and U = P between xyz rows and a column-major block; the handle rows of U from hp (nh x 3 column-major, leading dimension ldh)
 hipError_t launch_arap_rows(int n, const double* U, int ldu, double* P, hipStream_t st);
 hipError_t launch_arap_columns(int n, const double* P, double* U, int ldu, hipStream_t st);
 hipError_t launch_arap_set_handles(int nh, const int* handles, const double* hp, int ldh, double* U, int ldu, hipStream_t st);
+
+// the fixed-order sum (smg_fixed_sum_device.hip): *sum = sum_i term[i] by fixed row chunks (part: fixed_sum_groups(n) doubles of scratch) and a
+// fixed-order finalize; the bits depend on n and the terms alone ---------------------------------------------------------------------------
+int fixed_sum_groups(int n);
+hipError_t launch_fixed_sum(const double* term, int n, double* part, double* sum, hipStream_t st);
 
 // neo-Hookean membrane time step (smg_membrane_device.hip).  Vectors over the vertices are xyz rows (entry 3 v + l); per-face arrays are
 // face-major planes (plane e at [e * nF + f]); m_ptr / m_idx: the corner lists t = 3 f + j of every vertex, faces ascending -----------------

@@ -2,29 +2,21 @@
 // The object owns two handles built from the caller's prolongations -- the heat handle (M - tL) and the Poisson handle (-L, vertex 0 pinned)
 // -- and the geometry the three kernels of a query read (csrc/smg_geodesics_device.hip).  A query: scatter the indicator block, heat solve,
 // the fused gradient / normalise / divergence kernel, Poisson solve, shift by the sources' mean.  All of it is enqueued on one stream that
-// both handles use; the only host synchronisations are the solves' own.
+// both handles use; the only host synchronisations are the solves' own.  Checks, stream, handles and the cotangent system: smg_mesh_object.hpp.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <memory>
-#include <numeric>
-#include <string>
 #include <vector>
 
-#include "smg_bsr3.hpp"
 #include "smg_device.hpp"
-#include "smg_internal.hpp"
+#include "smg_mesh_object.hpp"
 
 using namespace smg;
 
-struct smg_geodesics {
-    smg_hierarchy* heat = nullptr;
-    smg_hierarchy* pois = nullptr;
-    hipStream_t stream = nullptr;
-    int device = -1;
+struct smg_geodesics : MeshObject {
+    enum { HEAT = 0, POIS = 1 };          // handle[]: M - tL, and -L with vertex 0 pinned
     int nV = 0, nF = 0, voronoi = 0;
     double t = 0.0, area = 0.0;
     int heat_pcg = 1, pois_pcg = 1;
@@ -34,73 +26,8 @@ struct smg_geodesics {
     DevBuf<double> B, U, Z, mean;         // n x kcap blocks: heat RHS / Poisson RHS / staging of D, heat solution / phi, zeros; k means
     int kcap = 0;
     std::vector<int> h_src_ptr, h_src;    // host side of the source lists (alive until the next query: the uploads are asynchronous)
-    ~smg_geodesics()
-    {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (pois) smg_hierarchy_destroy(pois);
-        if (heat) smg_hierarchy_destroy(heat);
-        F.release(); m_ptr.release(); m_idx.release(); W.release(); Af.release(); d_src_ptr.release(); d_src.release();
-        B.release(); U.release(); Z.release(); mean.release();
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~smg_geodesics() { quiesce(); }
 };
-
-// ---- what every object built on a mesh and a caller's hierarchy checks and copies (smg_internal.hpp; smg_arap.cpp uses them too) ----
-namespace smg {
-
-// twice the area of face f, the expression of k_face_terms / k_geo_basis
-double double_area(const double* V, const int* F, int f)
-{
-    const double* a = V + 3 * (size_t)F[3 * (size_t)f];
-    const double* b = V + 3 * (size_t)F[3 * (size_t)f + 1];
-    const double* c = V + 3 * (size_t)F[3 * (size_t)f + 2];
-    const double ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
-    const double vx = c[0] - a[0], vy = c[1] - a[1], vz = c[2] - a[2];
-    const double wx = uy * vz - uz * vy, wy = uz * vx - ux * vz, wz = ux * vy - uy * vx;
-    return std::sqrt(wx * wx + wy * wy + wz * wz);
-}
-
-// number of connected components of the vertex graph of F (a vertex in no face is a component of its own)
-int components(const int* F, int nF, int nV)
-{
-    std::vector<int> parent(nV);
-    std::iota(parent.begin(), parent.end(), 0);
-    auto find = [&](int x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
-    for (size_t f = 0; f < (size_t)nF; f++)
-        for (int c = 1; c < 3; c++) {
-            const int a = find(F[3 * f]), b = find(F[3 * f + c]);
-            if (a != b) parent[std::max(a, b)] = std::min(a, b);
-        }
-    int n = 0;
-    for (int v = 0; v < nV; v++) n += find(v) == v ? 1 : 0;
-    return n;
-}
-
-// rows of level 0 of a hierarchy whose prolongations are set (-1: none set)
-int level0_rows(const smg_hierarchy* h)
-{
-    if (h->n_levels >= 2) return h->lv[1].P_full.nr > 0 ? h->lv[1].P_full.nr : -1;
-    return h->lv[0].V.empty() ? -1 : (int)(h->lv[0].V.size() / 3);
-}
-
-long long handle_bytes(const smg_hierarchy* h)
-{
-    std::vector<char> buf(1 << 16);
-    if (smg_debug_device_bytes(h, buf.data(), (int)buf.size()) != SMG_OK) return 0;
-    const char* tot = std::strstr(buf.data(), "total ");
-    return tot ? std::atoll(tot + 6) : 0;
-}
-
-int copy_prolongations(const smg_hierarchy* src, smg_hierarchy* dst)
-{
-    for (int lv = 1; lv < src->n_levels; lv++) {
-        Csr P = src->lv[lv].P_full;
-        if (int rc = set_prolong(dst, lv, std::move(P))) return rc;
-    }
-    return SMG_OK;
-}
-
-}  // namespace smg
 
 namespace {
 
@@ -108,28 +35,11 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
 {
     if (!h || !V || !F || !out || nV <= 0 || nF <= 0) return fail(SMG_ERR_INVALID, "smg_geodesics_create: bad arguments");
     *out = nullptr;
-    if (!std::isfinite(t) || t < 0.0) return fail(SMG_ERR_INVALID, "smg_geodesics_create: t must be finite and >= 0 (0: the default)");
-    if (h->union_m > 0) return fail(SMG_ERR_INVALID, "smg_geodesics_create: union handles are not supported");
-    Csr Pv;
-    if (h->bs == 3 || h->block_mode == 3 || (h->n_levels >= 2 && h->lv[1].P_full.nr > 0 && kron3_factor(h->lv[1].P_full, Pv)))
-        return fail(SMG_ERR_INVALID, "smg_geodesics_create: block (3-DOF) hierarchies are not supported");
-    const int rows = level0_rows(h);
-    if (rows != nV) return fail(SMG_ERR_INVALID, "smg_geodesics_create: nV = %d, but level 0 of the hierarchy has %d rows", nV, rows);
-    for (size_t i = 0; i < (size_t)nF * 3; i++)
-        if (F[i] < 0 || F[i] >= nV) return fail(SMG_ERR_INVALID, "smg_geodesics_create: face index out of range");
+    const char* who = "smg_geodesics_create";
     double area2 = 0.0;
-    for (int f = 0; f < nF; f++) {
-        const double dA = double_area(V, F, f);
-        if (!(dA > 0.0)) return fail(SMG_ERR_INVALID, "smg_geodesics_create: face %d has zero double area", f);
-        area2 += dA;
-    }
-    for (size_t i = 0; i < (size_t)nV * 3; i++)
-        if (!std::isfinite(V[i])) return fail(SMG_ERR_INVALID, "smg_geodesics_create: non-finite vertex coordinate");
-    if (const int nc = components(F, nF, nV); nc != 1)
-        return fail(SMG_ERR_INVALID, "smg_geodesics_create: the mesh has %d connected components (vertices in no face count)", nc);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SMG_ERR_NO_DEVICE, "smg_geodesics_create: no HIP device: libsmg has no CPU fallback");
-
+    if (int rc = check_hierarchy(who, h, 1, nV)) return rc;
+    if (int rc = check_mesh(who, V, nV, F, nF, true, &area2)) return rc;
+    if (!std::isfinite(t) || t < 0.0) return fail(SMG_ERR_INVALID, "%s: t must be finite and >= 0 (0: the default)", who);
     if (t == 0.0) {   // default: (bounding-box diagonal / 12)^2
         double lo[3], hi[3];
         for (int d = 0; d < 3; d++) lo[d] = hi[d] = V[d];
@@ -141,48 +51,27 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
 
     std::unique_ptr<smg_geodesics> g(new smg_geodesics());
     g->nV = nV; g->nF = nF; g->voronoi = voronoi ? 1 : 0; g->t = t; g->area = 0.5 * area2;
-    HIPCHK(hipGetDevice(&g->device));
-    HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    g->heat = smg_hierarchy_create(h->n_levels);
-    g->pois = smg_hierarchy_create(h->n_levels);
-    if (!g->heat || !g->pois) return fail(SMG_ERR_ALLOC, "smg_geodesics_create: out of memory");
-    if (int rc = copy_prolongations(h, g->heat)) return rc;
-    if (int rc = copy_prolongations(h, g->pois)) return rc;
-    if (int rc = smg_hierarchy_set_stream(g->heat, g->stream)) return rc;
-    if (int rc = smg_hierarchy_set_stream(g->pois, g->stream)) return rc;
+    if (int rc = g->open(who)) return rc;
+    if (int rc = g->clone(who, h, g->HEAT)) return rc;
+    if (int rc = g->clone(who, h, g->POIS)) return rc;
 
-    // M - tL and L on the device (smg_assemble), then the two precomputes
-    smg_assembler* a = nullptr;
-    if (int rc = smg_assembler_create(F, nF, nV, &a)) return rc;
-    struct AsmOwner { smg_assembler* a; ~AsmOwner() { smg_assembler_destroy(a); } } own_a{a};
-    int nnz = 0;
-    smg_assembler_pattern(a, &nnz, nullptr, nullptr);
-    std::vector<int> ptr((size_t)nV + 1), col((size_t)nnz);
-    smg_assembler_pattern(a, nullptr, ptr.data(), col.data());
-    std::vector<double> hval((size_t)nnz), lval((size_t)nnz);
-    {
-        DevBuf<double> dV, dval, dL;
-        std::vector<double> Vh(V, V + (size_t)nV * 3);
-        HIPCHK(dV.upload(Vh));
-        HIPCHK(dval.alloc((size_t)nnz));
-        HIPCHK(dL.alloc((size_t)nnz));
-        if (int rc = smg_assemble(a, dV.p, g->voronoi, 1.0, -t, dval.p, nullptr, dL.p, g->stream)) return rc;
-        std::vector<int> Fh(F, F + (size_t)nF * 3), mp, mi;
-        vertex_corner_lists(Fh, nV, mp, mi);
-        HIPCHK(g->F.upload(Fh));
-        HIPCHK(g->m_ptr.upload(mp));
-        HIPCHK(g->m_idx.upload(mi));
-        HIPCHK(g->W.alloc((size_t)nF * 9));
-        HIPCHK(g->Af.alloc((size_t)nF));
-        HIPCHK(launch_geo_basis(dV.p, g->F.p, nF, g->W.p, g->Af.p, g->stream));
-        HIPCHK(hipStreamSynchronize(g->stream));
-        HIPCHK(hipMemcpy(hval.data(), dval.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(lval.data(), dL.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    for (double& v : lval) v = -v;
-    if (int rc = smg_precompute(g->heat, nV, ptr.data(), col.data(), hval.data(), nullptr, 0)) return rc;
+    // the geometry of a query, then M - tL and L on the device and the two precomputes
+    DevBuf<double> dV;
+    HIPCHK(dV.upload(std::vector<double>(V, V + (size_t)nV * 3)));
+    std::vector<int> Fh(F, F + (size_t)nF * 3), mp, mi;
+    vertex_corner_lists(Fh, nV, mp, mi);
+    HIPCHK(g->F.upload(Fh));
+    HIPCHK(g->m_ptr.upload(mp));
+    HIPCHK(g->m_idx.upload(mi));
+    HIPCHK(g->W.alloc((size_t)nF * 9));
+    HIPCHK(g->Af.alloc((size_t)nF));
+    HIPCHK(launch_geo_basis(dV.p, g->F.p, nF, g->W.p, g->Af.p, g->stream));
+    CotanSystem S;
+    if (int rc = cotan_system(F, nF, nV, dV.p, g->voronoi, 1.0, -t, g->stream, S, true)) return rc;
+    for (double& v : S.L) v = -v;
+    if (int rc = smg_precompute(g->handle[g->HEAT], nV, S.ptr.data(), S.col.data(), S.val.data(), nullptr, 0)) return rc;
     const int pin = 0;
-    if (int rc = smg_precompute(g->pois, nV, ptr.data(), col.data(), lval.data(), &pin, 1)) return rc;
+    if (int rc = smg_precompute(g->handle[g->POIS], nV, S.ptr.data(), S.col.data(), S.L.data(), &pin, 1)) return rc;
     *out = g.release();
     return SMG_OK;
 }
@@ -222,20 +111,15 @@ int solve_impl(smg_geodesics* g, int k, const int* src_ptr, const int* src, int 
     else { smg_solve_opts_default(&ho); ho.max_iter = 100; ho.tol = 1e-11 * std::sqrt((double)total); }
     if (poisson_opts) po = *poisson_opts;
     else { smg_solve_opts_default(&po); po.max_iter = 100; po.tol = 1e-11 * std::sqrt((double)k * g->area); }
-    std::vector<double> his((size_t)std::max(1, std::max(ho.max_iter, po.max_iter)));
-    int nh = 0, conv = 0, rc = SMG_OK;
+    smg_hierarchy *heat = g->handle[g->HEAT], *pois = g->handle[g->POIS];
 
     // 1. heat: (M - tL) U = indicator block B
     HIPCHK(launch_geo_scatter(n, k, g->d_src_ptr.p, g->d_src.p, g->B.p, n, g->stream));
-    rc = (g->heat_pcg ? smg_solve_pcg : smg_solve)(g->heat, g->B.p, n, nullptr, 0, g->Z.p, n, k, SMG_DEVICE, &ho, g->U.p, n, his.data(), &nh, &conv);
-    if (rc) return rc;
-    if (cycles) cycles[0] = nh;
+    if (int rc = inner_solve(heat, g->heat_pcg, g->B.p, n, nullptr, 0, g->Z.p, n, k, ho, g->U.p, n, cycles)) return rc;
     // 2. B = -div X, X = -grad U / |grad U|
     HIPCHK(launch_geo_divergence(n, k, g->F.p, g->W.p, g->Af.p, g->m_ptr.p, g->m_idx.p, g->U.p, n, g->B.p, n, g->stream));
     // 3. Poisson: -L phi = B, phi_0 = 0 (known values: the zero block read with leading dimension 1)
-    rc = (g->pois_pcg ? smg_solve_pcg : smg_solve)(g->pois, g->B.p, n, g->Z.p, 1, g->Z.p, n, k, SMG_DEVICE, &po, g->U.p, n, his.data(), &nh, &conv);
-    if (rc) return rc;
-    if (cycles) cycles[1] = nh;
+    if (int rc = inner_solve(pois, g->pois_pcg, g->B.p, n, g->Z.p, 1, g->Z.p, n, k, po, g->U.p, n, cycles ? cycles + 1 : nullptr)) return rc;
     // 4. D = phi - mean over the sources
     if (memspace == SMG_DEVICE) {
         HIPCHK(launch_geo_shift(n, k, g->d_src_ptr.p, g->d_src.p, g->U.p, n, g->mean.p, D, ld_d, g->stream));
@@ -263,17 +147,14 @@ extern "C" double smg_geodesics_time(const smg_geodesics* g) { return g ? g->t :
 extern "C" int smg_geodesics_set_solver(smg_geodesics* g, int heat_pcg, int poisson_pcg)
 {
     if (!g) return fail(SMG_ERR_INVALID, "null geodesics object");
-    if (heat_pcg >= 0) g->heat_pcg = heat_pcg ? 1 : 0;
-    if (poisson_pcg >= 0) g->pois_pcg = poisson_pcg ? 1 : 0;
+    latch_solver(g->heat_pcg, heat_pcg);
+    latch_solver(g->pois_pcg, poisson_pcg);
     return SMG_OK;
 }
 
 extern "C" long long smg_geodesics_device_bytes(const smg_geodesics* g)
 {
-    if (!g) return 0;
-    auto B = [](const auto& d) { return (long long)(d.n * sizeof(*d.p)); };
-    return handle_bytes(g->heat) + handle_bytes(g->pois) + B(g->F) + B(g->m_ptr) + B(g->m_idx) + B(g->W) + B(g->Af) + B(g->d_src_ptr) +
-           B(g->d_src) + B(g->B) + B(g->U) + B(g->Z) + B(g->mean);
+    return g ? device_bytes(*g, g->F, g->m_ptr, g->m_idx, g->W, g->Af, g->d_src_ptr, g->d_src, g->B, g->U, g->Z, g->mean) : 0;
 }
 
 extern "C" int smg_geodesics_solve(smg_geodesics* g, int k, const int* src_ptr, const int* src, int memspace, const smg_solve_opts* heat_opts,

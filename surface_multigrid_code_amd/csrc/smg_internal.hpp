@@ -5,6 +5,7 @@
 //   smg_solve.cpp       min_quad_with_fixed_mg_solve: the steps of the solve loops and their graph cache, outer loops (stationary, split-phase, sharded, PCG)
 //   smg_sweep_plans.cpp the plan-based Gauss-Seidel sweeps: which one a level uses, building, value refresh, introspection, self-checks
 //   smg_hierarchy_io.cpp mg_precompute / mg_precompute_block builders, point queries, .smgh files
+// The objects built on a mesh and a caller's hierarchy (smg_geodesics.cpp, smg_arap.cpp, smg_membrane.cpp) share smg_mesh_object.hpp, not this file.
 // Nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -15,6 +16,8 @@
 #include <exception>
 #include <new>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "../../include/smg.h"
 #include "smg_hier.hpp"
@@ -114,18 +117,8 @@ struct ProfGuard {
 const char* check_compressed(int n_major, int n_minor, const int* ptr, const int* idx);
 int set_prolong(smg_hierarchy* h, int lv, Csr&& P);   // mg[lv].P = PT^T = P_full = P  (reference src/mg_precompute.cpp:74-76)
 Mesh wrap_mesh(const double* V, int nV, const int* F, int nF);
-
-// ---- objects built on a mesh and a caller's hierarchy: smg_geodesics, smg_arap (helpers in smg_geodesics.cpp) --------------------------
-double double_area(const double* V, const int* F, int f);          // twice the area of face f
-int components(const int* F, int nF, int nV);                      // connected components of the vertex graph (a vertex in no face is one)
-int level0_rows(const smg_hierarchy* h);                           // rows of level 0 of a hierarchy whose prolongations are set (-1: none set)
-long long handle_bytes(const smg_hierarchy* h);                    // the "total" of smg_debug_device_bytes
-int copy_prolongations(const smg_hierarchy* src, smg_hierarchy* dst);
-
-// ---- the membrane's lists (smg_membrane.cpp): the block CSR of (adjacency + I), columns ascending, the block row of every block, and per block
-// the face sub-blocks 9 f + 3 a + b that k_membrane_matrix sums, faces ascending
-struct MembraneLists { std::vector<int> bptr, bcol, brow, c_ptr, c_src; };
-void membrane_lists(const int* F, int nF, int nV, MembraneLists& L);
+// what the handle holds in HBM, by purpose: the non-zero (name, bytes) entries that smg_debug_device_bytes prints and totals
+std::vector<std::pair<std::string, long long>> device_byte_entries(const smg_hierarchy* h);
 
 // ---- precompute (smg_precompute.cpp) ------------------------------------------------------------------------------------------------
 int spectral_bounds(smg_hierarchy* h);          // Gershgorin bounds of D^-1 A on every smoothed level (Chebyshev-Jacobi)

@@ -5,7 +5,8 @@
 // (pos, qdot) with the buffers of a step.  A Newton iteration: per-face energy / gradient / fixed Hessian (k_membrane_faces), H in the
 // caller-order CSR (k_membrane_matrix), b (k_membrane_gradient), the value-only re-precompute, one solve from zero, b . dx, and the
 // backtracking line search, which per trial costs k_membrane_trial + the energy-only face kernel + the fixed-order reduction and one double
-// read by the host.  All of it is enqueued on the object's stream, which the handle uses too.
+// read by the host.  All of it is enqueued on the object's stream, which the handle uses too.  Checks, stream, handle and the inner solve:
+// smg_mesh_object.hpp; the lists and lame(): smg_membrane_inl.hpp; the objective's sum: launch_fixed_sum.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -13,10 +14,9 @@
 #include <memory>
 #include <vector>
 
-#include "smg_bsr3.hpp"
 #include "smg_device.hpp"
-#include "smg_internal.hpp"
 #include "smg_membrane_inl.hpp"
+#include "smg_mesh_object.hpp"
 
 using namespace smg;
 
@@ -51,10 +51,7 @@ void membrane_lists(const int* F, int nF, int nV, MembraneLists& L)
 
 }  // namespace smg
 
-struct smg_membrane {
-    smg_hierarchy* h = nullptr;
-    hipStream_t stream = nullptr;
-    int device = -1;
+struct smg_membrane : MeshObject {             // handle[0]: H = M + dt^2 K, block
     int nV = 0, nF = 0, nB = 0;
     int pcg = 0;                               // the inner solver: 0 smg_solve (the reference's loop), 1 smg_solve_pcg
     smg_membrane_params p;
@@ -64,16 +61,7 @@ struct smg_membrane {
     DevBuf<double> pos, qdot, posT, qdotT, pos0, qdot0;   // the state, the line search's trial, the state at the start of the step
     DevBuf<double> fext, b, dx, zero, Hval;    // pressure force, right-hand side, Newton direction, the solve's start, H in the caller's CSR order
     DevBuf<double> G, H, Qn, terms, part, E;   // per-face planes (9, 45, 6), the objective's terms (nF + nV), their chunk sums, the reduced values
-    ~smg_membrane()
-    {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (h) smg_hierarchy_destroy(h);
-        F.release(); m_ptr.release(); m_idx.release(); brow.release(); bcol.release(); bptr.release(); c_ptr.release(); c_src.release();
-        V0.release(); rest.release(); mass0.release(); pos.release(); qdot.release(); posT.release(); qdotT.release(); pos0.release();
-        qdot0.release(); fext.release(); b.release(); dx.release(); zero.release(); Hval.release(); G.release(); H.release(); Qn.release();
-        terms.release(); part.release(); E.release();
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~smg_membrane() { quiesce(); }
 };
 
 namespace {
@@ -91,27 +79,6 @@ const char* bad_params(const smg_membrane_params& p)
     if (!finite(p.pressure) || !finite(p.eig_floor) || !finite(p.ls_c)) return "a parameter is not finite";
     if (!(p.ls_shrink > 0.0 && p.ls_shrink < 1.0) || !(p.ls_min_alpha > 0.0)) return "ls_shrink must lie in (0, 1) and ls_min_alpha be > 0";
     return nullptr;
-}
-
-void lame(const smg_membrane_params& p, double& alpha, double& beta)
-{
-    alpha = p.young * p.poisson / (1.0 - p.poisson * p.poisson);
-    beta = p.young / 2.0 / (1.0 + p.poisson);
-}
-
-// the checks on the mesh that smg_geodesics_create and smg_arap_create make too
-int check_mesh(const char* who, const double* V, int nV, const int* F, int nF, bool connected)
-{
-    for (size_t i = 0; i < (size_t)nF * 3; i++)
-        if (F[i] < 0 || F[i] >= nV) return fail(SMG_ERR_INVALID, "%s: face index out of range", who);
-    for (int f = 0; f < nF; f++)
-        if (!(double_area(V, F, f) > 0.0)) return fail(SMG_ERR_INVALID, "%s: face %d has zero double area", who, f);
-    for (size_t i = 0; i < (size_t)nV * 3; i++)
-        if (!std::isfinite(V[i])) return fail(SMG_ERR_INVALID, "%s: non-finite vertex coordinate", who);
-    if (connected)
-        if (const int nc = components(F, nF, nV); nc != 1)
-            return fail(SMG_ERR_INVALID, "%s: the mesh has %d connected components (vertices in no face count)", who, nc);
-    return SMG_OK;
 }
 
 // W, G, H' at P into the object's planes (W in terms[0 .. nF)), then H in the CSR order and b
@@ -135,7 +102,7 @@ int objective(smg_membrane* m, const double* dx, double step, double* f)
     HIPCHK(launch_membrane_trial(m->nV, m->qdot.p, dx, step, m->qdot0.p, m->pos0.p, m->fext.p, m->mass0.p, p.mass_scale, p.dt, m->qdotT.p, m->posT.p,
                                  m->terms.p + m->nF, st));
     HIPCHK(launch_membrane_faces(0, m->nF, m->F.p, m->posT.p, m->rest.p, m->alpha, m->beta, p.eig_floor, p.eig_value, m->terms.p, nullptr, nullptr, st));
-    HIPCHK(launch_arap_energy(m->terms.p, m->nF + m->nV, m->part.p, m->E.p, st));
+    HIPCHK(launch_fixed_sum(m->terms.p, m->nF + m->nV, m->part.p, m->E.p, st));
     HIPCHK(hipMemcpyAsync(f, m->E.p, sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return SMG_OK;
@@ -144,30 +111,18 @@ int objective(smg_membrane* m, const double* dx, double step, double* f)
 int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, int nF, const smg_membrane_params* pp, smg_membrane** out)
 {
     if (out) *out = nullptr;
-    if (!h || !V || !F || !pp || !out || nV <= 0 || nF <= 0) return fail(SMG_ERR_INVALID, "smg_membrane_create: bad arguments");
-    if (const char* why = bad_params(*pp)) return fail(SMG_ERR_INVALID, "smg_membrane_create: %s", why);
-    if (h->union_m > 0) return fail(SMG_ERR_INVALID, "smg_membrane_create: union handles are not supported");
-    const int rows = level0_rows(h);
-    Csr Pv;
-    if (h->block_mode == 0 || h->n_levels < 2 || rows <= 0 || !kron3_factor(h->lv[1].P_full, Pv))
-        return fail(SMG_ERR_INVALID, "smg_membrane_create: a block (3-DOF) hierarchy is needed (smg_mg_precompute_block; prolongations Pv (x) I_3)");
-    for (int lv = 2; lv < h->n_levels; lv++)
-        if (!kron3_factor(h->lv[lv].P_full, Pv)) return fail(SMG_ERR_INVALID, "smg_membrane_create: the prolongation of level %d is not Pv (x) I_3", lv);
-    if ((long long)rows != 3LL * nV) return fail(SMG_ERR_INVALID, "smg_membrane_create: nV = %d, but level 0 of the hierarchy has %d rows (3 nV expected)", nV, rows);
-    if (int rc = check_mesh("smg_membrane_create", V, nV, F, nF, true)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SMG_ERR_NO_DEVICE, "smg_membrane_create: no HIP device: libsmg has no CPU fallback");
+    const char* who = "smg_membrane_create";
+    if (!h || !V || !F || !pp || !out || nV <= 0 || nF <= 0) return fail(SMG_ERR_INVALID, "%s: bad arguments", who);
+    if (int rc = check_hierarchy(who, h, 3, nV)) return rc;
+    if (int rc = check_mesh(who, V, nV, F, nF, true)) return rc;
+    if (const char* why = bad_params(*pp)) return fail(SMG_ERR_INVALID, "%s: %s", who, why);
 
     std::unique_ptr<smg_membrane> m(new smg_membrane());
     m->nV = nV; m->nF = nF; m->p = *pp;
     lame(*pp, m->alpha, m->beta);
-    HIPCHK(hipGetDevice(&m->device));
-    HIPCHK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+    if (int rc = m->open(who)) return rc;
+    if (int rc = m->clone(who, h, 0)) return rc;
     hipStream_t st = m->stream;
-    m->h = smg_hierarchy_create(h->n_levels);
-    if (!m->h) return fail(SMG_ERR_ALLOC, "smg_membrane_create: out of memory");
-    if (int rc = copy_prolongations(h, m->h)) return rc;
-    if (int rc = smg_hierarchy_set_stream(m->h, st)) return rc;
 
     MembraneLists L;
     membrane_lists(F, nF, nV, L);
@@ -193,7 +148,7 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
     HIPCHK(m->H.alloc(45 * nf));
     HIPCHK(m->Qn.alloc(6 * nf));
     HIPCHK(m->terms.alloc(nf + (size_t)nV));
-    HIPCHK(m->part.alloc((size_t)arap_groups(nF + nV)));
+    HIPCHK(m->part.alloc((size_t)fixed_sum_groups(nF + nV)));
     HIPCHK(m->E.alloc(2));
     for (DevBuf<double>* d : {&m->qdot, &m->qdot0, &m->fext, &m->zero}) HIPCHK(hipMemsetAsync(d->p, 0, n3 * sizeof(double), st));
     HIPCHK(hipMemcpyAsync(m->pos.p, m->V0.p, n3 * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -216,8 +171,8 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
         }
     }
     ptr[n3] = (int)nval;
-    if (int rc = smg_precompute(m->h, (int)n3, ptr.data(), col.data(), val.data(), nullptr, 0)) return rc;
-    if (smg_hierarchy_block_size(m->h) != 3) return fail(SMG_ERR_INVALID, "smg_membrane_create: the precompute did not take the block path");
+    if (int rc = smg_precompute(m->handle[0], (int)n3, ptr.data(), col.data(), val.data(), nullptr, 0)) return rc;
+    if (smg_hierarchy_block_size(m->handle[0]) != 3) return fail(SMG_ERR_INVALID, "%s: the precompute did not take the block path", who);
     *out = m.release();
     return SMG_OK;
 }
@@ -234,7 +189,6 @@ int step_impl(smg_membrane* m, const smg_solve_opts* opts, double* objective_his
     smg_solve_opts so;
     if (opts) so = *opts;
     else { smg_solve_opts_default(&so); so.tol = 2e-1; }      // the reference's mg_tolerance (main.cpp)
-    std::vector<double> his((size_t)std::max(1, so.max_iter));
 
     HIPCHK(hipMemcpyAsync(m->pos0.p, m->pos.p, vec, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(m->qdot0.p, m->qdot.p, vec, hipMemcpyDeviceToDevice, st));
@@ -246,14 +200,11 @@ int step_impl(smg_membrane* m, const smg_solve_opts* opts, double* objective_his
 
     for (int i = 0; i < p.newton_iters; i++) {
         if (int rc = assemble(m, m->pos.p, m->qdot.p, m->qdot0.p)) return rc;
-        if (int rc = smg_precompute_values_device(m->h, m->Hval.p)) return rc;
-        int nhis = 0, conv = 0;
-        if (int rc = (m->pcg ? smg_solve_pcg : smg_solve)(m->h, m->b.p, n3, nullptr, 0, m->zero.p, n3, 1, SMG_DEVICE, &so, m->dx.p, n3, his.data(), &nhis, &conv))
-            return rc;
-        if (cycles) cycles[i] = nhis;
+        if (int rc = smg_precompute_values_device(m->handle[0], m->Hval.p)) return rc;
+        if (int rc = inner_solve(m->handle[0], m->pcg, m->b.p, n3, nullptr, 0, m->zero.p, n3, 1, so, m->dx.p, n3, cycles ? cycles + i : nullptr)) return rc;
         double bdx = 0.0;
         HIPCHK(launch_membrane_dot3(nV, m->b.p, m->dx.p, m->terms.p, st));
-        HIPCHK(launch_arap_energy(m->terms.p, nV, m->part.p, m->E.p + 1, st));
+        HIPCHK(launch_fixed_sum(m->terms.p, nV, m->part.p, m->E.p + 1, st));
         HIPCHK(hipMemcpyAsync(&bdx, m->E.p + 1, sizeof(double), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         // the reference's acceptance test: s = f0 + c b . dx with b the NEGATIVE gradient
@@ -323,13 +274,9 @@ extern "C" void smg_membrane_destroy(smg_membrane* m) { delete m; }
 
 extern "C" long long smg_membrane_device_bytes(const smg_membrane* m)
 {
-    if (!m) return 0;
-    long long total = handle_bytes(m->h);
-    for (const DevBuf<int>* d : {&m->F, &m->m_ptr, &m->m_idx, &m->brow, &m->bcol, &m->bptr, &m->c_ptr, &m->c_src}) total += d->bytes();
-    for (const DevBuf<double>* d : {&m->V0, &m->rest, &m->mass0, &m->pos, &m->qdot, &m->posT, &m->qdotT, &m->pos0, &m->qdot0, &m->fext, &m->b, &m->dx,
-                                    &m->zero, &m->Hval, &m->G, &m->H, &m->Qn, &m->terms, &m->part, &m->E})
-        total += d->bytes();
-    return total;
+    if (!m) return 0;   // one list: every DevBuf of the struct
+    return device_bytes(*m, m->F, m->m_ptr, m->m_idx, m->brow, m->bcol, m->bptr, m->c_ptr, m->c_src, m->V0, m->rest, m->mass0, m->pos, m->qdot, m->posT,
+                        m->qdotT, m->pos0, m->qdot0, m->fext, m->b, m->dx, m->zero, m->Hval, m->G, m->H, m->Qn, m->terms, m->part, m->E);
 }
 
 extern "C" int smg_membrane_set_state(smg_membrane* m, const double* pos, const double* qdot, int memspace)
@@ -345,7 +292,7 @@ extern "C" int smg_membrane_get_state(smg_membrane* m, double* pos, double* qdot
 extern "C" int smg_membrane_set_solver(smg_membrane* m, int pcg)
 {
     if (!m) return fail(SMG_ERR_INVALID, "null membrane object");
-    if (pcg >= 0) m->pcg = pcg ? 1 : 0;
+    latch_solver(m->pcg, pcg);
     return SMG_OK;
 }
 
@@ -358,8 +305,7 @@ extern "C" int smg_membrane_lists(const int* F, int nF, int nV, int* n_blocks, i
 {
     return guarded("smg_membrane_lists", [&]() -> int {
         if (!F || nF <= 0 || nV <= 0) return fail(SMG_ERR_INVALID, "smg_membrane_lists: bad arguments");
-        for (size_t i = 0; i < (size_t)nF * 3; i++)
-            if (F[i] < 0 || F[i] >= nV) return fail(SMG_ERR_INVALID, "smg_membrane_lists: face index out of range");
+        if (int rc = check_faces("smg_membrane_lists", F, nF, nV)) return rc;
         MembraneLists L;
         membrane_lists(F, nF, nV, L);
         if (n_blocks) *n_blocks = (int)L.bcol.size();

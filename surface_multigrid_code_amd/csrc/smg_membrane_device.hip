@@ -6,7 +6,7 @@
 // gradient (9), the upper triangle of the Hessian (45), pressure terms (6: e1 x e2, the three corner shares of the Voronoi mass).
 //
 // Determinism: no atomics.  A matrix block sums its faces' sub-blocks in the order of its contribution list (faces ascending), a vertex sums
-// its corners in the order of its corner list (faces ascending), the objective is reduced over fixed chunks by a fixed tree (launch_arap_energy).
+// its corners in the order of its corner list (faces ascending), the objective is reduced over fixed chunks by a fixed tree (launch_fixed_sum).
 // Expressions are written operation by operation (-ffp-contract=off): tests/test_membrane_host.py restates the sums in numpy in the same order.
 #include <hip/hip_runtime.h>
 

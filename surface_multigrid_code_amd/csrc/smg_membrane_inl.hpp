@@ -1,5 +1,6 @@
 // smg_membrane_inl.hpp -- the neo-Hookean membrane energy of one triangle, its gradient, its Hessian and the Hessian's eigenvalue fix, in
-// registers (k_membrane_faces, csrc/smg_membrane_device.hip; smg_membrane_faces_host).
+// registers (k_membrane_faces, csrc/smg_membrane_device.hip; smg_membrane_faces_host); and what smg_membrane.cpp shares
+// with the kernel hooks: the Lame parameters and the lists of the matrix kernel.
 //
 // Corners q0, q1, q2, e1 = q1 - q0, e2 = q2 - q0, a = [[e1.e1, e1.e2], [e1.e2, e2.e2]], abar = a of the rest pose:
 //   lnJ = log(det a / det abar) / 2,   W = coeff (beta (tr(abar^-1 a) - 2 - 2 lnJ) + alpha lnJ^2),   coeff = h sqrt(det abar) / 4.
@@ -21,6 +22,9 @@
 // Host and device compile the same text (the library is built with -ffp-contract=off).
 #pragma once
 #include <cmath>
+#include <vector>
+
+#include "../../include/smg.h"
 
 #if defined(__HIPCC__)
 #define SMG_MEM_HD __host__ __device__ __forceinline__
@@ -50,6 +54,13 @@ SMG_MEM_HD void mem_comb(const double (&e1)[3], const double (&e2)[3], double c0
         out[3 + d] = u;
         out[6 + d] = v;
     }
+}
+
+// the Lame parameters of the material (the reference's main.cpp:63-67)
+inline void lame(const smg_membrane_params& p, double& alpha, double& beta)
+{
+    alpha = p.young * p.poisson / (1.0 - p.poisson * p.poisson);
+    beta = p.young / 2.0 / (1.0 + p.poisson);
 }
 
 // q: the corners (q0, q1, q2), 9 doubles.  rest: (abar^-1)00, 01, 11, det abar, coeff.  Returns W (+inf where det a <= 0 or is not a
@@ -204,5 +215,10 @@ SMG_MEM_HD void membrane_fix(double (&H)[45], double floor, double value)
             H[mem_tri(r, c)] = l == m ? acc + third : acc;
         }
 }
+
+// the membrane's lists (smg_membrane.cpp): the block CSR of (adjacency + I), columns ascending, the block row of every block, and per block
+// the face sub-blocks 9 f + 3 a + b that k_membrane_matrix sums, faces ascending
+struct MembraneLists { std::vector<int> bptr, bcol, brow, c_ptr, c_src; };
+void membrane_lists(const int* F, int nF, int nV, MembraneLists& L);
 
 }  // namespace smg

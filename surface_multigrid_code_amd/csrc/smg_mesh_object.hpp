@@ -1,0 +1,55 @@
+// smg_mesh_object.hpp -- what an object built on a triangle mesh and a caller's hierarchy starts from (smg_geodesics.cpp, smg_arap.cpp,
+// smg_membrane.cpp): the checks of a create call, the object's stream, device and cloned handles, the cotangent system
+// assembled on the device, the inner solve, and the byte total.  `who` is the entry point's name, the prefix of every message.
+#pragma once
+#include <vector>
+
+#include "smg_internal.hpp"
+
+namespace smg {
+
+double double_area(const double* V, const int* F, int f);   // twice the area of face f, the expression of k_face_terms / k_geo_basis
+int components(const int* F, int nF, int nV);               // connected components of the vertex graph (a vertex in no face is one)
+int level0_rows(const smg_hierarchy* h);                    // rows of level 0 of a hierarchy whose prolongations are set (-1: none set)
+int copy_prolongations(const smg_hierarchy* src, smg_hierarchy* dst);
+long long handle_bytes(const smg_hierarchy* h);             // the sum of device_byte_entries (nullptr: 0)
+
+// ---- the checks of a create call, in this order; none of them touches the device ------------------------------------------------------------
+// h is no union handle, has `dofs` (1 or 3) unknowns per vertex, and dofs * nV rows on level 0
+int check_hierarchy(const char* who, const smg_hierarchy* h, int dofs, int nV);
+int check_faces(const char* who, const int* F, int nF, int nV);   // every index in [0, nV)
+// check_faces, every double area > 0 (*area2, optional: their sum), every coordinate finite, and with `connected` one component
+int check_mesh(const char* who, const double* V, int nV, const int* F, int nF, bool connected, double* area2 = nullptr);
+
+// ---- the object's stream, device and handles.  The object derives from this and declares its buffers as DevBuf members; its destructor is
+// { quiesce(); }, so that teardown runs: stream synchronised, handles destroyed (quiesce), buffers freed (the members), stream destroyed (here).
+struct MeshObject {
+    hipStream_t stream = nullptr;
+    int device = -1;
+    smg_hierarchy* handle[2] = {nullptr, nullptr};
+    MeshObject() = default;
+    MeshObject(const MeshObject&) = delete;
+    MeshObject& operator=(const MeshObject&) = delete;
+    int open(const char* who);                                        // a HIP device exists (SMG_ERR_NO_DEVICE); the current device, a stream of its own
+    int clone(const char* who, const smg_hierarchy* src, int slot);   // handle[slot] = src's levels and prolongations, on the object's stream
+    void quiesce();
+    ~MeshObject() { if (stream) (void)hipStreamDestroy(stream); }
+};
+
+// the object's share of HBM: its handles and every buffer of the one list the object passes
+template <class... Bufs>
+long long device_bytes(const MeshObject& o, const Bufs&... bufs) { return ((handle_bytes(o.handle[0]) + handle_bytes(o.handle[1])) + ... + bufs.bytes()); }
+
+// ---- smg_assemble on d_V (nV x 3 row-major, device) back on the host as CSR: the pattern, L's values, and with `val` c_mass M + c_L L
+// (voronoi: the mass type).  keep_L (optional) keeps L's values on the device.  Synchronises the stream.
+struct CotanSystem { std::vector<int> ptr, col; std::vector<double> L, val; };
+int cotan_system(const int* F, int nF, int nV, const double* d_V, int voronoi, double c_mass, double c_L, hipStream_t st, CotanSystem& S, bool val,
+                 DevBuf<double>* keep_L = nullptr);
+
+// ---- the inner solver of an object: smg_solve_pcg (pcg != 0) or smg_solve on device blocks; *entries (optional) = the loop entries of a
+// solve that returned SMG_OK.  latch_solver: the rule of the set_solver calls, -1 keeps, else 0 / 1.
+int inner_solve(smg_hierarchy* h, int pcg, const double* B, int ldb, const double* known, int ld_kv, const double* z0, int ld_z0, int k,
+                const smg_solve_opts& o, double* z, int ld_z, int* entries);
+inline void latch_solver(int& pcg, int v) { if (v >= 0) pcg = v ? 1 : 0; }
+
+}  // namespace smg

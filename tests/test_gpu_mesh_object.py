@@ -1,0 +1,51 @@
+"""GPU (-m gpu): what the three objects built on a mesh and a caller's hierarchy hold in HBM (csrc/smg_mesh_object.hpp).  Per object: create,
+use once, read device_bytes() and the library's count of live DevBuf bytes, destroy.  Everything device_bytes() counts is a live buffer and
+nothing is counted twice, and the teardown -- which names no buffer -- gives every byte back."""
+import gc
+
+import numpy as np
+import pytest
+
+from test_arap_host import twist
+from test_geodesics_host import icosphere
+from test_gpu_parity import smg  # noqa: F401  (fixture)
+from test_membrane_host import load_mesh
+
+pytestmark = pytest.mark.gpu
+
+
+def _geodesics(smg):
+    V, F = icosphere(3)
+    mg = smg.mg_precompute(V, F, 0.25, 50, 1)
+    return mg, lambda: smg.HeatGeodesics(mg, V, F), lambda g: g.distance([0, [5, 100, 641]])
+
+
+def _arap(smg):
+    V, F = icosphere(3)
+    mg = smg.mg_precompute(V, F, 0.25, 50, 1)
+    handles, hp = twist(V)
+    return mg, lambda: smg.ArapDeformer(mg, V, F, handles), lambda a: a.deform(hp, max_iter=2)
+
+
+def _membrane(smg):
+    V, F = load_mesh("ogre_sim.smgm")
+    mg = smg.mg_precompute_block(V, F)
+    return mg, lambda: smg.MembraneSim(mg, V, F, newton_iters=2), lambda m: m.step()
+
+
+@pytest.mark.parametrize("which", ["geodesics", "arap", "membrane"])
+def test_device_bytes_are_live_buffers_and_destroy_frees_them(smg, which):
+    live = smg._lib.load().smg_device_bytes_live
+    mg, create, use = {"geodesics": _geodesics, "arap": _arap, "membrane": _membrane}[which](smg)    # the caller's hierarchy stays alive throughout
+    gc.collect()
+    before = live()
+    obj = create()
+    use(obj)
+    counted, held = obj.device_bytes(), live() - before
+    print("%s: device_bytes %d, live DevBuf bytes held %d, difference %d" % (which, counted, held, held - counted))
+    del obj
+    gc.collect()
+    after = live()
+    assert 0 < counted == held
+    assert after == before
+    assert mg.n_levels >= 2

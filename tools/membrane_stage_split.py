@@ -6,7 +6,7 @@
 
 A step runs from k_membrane_pressure_faces to the launch before the next one.  Inside it a Newton iteration starts at k_membrane_faces<2>;
 k_membrane_faces<2>, k_membrane_matrix and k_membrane_gradient are the assembly; the kernels of the value-only re-precompute and of the solve are
-not told apart by name alone, so every launch that is not k_membrane_* / k_arap_energy_* counts as "re-precompute + solve"; k_membrane_trial, the energy-only k_membrane_faces<0>, k_membrane_dot3 and the
+not told apart by name alone, so every launch that is not k_membrane_* / k_fixed_sum_* counts as "re-precompute + solve"; k_membrane_trial, the energy-only k_membrane_faces<0>, k_membrane_dot3 and the
 reductions are the line search.  Prints the median per step of every stage over the steps with the most Newton iterations."""
 import collections
 import re
@@ -22,7 +22,7 @@ for n, s, e in cur.execute(q):
     rows.append((nm + (mode.group(1) if mode else ""), s, e))
 STAGE = {"k_membrane_faces2": "assembly", "k_membrane_matrix": "assembly", "k_membrane_gradient": "assembly", "k_membrane_pressure_faces": "pressure",
          "k_membrane_pressure": "pressure", "k_membrane_trial": "line search", "k_membrane_faces0": "line search", "k_membrane_dot3": "line search",
-         "k_arap_energy_part": "line search", "k_arap_energy_final": "line search"}
+         "k_fixed_sum_part": "line search", "k_fixed_sum_final": "line search"}
 steps, cur_step = [], None
 for nm, s, e in rows:
     if nm == "k_membrane_pressure_faces":
