@@ -46,7 +46,7 @@ std::vector<std::pair<std::string, long long>> smg::device_byte_entries(const sm
 {
     std::vector<std::pair<std::string, long long>> out;
     auto B = [](const auto& d) { return (long long)(d.n * sizeof(*d.p)); };
-    auto sell = [&](const smg::SellBuf& S) { return B(S.slice_row) + B(S.slice_off) + B(S.slice_w) + B(S.col) + B(S.order) + B(S.val) + B(S.diag_slot) + B(S.long_row) + B(S.long_ptr) + B(S.long_col) + B(S.long_val) + B(S.long_valf); };
+    auto sell = [&](const smg::SellBuf& S) { return B(S.slice_row) + B(S.slice_off) + B(S.slice_w) + B(S.col) + B(S.order) + B(S.order_part) + B(S.val) + B(S.diag_slot) + B(S.long_row) + B(S.long_ptr) + B(S.long_col) + B(S.long_val) + B(S.long_valf); };
     auto line = [&](const std::string& nm, long long v) { if (v) out.emplace_back(nm, v); };
     for (int lv = 0; lv < h->n_levels; lv++) {
         const smg::Level& L = h->lv[lv];
@@ -137,6 +137,19 @@ int smg::ensure_device(smg_hierarchy* h)
 
 void smg::drop_graphs(smg_hierarchy* h) { h->graphs.drop(); }
 
+hipError_t SellBuf::set_part_order(int r0, int r1)
+{
+    Sell S;     // (the tables order_without_rows reads)
+    S.n_slices = view.n_slices; S.slice_row = host_slice_row; S.region_order = host_order;
+    n_part = 0;
+    if (host_slice_row.size() != (size_t)view.n_slices + 1) { order_part.release(); return hipSuccess; }
+    const std::vector<int> part = order_without_rows(S, r0, r1);
+    if (part.empty() || part.size() == (size_t)view.n_slices) { order_part.release(); return hipSuccess; }   // nothing left / nothing to leave out
+    const hipError_t e = order_part.upload(part);
+    if (e == hipSuccess) n_part = (int)part.size();
+    return e;
+}
+
 hipError_t SellBuf::upload(const Sell& S)
 {
     hipError_t e;
@@ -168,6 +181,11 @@ hipError_t SellBuf::upload(const Sell& S)
     }
     color_slice_ptr = S.color_slice_ptr;
     stored = S.nnz; padded = S.padded(); used = S.used();
+    host_slice_row = S.slice_row; host_order = S.region_order;
+    order_part.release(); n_part = 0;
+    if (S.n_rows == S.n_cols && S.color_slice_ptr.size() >= 3) {      // (without the last colour: the level residual of the V-cycle)
+        if ((e = set_part_order(S.slice_row[(size_t)S.color_slice_ptr[S.color_slice_ptr.size() - 2]], S.n_rows)) != hipSuccess) return e;
+    }
     // where the diagonal of each row sits in the value array (restriction launches that produce the first launch of the coarse
     // level's first sweep themselves: the first colour of a Gauss-Seidel sweep / the whole first Jacobi sweep)
     n_first = 0; n_all = 0;

@@ -301,8 +301,11 @@ static const std::vector<int>& colour_slices(const smg_hierarchy* h, const Level
 // `iters` forward Gauss-Seidel sweeps in place, with the level's wave / block plan sp (sweep_plan) or one launch per colour (reference relax(),
 // src/mg_VCycle.cpp:113-178).  first = FIRST_LAUNCH: the first colour of the first sweep is already in u.  FIRST_SWEEP: the whole first sweep is in `t`:
 // the second sweep goes from t back into u (out-of-place colour launches: same values), the rest run in place on u; needs iters >= 2.
+// res (one launch per colour, fp64, scalar levels, k < 8; see resid_byproduct below): the last launch of the last sweep also stores the residual of its
+// rows there (SELL_GS_RES / SELL_GS_OOP_RES).
 template <typename T>
-static int enqueue_gs(smg_hierarchy* h, int lv, const SweepPlan& sp, const T* b, T* u, int k, int iters, const Ctrl* ctrl, int first = FIRST_NONE, T* t = nullptr)
+static int enqueue_gs(smg_hierarchy* h, int lv, const SweepPlan& sp, const T* b, T* u, int k, int iters, const Ctrl* ctrl, int first = FIRST_NONE, T* t = nullptr,
+                      T* res = nullptr)
 {
     Level& Lv = h->lv[lv];
     ProfGuard pg(h, "MG: relaxation");  // PROFC_NODE at src/mg_VCycle.cpp:121
@@ -319,9 +322,13 @@ static int enqueue_gs(smg_hierarchy* h, int lv, const SweepPlan& sp, const T* b,
         return SMG_OK;
     }
     const std::vector<int>& cs = colour_slices(h, Lv);
+    FirstColour fr;      // (only its d is read: the by-product's output)
+    if constexpr (std::is_same<T, double>::value) fr.d = res;
     for (int it = first == FIRST_SWEEP ? 1 : 0; it < iters; it++)
         for (size_t c = (it == 0 && first == FIRST_LAUNCH) ? 1 : 0; c + 1 < cs.size(); c++) {
-            if (it == 1 && first == FIRST_SWEEP) HIPCHK(Prec<T>::sell(SELL_GS_OOP, Prec<T>::G(Lv), cs[c], cs[c + 1], t, b, u, k, ctrl, h->stream));   // (scalar levels only)
+            const bool last = res && it == iters - 1 && c + 2 == cs.size();
+            if (it == 1 && first == FIRST_SWEEP) HIPCHK(Prec<T>::sell(last ? SELL_GS_OOP_RES : SELL_GS_OOP, Prec<T>::G(Lv), cs[c], cs[c + 1], t, b, u, k, ctrl, h->stream, nullptr, last ? &fr : nullptr));   // (scalar levels only)
+            else if (last) HIPCHK(Prec<T>::sell(SELL_GS_RES, Prec<T>::G(Lv), cs[c], cs[c + 1], u, b, u, k, ctrl, h->stream, nullptr, &fr));
             else HIPCHK(Prec<T>::opA(h, Lv, true, SELL_GS, cs[c], cs[c + 1], u, b, u, k, ctrl));
         }
     return SMG_OK;
@@ -372,6 +379,12 @@ static int enqueue_cheby(smg_hierarchy* h, int lv, const T* b, T* const buf[2], 
 
 // reference mg_VCycle(), src/mg_VCycle.cpp:3-59.  B and u of level lv are Lv.b / Lv.u (level 0: RHS_u / z_u).
 static bool fuse_first_colour() { static const int on = env_int("SMG_FUSE_FIRST", 1); return on != 0; }
+// Two quarter passes whose results nobody reads, on the levels smoothed with one launch per colour (A/B knobs; same bits either way):
+// the level residual of the last colour's rows comes out of the last pre-smoothing launch, which holds all it takes (SELL_GS_RES in
+// smg_device.hpp), and the residual launch walks the other colours only;
+static bool resid_byproduct() { static const int on = env_int("SMG_RESID_BYPRODUCT", 1); return on != 0; }
+// the prolongation leaves out the slices inside the first colour: the first post-smoothing launch overwrites those rows without reading them.
+static bool prolong_skip_first() { static const int on = env_int("SMG_PROLONG_SKIP_FIRST", 1); return on != 0; }
 
 // first: what of this level's first pre-smoothing sweep already exists (FIRST_*).
 template <typename T>
@@ -394,6 +407,9 @@ static int enqueue_vcycle_t(smg_hierarchy* h, int lv, int k, int pre, int post, 
     const bool fp64 = std::is_same<T, double>::value;
     const SweepPlan sp_pre = sweep_plan(h, lv, k, pre, fp64, first), sp_post = sweep_plan(h, lv, k, post, fp64, FIRST_NONE);
     int rc;
+    // (fp64 only: the fp32 cycle keeps the whole residual launch.  The smoother must stream A itself, and the last launch of the last sweep must exist)
+    const bool byprod = fp64 && resid_byproduct() && h->bs == 1 && kind == LV_GS && sp_pre.colours() && pre >= 1 && k < 8 && !Lv.gs_on_transpose &&
+                        Lv.dA.n_part > 0 && Lv.dA.color_slice_ptr.size() >= 3 && (first != FIRST_SWEEP || pre >= 2);
     if (kind == LV_JACOBI) {
         if (first_done) cur = 1;
         rc = enqueue_jacobi<T>(h, lv, Prec<T>::b(Lv), buf, &cur, k, pre - (first_done ? 1 : 0), ctrl);            // :36
@@ -401,11 +417,12 @@ static int enqueue_vcycle_t(smg_hierarchy* h, int lv, int k, int pre, int post, 
         if (first_done) cur = 1;
         rc = enqueue_cheby<T>(h, lv, Prec<T>::b(Lv), buf, &cur, k, pre, ctrl, first_done);                         // :36
     } else if (sp_pre.tiled) rc = enqueue_gs_tiled<T>(h, *sp_pre.tiled, Prec<T>::b(Lv), buf, &cur, k, ctrl);                    // :36, one launch
-    else rc = enqueue_gs<T>(h, lv, sp_pre, Prec<T>::b(Lv), buf[0], k, pre, ctrl, first, buf[1]);                  // :36
+    else rc = enqueue_gs<T>(h, lv, sp_pre, Prec<T>::b(Lv), buf[0], k, pre, ctrl, first, buf[1], byprod ? Prec<T>::r(Lv) : nullptr);   // :36
     if (rc) return rc;
-    {   // r = B - A u  (:40-42)
+    {   // r = B - A u  (:40-42); with the by-product: of the rows outside the last colour, in the region order without that colour's slices
         ProfGuard pg(h, "MG: residual");
-        HIPCHK(Prec<T>::opA(h, Lv, false, SELL_RESID, 0, -1, buf[cur], Prec<T>::b(Lv), Prec<T>::r(Lv), k, ctrl));
+        if (byprod) HIPCHK(Prec<T>::sell(SELL_RESID, Lv.dA.part_view(), 0, Lv.dA.n_part, buf[cur], Prec<T>::b(Lv), Prec<T>::r(Lv), k, ctrl, h->stream));
+        else HIPCHK(Prec<T>::opA(h, Lv, false, SELL_RESID, 0, -1, buf[cur], Prec<T>::b(Lv), Prec<T>::r(Lv), k, ctrl));
     }
     // With uc = 0 the first launch of the coarse level's first pre-smoothing sweep computes (rc_i - 0) / a_ii for the rows it covers
     // (the first colour / with Jacobi all rows, damped): the restriction launch writes that itself, bit for bit the same value, and
@@ -445,7 +462,11 @@ static int enqueue_vcycle_t(smg_hierarchy* h, int lv, int k, int pre, int post, 
         const int flips = sp_post.tiled ? 1 : kind == LV_CHEBY ? (post > 0 ? post + 1 : 0) : post;   // buffer switches of the post-smoothing
         if ((jac || sp_post.tiled) && ((cur + flips) & 1)) dst = 1 - cur;
         if (!jac && !sp_post.tiled && cur == 1) dst = 0;      // in-place Gauss-Seidel sweeps follow: they work on u
-        HIPCHK(Prec<T>::sell(SELL_ADD, Prec<T>::P(Lc), 0, Prec<T>::P(Lc).n_slices, Prec<T>::u(Lc), buf[cur], buf[dst], kt, ctrl, h->stream));
+        // in-place colour launches follow: the first of them overwrites the first colour's rows unread, the prolongation leaves their slices out
+        const bool skip = prolong_skip_first() && h->bs == 1 && kind == LV_GS && sp_post.colours() && post >= 1 && Lc.dP.n_part > 0;
+        SellDev Pv = Prec<T>::P(Lc);
+        if (skip) { Pv.order = Lc.dP.order_part.p; Pv.n_slices = Lc.dP.n_part; }
+        HIPCHK(Prec<T>::sell(SELL_ADD, Pv, 0, Pv.n_slices, Prec<T>::u(Lc), buf[cur], buf[dst], kt, ctrl, h->stream));
         cur = dst;
     }
     if (kind == LV_CHEBY) return enqueue_cheby<T>(h, lv, Prec<T>::b(Lv), buf, &cur, k, post, ctrl);   // :57  (ends with cur == 0)

@@ -77,6 +77,7 @@ __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_
     // values one colour launch writes are still in that XCD's L2 when the next launch gathers them -- a small level's launch chain
     // is pure latency, and this takes the trip to the Infinity Cache out of it (tools/micro/xcd_local.hip: 3.6 -> 2.85 us per launch)
     constexpr bool GS = sell_is_gs(MODE), OOP = sell_is_oop(MODE), JAC = sell_is_jacobi(MODE), CHEB = sell_is_cheby(MODE), HEAD = sell_is_head(MODE);
+    constexpr bool RES = sell_has_res(MODE);   // the last colour launch of a pre-smoothing: also stores the residual of its rows (into z.d)
     int bid;
     if (GS && n_blocks < 0) { if (blockIdx.x & 7) return; bid = blockIdx.x >> 3; }
     else bid = xcd_remap(blockIdx.x, n_blocks);
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_
         {
             size_t keep = (size_t)x ^ (size_t)A.slice_row ^ (size_t)A.slice_w ^ (size_t)b ^ (size_t)y ^ (size_t)done ^ (size_t)ld;
             if (MODE == SELL_AX) keep ^= (size_t)z.u ^ (size_t)z.gs_val ^ (size_t)z.diag_slot ^ (size_t)z.n_first ^ (size_t)z.jacobi ^ (size_t)z.d;
-            if (CHEB) keep ^= (size_t)z.d;
+            if (CHEB || RES) keep ^= (size_t)z.d;
             asm("" : "+s"(keep));
             if (keep == 0x5a5a5a5a5a5a5a5bull) return;   // never: only there to consume `keep`
         }
@@ -139,6 +140,7 @@ __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_
             if (CHEB && live && z.c1 != (T)0) dold[q] = z.d[(size_t)rowb * ld + q];
         }
         // one batch of U panel columns: gather x for all of them, then accumulate in ascending column order
+        bool has_diag = false;   // (RES modes)
         auto consume = [&](const int (&cw)[U], const T (&vw)[U]) {
             int c[U];
             T v[U];
@@ -158,7 +160,7 @@ __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_
                     // the first: seven dependent round trips per row)
                     gather_kb<KB, T>(x + (size_t)c[t] * ld, c[t] >= 0, xo[t]);
                     gather_kb<KB, T>((const T*)y + (size_t)c[t] * ld, use && c[t] < split, xv[t]);
-                } else if constexpr (MODE == SELL_GS_OOP) {
+                } else if constexpr (MODE == SELL_GS_OOP || MODE == SELL_GS_OOP_RES) {
                     gather_kb<KB, T>((c[t] < split ? (const T*)y : x) + (size_t)c[t] * ld, use, xv[t]);
                 } else {
                     gather_kb<KB, T>(x + (size_t)c[t] * ld, use, xv[t]);
@@ -173,6 +175,7 @@ __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_
                     }
                     if (GS && c[t] == rowb) {
                         diag = v[t];
+                        if (RES) has_diag = true;
                     } else if ((JAC || CHEB) && c[t] == rowb) {
                         diag = v[t];
 #pragma unroll
@@ -195,6 +198,22 @@ __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_
             }
             consume(c, v);
         }
+        // RES modes: the launch covers the LAST colour (launch_sell_mode insists on it), so every row of the level is final once it has stored,
+        // and r_i = b_i - sum_j a_ij u_j of its rows needs nothing more than the wave holds.  The colour's rows close the colour-major
+        // numbering and are no neighbours of each other: every other stored column of a row is smaller than the row, the diagonal is its LAST
+        // stored entry.  SELL_RESID's sum -- one accumulator from +0 over all stored entries in slot order, separate multiply and add -- is
+        // therefore the sweep's own sum (same products, same order, the same operands: the final iterate of the other colours) plus one more
+        // term, the diagonal times the value just computed.  Slices of any width: nothing is kept, nothing is read twice.
+        T unew[KB];
+#pragma unroll
+        for (int q = 0; q < KB; q++) unew[q] = (T)0;
+        if constexpr (RES) {
+#pragma unroll
+            for (int q = 0; q < KB; q++) {
+                unew[q] = (bv[q] - acc[q]) / diag;
+                accr[q] = has_diag ? acc[q] + diag * unew[q] : acc[q];
+            }
+        }
         if (live && !stop) {
             const size_t o = (size_t)rowb * ld;
 #pragma unroll
@@ -209,6 +228,7 @@ __global__ __launch_bounds__(64 * WPB) void k_sell(const int* a_col, const T* a_
                 }
                 else if (MODE == SELL_RESID) y[o + q] = bv[q] - acc[q];
                 else if (MODE == SELL_ADD) y[o + q] = bv[q] + acc[q];
+                else if (RES) { y[o + q] = unew[q]; z.d[o + q] = bv[q] - accr[q]; }
                 else if (GS) y[o + q] = (bv[q] - acc[q]) / diag;
                 else if (JAC) { const T t = (bv[q] - acc[q]) / diag; y[o + q] = xi[q] + z.omega * (t - xi[q]); }
                 else if (CHEB) {
@@ -688,6 +708,9 @@ static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, 
 {
     int s_end = s_end_in;
     if (MODE == SELL_ADD && !b) b = y;   // in place: the iterate the correction is added to is the output
+    // the residual by-product exists in the narrow kernel only, needs its second output, and is the residual only where the launch's rows
+    // are the last of the matrix (see k_sell)
+    if constexpr (sell_has_res(MODE)) { if (k >= 8 || !first || !first->d || zero_rows || s_end_in != A.n_slices) return hipErrorInvalidValue; }
     const int ns = s_end - s_begin;
     const int nb = sell_blocks(ns);
     const int* done = ctrl ? &ctrl->done : never_done();
@@ -699,7 +722,7 @@ static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, 
     if (ns <= 0) return hipSuccess;
     int c0 = 0;
     size_t poff = 0;  // partial sums written so far
-    {
+    if constexpr (!sell_has_res(MODE)) {
         while (k - c0 >= 8) {
             int kw = 64;
             while (kw > k - c0) kw >>= 1;
@@ -804,6 +827,13 @@ static hipError_t launch_sell_any(SellMode mode, const SellDev& A, int s_begin, 
             else return hipErrorInvalidValue;
         case SELL_CHEBY_HEAD:
             if constexpr (std::is_same<T, double>::value) return launch_sell_mode<SELL_CHEBY_HEAD, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
+            else return hipErrorInvalidValue;
+        // the V-cycle's level residual out of the last pre-smoothing launch: fp64 only (the fp32 cycle keeps the whole residual launch)
+        case SELL_GS_RES:
+            if constexpr (std::is_same<T, double>::value) return launch_sell_mode<SELL_GS_RES, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
+            else return hipErrorInvalidValue;
+        case SELL_GS_OOP_RES:
+            if constexpr (std::is_same<T, double>::value) return launch_sell_mode<SELL_GS_OOP_RES, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
             else return hipErrorInvalidValue;
     }
     return hipErrorInvalidValue;

@@ -79,9 +79,18 @@ enum SellMode {
     SELL_GS_HEAD = 9,     // SELL_GS_OOP + partial sums of |b - A x|^2 over the rows of the colour
     SELL_JACOBI_HEAD = 10,  // SELL_JACOBI + partial sums of |b - A x|^2
     SELL_CHEBY_HEAD = 11,   // SELL_CHEBY + partial sums of |b - A x|^2
+    // ---- the level residual of the V-cycle as a by-product of the LAST colour launch of the pre-smoothing (fp64, k < 8, scalar levels) ----
+    // After that launch every row of the level is final, and the launch holds every stored entry of its rows, the final iterate at every
+    // column and its own new value: it also stores r_i = b_i - sum_j a_ij u_j of its rows into first->d.  The rows of the last colour close
+    // the numbering, so the diagonal is the last stored entry of each: the sweep's sum plus diagonal times new value IS SELL_RESID's sum, term
+    // by term in slot order -- the same bits.  The slice range must end with the matrix.  The residual launch that follows covers the other
+    // colours only (SellBuf::order_part).
+    SELL_GS_RES = 12,       // SELL_GS on the last colour + the residual of its rows
+    SELL_GS_OOP_RES = 13,   // SELL_GS_OOP on the last colour + the residual of its rows
 };
-constexpr bool sell_is_gs(int m) { return m == SELL_GS || m == SELL_GS_OOP || m == SELL_GS_HEAD; }
-constexpr bool sell_is_oop(int m) { return m == SELL_GS_OOP || m == SELL_GS_HEAD; }
+constexpr bool sell_has_res(int m) { return m == SELL_GS_RES || m == SELL_GS_OOP_RES; }
+constexpr bool sell_is_gs(int m) { return m == SELL_GS || m == SELL_GS_OOP || m == SELL_GS_HEAD || sell_has_res(m); }
+constexpr bool sell_is_oop(int m) { return m == SELL_GS_OOP || m == SELL_GS_HEAD || m == SELL_GS_OOP_RES; }
 constexpr bool sell_is_jacobi(int m) { return m == SELL_JACOBI || m == SELL_JACOBI_HEAD; }
 constexpr bool sell_is_cheby(int m) { return m == SELL_CHEBY || m == SELL_CHEBY_HEAD; }
 constexpr bool sell_is_head(int m) { return m == SELL_GS_HEAD || m == SELL_JACOBI_HEAD || m == SELL_CHEBY_HEAD; }
@@ -104,7 +113,8 @@ struct FirstColour {
     int jacobi = 0;                   // 1: the coarse level is smoothed by damped Jacobi: n_first = all its rows, and they receive the
     double omega = 1.0;               //    first sweep from u = 0:  0 + omega * (y_i / a_ii - 0).  2: Chebyshev-Jacobi: d_i = omega * (y_i /
                                       //    a_ii - 0), u_i = 0 + d_i, both written (d / df below)
-    double* d = nullptr;              // SELL_CHEBY launches and jacobi == 2: the update vector (n x k, internal layout) ...
+    double* d = nullptr;              // SELL_CHEBY launches and jacobi == 2: the update vector (n x k, internal layout) ...; SELL_GS_RES /
+                                      // SELL_GS_OOP_RES: where the residual of the launch's rows goes
     float* df = nullptr;              // ... its fp32 twin
     double c1 = 0.0;                  // SELL_CHEBY: coefficient of the old update (0 = first step, d is not read); `omega` is c2
 };

@@ -95,6 +95,15 @@ struct SellBuf {  // device image of one SELL matrix
     int n_all = 0;                           // ... all rows (0: some row has no stored diagonal), see FirstColour in smg_device.hpp
     long stored = 0, padded = 0, used = 0;   // CSR entries / allocated slots / slots the kernels read
     hipError_t upload(const Sell& S);          // S.col / S.val empty: the panels are allocated only (filled on the device, launch_sell_fill)
+    // A second launch order for the one whole-matrix launch of the V-cycle whose results in some rows nobody reads (order_without_rows,
+    // smg_order.hpp): coloured square images leave out the LAST colour's slices (level residual: those rows' residual comes out of the last
+    // pre-smoothing launch); a prolongation's image leaves out the slices inside the fine level's FIRST colour (set_part_order from the
+    // precompute: the first post-smoothing launch overwrites those rows unread).  n_part == 0: there is none.
+    std::vector<int> host_slice_row, host_order;   // what set_part_order works from
+    DevBuf<int> order_part;
+    int n_part = 0;
+    hipError_t set_part_order(int r0, int r1);
+    SellDev part_view() const { SellDev V = view; V.order = order_part.p; V.n_slices = n_part; return V; }
     // long rows kept out of the panels (SellDev::long_*), see csrc/smg_device.hpp
     DevBuf<int> long_row, long_ptr, long_col;
     DevBuf<double> long_val;

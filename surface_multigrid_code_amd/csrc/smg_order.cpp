@@ -665,6 +665,19 @@ Sell sell_layout(const std::vector<int>& row_len, int n_cols, long nnz, const st
     return S;
 }
 
+std::vector<int> order_without_rows(const Sell& S, int r0, int r1)
+{
+    std::vector<int> out;
+    out.reserve((size_t)S.n_slices);
+    for (int i = 0; i < S.n_slices; i++) {
+        const int s = S.region_order.empty() ? i : S.region_order[(size_t)i];
+        const int a = S.slice_row[(size_t)s], b = S.slice_row[(size_t)s + 1];
+        if (a < b && a >= r0 && b <= r1) continue;
+        out.push_back(s);
+    }
+    return out;
+}
+
 Sell build_sell(const Csr& A, const std::vector<int>* row_breaks, int C, bool region_order, int pitch_policy)
 {
     std::vector<int> row_len((size_t)A.nr);

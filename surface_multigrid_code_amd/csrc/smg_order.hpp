@@ -69,6 +69,10 @@ struct Sell {
     std::vector<int> entry;            // per stored slot: index of the CSR entry it holds (-1 = padding); value refresh map
 };
 
+// The launch order of S's slices for a whole-matrix kernel whose results in rows [r0, r1) nobody reads: S.region_order (or the identity)
+// without the slices whose rows ALL lie in that range; a slice that straddles an end of the range stays.
+std::vector<int> order_without_rows(const Sell& S, int r0, int r1);
+
 // row_breaks: optional ascending row offsets (e.g. Ordering::color_ptr) at which a new slice must start.
 Sell build_sell(const Csr& A, const std::vector<int>* row_breaks, int C = SELL_C, bool region_order = false, int pitch_policy = -1);
 // the same container from the row lengths alone: slice tables, pitch, launch order -- col / val / entry stay empty (the panels are then

@@ -962,9 +962,12 @@ static int level_images(smg_hierarchy* h, int lv, int sym0)
         // block hierarchies: the device applies the VERTEX-level factor of P (x) I_3 to 3 k columns (smg_bsr3.hpp)
         const Ordering& Of = blk ? Lw.vord : Lw.ord;
         const bool cut = tr_region && region && Of.color_ptr.size() > 2;
+        // the prolongation launch of the V-cycle may leave out the slices that lie inside the fine level's first colour (SellBuf::order_part)
+        const int n_first_fine = Of.color_ptr.size() > 2 ? Of.color_ptr[1] : 0;
         if (!blk && Lp.P_device_filled) {
             eP = device_fill_sell(Lp.dP, Lp.P, Of.perm, Lp.ord.iperm, cut ? &Of.color_ptr : nullptr, cut, h->aux[1], h->mem_lean ? 0 : -1);
             if (eP == hipSuccess) eP = Lp.dP.encode_codes(Lp.P.val.data(), Lp.P.val.size(), h->aux[1]);
+            if (eP == hipSuccess && n_first_fine > 0) eP = Lp.dP.set_part_order(0, n_first_fine);
             return;
         }
         Csr Pvi;
@@ -972,6 +975,7 @@ static int level_images(smg_hierarchy* h, int lv, int sym0)
         Sell S = build_sell(blk ? Pvi : Lp.P_int, cut ? &Of.color_ptr : nullptr, sellC, cut, h->mem_lean ? 0 : -1);
         eP = Lp.dP.upload(S);
         if (eP == hipSuccess) eP = Lp.dP.encode_codes((blk ? Pvi : Lp.P_int).val.data(), (blk ? Pvi : Lp.P_int).val.size(), h->aux[1]);
+        if (eP == hipSuccess && !blk && n_first_fine > 0) eP = Lp.dP.set_part_order(0, n_first_fine);
     });
     tasks.push_back([&] {
         DeviceScope ds(h->device);
