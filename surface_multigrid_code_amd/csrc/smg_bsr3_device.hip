@@ -283,33 +283,33 @@ static hipError_t launch_bsr3_mode(const Bsr3Dev& A, const T* vals, int s_begin,
     return hipGetLastError();
 }
 
-hipError_t launch_bsr3(SellMode mode, const Bsr3Dev& A, int s_begin, int s_end, const double* x, const double* b, double* y, int k, const Ctrl* ctrl,
-                       double* partials, int* n_blocks, hipStream_t st, double omega, double c1, double* dvec)
+// One dispatch for both precisions; the fp32 twin (the V-cycle of the mixed-precision mode) needs the image Bsr3Dev::valf and has no norms.
+template <typename T>
+static hipError_t launch_bsr3_any(SellMode mode, const Bsr3Dev& A, int s_begin, int s_end, const T* x, const T* b, T* y, int k, const Ctrl* ctrl,
+                                  double* partials, int* n_blocks, hipStream_t st, double omega, double c1, T* dvec)
 {
+    constexpr bool fp64 = std::is_same<T, double>::value;
+    if (!fp64 && (!A.valf || partials)) return hipErrorInvalidValue;
     switch (mode) {
-        case SELL_AX: return launch_bsr3_mode<SELL_AX, double>(A, A.val, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, omega, c1, dvec);
-        case SELL_RESID: return launch_bsr3_mode<SELL_RESID, double>(A, A.val, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, omega, c1, dvec);
-        case SELL_RESID_SS: return launch_bsr3_mode<SELL_RESID_SS, double>(A, A.val, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, omega, c1, dvec);
-        case SELL_RESID_BOTH: return launch_bsr3_mode<SELL_RESID_BOTH, double>(A, A.val, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, omega, c1, dvec);
-        case SELL_GS: return launch_bsr3_mode<SELL_GS, double>(A, A.val, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, omega, c1, dvec);
-        case SELL_JACOBI: return launch_bsr3_mode<SELL_JACOBI, double>(A, A.val, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, omega, c1, dvec);
-        case SELL_CHEBY: return launch_bsr3_mode<SELL_CHEBY, double>(A, A.val, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, omega, c1, dvec);
+#define SMG_BSR3_CASE(M) \
+        case M: \
+            if constexpr (fp64 || !sell_fp64_only(M)) return launch_bsr3_mode<M, T>(A, A.vals<T>(), s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, omega, c1, dvec); \
+            else return hipErrorInvalidValue;
+        SMG_BSR3_CASE(SELL_AX) SMG_BSR3_CASE(SELL_RESID) SMG_BSR3_CASE(SELL_RESID_SS) SMG_BSR3_CASE(SELL_RESID_BOTH) SMG_BSR3_CASE(SELL_GS)
+        SMG_BSR3_CASE(SELL_JACOBI) SMG_BSR3_CASE(SELL_CHEBY)
+#undef SMG_BSR3_CASE
         default: return hipErrorInvalidValue;
     }
 }
-// the fp32 image (Bsr3Dev::valf): what the V-cycle of the mixed-precision mode needs
-hipError_t launch_bsr3_f32(SellMode mode, const Bsr3Dev& A, int s_begin, int s_end, const float* x, const float* b, float* y, int k, const Ctrl* ctrl, hipStream_t st,
-                           double omega, double c1, float* dvec)
+hipError_t launch_bsr3(SellMode mode, const Bsr3Dev& A, int s_begin, int s_end, const double* x, const double* b, double* y, int k, const Ctrl* ctrl,
+                       double* partials, int* n_blocks, hipStream_t st, double omega, double c1, double* dvec)
 {
-    if (!A.valf) return hipErrorInvalidValue;
-    switch (mode) {
-        case SELL_AX: return launch_bsr3_mode<SELL_AX, float>(A, A.valf, s_begin, s_end, x, b, y, k, ctrl, nullptr, nullptr, st, omega, c1, dvec);
-        case SELL_RESID: return launch_bsr3_mode<SELL_RESID, float>(A, A.valf, s_begin, s_end, x, b, y, k, ctrl, nullptr, nullptr, st, omega, c1, dvec);
-        case SELL_GS: return launch_bsr3_mode<SELL_GS, float>(A, A.valf, s_begin, s_end, x, b, y, k, ctrl, nullptr, nullptr, st, omega, c1, dvec);
-        case SELL_JACOBI: return launch_bsr3_mode<SELL_JACOBI, float>(A, A.valf, s_begin, s_end, x, b, y, k, ctrl, nullptr, nullptr, st, omega, c1, dvec);
-        case SELL_CHEBY: return launch_bsr3_mode<SELL_CHEBY, float>(A, A.valf, s_begin, s_end, x, b, y, k, ctrl, nullptr, nullptr, st, omega, c1, dvec);
-        default: return hipErrorInvalidValue;
-    }
+    return launch_bsr3_any<double>(mode, A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, omega, c1, dvec);
+}
+hipError_t launch_bsr3(SellMode mode, const Bsr3Dev& A, int s_begin, int s_end, const float* x, const float* b, float* y, int k, const Ctrl* ctrl,
+                       double* partials, int* n_blocks, hipStream_t st, double omega, double c1, float* dvec)
+{
+    return launch_bsr3_any<float>(mode, A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, omega, c1, dvec);
 }
 
 // Gershgorin bound of D^-1 A over the scalar rows of the block matrix (see k_gershgorin): explicit zeros add |0| = 0.

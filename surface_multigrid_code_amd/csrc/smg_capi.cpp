@@ -61,8 +61,8 @@ std::vector<std::pair<std::string, long long>> smg::device_byte_entries(const sm
         line(p + "tiled_plans", t);
         line(p + "bgs_plan", L.bgs.bytes());
         line(p + "wgs_plan", L.wgs.bytes());
-        line(p + "fp32_images", B(L.a32) + B(L.at32) + B(L.p32) + B(L.pt32) + B(L.b32) + B(L.u32) + B(L.r32) + B(L.t32) + B(L.d32));
-        line(p + "vectors", B(L.b) + B(L.u) + B(L.r) + B(L.t) + B(L.d));
+        line(p + "fp32_images", B(L.dA.valf) + B(L.dAT.valf) + B(L.dP.valf) + B(L.dPT.valf) + L.f32.bytes());
+        line(p + "vectors", vecs<double>(L).bytes());
     }
     line("coarse.dense_inverse", B(h->d_Ainv) + B(h->d_Ainv32));
     line("coarse.sym_partials", B(h->d_sympart));
@@ -168,6 +168,7 @@ hipError_t SellBuf::upload(const Sell& S)
     view.n_rows = S.n_rows; view.n_cols = S.n_cols; view.n_slices = S.n_slices; view.C = S.C;
     view.order = S.region_order.empty() ? nullptr : order.p;
     view.slice_row = slice_row.p; view.slice_off = slice_off.p; view.slice_w = slice_w.p; view.col = col.p; view.val = val.p;
+    view.valf = nullptr;     // (the new values have no fp32 image yet: ensure_f32)
     view.codes = 0;
     view.stride = S.stride; view.w_lo = S.w_lo;
     view.w_max = 0;
@@ -257,6 +258,31 @@ hipError_t SellBuf::encode_codes(const double* vals, size_t n_vals, hipStream_t 
     return hipSuccess;
 }
 
+hipError_t SellBuf::ensure_f32(hipStream_t st)
+{
+    hipError_t e;
+    if (view.long_n > 0) {     // the long rows' values, too
+        if ((e = long_valf.ensure(long_val.n)) != hipSuccess) return e;
+        if ((e = launch_cvt_f64_f32(long_valf.p, long_val.p, long_val.n, st)) != hipSuccess) return e;
+        view.long_valf = long_valf.p;
+    }
+    view.valf = nullptr;
+    if (padded == 0 || view.codes) return hipSuccess;   // weight codes: the fp32 table is in the view
+    if ((e = valf.ensure((size_t)padded)) != hipSuccess) return e;
+    if ((e = launch_cvt_f64_f32(valf.p, view.val, (size_t)padded, st)) != hipSuccess) return e;
+    view.valf = valf.p;
+    return hipSuccess;
+}
+
+hipError_t Bsr3Buf::ensure_f32(hipStream_t st)
+{
+    hipError_t e;
+    if ((e = valf.ensure(val.n)) != hipSuccess) return e;
+    if ((e = launch_cvt_f64_f32(valf.p, val.p, val.n, st)) != hipSuccess) return e;
+    view.valf = valf.p;
+    return hipSuccess;
+}
+
 hipError_t Bsr3Buf::upload(const Bsr3Sell& S)
 {
     hipError_t e;
@@ -275,6 +301,7 @@ hipError_t Bsr3Buf::upload(const Bsr3Sell& S)
     if ((e = order.upload(S.region_order)) != hipSuccess) return e;
     view.n_vert = S.n_vert; view.n_slices = S.n_slices; view.w_max = S.w_max;
     view.slice_row = slice_row.p; view.slice_off = slice_off.p; view.slice_w = slice_w.p; view.col = col.p; view.val = val.p;
+    view.valf = nullptr;
     view.order = S.region_order.empty() ? nullptr : order.p;
     color_slice_ptr = S.color_slice_ptr;
     stored = S.nnz_scalar; blocks = S.n_blocks; padded = (long)(slots * 9);

@@ -24,71 +24,91 @@ using namespace smg;
 
 // ------------------------------------------------------------------------------------------------ V-cycle
 
-int smg::ensure_work(smg_hierarchy* h, int k)
+// The level vectors (and the Schur solver's separator pair) of one precision for solves of k columns: allocated and zeroed when k outgrows what is
+// there, the second iterate and the update vector when the level's smoother asks for them.  The fp64 set serves more than the cycle -- the outer
+// residual and its partial sums, the fused head, the pieces -- and the conditions on `fp64` below are those extras.
+template <typename T>
+static int ensure_vectors(smg_hierarchy* h, int k)
 {
+    constexpr bool fp64 = std::is_same<T, double>::value;
     const int L = h->n_levels;
-    if (k > h->kcap) {
+    int& kcap = fp64 ? h->kcap : h->kcap32;
+    int rc;
+    auto zeroed = [&](DevBuf<T>& v, size_t cnt) -> int {
+        HIPCHK(v.alloc(cnt));
+        HIPCHK(hipMemsetAsync(v.p, 0, cnt * sizeof(T), h->stream));
+        return SMG_OK;
+    };
+    if (k > kcap) {
         drop_graphs(h);
         size_t maxblocks = 0;
         for (int lv = 0; lv < L; lv++) {
             Level& Lv = h->lv[lv];
-            size_t rows = (lv == L - 1) ? (size_t)h->nc_pad : (size_t)Lv.n;
-            HIPCHK(Lv.b.alloc(rows * k));
-            HIPCHK(Lv.u.alloc(rows * k));
-            HIPCHK(hipMemsetAsync(Lv.b.p, 0, rows * k * sizeof(double), h->stream));
-            HIPCHK(hipMemsetAsync(Lv.u.p, 0, rows * k * sizeof(double), h->stream));
-            Lv.t.release(); Lv.d.release();
-            if (lv < L - 1 || L == 1) HIPCHK(Lv.r.alloc(rows * k));
-            if (lv < L - 1 || L == 1) {
+            LevelVecs<T>& V = vecs<T>(Lv);
+            const size_t rows = (lv == L - 1) ? (size_t)h->nc_pad : (size_t)Lv.n;
+            if ((rc = zeroed(V.b, rows * k)) || (rc = zeroed(V.u, rows * k))) return rc;
+            V.t.release(); V.d.release();
+            const bool has_resid = lv < L - 1 || (fp64 && L == 1);      // (a single level: the outer loop's residual)
+            if (has_resid) HIPCHK(V.r.alloc(rows * k));
+            if (fp64 && has_resid) {
                 if (h->bs == 3) maxblocks = std::max(maxblocks, (size_t)bsr3_blocks(Lv.bA.view.n_slices) * (size_t)k);
                 else maxblocks = std::max(maxblocks, (size_t)sell_blocks(Lv.dA.view.n_slices) * ((k + 3) / 4) + (size_t)sell_wide_blocks(Lv.dA.view.n_slices, k));
             }
         }
-        // colour by colour (the level-0 head of an outer iteration, enqueue_residual_ss) every launch rounds its block count up on its own
-        maxblocks += (h->lv[0].dA.color_slice_ptr.size() + 1) * (size_t)((k + 3) / 4 + 8);
-        HIPCHK(h->d_partials.alloc(std::max<size_t>(maxblocks, 1) + (size_t)ss_partials_room()));
-        h->kcap = k;
+        if (fp64) {
+            // colour by colour (the level-0 head of an outer iteration, enqueue_residual_ss) every launch rounds its block count up on its own
+            maxblocks += (h->lv[0].dA.color_slice_ptr.size() + 1) * (size_t)((k + 3) / 4 + 8);
+            HIPCHK(h->d_partials.alloc(std::max<size_t>(maxblocks, 1) + (size_t)ss_partials_room()));
+        }
+        kcap = k;
     }
     // Jacobi-smoothed levels ping-pong between u and a second iterate
     for (int lv = 0; lv < L - 1; lv++) {
         Level& Lv = h->lv[lv];
-        // (level 0 always: the first sweep of an outer iteration is written out of place, see enqueue_residual_ss)
-        if ((level_is_jacobi(h, lv) || lv == 0) && Lv.t.n < (size_t)Lv.n * h->kcap) {
+        LevelVecs<T>& V = vecs<T>(Lv);
+        const size_t cnt = (size_t)Lv.n * kcap;
+        // (fp64, level 0 always: the first sweep of an outer iteration is written out of place, see enqueue_residual_ss)
+        if ((level_is_jacobi(h, lv) || (fp64 && lv == 0)) && V.t.n < cnt) {
             drop_graphs(h);
-            HIPCHK(Lv.t.alloc((size_t)Lv.n * h->kcap));
-            HIPCHK(hipMemsetAsync(Lv.t.p, 0, (size_t)Lv.n * h->kcap * sizeof(double), h->stream));
+            if ((rc = zeroed(V.t, cnt))) return rc;
         }
-        if (level_kind(h, lv) == LV_CHEBY && Lv.d.n < (size_t)Lv.n * h->kcap) {
+        if (level_kind(h, lv) == LV_CHEBY && V.d.n < cnt) {
             drop_graphs(h);
-            HIPCHK(Lv.d.alloc((size_t)Lv.n * h->kcap));
-            HIPCHK(hipMemsetAsync(Lv.d.p, 0, (size_t)Lv.n * h->kcap * sizeof(double), h->stream));
+            if ((rc = zeroed(V.d, cnt))) return rc;
         }
     }
     if (h->coarse_schur) {       // the separator's right-hand side and solution (the solver may have arrived with a value-only re-precompute, after the vectors)
-        const size_t need = (size_t)h->sch.view.ns_pad * std::max(h->kcap, 1);
-        if (h->sch.g.n < need || h->sch.xs.n < need) {
+        const size_t need = (size_t)h->sch.view.ns_pad * std::max(kcap, 1);
+        DevBuf<T>&g = h->sch.rhs<T>(), &xs = h->sch.sol<T>();
+        if (g.n < need || xs.n < need) {
             drop_graphs(h);
-            HIPCHK(h->sch.g.alloc(need));
-            HIPCHK(h->sch.xs.alloc(need));
-            HIPCHK(hipMemsetAsync(h->sch.g.p, 0, need * sizeof(double), h->stream));
-            HIPCHK(hipMemsetAsync(h->sch.xs.p, 0, need * sizeof(double), h->stream));
+            if ((rc = zeroed(g, need)) || (rc = zeroed(xs, need))) return rc;
         }
-        h->sch.view.g = h->sch.g.p; h->sch.view.xs = h->sch.xs.p;
+        SchurDev& S = h->sch.view;
+        if constexpr (fp64) { S.g = g.p; S.xs = xs.p; } else { S.g32 = g.p; S.xs32 = xs.p; }
     }
-    if (h->coarse_sparse) {      // the triangular solves take up to 64 columns per pass: 2 n doubles of scratch per column of a pass
-        const size_t need = (size_t)2 * h->chol.n * sparse_coarse_work_cols(std::max(h->kcap, 1));
+    if (fp64 && h->coarse_sparse) {      // the triangular solves take up to 64 columns per pass: 2 n doubles of scratch per column of a pass
+        const size_t need = (size_t)2 * h->chol.n * sparse_coarse_work_cols(std::max(kcap, 1));
         if (h->c_work.n < need) {
             drop_graphs(h);          // the captured launches hold the scratch pointer
             HIPCHK(h->c_work.alloc(need));
             h->c_view.work = h->c_work.p;
         }
     }
-    int rc = prepare_sweep_plans(h, k, h->pre, h->post);
+    return SMG_OK;
+}
+
+int smg::ensure_work(smg_hierarchy* h, int k)
+{
+    int rc = ensure_vectors<double>(h, k);
     if (rc) return rc;
+    if ((rc = prepare_sweep_plans(h, k, h->pre, h->post))) return rc;
     return ensure_spectral_bounds(h);
 }
 
 // ---- mixed precision: fp32 images of the operators and an fp32 V-cycle ------------------------------------------------
+// The images belong to the matrices (SellBuf / Bsr3Buf::ensure_f32 fill valf and point the matrix's own view at it): both cycles launch on the
+// same views.  f32_valid says that the images hold the current values; whoever changes values lowers it (smg_precompute.cpp).
 int smg::ensure_fp32(smg_hierarchy* h, int k)
 {
     const int L = h->n_levels;
@@ -96,38 +116,18 @@ int smg::ensure_fp32(smg_hierarchy* h, int k)
     if (h->coarse_sparse) return fail(SMG_ERR_INVALID, "the mixed-precision cycle is not available with a sparse coarse factorisation (coarsest level of %d unknowns)", h->nc);
     if (!h->f32_valid) {
         drop_graphs(h);
-        auto mk = [&](SellBuf& src, DevBuf<float>& dst, SellDev& view) -> int {
-            if (src.view.long_n > 0) {     // the long rows' values, too
-                HIPCHK(src.long_valf.ensure(src.long_val.n));
-                HIPCHK(launch_cvt_f64_f32(src.long_valf.p, src.long_val.p, src.long_val.n, h->stream));
-                src.view.long_valf = src.long_valf.p;
-            }
-            view = src.view;
-            if (src.padded == 0 || src.view.codes) { view.valf = nullptr; return SMG_OK; }   // weight codes: the fp32 table is in the view
-            HIPCHK(dst.ensure((size_t)src.padded));
-            HIPCHK(launch_cvt_f64_f32(dst.p, src.view.val, (size_t)src.padded, h->stream));
-            view.valf = dst.p;
-            return SMG_OK;
-        };
         for (int lv = 0; lv < L; lv++) {
             Level& Lv = h->lv[lv];
-            int rc;
             if (lv < L - 1 && h->bs == 3) {     // block hierarchies: the nine value planes of every panel column
-                auto mkb = [&](Bsr3Buf& B) -> int {
-                    HIPCHK(B.valf.ensure(B.val.n));
-                    HIPCHK(launch_cvt_f64_f32(B.valf.p, B.val.p, B.val.n, h->stream));
-                    B.view.valf = B.valf.p;
-                    return SMG_OK;
-                };
-                if ((rc = mkb(Lv.bA))) return rc;
-                if (Lv.gs_on_transpose) { if ((rc = mkb(Lv.bAT))) return rc; }
+                HIPCHK(Lv.bA.ensure_f32(h->stream));
+                if (Lv.gs_on_transpose) HIPCHK(Lv.bAT.ensure_f32(h->stream));
             } else if (lv < L - 1) {
-                if ((rc = mk(Lv.dA, Lv.a32, Lv.dA32))) return rc;
-                if (Lv.gs_on_transpose) { if ((rc = mk(Lv.dAT, Lv.at32, Lv.dAT32))) return rc; }
+                HIPCHK(Lv.dA.ensure_f32(h->stream));
+                if (Lv.gs_on_transpose) HIPCHK(Lv.dAT.ensure_f32(h->stream));
             }
             if (lv >= 1) {
-                if ((rc = mk(Lv.dP, Lv.p32, Lv.dP32))) return rc;
-                if ((rc = mk(Lv.dPT, Lv.pt32, Lv.dPT32))) return rc;
+                HIPCHK(Lv.dP.ensure_f32(h->stream));
+                HIPCHK(Lv.dPT.ensure_f32(h->stream));
             }
         }
         if (h->coarse_schur) {
@@ -140,45 +140,7 @@ int smg::ensure_fp32(smg_hierarchy* h, int k)
         }
         h->f32_valid = true;
     }
-    if (k > h->kcap32) {
-        drop_graphs(h);
-        for (int lv = 0; lv < L; lv++) {
-            Level& Lv = h->lv[lv];
-            const size_t rows = (lv == L - 1) ? (size_t)h->nc_pad : (size_t)Lv.n;
-            HIPCHK(Lv.b32.alloc(rows * k));
-            HIPCHK(Lv.u32.alloc(rows * k));
-            HIPCHK(hipMemsetAsync(Lv.b32.p, 0, rows * k * sizeof(float), h->stream));
-            HIPCHK(hipMemsetAsync(Lv.u32.p, 0, rows * k * sizeof(float), h->stream));
-            if (lv < L - 1) HIPCHK(Lv.r32.alloc(rows * k));
-            Lv.t32.release(); Lv.d32.release();
-        }
-        h->kcap32 = k;
-    }
-    for (int lv = 0; lv < L - 1; lv++) {
-        Level& Lv = h->lv[lv];
-        if (level_is_jacobi(h, lv) && Lv.t32.n < (size_t)Lv.n * h->kcap32) {
-            drop_graphs(h);
-            HIPCHK(Lv.t32.alloc((size_t)Lv.n * h->kcap32));
-            HIPCHK(hipMemsetAsync(Lv.t32.p, 0, (size_t)Lv.n * h->kcap32 * sizeof(float), h->stream));
-        }
-        if (level_kind(h, lv) == LV_CHEBY && Lv.d32.n < (size_t)Lv.n * h->kcap32) {
-            drop_graphs(h);
-            HIPCHK(Lv.d32.alloc((size_t)Lv.n * h->kcap32));
-            HIPCHK(hipMemsetAsync(Lv.d32.p, 0, (size_t)Lv.n * h->kcap32 * sizeof(float), h->stream));
-        }
-    }
-    if (h->coarse_schur) {
-        const size_t need = (size_t)h->sch.view.ns_pad * std::max(h->kcap32, 1);
-        if (h->sch.g32.n < need || h->sch.xs32.n < need) {
-            drop_graphs(h);
-            HIPCHK(h->sch.g32.alloc(need));
-            HIPCHK(h->sch.xs32.alloc(need));
-            HIPCHK(hipMemsetAsync(h->sch.g32.p, 0, need * sizeof(float), h->stream));
-            HIPCHK(hipMemsetAsync(h->sch.xs32.p, 0, need * sizeof(float), h->stream));
-        }
-        h->sch.view.g32 = h->sch.g32.p; h->sch.view.xs32 = h->sch.xs32.p;
-    }
-    return SMG_OK;
+    return ensure_vectors<float>(h, k);
 }
 
 // ---- the smoother of a level -------------------------------------------------------------------------------------------
@@ -217,79 +179,44 @@ static void cheby_coefs(double lam, double frac, int degree, std::vector<ChebyCo
     }
 }
 
-// one accessor set per arithmetic: fp64 (the reference's) and the fp32 images of the mixed-precision V-cycle
-template <typename T> struct Prec;
 // The dense coarse product of a padded solve (internal_cols below) is formed for the caller's columns only: which of its kernels serves a column
 // (1 / 2 - 7 / 8 and more columns) then follows the CALLER's column count, as it would without padding -- a column-sharded solve stays bit-identical
 // to the fused one (tests/test_gpu_dist.py), and the padding columns' coarse iterate stays the zero the restriction wrote.
 static inline int coarse_cols(const smg_hierarchy* h, int k) { return (h->coarse_cols > 0 && h->coarse_cols < k) ? h->coarse_cols : k; }
 
-template <> struct Prec<double> {
-    static double* b(Level& L) { return L.b.p; }
-    static double* u(Level& L) { return L.u.p; }
-    static double* r(Level& L) { return L.r.p; }
-    static double* t(Level& L) { return L.t.p; }
-    static double* d(Level& L) { return L.d.p; }
-    static void set_d(FirstColour& fc, Level& L) { fc.d = L.d.p; }
-    static const SellDev& A(Level& L) { return L.dA.view; }
-    static const SellDev& G(Level& L) { return L.gs_on_transpose ? L.dAT.view : L.dA.view; }   // what the smoother streams
-    static const SellDev& P(Level& L) { return L.dP.view; }
-    static const SellDev& PT(Level& L) { return L.dPT.view; }
-    static bool has_vals(const SellDev& V) { return V.val != nullptr; }
-    static hipError_t sell(SellMode m, const SellDev& V, int s0, int s1, const double* x, const double* bb, double* y, int k, const Ctrl* ctrl,
-                           hipStream_t st, double* zero_rows = nullptr, const FirstColour* first = nullptr, double omega = 1.0)
-    { return launch_sell(m, V, s0, s1, x, bb, y, k, ctrl, nullptr, nullptr, st, zero_rows, first, omega); }
-    static hipError_t coarse(smg_hierarchy* h, Level& L, int k, const Ctrl* ctrl)
-    {
-        if (h->union_m > 0) return launch_blockdiag_gemv_add(h->un.view, h->d_Ainv.p, h->nc, L.b.p, L.u.p, k, ctrl, h->stream);   // the members' own inverses (smg_union.cpp)
-        if (h->coarse_sparse) return launch_sparse_coarse_solve(h->c_view, L.b.p, L.u.p, k, ctrl, h->stream);
-        if (h->coarse_schur) return launch_schur_solve(h->sch.view, L.b.p, L.u.p, k, ctrl, h->stream);
-        return launch_dense_gemv_add(h->d_Ainv.p, h->nc, h->nc_pad, L.b.p, L.u.p, coarse_cols(h, k), k, ctrl, h->stream, h->d_sympart.p);
+// Every routine of the cycle is written once for T = double (the reference's arithmetic) and T = float (the mixed-precision V-cycle): the level
+// vectors are vecs<T>(level), a matrix view hands out its values of type T (SellDev::vals<T>()), and launch_sell / launch_bsr3 / launch_schur_solve /
+// launch_dense_gemv_add are overloaded on the vectors' type.
+
+// what the smoother of a scalar level streams: A^T where A is not bit-symmetric, else A
+static const SellBuf& smoothed(const Level& L) { return L.gs_on_transpose ? L.dAT : L.dA; }
+
+// coarseSolve on the coarsest level's b / u; the member blocks of a union and the sparse factorisation exist in fp64 only (ensure_fp32 refuses them)
+template <typename T>
+static hipError_t coarse_solve(smg_hierarchy* h, Level& L, int k, const Ctrl* ctrl)
+{
+    LevelVecs<T>& V = vecs<T>(L);
+    if constexpr (std::is_same<T, double>::value) {
+        if (h->union_m > 0) return launch_blockdiag_gemv_add(h->un.view, h->d_Ainv.p, h->nc, V.b.p, V.u.p, k, ctrl, h->stream);   // the members' own inverses (smg_union.cpp)
+        if (h->coarse_sparse) return launch_sparse_coarse_solve(h->c_view, V.b.p, V.u.p, k, ctrl, h->stream);
     }
-    // an operation with the level's matrix in whatever format it lives in: SELL panels, or 3 x 3 blocks on block hierarchies.
-    // smoother_image: the matrix the smoother streams (A^T where A is not bit-symmetric), else A.  s1 < 0: all slices.
-    static hipError_t opA(smg_hierarchy* h, Level& L, bool smoother_image, SellMode m, int s0, int s1, const double* x, const double* bb, double* y, int k,
-                          const Ctrl* ctrl, const FirstColour* fc = nullptr, double omega = 1.0)
-    {
-        if (h->bs == 3) {
-            const Bsr3Dev& V = (smoother_image && L.gs_on_transpose) ? L.bAT.view : L.bA.view;
-            return launch_bsr3(m, V, s0, s1 < 0 ? V.n_slices : s1, x, bb, y, k, ctrl, nullptr, nullptr, h->stream, omega, fc ? fc->c1 : 0.0, fc ? fc->d : nullptr);
-        }
-        const SellDev& V = smoother_image ? G(L) : A(L);
-        return sell(m, V, s0, s1 < 0 ? V.n_slices : s1, x, bb, y, k, ctrl, h->stream, nullptr, fc, omega);
+    if (h->coarse_schur) return launch_schur_solve(h->sch.view, V.b.p, V.u.p, k, ctrl, h->stream);
+    return launch_dense_gemv_add(by_type<T>(h->d_Ainv.p, h->d_Ainv32.p), h->nc, h->nc_pad, V.b.p, V.u.p, coarse_cols(h, k), k, ctrl, h->stream, (T*)h->d_sympart.p);
+}
+
+// an operation with the level's matrix in whatever format it lives in: SELL panels, or 3 x 3 blocks on block hierarchies.
+// smoother_image: the matrix the smoother streams (A^T where A is not bit-symmetric), else A.  s1 < 0: all slices.
+template <typename T>
+static hipError_t op_A(smg_hierarchy* h, Level& L, bool smoother_image, SellMode m, int s0, int s1, const T* x, const T* bb, T* y, int k, const Ctrl* ctrl,
+                       const FirstColour* fc = nullptr, double omega = 1.0)
+{
+    if (h->bs == 3) {
+        const Bsr3Dev& V = (smoother_image && L.gs_on_transpose) ? L.bAT.view : L.bA.view;
+        return launch_bsr3(m, V, s0, s1 < 0 ? V.n_slices : s1, x, bb, y, k, ctrl, nullptr, nullptr, h->stream, omega, fc ? fc->c1 : 0.0, fc ? fc->update<T>() : nullptr);
     }
-};
-template <> struct Prec<float> {
-    static float* b(Level& L) { return L.b32.p; }
-    static float* u(Level& L) { return L.u32.p; }
-    static float* r(Level& L) { return L.r32.p; }
-    static float* t(Level& L) { return L.t32.p; }
-    static float* d(Level& L) { return L.d32.p; }
-    static void set_d(FirstColour& fc, Level& L) { fc.df = L.d32.p; }
-    static const SellDev& A(Level& L) { return L.dA32; }
-    static const SellDev& G(Level& L) { return L.gs_on_transpose ? L.dAT32 : L.dA32; }
-    static const SellDev& P(Level& L) { return L.dP32; }
-    static const SellDev& PT(Level& L) { return L.dPT32; }
-    static bool has_vals(const SellDev& V) { return V.valf != nullptr; }
-    static hipError_t sell(SellMode m, const SellDev& V, int s0, int s1, const float* x, const float* bb, float* y, int k, const Ctrl* ctrl,
-                           hipStream_t st, float* zero_rows = nullptr, const FirstColour* first = nullptr, double omega = 1.0)
-    { return launch_sell_f32(m, V, s0, s1, x, bb, y, k, ctrl, st, zero_rows, first, omega); }
-    static hipError_t coarse(smg_hierarchy* h, Level& L, int k, const Ctrl* ctrl)
-    {
-        if (h->coarse_schur) return launch_schur_solve_f32(h->sch.view, L.b32.p, L.u32.p, k, ctrl, h->stream);
-        return launch_dense_gemv_add_f32(h->d_Ainv32.p, h->nc, h->nc_pad, L.b32.p, L.u32.p, coarse_cols(h, k), k, ctrl, h->stream, (float*)h->d_sympart.p);
-    }
-    static hipError_t opA(smg_hierarchy* h, Level& L, bool smoother_image, SellMode m, int s0, int s1, const float* x, const float* bb, float* y, int k,
-                          const Ctrl* ctrl, const FirstColour* fc = nullptr, double omega = 1.0)
-    {
-        if (h->bs == 3) {
-            const Bsr3Dev& V = (smoother_image && L.gs_on_transpose) ? L.bAT.view : L.bA.view;
-            return launch_bsr3_f32(m, V, s0, s1 < 0 ? V.n_slices : s1, x, bb, y, k, ctrl, h->stream, omega, fc ? fc->c1 : 0.0, fc ? fc->df : nullptr);
-        }
-        const SellDev& V = smoother_image ? G(L) : A(L);
-        return sell(m, V, s0, s1 < 0 ? V.n_slices : s1, x, bb, y, k, ctrl, h->stream, nullptr, fc, omega);
-    }
-};
+    const SellDev& V = smoother_image ? smoothed(L).view : L.dA.view;
+    return launch_sell(m, V, s0, s1 < 0 ? V.n_slices : s1, x, bb, y, k, ctrl, nullptr, nullptr, h->stream, nullptr, fc, omega);
+}
 
 // slice ranges of the colours of the matrix the smoother streams
 static const std::vector<int>& colour_slices(const smg_hierarchy* h, const Level& Lv)
@@ -322,14 +249,15 @@ static int enqueue_gs(smg_hierarchy* h, int lv, const SweepPlan& sp, const T* b,
         return SMG_OK;
     }
     const std::vector<int>& cs = colour_slices(h, Lv);
-    FirstColour fr;      // (only its d is read: the by-product's output)
-    if constexpr (std::is_same<T, double>::value) fr.d = res;
+    const SellDev& G = smoothed(Lv).view;
+    FirstColour fr;      // (only its update vector is read: the by-product's output)
+    fr.set_update(res);
     for (int it = first == FIRST_SWEEP ? 1 : 0; it < iters; it++)
         for (size_t c = (it == 0 && first == FIRST_LAUNCH) ? 1 : 0; c + 1 < cs.size(); c++) {
             const bool last = res && it == iters - 1 && c + 2 == cs.size();
-            if (it == 1 && first == FIRST_SWEEP) HIPCHK(Prec<T>::sell(last ? SELL_GS_OOP_RES : SELL_GS_OOP, Prec<T>::G(Lv), cs[c], cs[c + 1], t, b, u, k, ctrl, h->stream, nullptr, last ? &fr : nullptr));   // (scalar levels only)
-            else if (last) HIPCHK(Prec<T>::sell(SELL_GS_RES, Prec<T>::G(Lv), cs[c], cs[c + 1], u, b, u, k, ctrl, h->stream, nullptr, &fr));
-            else HIPCHK(Prec<T>::opA(h, Lv, true, SELL_GS, cs[c], cs[c + 1], u, b, u, k, ctrl));
+            if (it == 1 && first == FIRST_SWEEP) HIPCHK(launch_sell(last ? SELL_GS_OOP_RES : SELL_GS_OOP, G, cs[c], cs[c + 1], t, b, u, k, ctrl, nullptr, nullptr, h->stream, nullptr, last ? &fr : nullptr));   // (scalar levels only)
+            else if (last) HIPCHK(launch_sell(SELL_GS_RES, G, cs[c], cs[c + 1], u, b, u, k, ctrl, nullptr, nullptr, h->stream, nullptr, &fr));
+            else HIPCHK(op_A<T>(h, Lv, true, SELL_GS, cs[c], cs[c + 1], u, b, u, k, ctrl));
         }
     return SMG_OK;
 }
@@ -351,7 +279,7 @@ static int enqueue_jacobi(smg_hierarchy* h, int lv, const T* b, T* const buf[2],
     Level& Lv = h->lv[lv];
     ProfGuard pg(h, "MG: relaxation");
     for (int it = 0; it < iters; it++) {
-        HIPCHK(Prec<T>::opA(h, Lv, true, SELL_JACOBI, 0, -1, buf[*cur], b, buf[1 - *cur], k, ctrl, nullptr, h->omega));
+        HIPCHK(op_A<T>(h, Lv, true, SELL_JACOBI, 0, -1, buf[*cur], b, buf[1 - *cur], k, ctrl, nullptr, h->omega));
         *cur ^= 1;
     }
     return SMG_OK;
@@ -369,9 +297,9 @@ static int enqueue_cheby(smg_hierarchy* h, int lv, const T* b, T* const buf[2], 
     cheby_coefs(Lv.lam, h->cheby_fraction, iters + 1, cf);
     for (int s = first_done ? 1 : 0; s <= iters; s++) {
         FirstColour fc;
-        Prec<T>::set_d(fc, Lv);
+        fc.set_update(vecs<T>(Lv).d.p);
         fc.c1 = cf[s].c1;
-        HIPCHK(Prec<T>::opA(h, Lv, true, SELL_CHEBY, 0, -1, buf[*cur], b, buf[1 - *cur], k, ctrl, &fc, cf[s].c2));
+        HIPCHK(op_A<T>(h, Lv, true, SELL_CHEBY, 0, -1, buf[*cur], b, buf[1 - *cur], k, ctrl, &fc, cf[s].c2));
         *cur ^= 1;
     }
     return SMG_OK;
@@ -395,13 +323,14 @@ static int enqueue_vcycle_t(smg_hierarchy* h, int lv, int k, int pre, int post, 
     Level& Lv = h->lv[lv];
     if (lv == L - 1) {  // coarseSolve: u = u + solver.solve(B)  (:28-33, :199-200)
         ProfGuard pg(h, "MG: coarse solve");
-        HIPCHK(Prec<T>::coarse(h, Lv, k, ctrl));
+        HIPCHK(coarse_solve<T>(h, Lv, k, ctrl));
         return SMG_OK;
     }
     Level& Lc = h->lv[lv + 1];
+    LevelVecs<T>&V = vecs<T>(Lv), &Vc = vecs<T>(Lc);
     const int kind = level_kind(h, lv);
     const bool jac = kind != LV_GS;
-    T* const buf[2] = {Prec<T>::u(Lv), Prec<T>::t(Lv)};   // Jacobi-type levels ping-pong; the level's result always ends in buf[0] = u
+    T* const buf[2] = {V.u.p, V.t.p};   // Jacobi-type levels ping-pong; the level's result always ends in buf[0] = u
     int cur = 0;
     // Gauss-Seidel levels whose relax() runs as one out-of-place launch (overlapped tiling): they ping-pong like the Jacobi-type ones.
     const bool fp64 = std::is_same<T, double>::value;
@@ -412,46 +341,45 @@ static int enqueue_vcycle_t(smg_hierarchy* h, int lv, int k, int pre, int post, 
                         Lv.dA.n_part > 0 && Lv.dA.color_slice_ptr.size() >= 3 && (first != FIRST_SWEEP || pre >= 2);
     if (kind == LV_JACOBI) {
         if (first_done) cur = 1;
-        rc = enqueue_jacobi<T>(h, lv, Prec<T>::b(Lv), buf, &cur, k, pre - (first_done ? 1 : 0), ctrl);            // :36
+        rc = enqueue_jacobi<T>(h, lv, V.b.p, buf, &cur, k, pre - (first_done ? 1 : 0), ctrl);            // :36
     } else if (kind == LV_CHEBY) {
         if (first_done) cur = 1;
-        rc = enqueue_cheby<T>(h, lv, Prec<T>::b(Lv), buf, &cur, k, pre, ctrl, first_done);                         // :36
-    } else if (sp_pre.tiled) rc = enqueue_gs_tiled<T>(h, *sp_pre.tiled, Prec<T>::b(Lv), buf, &cur, k, ctrl);                    // :36, one launch
-    else rc = enqueue_gs<T>(h, lv, sp_pre, Prec<T>::b(Lv), buf[0], k, pre, ctrl, first, buf[1], byprod ? Prec<T>::r(Lv) : nullptr);   // :36
+        rc = enqueue_cheby<T>(h, lv, V.b.p, buf, &cur, k, pre, ctrl, first_done);                         // :36
+    } else if (sp_pre.tiled) rc = enqueue_gs_tiled<T>(h, *sp_pre.tiled, V.b.p, buf, &cur, k, ctrl);                    // :36, one launch
+    else rc = enqueue_gs<T>(h, lv, sp_pre, V.b.p, buf[0], k, pre, ctrl, first, buf[1], byprod ? V.r.p : nullptr);   // :36
     if (rc) return rc;
     {   // r = B - A u  (:40-42); with the by-product: of the rows outside the last colour, in the region order without that colour's slices
         ProfGuard pg(h, "MG: residual");
-        if (byprod) HIPCHK(Prec<T>::sell(SELL_RESID, Lv.dA.part_view(), 0, Lv.dA.n_part, buf[cur], Prec<T>::b(Lv), Prec<T>::r(Lv), k, ctrl, h->stream));
-        else HIPCHK(Prec<T>::opA(h, Lv, false, SELL_RESID, 0, -1, buf[cur], Prec<T>::b(Lv), Prec<T>::r(Lv), k, ctrl));
+        if (byprod) HIPCHK(launch_sell(SELL_RESID, Lv.dA.part_view(), 0, Lv.dA.n_part, buf[cur], V.b.p, V.r.p, k, ctrl, nullptr, nullptr, h->stream));
+        else HIPCHK(op_A<T>(h, Lv, false, SELL_RESID, 0, -1, buf[cur], V.b.p, V.r.p, k, ctrl));
     }
     // With uc = 0 the first launch of the coarse level's first pre-smoothing sweep computes (rc_i - 0) / a_ii for the rows it covers
     // (the first colour / with Jacobi all rows, damped): the restriction launch writes that itself, bit for bit the same value, and
     // the sweep starts one launch later.
-    const SellBuf& Gc = Lc.gs_on_transpose ? Lc.dAT : Lc.dA;
+    const SellBuf& Gc = smoothed(Lc);
     const int kind_c = level_kind(h, lv + 1);
     const bool jac_c = kind_c != LV_GS;
     // (block hierarchies: the first launch of a coarse sweep is not a plain division -- row 3v+1 of the first colour already reads 3v; a coarse level with
     // a sweep plan runs all its phases itself)
-    const bool fuse = h->bs == 1 && sweep_plan(h, lv + 1, k, pre, fp64, FIRST_NONE).colours() && fuse_first_colour() && lv + 1 < L - 1 && pre > 0 && Prec<T>::has_vals(Prec<T>::G(Lc)) && (jac_c ? Gc.n_all > 0 : Gc.n_first > 0);
+    const bool fuse = h->bs == 1 && sweep_plan(h, lv + 1, k, pre, fp64, FIRST_NONE).colours() && fuse_first_colour() && lv + 1 < L - 1 && pre > 0 && Gc.view.vals<T>() && (jac_c ? Gc.n_all > 0 : Gc.n_first > 0);
     const int kt = k * h->bs;   // block hierarchies: dP / dPT hold the vertex-level factor of P (x) I_3, applied to 3 k columns
     {   // rc = PT r  (:43-44, :80) and uc = 0 (:46-47) in one launch: both are indexed by the coarse row
         ProfGuard pg(h, "MG: restrict");
         FirstColour fc;
         if (fuse) {
             fc.diag_slot = Gc.diag_slot.p; fc.n_first = jac_c ? Gc.n_all : Gc.n_first;
-            fc.val = Prec<T>::G(Lc).val; fc.valf = Prec<T>::G(Lc).valf;
+            fc.val = Gc.view.val; fc.valf = Gc.view.valf;
             fc.jacobi = kind_c == LV_CHEBY ? 2 : (jac_c ? 1 : 0); fc.omega = h->omega;
             if (kind_c == LV_CHEBY) {   // step 0 of the coarse level's polynomial: d = (rc_i / a_ii - 0) / theta, uc = 0 + d
                 std::vector<ChebyCoef> cf;
                 cheby_coefs(Lc.lam, h->cheby_fraction, 1, cf);
                 fc.omega = cf[0].c2;
-                Prec<T>::set_d(fc, Lc);
+                fc.set_update(Vc.d.p);
             }
         }
         // Jacobi + fuse: the first sweep's output buffer (t) receives the sweep, u = 0 is never read
-        T* init = (fuse && jac_c) ? Prec<T>::t(Lc) : Prec<T>::u(Lc);
-        HIPCHK(Prec<T>::sell(SELL_AX, Prec<T>::PT(Lc), 0, Prec<T>::PT(Lc).n_slices, Prec<T>::r(Lv), nullptr, Prec<T>::b(Lc), kt, ctrl, h->stream, init,
-                             fuse ? &fc : nullptr));
+        T* init = (fuse && jac_c) ? Vc.t.p : Vc.u.p;
+        HIPCHK(launch_sell(SELL_AX, Lc.dPT.view, 0, Lc.dPT.view.n_slices, V.r.p, nullptr, Vc.b.p, kt, ctrl, nullptr, nullptr, h->stream, init, fuse ? &fc : nullptr));
     }
     rc = enqueue_vcycle_t<T>(h, lv + 1, k, pre, post, ctrl, fuse ? FIRST_LAUNCH : FIRST_NONE);  // :48
     if (rc) return rc;
@@ -464,15 +392,14 @@ static int enqueue_vcycle_t(smg_hierarchy* h, int lv, int k, int pre, int post, 
         if (!jac && !sp_post.tiled && cur == 1) dst = 0;      // in-place Gauss-Seidel sweeps follow: they work on u
         // in-place colour launches follow: the first of them overwrites the first colour's rows unread, the prolongation leaves their slices out
         const bool skip = prolong_skip_first() && h->bs == 1 && kind == LV_GS && sp_post.colours() && post >= 1 && Lc.dP.n_part > 0;
-        SellDev Pv = Prec<T>::P(Lc);
-        if (skip) { Pv.order = Lc.dP.order_part.p; Pv.n_slices = Lc.dP.n_part; }
-        HIPCHK(Prec<T>::sell(SELL_ADD, Pv, 0, Pv.n_slices, Prec<T>::u(Lc), buf[cur], buf[dst], kt, ctrl, h->stream));
+        const SellDev Pv = skip ? Lc.dP.part_view() : Lc.dP.view;
+        HIPCHK(launch_sell(SELL_ADD, Pv, 0, Pv.n_slices, Vc.u.p, buf[cur], buf[dst], kt, ctrl, nullptr, nullptr, h->stream));
         cur = dst;
     }
-    if (kind == LV_CHEBY) return enqueue_cheby<T>(h, lv, Prec<T>::b(Lv), buf, &cur, k, post, ctrl);   // :57  (ends with cur == 0)
-    if (jac) return enqueue_jacobi<T>(h, lv, Prec<T>::b(Lv), buf, &cur, k, post, ctrl);   // :57  (ends with cur == 0)
-    if (sp_post.tiled) return enqueue_gs_tiled<T>(h, *sp_post.tiled, Prec<T>::b(Lv), buf, &cur, k, ctrl);   // :57  (ends with cur == 0)
-    return enqueue_gs<T>(h, lv, sp_post, Prec<T>::b(Lv), buf[0], k, post, ctrl);          // :57
+    if (kind == LV_CHEBY) return enqueue_cheby<T>(h, lv, V.b.p, buf, &cur, k, post, ctrl);   // :57  (ends with cur == 0)
+    if (jac) return enqueue_jacobi<T>(h, lv, V.b.p, buf, &cur, k, post, ctrl);   // :57  (ends with cur == 0)
+    if (sp_post.tiled) return enqueue_gs_tiled<T>(h, *sp_post.tiled, V.b.p, buf, &cur, k, ctrl);   // :57  (ends with cur == 0)
+    return enqueue_gs<T>(h, lv, sp_post, V.b.p, buf[0], k, post, ctrl);          // :57
 }
 
 // the cycle of a solve: level 0, the handle's sweeps, in the handle's precision (the fp32 cycle starts from nothing: `first` is the fp64 one's)
@@ -484,24 +411,35 @@ int smg::enqueue_vcycle(smg_hierarchy* h, int k, const Ctrl* ctrl, int first)
 
 int smg::apply_A(smg_hierarchy* h, int lv, SellMode mode, const double* x, const double* b, double* y, int k, const Ctrl* ctrl)
 {
-    HIPCHK(Prec<double>::opA(h, h->lv[lv], false, mode, 0, -1, x, b, y, k, ctrl));
+    HIPCHK(op_A<double>(h, h->lv[lv], false, mode, 0, -1, x, b, y, k, ctrl));
     return SMG_OK;
 }
 
 
-// relax() on caller-provided device vectors (pieces, raw interface): the result always ends in u
-static int enqueue_relax(smg_hierarchy* h, int lv, const double* b, double* u, int k, int iters, const Ctrl* ctrl)
+// relax(iters) of either cycle on device vectors b / u (pieces, raw interface, test hooks): returns the buffer the result is in through *res -- u or,
+// after an odd number of out-of-place launches (Jacobi-type sweeps, the one-launch relax()), the level's second iterate.  (The cycle itself arranges its
+// prolongation so that the last sweep lands in u, see enqueue_vcycle_t.)
+template <typename T>
+static int enqueue_relax(smg_hierarchy* h, int lv, const T* b, T* u, int k, int iters, const Ctrl* ctrl, T** res)
 {
-    Level& Lv = h->lv[lv];
     const int kind = level_kind(h, lv);
-    const SweepPlan sp = sweep_plan(h, lv, k, iters, true, FIRST_NONE);
-    if (kind == LV_GS && !sp.tiled) return enqueue_gs<double>(h, lv, sp, b, u, k, iters, ctrl);
-    double* const buf[2] = {u, Lv.t.p};      // Jacobi-type levels and the one-launch relax() ping-pong
-    int cur = 0;
-    int rc = kind == LV_GS ? enqueue_gs_tiled<double>(h, *sp.tiled, b, buf, &cur, k, ctrl)
-             : kind == LV_CHEBY ? enqueue_cheby<double>(h, lv, b, buf, &cur, k, iters, ctrl) : enqueue_jacobi<double>(h, lv, b, buf, &cur, k, iters, ctrl);
+    const SweepPlan sp = sweep_plan(h, lv, k, iters, std::is_same<T, double>::value, FIRST_NONE);
+    T* const buf[2] = {u, vecs<T>(h->lv[lv]).t.p};
+    int cur = 0, rc;
+    if (kind == LV_GS && !sp.tiled) rc = enqueue_gs<T>(h, lv, sp, b, u, k, iters, ctrl);
+    else if (kind == LV_GS) rc = enqueue_gs_tiled<T>(h, *sp.tiled, b, buf, &cur, k, ctrl);
+    else if (kind == LV_CHEBY) rc = enqueue_cheby<T>(h, lv, b, buf, &cur, k, iters, ctrl);
+    else rc = enqueue_jacobi<T>(h, lv, b, buf, &cur, k, iters, ctrl);
+    *res = buf[cur];
+    return rc;
+}
+// the fp64 callers want the result in u
+static int enqueue_relax_into(smg_hierarchy* h, int lv, const double* b, double* u, int k, int iters, const Ctrl* ctrl)
+{
+    double* res = nullptr;
+    int rc = enqueue_relax<double>(h, lv, b, u, k, iters, ctrl, &res);
     if (rc) return rc;
-    if (cur == 1) HIPCHK(hipMemcpyAsync(u, Lv.t.p, (size_t)Lv.n * k * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (res != u) HIPCHK(hipMemcpyAsync(u, res, (size_t)h->lv[lv].n * k * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return SMG_OK;
 }
 
@@ -585,10 +523,10 @@ int smg::enqueue_cycle_part(smg_hierarchy* h, int k, const double* d_sumsq)
             // z += V32(r): the V-cycle is affine in (B, u), so V(B, z) = z + V(B - A z, 0) in exact arithmetic
             Level& L0 = h->lv[0];
             const size_t cnt = (size_t)L0.n * k;
-            HIPCHK(launch_residual_to_f32(L0.b32.p, L0.u32.p, L0.r.p, cnt, h->d_ctrl.p, h->stream));
+            HIPCHK(launch_residual_to_f32(L0.f32.b.p, L0.f32.u.p, L0.r.p, cnt, h->d_ctrl.p, h->stream));
             int rc = enqueue_vcycle(h, k, h->d_ctrl.p, FIRST_NONE);
             if (rc) return rc;
-            HIPCHK(launch_add_correction(L0.u.p, L0.u32.p, cnt, h->d_ctrl.p, h->stream));
+            HIPCHK(launch_add_correction(L0.u.p, L0.f32.u.p, cnt, h->d_ctrl.p, h->stream));
         } else {
             int rc = enqueue_vcycle(h, k, h->d_ctrl.p, h->head_fuse ? FIRST_SWEEP : FIRST_NONE);
             if (rc) return rc;
@@ -682,7 +620,7 @@ extern "C" int smg_bench_relax(smg_hierarchy* h, int lv, int k, int sweeps, int 
     if ((rc = prepare_sweep_plans(h, k, sweeps, sweeps))) return rc;
     Level& Lv = h->lv[lv];
     hipGraphExec_t g = nullptr;
-    rc = capture_graph(h, &g, [&]() { return enqueue_relax(h, lv, Lv.b.p, Lv.u.p, k, sweeps, nullptr); });
+    rc = capture_graph(h, &g, [&]() { return enqueue_relax_into(h, lv, Lv.b.p, Lv.u.p, k, sweeps, nullptr); });
     if (rc) return rc;
     return time_graph(h, g, reps, us_per_call);
 }
@@ -744,7 +682,7 @@ extern "C" int smg_apply_A(smg_hierarchy* h, int lv, const double* u, int k, dou
     DeviceScope dsc(h->device);
     Level& Lv = h->lv[lv];
     if ((rc = put_block(h, lv, u, k, Lv.u.p))) return rc;
-    HIPCHK(Prec<double>::opA(h, Lv, false, SELL_AX, 0, -1, Lv.u.p, nullptr, Lv.r.p, k, nullptr));
+    HIPCHK(op_A<double>(h, Lv, false, SELL_AX, 0, -1, Lv.u.p, nullptr, Lv.r.p, k, nullptr));
     return get_block(h, lv, Lv.r.p, k, Au);
 }
 
@@ -779,7 +717,7 @@ extern "C" int smg_relax(smg_hierarchy* h, int lv, const double* B, int k, int i
     if ((rc = prepare_sweep_plans(h, k, iters, iters))) return rc;
     if ((rc = put_block(h, lv, B, k, Lv.b.p))) return rc;
     if ((rc = put_block(h, lv, u, k, Lv.u.p))) return rc;
-    if ((rc = enqueue_relax(h, lv, Lv.b.p, Lv.u.p, k, iters, nullptr))) return rc;
+    if ((rc = enqueue_relax_into(h, lv, Lv.b.p, Lv.u.p, k, iters, nullptr))) return rc;
     return get_block(h, lv, Lv.u.p, k, u);
 }
 
@@ -792,7 +730,7 @@ extern "C" int smg_coarse_solve(smg_hierarchy* h, const double* B, int k, double
     Level& Lv = h->lv[lv];
     if ((rc = put_block(h, lv, B, k, Lv.b.p))) return rc;
     if ((rc = put_block(h, lv, u, k, Lv.u.p))) return rc;
-    HIPCHK(Prec<double>::coarse(h, Lv, k, nullptr));
+    HIPCHK(coarse_solve<double>(h, Lv, k, nullptr));
     return get_block(h, lv, Lv.u.p, k, u);
 }
 
@@ -852,14 +790,13 @@ struct HookCtrlReset {
     ~HookCtrlReset() { if (reset_ctrl(h, 1) == SMG_OK) (void)hipStreamSynchronize(h->stream); }
 };
 
-// Every fp32 vector a launch of the cycle may write -- b32, u32, r32, t32, d32 of every level, the Schur solver's g32 / xs32 -- whole
+// Every fp32 vector a launch of the cycle may write -- the LevelVecs<float> of every level, the Schur solver's g32 / xs32 -- whole
 // allocations, as bytes: with the done flag set none of them may change between the uploads and the end of the launches.
 static int snapshot_f32(smg_hierarchy* h, std::vector<float>& out)
 {
     out.clear();
     std::vector<const DevBuf<float>*> bufs;
-    for (Level& Lv : h->lv)
-        for (const DevBuf<float>* b : {&Lv.b32, &Lv.u32, &Lv.r32, &Lv.t32, &Lv.d32}) bufs.push_back(b);
+    for (const Level& Lv : h->lv) LevelVecs<float>::each(Lv.f32, [&](const DevBuf<float>& v) { bufs.push_back(&v); });
     bufs.push_back(&h->sch.g32); bufs.push_back(&h->sch.xs32);
     size_t total = 0;
     for (const DevBuf<float>* b : bufs) total += b->n;
@@ -885,21 +822,6 @@ static int block_changed(smg_hierarchy* h, int lv, const T* dev, int k, const T*
     return SMG_OK;
 }
 
-// relax(iters) of the fp32 cycle on Lv.b32 / Lv.u32: *res = the buffer the result is in (u32 or, after an odd number of Jacobi-type
-// launches, t32 -- the cycle itself arranges its prolongation so that the last sweep lands in u32, see enqueue_vcycle_t)
-static int enqueue_relax_f32(smg_hierarchy* h, int lv, int k, int iters, const Ctrl* ctrl, float** res)
-{
-    Level& Lv = h->lv[lv];
-    const int kind = level_kind(h, lv);
-    float* const buf[2] = {Lv.u32.p, Lv.t32.p};
-    int cur = 0, rc;
-    if (kind == LV_GS) rc = enqueue_gs<float>(h, lv, sweep_plan(h, lv, k, iters, false, FIRST_NONE), Lv.b32.p, Lv.u32.p, k, iters, ctrl);
-    else if (kind == LV_CHEBY) rc = enqueue_cheby<float>(h, lv, Lv.b32.p, buf, &cur, k, iters, ctrl);
-    else rc = enqueue_jacobi<float>(h, lv, Lv.b32.p, buf, &cur, k, iters, ctrl);
-    *res = buf[cur];
-    return rc;
-}
-
 extern "C" int smg_debug_cycle_f32(smg_hierarchy* h, int op, int lv, int k, int pre, int post, int done, const float* in0, const float* in1,
                                    float* out, int* inputs_changed)
 {
@@ -919,74 +841,76 @@ extern "C" int smg_debug_cycle_f32(smg_hierarchy* h, int op, int lv, int k, int 
         const Ctrl* ctrl = h->d_ctrl.p;
         const int L = h->n_levels;
         Level& Lv = h->lv[lv];
+        LevelVecs<float>& F = Lv.f32;
         int changed = 0;
         std::vector<float> before, after;
         auto uploaded = [&]() -> int { return done ? snapshot_f32(h, before) : SMG_OK; };   // called between an op's uploads and its launches
         switch (op) {
             case SMG_F32_A:          // out = A in0
-                if ((rc = put_block<float>(h, lv, in0, k, Lv.u32.p))) return rc;
-                if ((rc = put_block<float>(h, lv, out, k, Lv.r32.p)) || (rc = uploaded())) return rc;
-                HIPCHK(Prec<float>::opA(h, Lv, false, SELL_AX, 0, -1, Lv.u32.p, nullptr, Lv.r32.p, k, ctrl));
-                if ((rc = block_changed<float>(h, lv, Lv.u32.p, k, in0, &changed))) return rc;
-                rc = get_block<float>(h, lv, Lv.r32.p, k, out);
+                if ((rc = put_block<float>(h, lv, in0, k, F.u.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, F.r.p)) || (rc = uploaded())) return rc;
+                HIPCHK(op_A<float>(h, Lv, false, SELL_AX, 0, -1, F.u.p, nullptr, F.r.p, k, ctrl));
+                if ((rc = block_changed<float>(h, lv, F.u.p, k, in0, &changed))) return rc;
+                rc = get_block<float>(h, lv, F.r.p, k, out);
                 break;
             case SMG_F32_RESID:      // out = in0 - A in1: the residual launch of the cycle
-                if ((rc = put_block<float>(h, lv, in0, k, Lv.b32.p))) return rc;
-                if ((rc = put_block<float>(h, lv, in1, k, Lv.u32.p))) return rc;
-                if ((rc = put_block<float>(h, lv, out, k, Lv.r32.p)) || (rc = uploaded())) return rc;
-                HIPCHK(Prec<float>::opA(h, Lv, false, SELL_RESID, 0, -1, Lv.u32.p, Lv.b32.p, Lv.r32.p, k, ctrl));
-                if ((rc = block_changed<float>(h, lv, Lv.b32.p, k, in0, &changed))) return rc;
-                if ((rc = block_changed<float>(h, lv, Lv.u32.p, k, in1, &changed))) return rc;
-                rc = get_block<float>(h, lv, Lv.r32.p, k, out);
+                if ((rc = put_block<float>(h, lv, in0, k, F.b.p))) return rc;
+                if ((rc = put_block<float>(h, lv, in1, k, F.u.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, F.r.p)) || (rc = uploaded())) return rc;
+                HIPCHK(op_A<float>(h, Lv, false, SELL_RESID, 0, -1, F.u.p, F.b.p, F.r.p, k, ctrl));
+                if ((rc = block_changed<float>(h, lv, F.b.p, k, in0, &changed))) return rc;
+                if ((rc = block_changed<float>(h, lv, F.u.p, k, in1, &changed))) return rc;
+                rc = get_block<float>(h, lv, F.r.p, k, out);
                 break;
             case SMG_F32_RESTRICT: { // out = [PT in0 | the zeroed coarse iterate]: the restriction launch without a fused first launch
                 Level& Lc = h->lv[lv + 1];
+                LevelVecs<float>& Fc = Lc.f32;
                 const size_t cc = (size_t)Lc.n * k;
-                if ((rc = put_block<float>(h, lv, in0, k, Lv.r32.p))) return rc;
-                if ((rc = put_block<float>(h, lv + 1, out, k, Lc.b32.p))) return rc;
-                if ((rc = put_block<float>(h, lv + 1, out + cc, k, Lc.u32.p)) || (rc = uploaded())) return rc;
-                HIPCHK(Prec<float>::sell(SELL_AX, Prec<float>::PT(Lc), 0, Prec<float>::PT(Lc).n_slices, Lv.r32.p, nullptr, Lc.b32.p, k * h->bs, ctrl, h->stream, Lc.u32.p,
-                                         nullptr));
-                if ((rc = block_changed<float>(h, lv, Lv.r32.p, k, in0, &changed))) return rc;
-                if ((rc = get_block<float>(h, lv + 1, Lc.b32.p, k, out))) return rc;
-                rc = get_block<float>(h, lv + 1, Lc.u32.p, k, out + cc);
+                if ((rc = put_block<float>(h, lv, in0, k, F.r.p))) return rc;
+                if ((rc = put_block<float>(h, lv + 1, out, k, Fc.b.p))) return rc;
+                if ((rc = put_block<float>(h, lv + 1, out + cc, k, Fc.u.p)) || (rc = uploaded())) return rc;
+                HIPCHK(launch_sell(SELL_AX, Lc.dPT.view, 0, Lc.dPT.view.n_slices, F.r.p, nullptr, Fc.b.p, k * h->bs, ctrl, nullptr, nullptr, h->stream, Fc.u.p));
+                if ((rc = block_changed<float>(h, lv, F.r.p, k, in0, &changed))) return rc;
+                if ((rc = get_block<float>(h, lv + 1, Fc.b.p, k, out))) return rc;
+                rc = get_block<float>(h, lv + 1, Fc.u.p, k, out + cc);
                 break;
             }
             case SMG_F32_PROLONG_ADD: { // out += P in0
                 Level& Lc = h->lv[lv + 1];
-                if ((rc = put_block<float>(h, lv + 1, in0, k, Lc.u32.p))) return rc;
-                if ((rc = put_block<float>(h, lv, out, k, Lv.u32.p)) || (rc = uploaded())) return rc;
-                HIPCHK(Prec<float>::sell(SELL_ADD, Prec<float>::P(Lc), 0, Prec<float>::P(Lc).n_slices, Lc.u32.p, Lv.u32.p, Lv.u32.p, k * h->bs, ctrl, h->stream));
-                if ((rc = block_changed<float>(h, lv + 1, Lc.u32.p, k, in0, &changed))) return rc;
-                rc = get_block<float>(h, lv, Lv.u32.p, k, out);
+                LevelVecs<float>& Fc = Lc.f32;
+                if ((rc = put_block<float>(h, lv + 1, in0, k, Fc.u.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, F.u.p)) || (rc = uploaded())) return rc;
+                HIPCHK(launch_sell(SELL_ADD, Lc.dP.view, 0, Lc.dP.view.n_slices, Fc.u.p, F.u.p, F.u.p, k * h->bs, ctrl, nullptr, nullptr, h->stream));
+                if ((rc = block_changed<float>(h, lv + 1, Fc.u.p, k, in0, &changed))) return rc;
+                rc = get_block<float>(h, lv, F.u.p, k, out);
                 break;
             }
             case SMG_F32_RELAX: {    // out = relax(pre) of out with right-hand side in0
-                if ((rc = put_block<float>(h, lv, in0, k, Lv.b32.p))) return rc;
-                if ((rc = put_block<float>(h, lv, out, k, Lv.u32.p))) return rc;
-                if (level_is_jacobi(h, lv) && (rc = put_block<float>(h, lv, out, k, Lv.t32.p))) return rc;   // the second iterate: an output, too
+                if ((rc = put_block<float>(h, lv, in0, k, F.b.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, F.u.p))) return rc;
+                if (level_is_jacobi(h, lv) && (rc = put_block<float>(h, lv, out, k, F.t.p))) return rc;   // the second iterate: an output, too
                 float* res = nullptr;
                 if ((rc = uploaded())) return rc;
-                if ((rc = enqueue_relax_f32(h, lv, k, pre, ctrl, &res))) return rc;
-                if ((rc = block_changed<float>(h, lv, Lv.b32.p, k, in0, &changed))) return rc;
+                if ((rc = enqueue_relax<float>(h, lv, F.b.p, F.u.p, k, pre, ctrl, &res))) return rc;
+                if ((rc = block_changed<float>(h, lv, F.b.p, k, in0, &changed))) return rc;
                 rc = get_block<float>(h, lv, res, k, out);
                 break;
             }
             case SMG_F32_COARSE:     // out += A^-1 in0 on the coarsest level
-                if ((rc = put_block<float>(h, lv, in0, k, Lv.b32.p))) return rc;
-                if ((rc = put_block<float>(h, lv, out, k, Lv.u32.p)) || (rc = uploaded())) return rc;
-                HIPCHK(Prec<float>::coarse(h, Lv, k, ctrl));
-                if ((rc = block_changed<float>(h, lv, Lv.b32.p, k, in0, &changed))) return rc;
-                rc = get_block<float>(h, lv, Lv.u32.p, k, out);
+                if ((rc = put_block<float>(h, lv, in0, k, F.b.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, F.u.p)) || (rc = uploaded())) return rc;
+                HIPCHK(coarse_solve<float>(h, Lv, k, ctrl));
+                if ((rc = block_changed<float>(h, lv, F.b.p, k, in0, &changed))) return rc;
+                rc = get_block<float>(h, lv, F.u.p, k, out);
                 break;
             case SMG_F32_VCYCLE:     // out = V(pre, post) from level lv with right-hand side in0
-                if ((rc = put_block<float>(h, lv, in0, k, Lv.b32.p))) return rc;
-                if ((rc = put_block<float>(h, lv, out, k, Lv.u32.p))) return rc;
-                if (lv < L - 1 && level_is_jacobi(h, lv) && (rc = put_block<float>(h, lv, out, k, Lv.t32.p))) return rc;
+                if ((rc = put_block<float>(h, lv, in0, k, F.b.p))) return rc;
+                if ((rc = put_block<float>(h, lv, out, k, F.u.p))) return rc;
+                if (lv < L - 1 && level_is_jacobi(h, lv) && (rc = put_block<float>(h, lv, out, k, F.t.p))) return rc;
                 if ((rc = uploaded())) return rc;
                 if ((rc = enqueue_vcycle_t<float>(h, lv, k, pre, post, ctrl))) return rc;
-                if ((rc = block_changed<float>(h, lv, Lv.b32.p, k, in0, &changed))) return rc;
-                rc = get_block<float>(h, lv, Lv.u32.p, k, out);
+                if ((rc = block_changed<float>(h, lv, F.b.p, k, in0, &changed))) return rc;
+                rc = get_block<float>(h, lv, F.u.p, k, out);
                 break;
         }
         if (rc) return rc;
@@ -1016,6 +940,7 @@ extern "C" int smg_debug_convert_f32(smg_hierarchy* h, int op, int k, int done, 
         if ((rc = hook_ctrl(h, done))) return rc;
         const Ctrl* ctrl = h->d_ctrl.p;
         Level& L0 = h->lv[0];
+        LevelVecs<float>& F = L0.f32;
         const size_t cnt = (size_t)L0.n * k;
         int changed = 0;
         // sentinel bytes behind the block, checked after the launch, then cleared again (the buffers start out as zeros)
@@ -1034,23 +959,23 @@ extern "C" int smg_debug_convert_f32(smg_hierarchy* h, int op, int k, int done, 
         if (op == SMG_F32_RESIDUAL_TO_F32) {      // b32 = (float) r, u32 = 0
             if (h->n_levels < 2) return fail(SMG_ERR_INVALID, "smg_debug_convert_f32: a one-level handle has no residual vector");
             if ((rc = put_block<double>(h, 0, in64, k, L0.r.p))) return rc;
-            if ((rc = put_block<float>(h, 0, out_b32, k, L0.b32.p))) return rc;
-            if ((rc = put_block<float>(h, 0, out_u32, k, L0.u32.p))) return rc;
-            if ((rc = tail_fill(L0.b32.p, L0.b32.n, sizeof(float), 0x5B)) || (rc = tail_fill(L0.u32.p, L0.u32.n, sizeof(float), 0x5B))) return rc;
-            HIPCHK(launch_residual_to_f32(L0.b32.p, L0.u32.p, L0.r.p, cnt, ctrl, h->stream));
-            if ((rc = tail_check(L0.b32.p, L0.b32.n, sizeof(float))) || (rc = tail_check(L0.u32.p, L0.u32.n, sizeof(float)))) return rc;
-            if ((rc = tail_fill(L0.b32.p, L0.b32.n, sizeof(float), 0)) || (rc = tail_fill(L0.u32.p, L0.u32.n, sizeof(float), 0))) return rc;
+            if ((rc = put_block<float>(h, 0, out_b32, k, F.b.p))) return rc;
+            if ((rc = put_block<float>(h, 0, out_u32, k, F.u.p))) return rc;
+            if ((rc = tail_fill(F.b.p, F.b.n, sizeof(float), 0x5B)) || (rc = tail_fill(F.u.p, F.u.n, sizeof(float), 0x5B))) return rc;
+            HIPCHK(launch_residual_to_f32(F.b.p, F.u.p, L0.r.p, cnt, ctrl, h->stream));
+            if ((rc = tail_check(F.b.p, F.b.n, sizeof(float))) || (rc = tail_check(F.u.p, F.u.n, sizeof(float)))) return rc;
+            if ((rc = tail_fill(F.b.p, F.b.n, sizeof(float), 0)) || (rc = tail_fill(F.u.p, F.u.n, sizeof(float), 0))) return rc;
             if ((rc = block_changed<double>(h, 0, L0.r.p, k, in64, &changed))) return rc;
-            if ((rc = get_block<float>(h, 0, L0.b32.p, k, out_b32))) return rc;
-            if ((rc = get_block<float>(h, 0, L0.u32.p, k, out_u32))) return rc;
+            if ((rc = get_block<float>(h, 0, F.b.p, k, out_b32))) return rc;
+            if ((rc = get_block<float>(h, 0, F.u.p, k, out_u32))) return rc;
         } else {                                  // z += (double) e
             if ((rc = put_block<double>(h, 0, out64, k, L0.u.p))) return rc;
-            if ((rc = put_block<float>(h, 0, in32, k, L0.u32.p))) return rc;
+            if ((rc = put_block<float>(h, 0, in32, k, F.u.p))) return rc;
             if ((rc = tail_fill(L0.u.p, L0.u.n, sizeof(double), 0x5B))) return rc;
-            HIPCHK(launch_add_correction(L0.u.p, L0.u32.p, cnt, ctrl, h->stream));
+            HIPCHK(launch_add_correction(L0.u.p, F.u.p, cnt, ctrl, h->stream));
             if ((rc = tail_check(L0.u.p, L0.u.n, sizeof(double)))) return rc;
             if ((rc = tail_fill(L0.u.p, L0.u.n, sizeof(double), 0))) return rc;
-            if ((rc = block_changed<float>(h, 0, L0.u32.p, k, in32, &changed))) return rc;
+            if ((rc = block_changed<float>(h, 0, F.u.p, k, in32, &changed))) return rc;
             if ((rc = get_block<double>(h, 0, L0.u.p, k, out64))) return rc;
         }
         if (inputs_changed) *inputs_changed = changed;
@@ -1085,7 +1010,7 @@ extern "C" int smg_raw_spmv_f32(smg_hierarchy* h, int lv, const float* x, float*
     if ((rc = ensure_work(h, k))) return rc;
     if ((rc = ensure_fp32(h, k))) return rc;
     Level& Lv = h->lv[lv];
-    HIPCHK(launch_sell_f32(SELL_AX, Lv.dA32, 0, Lv.dA32.n_slices, x, nullptr, y, k, nullptr, h->stream));
+    HIPCHK(launch_sell(SELL_AX, Lv.dA.view, 0, Lv.dA.view.n_slices, x, nullptr, y, k, nullptr, nullptr, nullptr, h->stream));
     return SMG_OK;
 }
 
@@ -1097,7 +1022,7 @@ extern "C" int smg_raw_relax(smg_hierarchy* h, int lv, const double* b, double* 
     if (lv < 0 || lv >= h->n_levels - 1 || k < 1) return fail(SMG_ERR_INVALID, "smg_raw_relax: bad level");
     if ((rc = ensure_work(h, k))) return rc;   // second iterate / update vector / spectral bound of a Jacobi-type level
     if ((rc = prepare_sweep_plans(h, k, iters, iters))) return rc;
-    return enqueue_relax(h, lv, b, u, k, iters, nullptr);
+    return enqueue_relax_into(h, lv, b, u, k, iters, nullptr);
 }
 
 // Algorithmic bytes of one outer iteration OF THE CYCLE THE HANDLE IS SET TO RUN (smoother selection of the

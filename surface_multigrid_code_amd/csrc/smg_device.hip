@@ -583,20 +583,15 @@ __global__ __launch_bounds__(256) void k_long_ax_cols(const int* rows, const int
         }
     }
 }
-template <typename T> static const T* host_long_vals(const SellDev& A);
-template <> const double* host_long_vals<double>(const SellDev& A) { return A.long_val; }
-template <> const float* host_long_vals<float>(const SellDev& A) { return A.long_valf; }
-
-template <typename T> static const T* host_vals(const SellDev& A);
 template <typename T> static CoarseInit<T> coarse_init(T* zero_rows, int c0, const FirstColour* first, double omega)
 {
     CoarseInit<T> z{zero_rows ? zero_rows + c0 : nullptr, nullptr, nullptr, 0, 0, (T)omega, nullptr, (T)0};
     if (first) {   // Chebyshev step / fused first Chebyshev step: the update vector and the old update's coefficient
-        if constexpr (std::is_same<T, double>::value) z.d = first->d ? first->d + c0 : nullptr; else z.d = first->df ? first->df + c0 : nullptr;
+        z.d = first->update<T>() ? first->update<T>() + c0 : nullptr;
         z.c1 = (T)first->c1;
     }
     if (zero_rows && first && first->n_first > 0) {
-        if constexpr (std::is_same<T, double>::value) z.gs_val = first->val; else z.gs_val = first->valf;
+        z.gs_val = first->vals<T>();
         z.diag_slot = first->diag_slot;
         z.n_first = (z.gs_val && z.diag_slot) ? first->n_first : 0;
         z.jacobi = first->jacobi;
@@ -604,16 +599,12 @@ template <typename T> static CoarseInit<T> coarse_init(T* zero_rows, int c0, con
     }
     return z;
 }
-template <> const double* host_vals<double>(const SellDev& A) { return A.val; }
-template <> const float* host_vals<float>(const SellDev& A) { return A.valf; }
 // coarse_init plus the weight-code table of A (SellDev::codes)
 template <typename T> static CoarseInit<T> coarse_codes(const SellDev& A, T* zero_rows, int c0, const FirstColour* first, double omega)
 {
     CoarseInit<T> z = coarse_init<T>(zero_rows, c0, first, omega);
     z.codes = A.codes;
-    for (int i = 0; i < 4; i++) {
-        if constexpr (std::is_same<T, double>::value) z.tab[i] = A.tab[i]; else z.tab[i] = A.tabf[i];
-    }
+    for (int i = 0; i < 4; i++) z.tab[i] = A.table<T>()[i];
     return z;
 }
 
@@ -634,7 +625,7 @@ static void launch_wide_one(const SellDev& A, int s_begin, int s_end, int use_or
     // 239 -> 264 us per Chebyshev cycle with one row per lane, 292 with two rows and batches of 32)
     if constexpr (KW < 64) if (wide_latency_variant(ns, KW)) {
         const int nb = (ns * KW + 3) / 4;   // 64 / G = KW waves per slice with one row per lane
-#define SMG_WIDE_LAT(UU) hipLaunchKernelGGL((k_sell_wide<MODE, KW, T, 1, UU>), dim3(nb), dim3(256), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, \
+#define SMG_WIDE_LAT(UU) hipLaunchKernelGGL((k_sell_wide<MODE, KW, T, 1, UU>), dim3(nb), dim3(256), 0, st, A.col, A.vals<T>(), A.order, A.slice_off, A.stride, \
                                              s_begin, s_end, nb, use_order, x, A.slice_row, A.slice_w, b, y, k, done, partials, zero_rows)
         if (A.w_max <= 8) SMG_WIDE_LAT(8);
         else if (A.w_max <= 16) SMG_WIDE_LAT(16);
@@ -645,7 +636,7 @@ static void launch_wide_one(const SellDev& A, int s_begin, int s_end, int use_or
     }
     const int waves = ns * (KW / 2);  // 64 / (R * G) waves per slice, R = 2
     const int nb = (waves + 3) / 4;
-    hipLaunchKernelGGL((k_sell_wide<MODE, KW, T>), dim3(nb), dim3(256), 0, st, A.col, host_vals<T>(A), A.order, A.slice_off, A.stride, s_begin, s_end, nb, use_order, x,
+    hipLaunchKernelGGL((k_sell_wide<MODE, KW, T>), dim3(nb), dim3(256), 0, st, A.col, A.vals<T>(), A.order, A.slice_off, A.stride, s_begin, s_end, nb, use_order, x,
                        A.slice_row, A.slice_w, b, y, k, done, partials, zero_rows);
     *nb_out = nb;
 }
@@ -664,10 +655,29 @@ static int gs_wpb() { static const int v = getenv("SMG_GS_WPB") ? atoi(getenv("S
 int sell_blocks(int n_slices) { return (n_slices + sell_wpb() - 1) / sell_wpb(); }
 
 // the narrow launches (kb <= 4 columns per lane) of one group of columns; CODED: the matrix holds weight codes (SELL_AX / SELL_ADD only)
-template <int MODE, typename T, bool CODED>
-static void launch_narrow(const SellDev& A, int kb, int nb, int ns, int grid, int nbarg, bool one_xcd, int s_begin, int s_end, int use_order, const T* xx,
-                          const T* bb, T* yy, int k, const int* done, double* pp, const CoarseInit<T>& zz, hipStream_t st)
+template <typename T>
+struct NarrowRun {   // what every variant below is launched with
+    int s_begin, s_end, use_order;
+    const T *xx, *bb;
+    T* yy;
+    int k;
+    const int* done;
+    double* pp;
+    const CoarseInit<T>& zz;
+    hipStream_t st;
+};
+// W0C: the look-ahead count fixed at compile time (-1: read from the matrix); WPB: waves per workgroup
+template <int MODE, int KB, typename T, int W0C, int WPB, bool CODED>
+static void narrow_one(const SellDev& A, int grid, int nbarg, const NarrowRun<T>& R)
 {
+    hipLaunchKernelGGL((k_sell<MODE, KB, T, W0C, WPB, CODED>), dim3(grid), dim3(64 * WPB), 0, R.st, A.col, CODED ? nullptr : A.vals<T>(), A.order, A.slice_off, A.stride, A.w_lo,
+                       R.s_begin, R.s_end, nbarg, R.use_order, R.xx, A.slice_row, A.slice_w, R.bb, R.yy, R.k, R.done, R.pp, R.zz);
+}
+template <int MODE, typename T, bool CODED>
+static void launch_narrow(const SellDev& A, int kb, int nb, int ns, int grid, int nbarg, bool one_xcd, const NarrowRun<T>& R)
+{
+    static_assert(sell_wpb() == 4, "the narrow kernels below are instantiated for 4 waves per workgroup");
+    const bool w7 = A.stride > 0 && A.w_lo == 7;
     switch (kb) {
         case 1: {
             // the usual widths get kernels with the look-ahead count fixed at compile time (no branch per panel column)
@@ -677,26 +687,26 @@ static void launch_narrow(const SellDev& A, int kb, int nb, int ns, int grid, in
             // workgroups lose with it)
             static const int pitch_env = getenv("SMG_PITCH_SPEC_MAX") ? atoi(getenv("SMG_PITCH_SPEC_MAX")) : -1;
             const int pitch_max = pitch_env >= 0 ? pitch_env : (sell_is_gs(MODE) ? 32 : 64);
-            if (nb <= pitch_max && A.stride == 12 && w0 >= 7) hipLaunchKernelGGL((k_sell<MODE, 1, T, 12, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-            else if (!CODED && w0 == 7 && MODE == SELL_GS && !one_xcd && gs_wpb() == 8) hipLaunchKernelGGL((k_sell<MODE == SELL_GS ? MODE : SELL_GS, 1, T, 7, 8>), dim3((ns + 7) / 8), dim3(512), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, (ns + 7) / 8, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-            else if (!CODED && w0 == 7 && MODE == SELL_GS && !one_xcd && gs_wpb() == 2) hipLaunchKernelGGL((k_sell<MODE == SELL_GS ? MODE : SELL_GS, 1, T, 7, 2>), dim3((ns + 1) / 2), dim3(128), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, (ns + 1) / 2, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-            else if (w0 == 7) hipLaunchKernelGGL((k_sell<MODE, 1, T, 7, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-            else if (w0 == 8) hipLaunchKernelGGL((k_sell<MODE, 1, T, 8, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-            else if (w0 == 2) hipLaunchKernelGGL((k_sell<MODE, 1, T, 2, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-            else hipLaunchKernelGGL((k_sell<MODE, 1, T, -1, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            if (nb <= pitch_max && A.stride == 12 && w0 >= 7) narrow_one<MODE, 1, T, 12, 4, CODED>(A, grid, nbarg, R);
+            else if (!CODED && w0 == 7 && MODE == SELL_GS && !one_xcd && gs_wpb() == 8) narrow_one<SELL_GS, 1, T, 7, 8, false>(A, (ns + 7) / 8, (ns + 7) / 8, R);
+            else if (!CODED && w0 == 7 && MODE == SELL_GS && !one_xcd && gs_wpb() == 2) narrow_one<SELL_GS, 1, T, 7, 2, false>(A, (ns + 1) / 2, (ns + 1) / 2, R);
+            else if (w0 == 7) narrow_one<MODE, 1, T, 7, 4, CODED>(A, grid, nbarg, R);
+            else if (w0 == 8) narrow_one<MODE, 1, T, 8, 4, CODED>(A, grid, nbarg, R);
+            else if (w0 == 2) narrow_one<MODE, 1, T, 2, 4, CODED>(A, grid, nbarg, R);
+            else narrow_one<MODE, 1, T, -1, 4, CODED>(A, grid, nbarg, R);
             break;
         }
         case 2:
-            if (A.stride > 0 && A.w_lo == 7) hipLaunchKernelGGL((k_sell<MODE, 2, T, 7, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-            else hipLaunchKernelGGL((k_sell<MODE, 2, T, -1, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            if (w7) narrow_one<MODE, 2, T, 7, 4, CODED>(A, grid, nbarg, R);
+            else narrow_one<MODE, 2, T, -1, 4, CODED>(A, grid, nbarg, R);
             break;
         case 3:
-            if (A.stride > 0 && A.w_lo == 7) hipLaunchKernelGGL((k_sell<MODE, 3, T, 7, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-            else hipLaunchKernelGGL((k_sell<MODE, 3, T, -1, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            if (w7) narrow_one<MODE, 3, T, 7, 4, CODED>(A, grid, nbarg, R);
+            else narrow_one<MODE, 3, T, -1, 4, CODED>(A, grid, nbarg, R);
             break;
         default:
-            if (A.stride > 0 && A.w_lo == 7) hipLaunchKernelGGL((k_sell<MODE, 4, T, 7, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
-            else hipLaunchKernelGGL((k_sell<MODE, 4, T, -1, 4, CODED>), dim3(grid), dim3(64 * sell_wpb()), 0, st, A.col, CODED ? nullptr : host_vals<T>(A), A.order, A.slice_off, A.stride, A.w_lo, s_begin, s_end, nbarg, use_order, xx, A.slice_row, A.slice_w, bb, yy, k, done, pp, zz);
+            if (w7) narrow_one<MODE, 4, T, 7, 4, CODED>(A, grid, nbarg, R);
+            else narrow_one<MODE, 4, T, -1, 4, CODED>(A, grid, nbarg, R);
             break;
     }
 }
@@ -775,21 +785,22 @@ static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, 
                 continue;
             }
         }
+        const NarrowRun<T> run{s_begin, s_end, use_order, xx, bb, yy, k, done, pp, zz, st};
         if constexpr (MODE == SELL_AX || MODE == SELL_ADD) {
-            if (A.codes) { launch_narrow<MODE, T, true>(A, kb, nb, ns, grid, nbarg, one_xcd, s_begin, s_end, use_order, xx, bb, yy, k, done, pp, zz, st); continue; }
+            if (A.codes) { launch_narrow<MODE, T, true>(A, kb, nb, ns, grid, nbarg, one_xcd, run); continue; }
         }
-        launch_narrow<MODE, T, false>(A, kb, nb, ns, grid, nbarg, one_xcd, s_begin, s_end, use_order, xx, bb, yy, k, done, pp, zz, st);
+        launch_narrow<MODE, T, false>(A, kb, nb, ns, grid, nbarg, one_xcd, run);
     }
-    if (MODE == SELL_AX && A.long_n > 0 && s_begin == 0 && s_end_in == A.n_slices && host_long_vals<T>(A)) {
+    if (MODE == SELL_AX && A.long_n > 0 && s_begin == 0 && s_end_in == A.n_slices && A.long_vals<T>()) {
         // the long rows of the matrix (their panel rows are empty: the launches above left zeros there), all k columns in one launch
         const CoarseInit<T> zz = coarse_codes<T>(A, zero_rows, 0, first, omega);
         if (k >= 8) {
             const long waves = (long)A.long_n * ((k + 63) / 64);
-            hipLaunchKernelGGL((k_long_ax_cols<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, A.long_row, A.long_ptr, A.long_col, host_long_vals<T>(A), A.long_n, x, y,
+            hipLaunchKernelGGL((k_long_ax_cols<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, A.long_row, A.long_ptr, A.long_col, A.long_vals<T>(), A.long_n, x, y,
                                k, k, done, zz);
         } else {
             const long waves = (long)A.long_n * k;
-            hipLaunchKernelGGL((k_long_ax<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, A.long_row, A.long_ptr, A.long_col, host_long_vals<T>(A), A.long_n, x, y, k, k,
+            hipLaunchKernelGGL((k_long_ax<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, A.long_row, A.long_ptr, A.long_col, A.long_vals<T>(), A.long_n, x, y, k, k,
                                done, zz);
         }
     }
@@ -797,44 +808,24 @@ static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, 
     return hipGetLastError();
 }
 
+// One dispatch for both precisions.  The fp32 twin serves the mixed-precision V-cycle: it needs A.valf (or weight codes), and the modes of
+// sell_fp64_only -- the norms, the level-0 head of an outer iteration, the residual by-product -- are not instantiated for it.
 template <typename T>
 static hipError_t launch_sell_any(SellMode mode, const SellDev& A, int s_begin, int s_end, const T* x, const T* b,
                                   T* y, int k, const Ctrl* ctrl, double* partials, int* n_blocks, hipStream_t st,
                                   T* zero_rows, const FirstColour* first, double omega)
 {
+    constexpr bool fp64 = std::is_same<T, double>::value;
+    if (!fp64 && ((!A.valf && !A.codes) || partials)) return hipErrorInvalidValue;
     switch (mode) {
-        case SELL_JACOBI: return launch_sell_mode<SELL_JACOBI, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-        case SELL_CHEBY: return launch_sell_mode<SELL_CHEBY, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-        case SELL_AX: return launch_sell_mode<SELL_AX, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-        case SELL_RESID: return launch_sell_mode<SELL_RESID, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-        case SELL_RESID_SS:
-            if constexpr (std::is_same<T, double>::value) return launch_sell_mode<SELL_RESID_SS, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
+#define SMG_SELL_CASE(M) \
+        case M: \
+            if constexpr (fp64 || !sell_fp64_only(M)) return launch_sell_mode<M, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega); \
             else return hipErrorInvalidValue;
-        case SELL_ADD: return launch_sell_mode<SELL_ADD, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-        case SELL_GS: return launch_sell_mode<SELL_GS, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-        case SELL_RESID_BOTH:
-            if constexpr (std::is_same<T, double>::value) return launch_sell_mode<SELL_RESID_BOTH, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-            else return hipErrorInvalidValue;
-        // the level-0 head of an outer iteration: fp64 only (the mixed-precision mode keeps its own residual pass)
-        case SELL_GS_OOP:
-            if constexpr (std::is_same<T, double>::value) return launch_sell_mode<SELL_GS_OOP, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-            else return hipErrorInvalidValue;
-        case SELL_GS_HEAD:
-            if constexpr (std::is_same<T, double>::value) return launch_sell_mode<SELL_GS_HEAD, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-            else return hipErrorInvalidValue;
-        case SELL_JACOBI_HEAD:
-            if constexpr (std::is_same<T, double>::value) return launch_sell_mode<SELL_JACOBI_HEAD, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-            else return hipErrorInvalidValue;
-        case SELL_CHEBY_HEAD:
-            if constexpr (std::is_same<T, double>::value) return launch_sell_mode<SELL_CHEBY_HEAD, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-            else return hipErrorInvalidValue;
-        // the V-cycle's level residual out of the last pre-smoothing launch: fp64 only (the fp32 cycle keeps the whole residual launch)
-        case SELL_GS_RES:
-            if constexpr (std::is_same<T, double>::value) return launch_sell_mode<SELL_GS_RES, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-            else return hipErrorInvalidValue;
-        case SELL_GS_OOP_RES:
-            if constexpr (std::is_same<T, double>::value) return launch_sell_mode<SELL_GS_OOP_RES, T>(A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
-            else return hipErrorInvalidValue;
+        SMG_SELL_CASE(SELL_JACOBI) SMG_SELL_CASE(SELL_CHEBY) SMG_SELL_CASE(SELL_AX) SMG_SELL_CASE(SELL_RESID) SMG_SELL_CASE(SELL_RESID_SS)
+        SMG_SELL_CASE(SELL_ADD) SMG_SELL_CASE(SELL_GS) SMG_SELL_CASE(SELL_RESID_BOTH) SMG_SELL_CASE(SELL_GS_OOP) SMG_SELL_CASE(SELL_GS_HEAD)
+        SMG_SELL_CASE(SELL_JACOBI_HEAD) SMG_SELL_CASE(SELL_CHEBY_HEAD) SMG_SELL_CASE(SELL_GS_RES) SMG_SELL_CASE(SELL_GS_OOP_RES)
+#undef SMG_SELL_CASE
     }
     return hipErrorInvalidValue;
 }
@@ -845,13 +836,11 @@ hipError_t launch_sell(SellMode mode, const SellDev& A, int s_begin, int s_end, 
 {
     return launch_sell_any<double>(mode, A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
 }
-
-// fp32 twin for the mixed-precision V-cycle (A.valf must be set, or A hold weight codes; the norm modes are fp64-only)
-hipError_t launch_sell_f32(SellMode mode, const SellDev& A, int s_begin, int s_end, const float* x, const float* b,
-                           float* y, int k, const Ctrl* ctrl, hipStream_t st, float* zero_rows, const FirstColour* first, double omega)
+hipError_t launch_sell(SellMode mode, const SellDev& A, int s_begin, int s_end, const float* x, const float* b,
+                       float* y, int k, const Ctrl* ctrl, double* partials, int* n_blocks, hipStream_t st,
+                       float* zero_rows, const FirstColour* first, double omega)
 {
-    if ((!A.valf && !A.codes) || mode == SELL_RESID_SS || mode == SELL_RESID_BOTH || mode >= SELL_GS_OOP) return hipErrorInvalidValue;
-    return launch_sell_any<float>(mode, A, s_begin, s_end, x, b, y, k, ctrl, nullptr, nullptr, st, zero_rows, first, omega);
+    return launch_sell_any<float>(mode, A, s_begin, s_end, x, b, y, k, ctrl, partials, n_blocks, st, zero_rows, first, omega);
 }
 
 // ---- Gershgorin bound of D^-1 A for the Chebyshev-Jacobi smoother: max over rows of (sum_j |a_ij|) / a_ii, the row sums accumulated in
@@ -1360,27 +1349,23 @@ static hipError_t launch_dense_T(const T* Ainv, int n, int lda, const T* b, T* u
     }
     return hipGetLastError();
 }
-hipError_t launch_sym_gemv_tiles(const double* Ainv, int lda, const double* b, double* part, hipStream_t st)
+template <typename T>
+static hipError_t launch_sym_tiles_T(const T* Ainv, int lda, const T* b, T* part, hipStream_t st)
 {
     if (lda <= 0 || lda % 64) return hipErrorInvalidValue;
     const int nt = lda / 64;
-    hipLaunchKernelGGL((k_sym_gemv_tiles<double>), dim3(nt * (nt + 1) / 2), dim3(256), 0, st, Ainv, lda, b, part, nt);
+    hipLaunchKernelGGL((k_sym_gemv_tiles<T>), dim3(nt * (nt + 1) / 2), dim3(256), 0, st, Ainv, lda, b, part, nt);
     return hipGetLastError();
 }
-hipError_t launch_sym_gemv_tiles_f32(const float* Ainv, int lda, const float* b, float* part, hipStream_t st)
-{
-    if (lda <= 0 || lda % 64) return hipErrorInvalidValue;
-    const int nt = lda / 64;
-    hipLaunchKernelGGL((k_sym_gemv_tiles<float>), dim3(nt * (nt + 1) / 2), dim3(256), 0, st, Ainv, lda, b, part, nt);
-    return hipGetLastError();
-}
+hipError_t launch_sym_gemv_tiles(const double* Ainv, int lda, const double* b, double* part, hipStream_t st) { return launch_sym_tiles_T<double>(Ainv, lda, b, part, st); }
+hipError_t launch_sym_gemv_tiles(const float* Ainv, int lda, const float* b, float* part, hipStream_t st) { return launch_sym_tiles_T<float>(Ainv, lda, b, part, st); }
 hipError_t launch_dense_gemv_add(const double* Ainv, int n, int lda, const double* b, double* u, int k, int ld,
                                  const Ctrl* ctrl, hipStream_t st, double* sym_work)
 {
     return launch_dense_T<double>(Ainv, n, lda, b, u, k, ld, ctrl, st, sym_work);
 }
-hipError_t launch_dense_gemv_add_f32(const float* Ainv, int n, int lda, const float* b, float* u, int k, int ld,
-                                     const Ctrl* ctrl, hipStream_t st, float* sym_work)
+hipError_t launch_dense_gemv_add(const float* Ainv, int n, int lda, const float* b, float* u, int k, int ld,
+                                 const Ctrl* ctrl, hipStream_t st, float* sym_work)
 {
     return launch_dense_T<float>(Ainv, n, lda, b, u, k, ld, ctrl, st, sym_work);
 }

@@ -7,8 +7,14 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+#include <type_traits>
 
 namespace smg {
+
+// Precision is a type: every view below that holds an fp64 member and its fp32 image hands out the one of type T through an accessor
+// (vals<T>() and the like), and this is the one place that says which is which.
+template <typename T, typename D, typename F>
+constexpr auto by_type(D d, F f) { if constexpr (std::is_same<T, double>::value) return d; else return f; }
 
 // Solve-loop control block, resident in HBM.  The outer loop of min_quad_with_fixed_mg_solve
 // (reference src/min_quad_with_fixed_mg.cpp:108-125) is enqueued without host round trips: the decide
@@ -55,6 +61,9 @@ struct SellDev {
     const int* long_col = nullptr;
     const double* long_val = nullptr;
     const float* long_valf = nullptr;
+    template <typename T> const T* vals() const { return by_type<T>(val, valf); }
+    template <typename T> const T* long_vals() const { return by_type<T>(long_val, long_valf); }
+    template <typename T> const T* table() const { return by_type<T>(tab, tabf); }
 };
 
 enum SellMode {
@@ -95,6 +104,8 @@ constexpr bool sell_is_jacobi(int m) { return m == SELL_JACOBI || m == SELL_JACO
 constexpr bool sell_is_cheby(int m) { return m == SELL_CHEBY || m == SELL_CHEBY_HEAD; }
 constexpr bool sell_is_head(int m) { return m == SELL_GS_HEAD || m == SELL_JACOBI_HEAD || m == SELL_CHEBY_HEAD; }
 constexpr bool sell_has_ss(int m) { return sell_is_head(m) || m == SELL_RESID_SS || m == SELL_RESID_BOTH; }
+// no fp32 twin: the norms belong to the fp64 outer loop, and the fp32 cycle keeps its whole first sweep and its whole residual launch
+constexpr bool sell_fp64_only(int m) { return sell_has_ss(m) || sell_is_oop(m) || sell_has_res(m); }
 
 // SELL_ADD: y = b + A x, where b is the iterate the correction is added to (b == nullptr: in place, b = y).
 // y/x/b: internal layout, ld = number of columns k.  Slices [s_begin, s_end).  `ctrl` may be null (no
@@ -117,13 +128,18 @@ struct FirstColour {
                                       // SELL_GS_OOP_RES: where the residual of the launch's rows goes
     float* df = nullptr;              // ... its fp32 twin
     double c1 = 0.0;                  // SELL_CHEBY: coefficient of the old update (0 = first step, d is not read); `omega` is c2
+    template <typename T> const T* vals() const { return by_type<T>(val, valf); }
+    template <typename T> T* update() const { return by_type<T>(d, df); }
+    template <typename T> void set_update(T* p) { if constexpr (std::is_same<T, double>::value) d = p; else df = p; }
 };
 hipError_t launch_sell(SellMode mode, const SellDev& A, int s_begin, int s_end, const double* x, const double* b,
                        double* y, int k, const Ctrl* ctrl, double* partials, int* n_blocks, hipStream_t st,
                        double* zero_rows = nullptr, const FirstColour* first = nullptr, double omega = 1.0);
-hipError_t launch_sell_f32(SellMode mode, const SellDev& A, int s_begin, int s_end, const float* x, const float* b,
-                           float* y, int k, const Ctrl* ctrl, hipStream_t st, float* zero_rows = nullptr,
-                           const FirstColour* first = nullptr, double omega = 1.0);
+// the same on the fp32 image (A.valf, or weight codes) for the mixed-precision V-cycle: the modes without a norm, a head or a residual
+// by-product (sell_fp64_only), partials == nullptr; anything else is hipErrorInvalidValue
+hipError_t launch_sell(SellMode mode, const SellDev& A, int s_begin, int s_end, const float* x, const float* b,
+                       float* y, int k, const Ctrl* ctrl, double* partials, int* n_blocks, hipStream_t st,
+                       float* zero_rows = nullptr, const FirstColour* first = nullptr, double omega = 1.0);
 // *out (device double) = max_i (sum_j |a_ij|) / a_ii over the rows of A: the Gershgorin bound of the spectrum of D^-1 A
 hipError_t launch_gershgorin(const SellDev& A, double* out, hipStream_t st);
 // ---- block (3 degrees of freedom per vertex) matrices: smg_bsr3.hpp (layout), smg_bsr3_device.hip (kernels) ------------------------
@@ -136,15 +152,17 @@ struct Bsr3Dev {
     const int* col = nullptr;        // block columns (vertices), -1 = padding
     const double* val = nullptr;     // nine planes per panel column
     const float* valf = nullptr;     // ... their fp32 image (mixed-precision cycle), or null
+    template <typename T> const T* vals() const { return by_type<T>(val, valf); }
 };
 // modes SELL_AX, _RESID, _RESID_SS, _GS (one vertex colour = slices [s_begin, s_end), in place: y == x), _JACOBI, _CHEBY with the meaning
 // they have per scalar row of the 3n x 3n matrix.  x / b / y / dvec: row-major (3 n_vert) x k.  omega, c1, dvec: as in launch_sell
 // (Jacobi damping; Chebyshev: omega = c2, c1, the update vector).  partials / n_blocks: SELL_RESID_SS, one double per launched block.
 hipError_t launch_bsr3(SellMode mode, const Bsr3Dev& A, int s_begin, int s_end, const double* x, const double* b, double* y, int k, const Ctrl* ctrl,
                        double* partials, int* n_blocks, hipStream_t st, double omega = 1.0, double c1 = 0.0, double* dvec = nullptr);
-// the same on the fp32 image (SELL_AX, _RESID, _GS, _JACOBI, _CHEBY); SELL_RESID_BOTH (fp64 only, above): y = b - A x and the partial sums of its squares
-hipError_t launch_bsr3_f32(SellMode mode, const Bsr3Dev& A, int s_begin, int s_end, const float* x, const float* b, float* y, int k, const Ctrl* ctrl, hipStream_t st,
-                           double omega = 1.0, double c1 = 0.0, float* dvec = nullptr);
+// the same on the fp32 image (A.valf; SELL_AX, _RESID, _GS, _JACOBI, _CHEBY, partials == nullptr); SELL_RESID_BOTH (fp64 only, above): y = b - A x and the
+// partial sums of its squares
+hipError_t launch_bsr3(SellMode mode, const Bsr3Dev& A, int s_begin, int s_end, const float* x, const float* b, float* y, int k, const Ctrl* ctrl,
+                       double* partials, int* n_blocks, hipStream_t st, double omega = 1.0, double c1 = 0.0, float* dvec = nullptr);
 hipError_t launch_bsr3_gershgorin(const Bsr3Dev& A, double* out, hipStream_t st);
 int bsr3_blocks(int n_slices);
 // the image B (laid out on the host, Bsr3Buf::upload of a layout; panel_cols = its panel columns) filled on the device from the scalar CSR arrays of A
@@ -248,6 +266,9 @@ struct SchurDev {
     float *g32 = nullptr, *xs32 = nullptr;
     double* sym_work = nullptr;                      // (ns_pad / 64)^2 x 64: the k = 1 product with S^-1 through its lower triangle
     double* gj_work = nullptr;                       // launch_spd_inverse's scratch for ns_pad
+    template <typename T> const T* factors() const { return by_type<T>(arena, arena32); }
+    template <typename T> T* rhs() const { return by_type<T>(g, g32); }
+    template <typename T> T* sol() const { return by_type<T>(xs, xs32); }
 };
 // arena <- the factorisation of the matrix whose values (CSR order of the plan's matrix) are vals
 hipError_t launch_schur_factor(const SchurDev& F, const double* vals, hipStream_t st);
@@ -255,7 +276,7 @@ hipError_t launch_schur_factor(const SchurDev& F, const double* vals, hipStream_
 hipError_t launch_schur_check(const SchurDev& F, int* d_flag, hipStream_t st);
 // u[:, c] += A^-1 b[:, c] for the k columns of the row-major n x k blocks (caller numbering of the coarsest level)
 hipError_t launch_schur_solve(const SchurDev& F, const double* b, double* u, int k, const Ctrl* ctrl, hipStream_t st);
-hipError_t launch_schur_solve_f32(const SchurDev& F, const float* b, float* u, int k, const Ctrl* ctrl, hipStream_t st);
+hipError_t launch_schur_solve(const SchurDev& F, const float* b, float* u, int k, const Ctrl* ctrl, hipStream_t st);   // on arena32 / g32 / xs32
 
 int sell_blocks(int n_slices);  // 4 slices (waves) per 256-thread block
 int sell_wide_blocks(int n_slices, int k);  // partial-sum slots the wide (k >= 8) path needs
@@ -331,11 +352,11 @@ hipError_t launch_eig_residual(const double* X, const double* AX, const double* 
 // b, u: row-major n x ld blocks of which the first k columns take part (ld >= k)
 hipError_t launch_dense_gemv_add(const double* Ainv, int n, int lda, const double* b, double* u, int k, int ld,
                                  const Ctrl* ctrl, hipStream_t st, double* sym_work = nullptr);
-hipError_t launch_dense_gemv_add_f32(const float* Ainv, int n, int lda, const float* b, float* u, int k, int ld,
-                                     const Ctrl* ctrl, hipStream_t st, float* sym_work = nullptr);
+hipError_t launch_dense_gemv_add(const float* Ainv, int n, int lda, const float* b, float* u, int k, int ld,
+                                 const Ctrl* ctrl, hipStream_t st, float* sym_work = nullptr);
 // first half of the symmetric k = 1 product alone: part[(I * (lda / 64) + J) * 64 + r] = the share of tile (I, J) in row 64 I + r of Ainv b; lda % 64 == 0
 hipError_t launch_sym_gemv_tiles(const double* Ainv, int lda, const double* b, double* part, hipStream_t st);
-hipError_t launch_sym_gemv_tiles_f32(const float* Ainv, int lda, const float* b, float* part, hipStream_t st);
+hipError_t launch_sym_gemv_tiles(const float* Ainv, int lda, const float* b, float* part, hipStream_t st);
 // mixed precision glue
 hipError_t launch_cvt_f64_f32(float* dst, const double* src, size_t n, hipStream_t st);
 hipError_t launch_residual_to_f32(float* b32, float* u32, const double* r64, size_t n, const Ctrl* ctrl, hipStream_t st);

@@ -374,7 +374,7 @@ int eig_update(smg_hierarchy* h, EigRun& R, EigBlocks S, EigBlocks AS, int* nb_u
     ProfGuard pg(h, "EIG: residual");
     const bool f32 = h->precision == 1;
     HIPCHK(launch_eig_residual(h->eig_x[nx].p, h->eig_ax[nx].p, h->eig_mass.p, R.lam, R.n, m, f32 ? nullptr : L0.b.p, f32 ? nullptr : L0.u.p,
-                               f32 ? L0.b32.p : nullptr, f32 ? L0.u32.p : nullptr, h->eig_part.p, R.groups, R.res, R.ctrl, h->stream));
+                               f32 ? L0.f32.b.p : nullptr, f32 ? L0.f32.u.p : nullptr, h->eig_part.p, R.groups, R.res, R.ctrl, h->stream));
     HIPCHK(hipMemcpyAsync(R.hres, R.res, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     return SMG_OK;
 }
@@ -457,7 +457,7 @@ extern "C" int smg_eigs(smg_hierarchy* h, const double* mass_diag, int nev, int 
                     if ((rc = enqueue_vcycle(h, m, R.ctrl, FIRST_NONE))) return rc;
                 }
                 const double* W = L0.u.p;
-                if (f32) { HIPCHK(launch_kry_widen(L0.u32.p, h->eig_w.p, cnt, R.ctrl, h->stream)); W = h->eig_w.p; }
+                if (f32) { HIPCHK(launch_kry_widen(L0.f32.u.p, h->eig_w.p, cnt, R.ctrl, h->stream)); W = h->eig_w.p; }
                 {
                     ProfGuard pg(h, "EIG: SpMV");
                     if ((rc = apply_A(h, 0, SELL_AX, W, nullptr, h->eig_aw.p, m, R.ctrl))) return rc;

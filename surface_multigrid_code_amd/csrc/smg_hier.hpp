@@ -88,6 +88,7 @@ struct DevBuf {
 struct SellBuf {  // device image of one SELL matrix
     DevBuf<int> slice_row, slice_off, slice_w, col, order;
     DevBuf<double> val;
+    DevBuf<float> valf;                      // fp32 image of val (mixed-precision cycle), made on demand by ensure_f32
     SellDev view;
     std::vector<int> color_slice_ptr;
     DevBuf<int> diag_slot;                   // coloured square matrices: slot of a_ii in the value array, per row ...
@@ -95,6 +96,11 @@ struct SellBuf {  // device image of one SELL matrix
     int n_all = 0;                           // ... all rows (0: some row has no stored diagonal), see FirstColour in smg_device.hpp
     long stored = 0, padded = 0, used = 0;   // CSR entries / allocated slots / slots the kernels read
     hipError_t upload(const Sell& S);          // S.col / S.val empty: the panels are allocated only (filled on the device, launch_sell_fill)
+    // The fp32 images follow the matrix: valf = (float) val and long_valf = (float) long_val, converted on st into allocations that are kept while
+    // they are large enough, and view.valf / view.long_valf set to them (view.valf stays null where there is no value array: weight codes, an
+    // empty image).  Every method here that rebuilds the view (upload, upload_long, encode_codes) leaves the two pointers null, and whoever
+    // rewrites val in place lowers smg_hierarchy::f32_valid: the next mixed-precision solve then calls this again before it launches (ensure_fp32).
+    hipError_t ensure_f32(hipStream_t st);
     // A second launch order for the one whole-matrix launch of the V-cycle whose results in some rows nobody reads (order_without_rows,
     // smg_order.hpp): coloured square images leave out the LAST colour's slices (level residual: those rows' residual comes out of the last
     // pre-smoothing launch); a prolongation's image leaves out the slices inside the fine level's FIRST colour (set_part_order from the
@@ -122,7 +128,8 @@ struct Bsr3Buf {  // device image of one block (3 x 3) SELL matrix, smg_bsr3.hpp
     Bsr3Dev view;
     std::vector<int> color_slice_ptr;
     long stored = 0, blocks = 0, padded = 0;   // scalar CSR entries / 3 x 3 blocks / allocated value slots (9 per panel slot)
-    hipError_t upload(const Bsr3Sell& S);
+    hipError_t upload(const Bsr3Sell& S);      // (leaves view.valf null)
+    hipError_t ensure_f32(hipStream_t st);     // valf = (float) val, view.valf: as SellBuf::ensure_f32
 };
 
 // The level values a sweep plan holds copies of -- its entry slots and its diagonals -- and the maps that refresh them from Level::d_Aval
@@ -167,8 +174,19 @@ struct WgsBuf {  // device image of the wave Gauss-Seidel plan of a level (smg_w
     long long bytes() const { return hdr.bytes() + grow.bytes() + meta.bytes() + rim.bytes() + eoff.bytes() + v.bytes(); }
 };
 
+// The work vectors of a level in one precision, internal layout n x kcap (ensure_vectors in smg_cycle.cpp allocates them).
+template <typename T>
+struct LevelVecs {
+    DevBuf<T> b, u, r;
+    DevBuf<T> t;            // second iterate of a Jacobi-smoothed level (the sweeps ping-pong between u and t); allocated on demand
+    DevBuf<T> d;            // update vector of a Chebyshev-Jacobi-smoothed level; allocated on demand
+    template <typename Self, typename F> static void each(Self& s, F f) { f(s.b); f(s.u); f(s.r); f(s.t); f(s.d); }   // the one list of them
+    void release() { each(*this, [](DevBuf<T>& v) { v.release(); }); }
+    long long bytes() const { long long s = 0; each(*this, [&](const DevBuf<T>& v) { s += v.bytes(); }); return s; }
+};
+
 // one element of std::vector<mg_data> (reference src/mg_data.h:11-27)
-struct Level {
+struct Level : LevelVecs<double> {   // the fp64 vectors are Level's own b, u, r, t, d; vecs<T>(level) reaches either precision
     // ---- host, caller numbering: the mg_data fields ----
     std::vector<double> V;  // mg_data::V (optional)
     std::vector<int> F;     // mg_data::F (optional)
@@ -206,16 +224,7 @@ struct Level {
     DevBuf<int> r1_ptr, r1_idx, r2_ptr, r2_idx;
     DevBuf<double> r1_coef, r2_coef;
     int nnzT = 0;
-    // ---- fp32 images for the mixed-precision V-cycle (values only; slots, columns, slice tables are shared) ----
-    DevBuf<float> a32, at32, p32, pt32;
-    SellDev dA32, dAT32, dP32, dPT32;
-    DevBuf<float> b32, u32, r32;
-    // ---- work vectors, internal layout n x kcap ----
-    DevBuf<double> b, u, r;
-    DevBuf<double> t;       // second iterate of a Jacobi-smoothed level (the sweeps ping-pong between u and t); allocated on demand
-    DevBuf<float> t32;
-    DevBuf<double> d;       // update vector of a Chebyshev-Jacobi-smoothed level; allocated on demand
-    DevBuf<float> d32;
+    LevelVecs<float> f32;   // the vectors of the mixed-precision V-cycle (the fp32 images of the matrices live with the matrices: SellBuf / Bsr3Buf::valf)
     double lam = 0.0;       // Gershgorin bound of the spectrum of D^-1 A (D^-1 A^T where the smoother streams A^T), device numbering
     int n = 0;
 };
@@ -261,6 +270,9 @@ struct GraphCache {
         if (s0 <= STEP_PCG && s1 > STEP_PCG) pcg_key = GraphKey();
     }
 };
+
+template <typename T> inline LevelVecs<T>& vecs(Level& L) { if constexpr (std::is_same<T, double>::value) return L; else return L.f32; }
+template <typename T> inline const LevelVecs<T>& vecs(const Level& L) { if constexpr (std::is_same<T, double>::value) return L; else return L.f32; }
 
 struct ProfScope { std::string name; long count = 0; double ms = 0.0; };
 struct ProfRec { int scope; hipEvent_t e0, e1; };
@@ -327,6 +339,8 @@ struct smg_hierarchy {
         smg::DevBuf<float> arena32, g32, xs32;
         smg::SchurDev view;
         void release() { *this = SchurBuf(); }
+        template <typename T> smg::DevBuf<T>& rhs() { if constexpr (std::is_same<T, double>::value) return g; else return g32; }
+        template <typename T> smg::DevBuf<T>& sol() { if constexpr (std::is_same<T, double>::value) return xs; else return xs32; }
     } sch;
     bool f32_valid = false;
     int kcap32 = 0;

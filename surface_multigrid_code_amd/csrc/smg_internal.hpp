@@ -1,7 +1,8 @@
 // smg_internal.hpp -- what the translation units behind the C ABI (include/smg.h) share with each other:
 //   smg_capi.cpp        errors, the handle (container, setters, introspection), profc mirror, mesh numerics shims
 //   smg_precompute.cpp  min_quad_with_fixed_mg_precompute: host sparse algebra, device images, value-only re-precompute, assembly
-//   smg_cycle.cpp       mg_VCycle: level vectors, smoothers, launch sequence of a cycle and of the outer residual, pieces, raw interface
+//   smg_cycle.cpp       mg_VCycle: level vectors, smoothers, launch sequence of a cycle and of the outer residual, pieces, raw interface -- each written
+//                       once for T = double / float (vecs<T>(level), the views' vals<T>(), launchers overloaded on the vectors' type)
 //   smg_solve.cpp       min_quad_with_fixed_mg_solve: the steps of the solve loops and their graph cache, outer loops (stationary, split-phase, sharded, PCG)
 //   smg_sweep_plans.cpp the plan-based Gauss-Seidel sweeps: which one a level uses, building, value refresh, introspection, self-checks
 //   smg_hierarchy_io.cpp mg_precompute / mg_precompute_block builders, point queries, .smgh files
@@ -145,7 +146,7 @@ enum { FIRST_NONE = 0,
 
 int ensure_work(smg_hierarchy* h, int k);         // the level vectors (and sweep plans, spectral bounds) for k internal columns
 int ensure_fp32(smg_hierarchy* h, int k);         // ... and the fp32 images and vectors of the mixed-precision cycle
-// one V-cycle on level 0 with the handle's sweeps and precision: L0.u = V(L0.b, L0.u) (precision 1: L0.u32 = V32(L0.b32, L0.u32)); first: FIRST_* of the fp64 cycle
+// one V-cycle on level 0 with the handle's sweeps and precision: L0.u = V(L0.b, L0.u) (precision 1: the same on vecs<float>(L0)); first: FIRST_* of the fp64 cycle
 int enqueue_vcycle(smg_hierarchy* h, int k, const Ctrl* ctrl, int first);
 int enqueue_residual_ss(smg_hierarchy* h, int k, bool fuse_decide = false, double* sumsq_out = nullptr);   // |RHS_u - A_0 z_u|^2 (+ break test), head-fused or not
 int enqueue_cycle_part(smg_hierarchy* h, int k, const double* d_sumsq);                                     // (break test on *d_sumsq,) the cycle of an outer iteration

@@ -722,10 +722,7 @@ static int device_begin(smg_hierarchy* h)
     HIPCHK(hipStreamSynchronize(h->stream));
     drop_graphs(h);
     drop_sweep_plans(h);
-    for (Level& Lv : h->lv) {
-        Lv.b.release(); Lv.u.release(); Lv.r.release(); Lv.t.release(); Lv.d.release();
-        Lv.b32.release(); Lv.u32.release(); Lv.r32.release(); Lv.t32.release(); Lv.d32.release();
-    }
+    for (Level& Lv : h->lv) { vecs<double>(Lv).release(); vecs<float>(Lv).release(); }
     h->kcap = 0; h->kcap32 = 0; h->f32_valid = false;
     return SMG_OK;
 }

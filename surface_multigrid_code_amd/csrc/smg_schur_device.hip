@@ -385,32 +385,14 @@ __global__ __launch_bounds__(256) void k_schur_x_wide(const T* __restrict__ D, c
         if (r0 + e < nr) { const size_t a = (size_t)ir[r0 + e] * k + col; u[a] += acc[e]; }
 }
 
-template <typename T> struct SchurPtrs;
-template <> struct SchurPtrs<double> {
-    static const double* arena(const SchurDev& F) { return F.arena; }
-    static double* g(const SchurDev& F) { return F.g; }
-    static double* xs(const SchurDev& F) { return F.xs; }
-    static hipError_t dense(const SchurDev& F, int k, const Ctrl* ctrl, hipStream_t st)
-    { return launch_dense_gemv_add(F.arena + F.off_S, F.ns, F.ns_pad, F.g, F.xs, k, k, ctrl, st, nullptr); }
-    static hipError_t tiles(const SchurDev& F, hipStream_t st) { return launch_sym_gemv_tiles(F.arena + F.off_S, F.ns_pad, F.g, F.sym_work, st); }
-};
-template <> struct SchurPtrs<float> {
-    static const float* arena(const SchurDev& F) { return F.arena32; }
-    static float* g(const SchurDev& F) { return F.g32; }
-    static float* xs(const SchurDev& F) { return F.xs32; }
-    static hipError_t dense(const SchurDev& F, int k, const Ctrl* ctrl, hipStream_t st)
-    { return launch_dense_gemv_add_f32(F.arena32 + F.off_S, F.ns, F.ns_pad, F.g32, F.xs32, k, k, ctrl, st, nullptr); }
-    static hipError_t tiles(const SchurDev& F, hipStream_t st) { return launch_sym_gemv_tiles_f32(F.arena32 + F.off_S, F.ns_pad, F.g32, (float*)F.sym_work, st); }
-};
-
 template <typename T>
 hipError_t schur_solve(const SchurDev& F, const T* b, T* u, int k, const Ctrl* ctrl, hipStream_t st)
 {
     if (k <= 0 || F.nb <= 0) return hipSuccess;
     const int* done = ctrl ? &ctrl->done : never_done();
-    const T* A = SchurPtrs<T>::arena(F);
-    T* g = SchurPtrs<T>::g(F);
-    T* xs = SchurPtrs<T>::xs(F);
+    const T* A = F.factors<T>();
+    T* g = F.rhs<T>();
+    T* xs = F.sol<T>();
     if (!A || !g || !xs) return hipErrorInvalidValue;
     const T *D = A + F.off_D, *W = A + F.off_W;
     if (k < 64) {
@@ -418,13 +400,13 @@ hipError_t schur_solve(const SchurDev& F, const T* b, T* u, int k, const Ctrl* c
         hipLaunchKernelGGL((k_schur_g<T>), dim3((F.ns_pad + 3) / 4, gy), dim3(256), 0, st, W, F.irow, F.srow, F.aptr, F.ablk, F.apan, F.ns, F.ns_pad, b, k, g, xs, done);
         if (k == 1 && F.sym_work) {
             // x_S = S^-1 g through the lower triangle of S^-1 (half the bytes); its 64-row shares are summed by the last kernel
-            hipError_t e = SchurPtrs<T>::tiles(F, st);
+            hipError_t e = launch_sym_gemv_tiles(A + F.off_S, F.ns_pad, g, (T*)F.sym_work, st);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL((k_schur_x<T, true>), dim3(F.nb + (F.ns + 255) / 256, 1), dim3(256), 0, st, D, W, F.sptr, F.sidx, F.irow, F.srow, F.nb, F.ns, b,
                                (const T*)F.sym_work, F.ns_pad / 64, k, u, done);
             return hipGetLastError();
         }
-        hipError_t e = SchurPtrs<T>::dense(F, k, ctrl, st);
+        hipError_t e = launch_dense_gemv_add(A + F.off_S, F.ns, F.ns_pad, g, xs, k, k, ctrl, st, nullptr);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((k_schur_x<T, false>), dim3(F.nb + (F.ns * SCHUR_KC + 255) / 256, gy), dim3(256), 0, st, D, W, F.sptr, F.sidx, F.irow, F.srow, F.nb, F.ns, b,
                            (const T*)xs, 0, k, u, done);
@@ -432,7 +414,7 @@ hipError_t schur_solve(const SchurDev& F, const T* b, T* u, int k, const Ctrl* c
         const int gy = (k + 63) / 64;
         hipLaunchKernelGGL((k_schur_g_wide<T>), dim3((F.ns_pad + 3) / 4, gy), dim3(256), 0, st, W, F.irow, F.bsize, F.srow, F.aptr, F.ablk, F.apan, F.ns, F.ns_pad, b, k, g, xs,
                            done);
-        hipError_t e = SchurPtrs<T>::dense(F, k, ctrl, st);
+        hipError_t e = launch_dense_gemv_add(A + F.off_S, F.ns, F.ns_pad, g, xs, k, k, ctrl, st, nullptr);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((k_schur_x_wide<T>), dim3(F.nb * (64 / (4 * SCHUR_XR)) + (F.ns + 3) / 4, gy), dim3(256), 0, st, D, W, F.sptr, F.sidx, F.irow, F.bsize, F.srow, F.nb, F.ns, b, (const T*)xs, k, u,
                            done);
@@ -482,6 +464,6 @@ hipError_t launch_schur_check(const SchurDev& F, int* d_flag, hipStream_t st)
 }
 
 hipError_t launch_schur_solve(const SchurDev& F, const double* b, double* u, int k, const Ctrl* ctrl, hipStream_t st) { return schur_solve<double>(F, b, u, k, ctrl, st); }
-hipError_t launch_schur_solve_f32(const SchurDev& F, const float* b, float* u, int k, const Ctrl* ctrl, hipStream_t st) { return schur_solve<float>(F, b, u, k, ctrl, st); }
+hipError_t launch_schur_solve(const SchurDev& F, const float* b, float* u, int k, const Ctrl* ctrl, hipStream_t st) { return schur_solve<float>(F, b, u, k, ctrl, st); }
 
 }  // namespace smg

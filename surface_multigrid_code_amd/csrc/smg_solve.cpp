@@ -464,7 +464,7 @@ extern "C" int smg_solve(smg_hierarchy* h, const double* RHS, int ld_rhs, const 
 
 // ---- conjugate gradients preconditioned by the V-cycle (include/smg.h: smg_solve_pcg) ------------------------------------------------
 // Flexible (Polak-Ribiere) PCG, one recurrence per column.  The vectors live in the handle's Krylov buffers; the V-cycle
-// keeps its own: its input r goes into L0.b (L0.b32), it starts from L0.u = 0 and leaves z in L0.u.  One iteration:
+// keeps its own: its input r goes into L0.b (L0.f32.b), it starts from L0.u = 0 and leaves z in L0.u.  One iteration:
 //   z = V(r, 0);  rz = z.r, beta = -alpha_prev z.q / rz_prev;  p = z + beta p;  q = A p;  alpha = rz / p.q;  x += alpha p, r -= alpha q;  |r|_F -> r_his
 // and every launch of it starts with `if (done) return`, so iterations enqueued after the break store nothing -- the schedule of the outer loop
 // (run_outer_loop) is smg_solve's.
@@ -501,11 +501,11 @@ static int enqueue_pcg_iteration(smg_hierarchy* h)
     const KryDev& K = h->kry;
     {
         ProfGuard pg(h, "MG: total VCycle");
-        if (h->precision == 1) HIPCHK(launch_residual_to_f32(L0.b32.p, L0.u32.p, h->kry_r.p, cnt, ctrl, h->stream));     // the fp32 cycle: z = (double) V32((float) r, 0)
+        if (h->precision == 1) HIPCHK(launch_residual_to_f32(L0.f32.b.p, L0.f32.u.p, h->kry_r.p, cnt, ctrl, h->stream));     // the fp32 cycle: z = (double) V32((float) r, 0)
         else HIPCHK(launch_kry_precond_in(h->kry_r.p, L0.b.p, L0.u.p, cnt, ctrl, h->stream));
         int rc = enqueue_vcycle(h, k, ctrl, FIRST_NONE);
         if (rc) return rc;
-        if (h->precision == 1) HIPCHK(launch_kry_widen(L0.u32.p, L0.u.p, cnt, ctrl, h->stream));
+        if (h->precision == 1) HIPCHK(launch_kry_widen(L0.f32.u.p, L0.u.p, cnt, ctrl, h->stream));
     }
     ProfGuard pg(h, "PCG: vectors");
     HIPCHK(launch_kry_dots_zr_zq(K, L0.u.p, h->kry_r.p, h->kry_q.p, ctrl, h->stream));

@@ -157,7 +157,7 @@ def cycle_f32(mg, op, lv, in0, in1=None, out=None, pre=0, post=0, done=0, check=
     assert rc == 0, L.smg_last_error()
     if check:
         assert not changed.value & 1, "%s on level %d: a buffer the op only reads was written" % (op, lv)
-        assert not changed.value & 4, "%s on level %d with done = 1: an fp32 vector of the cycle (some level's b32 / u32 / r32 / t32 / d32) was written" % (op, lv)
+        assert not changed.value & 4, "%s on level %d with done = 1: an fp32 vector of the cycle (some level's fp32 b / u / r / t / d) was written" % (op, lv)
         assert changed.value == 0, changed.value
     if op == "RESTRICT":
         return o[:rows_out * k].reshape((rows_out, k), order="F"), o[rows_out * k:].reshape((rows_out, k), order="F")

@@ -45,16 +45,17 @@ def _subdiv(smg, kind):
     return mg
 
 
-def _decimated(smg, name):
+def _decimated(smg, name, with_system=False):
     V, F = M.read_smgm(name)
     V = M.normalize_unit_area(V, F)
     mg = smg.mg_precompute(V, F, 0.25, 500, 1)
     b = M.boundary_loop(F)
     if len(b):
-        mg.precompute((-M.cotmatrix(V, F)).tocsr(), b)
+        A, known = (-M.cotmatrix(V, F)).tocsr(), b
     else:
-        mg.precompute((M.massmatrix(V, F, "barycentric") - 0.01 * M.cotmatrix(V, F)).tocsr())
-    return mg
+        A, known = (M.massmatrix(V, F, "barycentric") - 0.01 * M.cotmatrix(V, F)).tocsr(), None
+    mg.precompute(A, known)
+    return (mg, A, known) if with_system else mg
 
 
 def _random(smg, seed, n, levels, hub):
@@ -91,7 +92,7 @@ def _nonsym(smg):
     return mg
 
 
-def _block(smg, kron=False, pinned=False, schur=False, nVCoarsest=100, nonsym=False):
+def _block(smg, kron=False, pinned=False, schur=False, nVCoarsest=100, nonsym=False, with_system=False):
     from test_gpu_block import elastic_like_system
     V, F = M.read_smgm("ogre_sim.smgm")
     V = M.normalize_unit_area(V, F)
@@ -115,7 +116,7 @@ def _block(smg, kron=False, pinned=False, schur=False, nVCoarsest=100, nonsym=Fa
         mg.set_coarse_schur("always", 1)
     mg.precompute(A, known)
     assert mg.block_size() == 3
-    return mg
+    return (mg, A, known) if with_system else mg
 
 
 BUILDERS = {
@@ -259,7 +260,7 @@ def test_sparse_pieces_on_irregular_tiny_and_unsymmetric_systems_are_the_restate
 
 
 def unsymmetric_checks(smg_mod):
-    """The smoothers must stream the fp32 image of A^T (dAT32 / bAT), everything else that of A.  On matrices whose fp32 images differ from
+    """The smoothers must stream the fp32 image of A^T (dAT / bAT), everything else that of A.  On matrices whose fp32 images differ from
     their mirror images in most entries of every smoothed level -- asserted -- and for which the restatement itself gives other bits when it
     smooths with A instead of A^T -- asserted, for all three smoothers -- the sparse pieces are the restatement bit for bit, and the cycle
     (whose fused first launches take the coarse diagonal from the smoother's image) is the composition of its pieces.  Scalar and block."""
@@ -310,9 +311,67 @@ def test_the_smoothers_stream_the_fp32_image_of_the_transpose(smg, fill_min):
 @pytest.mark.parametrize("k", [1, 2, 3])
 @pytest.mark.parametrize("name", ["block", "block-kron", "block-pinned"])
 def test_sparse_pieces_on_block_hierarchies_are_the_restatement_bit_for_bit(smg, name, k):
-    """launch_bsr3_f32 (3 x 3 blocks; the restatement runs on the scalar 3n x 3n matrix: a block's structural zeros add +-0 to a sum that is
+    """launch_bsr3 on the fp32 image (3 x 3 blocks; the restatement runs on the scalar 3n x 3n matrix: a block's structural zeros add +-0 to a sum that is
     never -0) and the transfers on 3 k columns"""
     check_sparse_pieces(case(smg, name), k, ALL3 if name == "block" else ("gs",))
+
+
+def _more_diagonal(A):
+    """A + diag(0.5 diag A): the same pattern, as symmetric as A, other values"""
+    A2 = (A + 0.5 * sp.diags(A.diagonal())).tocsr()
+    A2.sort_indices()
+    return A2
+
+
+@pytest.mark.parametrize("name", ["subdiv-mcf", "bunny-dec", "block"])
+def test_the_fp32_images_follow_the_matrix(smg, name):
+    """The fp32 images are made on demand from the matrices' current values.  A handle that has run the fp32 pieces -- its images exist -- is
+    given new values for the same pattern (the value-only re-precompute, on the device), values that are not bit-symmetric (the smoothers move to
+    the image of A^T, which did not exist before), and a new pattern (a full precompute on the same handle): after each, the sparse pieces are
+    the restatement on the handle's current matrices, bit for bit.  bunny-dec: long rows and value-carrying transfers; block: 3 x 3 blocks.
+    On the scalar handle's last state a mixed-precision solve returns the bits of a freshly built handle.
+    (The unsymmetric step: D A1 D + diag differs from its transpose in the last bits of a double only -- its fp32 image is symmetric, 0 entries
+    of 284 933 differ -- so every entry is moved by a further 1e-5 relative, _unsymmetric_values: the image of A and that of A^T then differ in
+    most entries, asserted, and a smoother on the wrong one gives other bits.)"""
+    if name == "bunny-dec":
+        mg, A, known = _decimated(smg, "bunny.smgm", with_system=True)
+        steps = [(1, ("gs",)), (3, ALL3)]
+    elif name == "block":
+        mg, A, known = _block(smg, with_system=True)
+        steps = [(1, ("gs",)), (2, ("gs",))]
+    else:
+        p = subdiv_problem(kind="mcf", k=2, n_sub=2)
+        A, known = _csr(p["A"]), p["known"]
+        mg = smg.Hierarchy.from_prolongs(p["Ps"])
+        mg.precompute(A, known)
+        steps = [(1, ("gs",)), (3, ALL3)]
+    mg.set_smoother("gs", OMEGA, -1, FRAC)
+    check_sparse_pieces(Case(mg), steps[0][0], steps[0][1])          # the images now exist
+    A2s = _more_diagonal(A)
+    assert np.array_equal(A2s.indices, _csr(A).indices)
+    mg.precompute(A2s, known)                                        # value-only
+    check_sparse_pieces(Case(mg), steps[1][0], steps[1][1])
+    if name != "subdiv-mcf":
+        return
+    assert (A2s != A2s.T).nnz == 0                                   # (bit-symmetric: the smoothers stayed on the image of A)
+    rng = np.random.default_rng(42)
+    D = sp.diags(1.0 + 0.01 * rng.uniform(size=A.shape[0]))
+    A2 = _unsymmetric_values(_csr(D @ A @ D + sp.diags(rng.uniform(0, 0.5, A.shape[0]) * A.diagonal())))
+    assert np.array_equal(A2.indices, A.indices)
+    mg.precompute(A2, known)                                         # value-only, and no longer symmetric
+    c = Case(mg)
+    assert c.lv[0]["unsym32"] > 0, "the fp32 image of level 0 equals its mirror image: the wrong image would pass"
+    assert c.lv[0]["unsym32"] >= 0.5 * (A2.nnz - A2.shape[0])
+    check_sparse_pieces(c, 2)
+    known2 = np.array([3, 500, 20000], np.int32)                     # another set of unknowns: a new pattern, a full precompute
+    mg.precompute(A, known2)
+    check_sparse_pieces(Case(mg), 1)
+    fresh = smg.Hierarchy.from_prolongs(p["Ps"])
+    fresh.precompute(A, known2)
+    kv = np.zeros((len(known2), 2))
+    o = smg.SolveOpts(tol=1e-9, max_iter=30, precision="mixed")
+    r1, r2 = mg.solve(p["RHS"], p["z0"], kv, o), fresh.solve(p["RHS"], p["z0"], kv, o)
+    assert r1[0] and np.array_equal(r1[1], r2[1]) and np.array_equal(r1[2], r2[2])
 
 
 # ----------------------------------------------------------------------------------------------- coarse solve, derived bounds
@@ -338,7 +397,7 @@ def _coarse_handles(smg):
 
 @pytest.mark.parametrize("k", COARSE_KS)
 def test_dense_coarse_product_within_the_bound_of_its_roundings(smg, k):
-    """u += Ainv32 b with Ainv32 = fl32(A^-1), all three code paths of launch_dense_gemv_add_f32 (k = 1: the symmetric tiles; 2 - 7: a wave
+    """u += Ainv32 b with Ainv32 = fl32(A^-1), all three code paths of the fp32 launch_dense_gemv_add (k = 1: the symmetric tiles; 2 - 7: a wave
     per row; from 16 on 16-column tiles, 8 - 15 as narrow blocks in fp32).  Componentwise
         |got - (u + A^-1 b)| <= (gamma_32(n) + 2 u32) (|A^-1| |b|) + u32 |u + A^-1 b|
       gamma_32(n) |A^-1||b|   n rounded products and up to n rounded additions of a row's sum, in ANY order (tiles, partial sums, trees)
@@ -386,7 +445,7 @@ def _schur_factors(h):
 @pytest.mark.parametrize("k", COARSE_KS)
 @pytest.mark.parametrize("name", ["schur", "block-schur"])
 def test_schur_coarse_solve_within_the_bound_of_its_three_factors(smg, name, k):
-    """launch_schur_solve_f32 is not one product but three stages (csrc/smg_schur.hpp, csrc/smg_schur_device.hip: k_schur_g, the product with
+    """the fp32 launch_schur_solve is not one product but three stages (csrc/smg_schur.hpp, csrc/smg_schur_device.hip: k_schur_g, the product with
     S^-1, k_schur_x), each a sum of products with an fp32 image -- of W = D^-1 P, of S^-1, of D^-1 and W:
         g = b_S - W^T b_I,      x_S = S^-1 g,      x_I = D^-1 b_I - W x_S,      u += x
     so its error carries the size of the intermediates g and x_S, and |A^-1||b| alone does not bound it.  The same reasoning as for the dense

@@ -9,6 +9,7 @@ import pytest
 from test_arap_host import twist
 from test_geodesics_host import icosphere
 from test_gpu_parity import smg  # noqa: F401  (fixture)
+from problems import subdiv_problem
 from test_membrane_host import load_mesh
 
 pytestmark = pytest.mark.gpu
@@ -49,3 +50,26 @@ def test_device_bytes_are_live_buffers_and_destroy_frees_them(smg, which):
     assert 0 < counted == held
     assert after == before
     assert mg.n_levels >= 2
+
+
+def test_a_hierarchy_reports_the_bytes_it_holds_after_a_mixed_solve(smg):
+    """a plain hierarchy handle after an fp64 and a mixed-precision solve -- the fp32 images of its matrices and the fp32 vectors exist --
+    reports, line by line, what it holds: the total of device_bytes() is the growth of the library's count of live DevBuf bytes since before
+    the handle was created, and destroying the handle gives every byte back"""
+    live = smg._lib.load().smg_device_bytes_live
+    p = subdiv_problem(kind="mcf", k=2, n_sub=2)
+    gc.collect()
+    before = live()
+    mg = smg.Hierarchy.from_prolongs(p["Ps"])
+    mg.precompute(p["A"])
+    for precision in ("f64", "mixed"):
+        assert mg.solve(p["RHS"], p["z0"], None, smg.SolveOpts(tol=1e-8, max_iter=30, precision=precision))[0]
+    rep = mg.device_bytes()
+    held = live() - before
+    print("hierarchy: total %d, live DevBuf bytes held %d; fp32 images %d" % (rep["total"], held, sum(v for k, v in rep.items() if k.endswith("fp32_images"))))
+    assert 0 < rep["total"] == held
+    assert rep["total"] == sum(v for k, v in rep.items() if k != "total")
+    assert all(rep.get("level%d.fp32_images" % lv, 0) > 0 for lv in range(mg.n_levels - 1))
+    del mg
+    gc.collect()
+    assert live() == before
