@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 508
+#define SMG_VERSION 509
 
 enum {
     SMG_OK = 0,
@@ -530,6 +530,72 @@ int smg_membrane_lists(const int *F, int nF, int nV, int *n_blocks, int *n_contr
 int smg_membrane_faces_host(const double *V0, const double *P, int nV, const int *F, int nF, const smg_membrane_params *p, int fix, double *W,
                             double *G, double *H);
 
+/* ---- harmonic and as-rigid-as-possible flattening of a disk mesh (Tutte / cotangent-weight harmonic map to a circle; the local / global
+ * iteration of Liu, Zhang, Xu, Gotsman and Gortler 2008) -- an application object on a SCALAR hierarchy --------------------------------------
+ * An addition: the reference has no parameterization.  u is the nV x 2 map.
+ * Rest triangle: face f has corners p0, p1, p2 in the order of F, e1 = p1 - p0, e2 = p2 - p0; its isometric rest triangle in the plane is
+ *     x0 = (0, 0),  x1 = (|e1|, 0),  x2 = (e1 . e2 / |e1|, |e1 x e2| / |e1|).
+ * Weights: c_i, i = 0, 1, 2, is the cotangent of the angle at corner i + 2 (mod 3), the corner opposite edge (i, i + 1), computed from the rest
+ *     triangle.  With these weights -L of smg_assemble is (1/2) sum_f c_i on that edge: the matrix the other objects use.
+ * Energy:      E(R, u) = (1/2) sum_f sum_i c_i |(u_i - u_{i+1}) - R_f (x_i - x_{i+1})|^2
+ * Local step:  S_f = sum_i c_i (u_i - u_{i+1}) (x_i - x_{i+1})^T,  a = S00 + S11,  b = S10 - S01,  h = sqrt(a^2 + b^2),
+ *              R_f = [[a, -b], [b, a]] / h, the identity when h == 0.
+ * Global step: (-L) u = rhs,  rhs_v = sum over the faces at v, v being corner i, of (1/2) R_f (c_i (x_i - x_{i+1}) + c_{i-1} (x_i - x_{i-1}));
+ *              one vertex, the first of the boundary loop, is known with the value it has in the iterate.
+ * Iteration t: rotations from U_t, E_t, the right-hand side, then one 2-column solve warm-started at U_t.  After the last iteration one more
+ *     local step gives the last energy.  Negative cotangents are used as they are; -L is the Dirichlet form and stays semi-definite.  With
+ *     exact solves E_{t+1} <= E_t.
+ * Harmonic start: the longest boundary loop, as smg_mesh_boundary_loop returns it, goes to the circle of the mesh's area (radius
+ *     sqrt(area / pi)); the points are placed by cumulative 3D edge length, starting at angle 0 (libigl's map_vertices_to_circle, scaled);
+ *     (-L)_uu u = -(-L)_ub u_b, 2 columns, from zero.
+ * Distortion of a map, per face: J = [u1 - u0, u2 - u0] [x1, x2]^-1, det J, and the singular values in closed form,
+ *     Q = (1/2) sqrt((J00 + J11)^2 + (J10 - J01)^2),  T = (1/2) sqrt((J00 - J11)^2 + (J10 + J01)^2),  sigma1 = Q + T,  sigma2 = |Q - T|;
+ *     a face is flipped when det J <= 0.
+ * UV blocks are nV x 2 column-major with a leading dimension >= nV; memspace is SMG_HOST or SMG_DEVICE.
+ *
+ * smg_param_create: h gives the prolongations (any scalar hierarchy on this mesh); they are copied in memory into two internal handles, both
+ *   precomputed here with -L: one with the boundary loop known (the harmonic map), one with the loop's first vertex known (the global step).
+ *   h is not modified and may be destroyed afterwards.  V: nV x 3 row-major, F: nF x 3.  The rest triangles, the weights, the vertex ->
+ *   (face, corner) lists (faces ascending) and the scales of the default tolerances are computed here.  SMG_ERR_INVALID, before any device
+ *   work: a null argument, a union handle, a block (3-DOF) hierarchy, nV != the rows of level 0, a face index out of range, a face with zero
+ *   double area, a non-finite coordinate, a mesh of more than one connected component; then the object's own checks, each with its own
+ *   message: an edge shared by more than two faces (or by two faces in the same direction), a closed mesh, more or fewer than one boundary
+ *   loop (an annulus), an Euler characteristic other than 1 (handles), every vertex on the boundary.  SMG_ERR_NO_DEVICE without a GPU.
+ * smg_param_set_solver: pcg = 1 the solves run smg_solve_pcg (the default), 0 smg_solve's stationary loop; < 0 keeps
+ *   the choice.
+ * smg_param_device_bytes: the device memory held by the object -- both internal handles (as smg_debug_device_bytes counts them) and the
+ *   object's own buffers (faces, corner lists, 18 per-face planes, three nV x 2 blocks).
+ * smg_param_boundary: *n_loop (NULL ok) = the length of the boundary loop, loop (NULL ok; n_loop ints) = its vertices in order.
+ * smg_param_harmonic: the harmonic start into UV.  opts: the options of the solve (tol is absolute, as for smg_solve); NULL selects
+ *   smg_solve_opts_default with max_iter = 50 and tol = 1e-8 s, s the Frobenius norm of the reduced right-hand side -(-L)_ub u_b, computed
+ *   once at create.  *cycles (NULL ok): the loop entries of the solve.  The boundary rows of UV are the circle positions themselves.
+ * smg_param_arap: UV0: the start, or NULL = the harmonic map, computed inside with the same opts.  Runs max_iter iterations (>= 0; 0
+ *   returns the start and E_0).  rel_tol > 0 ends the loop before iteration t + 1 when E_t - E_{t+1} <= rel_tol |E_t|; rel_tol == 0 disables
+ *   that test.  energy_his (NULL ok) must hold max_iter + 1 doubles, *n_iter + 1 are written; cycles (NULL ok) must hold max_iter ints: the
+ *   loop entries of each inner solve; *n_iter (NULL ok): the iterations run.  opts == NULL selects smg_solve_opts_default with max_iter = 50
+ *   and tol = 1e-8 s, s = sqrt(sum_v (sum over the faces at v of (1/2) (|c_i| |x_i - x_{i+1}| + |c_{i-1}| |x_i - x_{i-1}|))^2), computed once
+ *   at create: it bounds |rhs|_F for every set of rotations.  An inner solve that ends unconverged is not an error (cycles[t] ==
+ *   opts->max_iter tells); a failing solve's code is returned unchanged; a non-finite energy returns SMG_ERR_NONFINITE.  Everything between
+ *   UV0 and UV stays on the object's stream; per iteration the host reads one energy double beside the inner solve's own history.  Every
+ *   call with the same inputs returns the same bits (graphs on or off, SMG_HOST or SMG_DEVICE).
+ * smg_param_distortion: sigma (NULL ok; in memspace) holds 2 nF doubles in planes, sigma1 then sigma2.  stats is a host array of 6 doubles:
+ *   the number of flipped faces; max sigma1 / sigma2 over the unflipped faces; the rest-area-weighted mean of sigma1 / sigma2 (all faces);
+ *   the same mean of sigma1 sigma2; the rest-area-weighted mean over the unflipped faces of the symmetric Dirichlet density
+ *   sigma1^2 + sigma2^2 + sigma1^-2 + sigma2^-2 (NaN when every face is flipped); the total rest area.  The sums are fixed-order reductions,
+ *   the maximum goes through a tree of the same shape.
+ * Not covered: free-boundary conformal maps (LSCM / ASAP), SLIM and other flip-free energies; meshes with several boundary loops or
+ * handles, seams and cuts; boundary shapes other than the circle; union / block / sharded forms. */
+typedef struct smg_param smg_param;
+int smg_param_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, smg_param **out);
+void smg_param_destroy(smg_param *p);
+int smg_param_set_solver(smg_param *p, int pcg);
+long long smg_param_device_bytes(const smg_param *p);
+int smg_param_boundary(const smg_param *p, int *n_loop, int *loop);
+int smg_param_harmonic(smg_param *p, int memspace, const smg_solve_opts *opts, double *UV, int ld_uv, int *cycles);
+int smg_param_arap(smg_param *p, const double *UV0, int ld_uv0, int memspace, int max_iter, double rel_tol, const smg_solve_opts *opts,
+                   double *UV, int ld_uv, double *energy_his, int *cycles, int *n_iter);
+int smg_param_distortion(smg_param *p, const double *UV, int ld_uv, int memspace, double *sigma, double *stats);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -761,6 +827,21 @@ enum { SMG_MEM_REST = 0, SMG_MEM_FACES_RAW = 1, SMG_MEM_FACES = 2, SMG_MEM_ENERG
        SMG_MEM_GRADIENT = 6, SMG_MEM_OBJECTIVE = 7 };
 int smg_debug_membrane(int op, int nV, int nF, const int *F, const double *V0, const double *P, const double *in, const smg_membrane_params *p,
                        double *out, int *guard_hits);
+
+/* One launcher of the disk parameterization (csrc/smg_param_device.hip), handle-free and guarded like the hooks above.  F: nF x 3, V0: nV x 3
+ * row-major, UV: nV x 2 column-major (leading dimension nV), R_in: the rotations as 2 planes (cos, sin); per-face results are planes (entry e
+ * of face f at [e nF + f]).  out is in/out.
+ *   SMG_PARAM_REST         V0               -> out = the rest constants (6 planes): x1.x, x2.x, x2.y, c0, c1, c2
+ *   SMG_PARAM_COVARIANCE   V0, UV           -> out = S_f (4 planes): S00, S01, S10, S11
+ *   SMG_PARAM_ROTATIONS    V0, UV           -> out = R_f (2 planes): cos, sin
+ *   SMG_PARAM_RHS          V0, R_in         -> out (nV x 2 column-major) = the right-hand side of the global step
+ *   SMG_PARAM_FACE_ENERGY  V0, UV, R_in     -> out[f] = (1/2) sum_i c_i |(u_i - u_{i+1}) - R_f (x_i - x_{i+1})|^2
+ *   SMG_PARAM_ENERGY       V0, UV, R_in     -> out[0] = the sum of those terms (fixed row chunks, fixed-order finalize)
+ *   SMG_PARAM_DISTORTION   V0, UV           -> out = det J, sigma1, sigma2 (3 planes)
+ * SMG_ERR_INVALID for an unknown op, a missing operand or a face index out of range; SMG_ERR_NO_DEVICE without a GPU. */
+enum { SMG_PARAM_REST = 0, SMG_PARAM_COVARIANCE = 1, SMG_PARAM_ROTATIONS = 2, SMG_PARAM_RHS = 3, SMG_PARAM_FACE_ENERGY = 4, SMG_PARAM_ENERGY = 5,
+       SMG_PARAM_DISTORTION = 6 };
+int smg_debug_param(int op, int nV, int nF, const int *F, const double *V0, const double *UV, const double *R_in, double *out, int *guard_hits);
 
 /* ---- profc.h mirror: named scopes accumulated with hipEvents (src/profc.h:9-13; mg_VCycle.cpp:121) ------------- */
 int smg_prof_enable(smg_hierarchy *h, int on);     /* forces eager launches while on */

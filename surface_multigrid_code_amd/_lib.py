@@ -103,6 +103,15 @@ def load():
         "smg_membrane_step": (i, [vp, C.POINTER(SolveOptsC), dp, dp, ip, ip]),
         "smg_membrane_lists": (i, [ip, i, i, ip, ip, ip, ip, ip, ip]),
         "smg_membrane_faces_host": (i, [dp, dp, i, ip, i, C.POINTER(MembraneParamsC), i, dp, dp, dp]),
+        "smg_debug_param": (i, [i, i, i, ip, dp, dp, dp, dp, ip]),
+        "smg_param_create": (i, [vp, dp, i, ip, i, C.POINTER(vp)]),
+        "smg_param_destroy": (None, [vp]),
+        "smg_param_set_solver": (i, [vp, i]),
+        "smg_param_device_bytes": (C.c_longlong, [vp]),
+        "smg_param_boundary": (i, [vp, ip, ip]),
+        "smg_param_harmonic": (i, [vp, i, C.POINTER(SolveOptsC), vp, i, ip]),
+        "smg_param_arap": (i, [vp, vp, i, i, i, d, C.POINTER(SolveOptsC), vp, i, dp, ip, ip]),
+        "smg_param_distortion": (i, [vp, vp, i, i, vp, dp]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

@@ -697,6 +697,96 @@ class ArapDeformer:
         return self._run(hp_ptr, ld_hp or self.handles.shape[0], U0_ptr, ld_u0 or self.n, SMG_DEVICE, max_iter, rel_tol, opts, U_ptr, ld_u or self.n)
 
 
+class Parameterizer:
+    """Harmonic and as-rigid-as-possible flattening of a disk mesh on the V-cycle (include/smg.h: smg_param_*): the cotangent-weight harmonic
+    map to the circle of the mesh's area, and the local / global iteration of Liu et al. 2008 from it.
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F), a disk (one boundary loop, Euler characteristic 1); its prolongations are
+    copied, it is not modified.  The system -L is precomputed here, twice: with the boundary loop known and with its first vertex known."""
+
+    STATS = ("flipped", "max_aspect", "mean_aspect", "mean_area_ratio", "symmetric_dirichlet", "area")
+
+    def __init__(self, hierarchy, V, F):
+        self.L = _lib.load()
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        F = np.ascontiguousarray(F, dtype=np.int32)
+        self.n, self.nF = V.shape[0], F.shape[0]
+        out = C.c_void_p()
+        _chk(self.L.smg_param_create(hierarchy.h, _dp(V), V.shape[0], _ip(F), F.shape[0], C.byref(out)), "smg_param_create")
+        self.p = C.c_void_p(out.value)
+        self.cycles = 0
+
+    def __del__(self):
+        try:
+            if self.p:
+                self.L.smg_param_destroy(self.p)
+                self.p = None
+        except Exception:
+            pass
+
+    def set_solver(self, pcg=-1):
+        """1: the solves run smg_solve_pcg (default), 0: smg_solve's stationary loop, -1: unchanged."""
+        _chk(self.L.smg_param_set_solver(self.p, int(pcg)), "smg_param_set_solver")
+
+    def device_bytes(self):
+        return self.L.smg_param_device_bytes(self.p)
+
+    def boundary(self):
+        """the boundary loop, in order; its first vertex is the one the global step pins"""
+        n = C.c_int(0)
+        _chk(self.L.smg_param_boundary(self.p, C.byref(n), None), "smg_param_boundary")
+        loop = np.zeros(n.value, dtype=np.int32)
+        _chk(self.L.smg_param_boundary(self.p, None, _ip(loop)), "smg_param_boundary")
+        return loop
+
+    @staticmethod
+    def _opts(o):
+        return C.byref(o.c) if o is not None else None
+
+    def harmonic_device(self, UV_ptr, ld_uv=None, opts=None, memspace=SMG_DEVICE):
+        """harmonic() into a column-major n x 2 block resident in HBM (device pointer).  Returns the loop entries of the solve."""
+        cyc = C.c_int(0)
+        _chk(self.L.smg_param_harmonic(self.p, memspace, self._opts(opts), UV_ptr, ld_uv or self.n, C.byref(cyc)), "smg_param_harmonic")
+        self.cycles = cyc.value
+        return self.cycles
+
+    def harmonic(self, opts=None):
+        """The n x 2 harmonic map to the circle; self.cycles = the loop entries of the solve."""
+        UV = np.zeros((self.n, 2), order="F")
+        self.harmonic_device(UV.ctypes.data, self.n, opts, SMG_HOST)
+        return UV
+
+    def flatten_device(self, UV_ptr, ld_uv=None, UV0_ptr=None, ld_uv0=None, max_iter=10, rel_tol=0.0, opts=None, memspace=SMG_DEVICE):
+        """flatten() between column-major n x 2 blocks resident in HBM (device pointers; leading dimensions default to n).  Returns
+        (energy_his, cycles)."""
+        E = np.zeros(max_iter + 1)
+        cyc = np.zeros(max(max_iter, 1), dtype=np.int32)
+        nit = C.c_int(0)
+        _chk(self.L.smg_param_arap(self.p, UV0_ptr, ld_uv0 or self.n, memspace, int(max_iter), float(rel_tol), self._opts(opts), UV_ptr,
+                                   ld_uv or self.n, _dp(E), _ip(cyc), C.byref(nit)), "smg_param_arap")
+        return E[:nit.value + 1].copy(), cyc[:nit.value].copy()
+
+    def flatten(self, UV0=None, max_iter=10, rel_tol=0.0, opts=None):
+        """ARAP flattening from UV0 (n x 2; None = the harmonic map).  Returns (UV, energy_his, cycles): the map after the iterations run,
+        E_0 .. E_n_iter, the loop entries of each inner solve."""
+        UV0 = None if UV0 is None else _colmajor(UV0)
+        assert UV0 is None or UV0.shape == (self.n, 2)
+        UV = np.zeros((self.n, 2), order="F")
+        E, cyc = self.flatten_device(UV.ctypes.data, self.n, UV0.ctypes.data if UV0 is not None else None, self.n, max_iter, rel_tol, opts, SMG_HOST)
+        return UV, E, cyc
+
+    def distortion(self, UV):
+        """(sigma, stats): sigma nF x 2 (the singular values of every face's Jacobian, larger first) and the dict of STATS."""
+        UV = _colmajor(UV)
+        assert UV.shape == (self.n, 2)
+        sigma = np.zeros((self.nF, 2), order="F")
+        st = np.zeros(6)
+        _chk(self.L.smg_param_distortion(self.p, UV.ctypes.data, self.n, SMG_HOST, sigma.ctypes.data, _dp(st)), "smg_param_distortion")
+        stats = dict(zip(self.STATS, st.tolist()))
+        stats["flipped"] = int(stats["flipped"])
+        return sigma, stats
+
+
 class MembraneSim:
     """Implicit-Euler steps of a pressurised neo-Hookean membrane on the block V-cycle (include/smg.h: smg_membrane_*), the time step of the
     reference's 06_example_balloon_sim.

@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap) and of the membrane kernels (smg_debug_membrane).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane) and of the parameterization kernels (smg_debug_param).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -447,6 +447,59 @@ extern "C" int smg_debug_membrane(int op, int nV, int nF, const int* F, const do
                 HIPCHK(launch_fixed_sum(terms, nF + nV, dpart, terms + nf + nv, st));
                 break;
             }
+        }
+        int bad = 0;
+        HIPCHK(X.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_param(int op, int nV, int nF, const int* F, const double* V0, const double* UV, const double* R_in, double* out,
+                               int* guard_hits)
+{
+    return guarded("smg_debug_param", [&]() -> int {
+        if (op < SMG_PARAM_REST || op > SMG_PARAM_DISTORTION || nV < 1 || nF < 1 || !F || !V0 || !out) return fail(SMG_ERR_INVALID, "smg_debug_param: bad arguments");
+        const bool needs_uv = op != SMG_PARAM_REST && op != SMG_PARAM_RHS, needs_rot = op >= SMG_PARAM_RHS && op <= SMG_PARAM_ENERGY;
+        if ((needs_uv && !UV) || (needs_rot && !R_in)) return fail(SMG_ERR_INVALID, "smg_debug_param: op %d misses an operand", op);
+        if (int rc = check_faces("smg_debug_param", F, nF, nV)) return rc;
+        if (int rc = need_device("smg_debug_param")) return rc;
+        const size_t D = sizeof(double), nf = (size_t)nF, nv = (size_t)nV;
+        const size_t out_n = op == SMG_PARAM_REST ? 6 * nf : op == SMG_PARAM_COVARIANCE ? 4 * nf : op == SMG_PARAM_ROTATIONS ? 2 * nf : op == SMG_PARAM_RHS ? 2 * nv
+                             : op == SMG_PARAM_FACE_ENERGY ? nf : op == SMG_PARAM_ENERGY ? 1 : 3 * nf;
+        Scratch X;
+        HIPCHK(X.init());
+        hipStream_t st = X.stream();
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr;
+        double *dV0 = nullptr, *dUV = nullptr, *dR = nullptr, *dout = nullptr, *drest = nullptr, *dterm = nullptr, *dpart = nullptr;
+        HIPCHK(X.add(F, nullptr, 3 * nf * sizeof(int), &dF));
+        HIPCHK(X.add(V0, nullptr, 3 * nv * D, &dV0));
+        if (UV) HIPCHK(X.add(UV, nullptr, 2 * nv * D, &dUV));
+        if (needs_rot) HIPCHK(X.add(R_in, nullptr, 2 * nf * D, &dR));
+        HIPCHK(X.add(out, out, out_n * D, &dout));
+        if (op != SMG_PARAM_REST) {
+            HIPCHK(X.add(nullptr, nullptr, 6 * nf * D, &drest));
+            HIPCHK(launch_param_rest(nF, dF, dV0, drest, st));
+        }
+        if (op == SMG_PARAM_ROTATIONS || op == SMG_PARAM_ENERGY) HIPCHK(X.add(nullptr, nullptr, nf * D, &dterm));
+        std::vector<int> mp, mi;
+        switch (op) {
+            case SMG_PARAM_REST: HIPCHK(launch_param_rest(nF, dF, dV0, dout, st)); break;
+            case SMG_PARAM_COVARIANCE: HIPCHK(launch_param_covariance(nF, dF, drest, dUV, nV, dout, st)); break;
+            case SMG_PARAM_ROTATIONS: HIPCHK(launch_param_local(nF, dF, drest, dUV, nV, dout, dterm, st)); break;
+            case SMG_PARAM_RHS:
+                vertex_corner_lists(std::vector<int>(F, F + 3 * nf), nV, mp, mi);
+                HIPCHK(X.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+                HIPCHK(X.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+                HIPCHK(launch_param_rhs(nV, nF, dmp, dmi, drest, dR, dout, nV, st));
+                break;
+            case SMG_PARAM_FACE_ENERGY: HIPCHK(launch_param_face_energy(nF, dF, drest, dUV, nV, dR, dout, st)); break;
+            case SMG_PARAM_ENERGY:
+                HIPCHK(X.add(nullptr, nullptr, (size_t)fixed_sum_groups(nF) * D, &dpart));
+                HIPCHK(launch_param_face_energy(nF, dF, drest, dUV, nV, dR, dterm, st));
+                HIPCHK(launch_fixed_sum(dterm, nF, dpart, dout, st));
+                break;
+            default: HIPCHK(launch_param_distortion(nF, dF, drest, dUV, nV, dout, nullptr, nullptr, st)); break;
         }
         int bad = 0;
         HIPCHK(X.finish(&bad));

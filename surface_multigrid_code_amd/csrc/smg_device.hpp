@@ -449,6 +449,24 @@ hipError_t launch_arap_set_handles(int nh, const int* handles, const double* hp,
 // fixed-order finalize; the bits depend on n and the terms alone ---------------------------------------------------------------------------
 int fixed_sum_groups(int n);
 hipError_t launch_fixed_sum(const double* term, int n, double* part, double* sum, hipStream_t st);
+// *out = max_i term[i] through the same chunks and the same tree
+hipError_t launch_fixed_max(const double* term, int n, double* part, double* out, hipStream_t st);
+
+// disk parameterization (smg_param_device.hip).  UV, B: column-major nV x 2; per-face arrays are face-major planes (plane e at [e * nF + f]):
+// rest (6: a, b, c, c0, c1, c2 of smg_param_inl.hpp), R (2: cos, sin), S (4); m_ptr / m_idx: the corner lists t = 3 f + i of every vertex,
+// faces ascending; V0: nV x 3 row-major -------------------------------------------------------------------------------------------------
+hipError_t launch_param_rest(int nF, const int* F, const double* V0, double* rest, hipStream_t st);
+// S_f = sum_i c_i (u_i - u_{i+1}) (x_i - x_{i+1})^T
+hipError_t launch_param_covariance(int nF, const int* F, const double* rest, const double* UV, int ld, double* S, hipStream_t st);
+// R_f = the rotation closest to S_f, eterm[f] = (1/2) sum_i c_i |(u_i - u_{i+1}) - R_f (x_i - x_{i+1})|^2
+hipError_t launch_param_local(int nF, const int* F, const double* rest, const double* UV, int ld, double* R, double* eterm, hipStream_t st);
+// eterm[f] with the given rotations
+hipError_t launch_param_face_energy(int nF, const int* F, const double* rest, const double* UV, int ld, const double* R, double* eterm, hipStream_t st);
+// B[c * ldb + v] = (sum over v's corners of (1/2) R_f (c_i (x_i - x_{i+1}) + c_{i-1} (x_i - x_{i-1})))_c
+hipError_t launch_param_rhs(int nV, int nF, const int* m_ptr, const int* m_idx, const double* rest, const double* R, double* B, int ldb, hipStream_t st);
+// per face det J, sigma1, sigma2: out3 (3 planes), sigma (2 planes) and the 7 planes of terms the statistics reduce; each may be nullptr
+hipError_t launch_param_distortion(int nF, const int* F, const double* rest, const double* UV, int ld, double* out3, double* sigma, double* terms,
+                                   hipStream_t st);
 
 // neo-Hookean membrane time step (smg_membrane_device.hip).  Vectors over the vertices are xyz rows (entry 3 v + l); per-face arrays are
 // face-major planes (plane e at [e * nF + f]); m_ptr / m_idx: the corner lists t = 3 f + j of every vertex, faces ascending -----------------

@@ -6,7 +6,7 @@
 //   smg_solve.cpp       min_quad_with_fixed_mg_solve: the steps of the solve loops and their graph cache, outer loops (stationary, split-phase, sharded, PCG)
 //   smg_sweep_plans.cpp the plan-based Gauss-Seidel sweeps: which one a level uses, building, value refresh, introspection, self-checks
 //   smg_hierarchy_io.cpp mg_precompute / mg_precompute_block builders, point queries, .smgh files
-// The objects built on a mesh and a caller's hierarchy (smg_geodesics.cpp, smg_arap.cpp, smg_membrane.cpp) share smg_mesh_object.hpp, not this file.
+// The objects built on a mesh and a caller's hierarchy (smg_geodesics.cpp, smg_arap.cpp, smg_membrane.cpp, smg_param.cpp) share smg_mesh_object.hpp, not this file.
 // Nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -1,5 +1,5 @@
 // smg_mesh_object.hpp -- what an object built on a triangle mesh and a caller's hierarchy starts from (smg_geodesics.cpp, smg_arap.cpp,
-// smg_membrane.cpp): the checks of a create call, the object's stream, device and cloned handles, the cotangent system
+// smg_membrane.cpp, smg_param.cpp): the checks of a create call, the object's stream, device and cloned handles, the cotangent system
 // assembled on the device, the inner solve, and the byte total.  `who` is the entry point's name, the prefix of every message.
 #pragma once
 #include <vector>
