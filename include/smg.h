@@ -843,6 +843,25 @@ enum { SMG_PARAM_REST = 0, SMG_PARAM_COVARIANCE = 1, SMG_PARAM_ROTATIONS = 2, SM
        SMG_PARAM_DISTORTION = 6 };
 int smg_debug_param(int op, int nV, int nF, const int *F, const double *V0, const double *UV, const double *R_in, double *out, int *guard_hits);
 
+/* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
+ * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.
+ *   SMG_UNION_SUMSQ_DECIDE  rptr[m + 1], rows (member i's rows of the block: rows[rptr[i] .. rptr[i + 1]), each row at most once), r, u, zsave,
+ *                           ss[m], mdone[m], nhis[m], his (m x cap, cap >= 1), tol and the control block
+ *                           -> zsave = u on the listed rows, ss[i] = the member's sum of r^2, every member's break test (mdone, nhis, his) and the
+ *                           handle's (the control block)
+ *   SMG_UNION_RESTORE       rptr, rows, u, zsave, mdone -> u = zsave on the rows of the members with mdone != 0
+ *   SMG_UNION_COARSE        Ainv (the members' dense blocks: block i at moff[i], mlda[i] x mlda[i] row-major), moff[m], mlda[m], mrow0[m + 1],
+ *                           row_member[n], b, u -> u[row] += (block of row_member[row])[row - mrow0[i], :] b[mrow0[i] ..]
+ * The control block: ctrl_i = {n_his, status, his_cap, -} and ctrl_d = {r_last, -, -} on entry (SUMSQ_DECIDE only; the other ops start from
+ * zeros), `done` as given; on return ctrl_i = {n_his, status, his_cap, done}, ctrl_d = {r_last, r_prev, sumsq}; r_his: its history, his_cap
+ * entries, in/out.  SMG_ERR_INVALID, before any launch, for an unknown op, m < 1, k < 1, a missing operand, a row outside [0, n) or listed
+ * twice, rptr / mrow0 that do not start at 0 or are not monotone, mrow0[m] != n, a row_member that disagrees with mrow0, an mlda that is no
+ * multiple of 64 or smaller than its member, an odd or negative moff; SMG_ERR_NO_DEVICE without a GPU. */
+enum { SMG_UNION_SUMSQ_DECIDE = 0, SMG_UNION_RESTORE = 1, SMG_UNION_COARSE = 2 };
+int smg_debug_union(int op, int m, int n, int k, const int *rptr, const int *rows, double *r, double *u, double *zsave, double *ss, int *mdone,
+                    int *nhis, double *his, int cap, const double *Ainv, const long long *moff, const int *mlda, const int *mrow0,
+                    const int *row_member, double *b, double tol, int done, double *ctrl_d, int *ctrl_i, double *r_his, int *guard_hits);
+
 /* ---- profc.h mirror: named scopes accumulated with hipEvents (src/profc.h:9-13; mg_VCycle.cpp:121) ------------- */
 int smg_prof_enable(smg_hierarchy *h, int on);     /* forces eager launches while on */
 int smg_prof_reset(smg_hierarchy *h);

@@ -1,9 +1,10 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane) and of the parameterization kernels (smg_debug_param).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane), of the parameterization kernels (smg_debug_param) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -503,6 +504,111 @@ extern "C" int smg_debug_param(int op, int nV, int nF, const int* F, const doubl
         }
         int bad = 0;
         HIPCHK(X.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+namespace {
+
+// what the union launchers index with: the level-0 row lists (SUMSQ_DECIDE, RESTORE) or the coarsest level's member blocks (COARSE)
+const char* check_union_lists(int op, int m, int n, const int* rptr, const int* rows, const long long* moff, const int* mlda, const int* mrow0,
+                              const int* row_member)
+{
+    if (op != SMG_UNION_COARSE) {
+        if (!rptr || !rows || rptr[0] != 0) return "missing or bad row lists";
+        for (int i = 0; i < m; i++) if (rptr[i + 1] < rptr[i]) return "row list pointers not monotone";
+        if (rptr[m] > n) return "more listed rows than rows";
+        std::vector<char> seen((size_t)n, 0);
+        for (int p = 0; p < rptr[m]; p++) {
+            if (rows[p] < 0 || rows[p] >= n) return "row index out of range";
+            if (seen[(size_t)rows[p]]++) return "a row is listed twice";
+        }
+        return nullptr;
+    }
+    if (!moff || !mlda || !mrow0 || !row_member || mrow0[0] != 0 || mrow0[m] != n) return "missing or bad member blocks";
+    for (int i = 0; i < m; i++) {
+        const int ni = mrow0[i + 1] - mrow0[i];
+        if (ni < 0) return "member rows not monotone";
+        if (mlda[i] < 64 || mlda[i] % 64 != 0 || mlda[i] < ni) return "a leading dimension that is no multiple of 64 or smaller than its member";
+        if (moff[i] < 0 || moff[i] % 2 != 0) return "a block offset that is negative or odd";
+        for (int r = mrow0[i]; r < mrow0[i + 1]; r++) if (row_member[r] != i) return "row_member disagrees with mrow0";
+    }
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" int smg_debug_union(int op, int m, int n, int k, const int* rptr, const int* rows, double* r, double* u, double* zsave, double* ss,
+                               int* mdone, int* nhis, double* his, int cap, const double* Ainv, const long long* moff, const int* mlda,
+                               const int* mrow0, const int* row_member, double* b, double tol, int done, double* ctrl_d, int* ctrl_i, double* r_his,
+                               int* guard_hits)
+{
+    return guarded("smg_debug_union", [&]() -> int {
+        if (op < SMG_UNION_SUMSQ_DECIDE || op > SMG_UNION_COARSE || m < 1 || m > 65535 || n < 1 || k < 1 || (long)n * k > (1L << 30) || !u)
+            return fail(SMG_ERR_INVALID, "smg_debug_union: bad arguments");
+        if (op != SMG_UNION_COARSE && (!zsave || !mdone)) return fail(SMG_ERR_INVALID, "smg_debug_union: op %d misses an operand", op);
+        if (op == SMG_UNION_SUMSQ_DECIDE && (!r || !ss || !nhis || !his || cap < 1 || !ctrl_i || !ctrl_d || ctrl_i[2] < 0 || (ctrl_i[2] > 0 && !r_his)))
+            return fail(SMG_ERR_INVALID, "smg_debug_union: op %d misses an operand", op);
+        if (op == SMG_UNION_COARSE && (!Ainv || !b)) return fail(SMG_ERR_INVALID, "smg_debug_union: op %d misses an operand", op);
+        if (const char* why = check_union_lists(op, m, n, rptr, rows, moff, mlda, mrow0, row_member)) return fail(SMG_ERR_INVALID, "smg_debug_union: %s", why);
+        if (int rc = need_device("smg_debug_union")) return rc;
+        Scratch X;
+        HIPCHK(X.init());
+        hipStream_t st = X.stream();
+        const size_t blk = (size_t)n * k * sizeof(double), mi = (size_t)m * sizeof(int), md = (size_t)m * sizeof(double);
+        UnionDev U;
+        U.m = m;
+        U.his_cap = cap;
+        int *drptr = nullptr, *drows = nullptr, *dmlda = nullptr, *dmrow0 = nullptr, *dmember = nullptr;
+        long long* dmoff = nullptr;
+        double *dr = nullptr, *du = nullptr, *db = nullptr, *dAinv = nullptr, *dhis = nullptr;
+        Ctrl* dctrl = nullptr;
+        HIPCHK(X.add(u, u, blk, &du));
+        Ctrl c = make_ctrl(done, tol, nullptr);
+        if (op != SMG_UNION_COARSE) {
+            HIPCHK(X.add(rptr, nullptr, ((size_t)m + 1) * sizeof(int), &drptr));
+            HIPCHK(X.add(rows, nullptr, (size_t)rptr[m] * sizeof(int), &drows));
+            HIPCHK(X.add(zsave, zsave, blk, &U.zsave));
+            HIPCHK(X.add(mdone, mdone, mi, &U.done));
+            U.rows = drows;
+            U.rptr = drptr;
+            for (int i = 0; i < m; i++) U.max_rows = std::max(U.max_rows, rptr[i + 1] - rptr[i]);
+        }
+        if (op == SMG_UNION_SUMSQ_DECIDE) {
+            HIPCHK(X.add(r, r, blk, &dr));
+            HIPCHK(X.add(ss, ss, md, &U.ss));
+            HIPCHK(X.add(nhis, nhis, mi, &U.nhis));
+            HIPCHK(X.add(his, his, (size_t)m * cap * sizeof(double), &U.his));
+            HIPCHK(X.add(r_his, r_his, (size_t)ctrl_i[2] * sizeof(double), &dhis));
+            c.r_his = dhis;
+            c.n_his = ctrl_i[0];
+            c.status = ctrl_i[1];
+            c.his_cap = ctrl_i[2];
+            c.r_last = ctrl_d[0];
+        }
+        if (op == SMG_UNION_COARSE) {
+            size_t len = 0;
+            for (int i = 0; i < m; i++) len = std::max(len, (size_t)moff[i] + (size_t)mlda[i] * mlda[i]);
+            HIPCHK(X.add(Ainv, nullptr, len * sizeof(double), &dAinv));
+            HIPCHK(X.add(moff, nullptr, (size_t)m * sizeof(long long), &dmoff));
+            HIPCHK(X.add(mlda, nullptr, mi, &dmlda));
+            HIPCHK(X.add(mrow0, nullptr, ((size_t)m + 1) * sizeof(int), &dmrow0));
+            HIPCHK(X.add(row_member, nullptr, (size_t)n * sizeof(int), &dmember));
+            HIPCHK(X.add(b, b, blk, &db));
+            U.crow_member = dmember;
+            U.moff = dmoff;
+            U.mlda = dmlda;
+            U.mrow0 = dmrow0;
+        }
+        HIPCHK(X.add(&c, &c, sizeof c, &dctrl));
+        if (op == SMG_UNION_SUMSQ_DECIDE) HIPCHK(launch_union_sumsq_decide(U, dr, du, k, dctrl, st));
+        else if (op == SMG_UNION_RESTORE) HIPCHK(launch_union_restore(U, du, k, dctrl, st));
+        else HIPCHK(launch_blockdiag_gemv_add(U, dAinv, n, db, du, k, dctrl, st));
+        int bad = 0;
+        HIPCHK(X.finish(&bad));
+        if (ctrl_d) { ctrl_d[0] = c.r_last; ctrl_d[1] = c.r_prev; ctrl_d[2] = c.sumsq; }
+        if (ctrl_i) { ctrl_i[0] = c.n_his; ctrl_i[1] = c.status; ctrl_i[3] = c.done; }
         if (guard_hits) *guard_hits = bad;
         return SMG_OK;
     });

@@ -62,8 +62,11 @@ __global__ __launch_bounds__(TILED_NT) void k_tiled_gs(const int* __restrict__ h
 #pragma unroll
     for (int c = 0; c < NC; c++) {
         gR[c] = -1; dR[c] = 1.0;
+        // slots beyond the tile's width: +0.0 times the row's OWN value, like the plan's padding slots -- not the image's first row, which in a union handle
+        // may belong to another member (0 x NaN of a diverging neighbour would be NaN); lanes without a row never reach the phases
+        const int own = c < nc ? Hs[4 + c * TILED_CSTRIDE + 3] + tid : 0;
 #pragma unroll
-        for (int j = 0; j < W; j++) { cR[c][j] = 0; vR[c][j] = 0.0; }      // slots beyond the tile's width, lanes without a row: +0.0 times the image's first (finite) value
+        for (int j = 0; j < W; j++) { cR[c][j] = own; vR[c][j] = 0.0; }
         if (c < nc) {
             const int* C = Hs + 4 + c * TILED_CSTRIDE;
             const int pan = C[0], m = C[1];

@@ -1,5 +1,5 @@
 """numpy wrappers of the kernel test hooks (include/smg.h: the handle-free smg_debug_eig_gram, smg_debug_eig_combine, smg_debug_eig_residual,
-smg_debug_krylov; on a handle smg_debug_cycle_f32, smg_debug_convert_f32) and the rounding-error bounds the tests hold them to.
+smg_debug_krylov, smg_debug_union; on a handle smg_debug_cycle_f32, smg_debug_convert_f32) and the rounding-error bounds the tests hold them to.
 
 Every wrapper asserts that the hook succeeded and that no guard region around a device buffer changed (no write out of place)."""
 import ctypes as C
@@ -113,6 +113,62 @@ def krylov(L, op, vecs, s=None, restart=None, e=None, tol=0.0, done=0):
     assert groups.value == kry_groups(n, k)
     ctrl = dict(sumsq=cd[0], r0=cd[1], n_his=ci[0], done=ci[1], status=ci[2])
     return vecs, s, (None if rs is None else rs.value), ctrl
+
+
+UNION_OPS = dict(SUMSQ_DECIDE=0, RESTORE=1, COARSE=2)
+
+
+def _union_call(L, op, m, n, k, a, tol=0.0, done=0, cap=0, ctrl_d=None, ctrl_i=None):
+    """smg_debug_union with the arrays of dict a (missing ones: NULL); asserts success and untouched guards"""
+    bad = C.c_int(-1)
+    g = lambda name, t=C.c_double: _p(a.get(name), t)
+    rc = L.smg_debug_union(UNION_OPS[op], m, n, k, g("rptr", C.c_int), g("rows", C.c_int), g("r"), g("u"), g("zsave"), g("ss"), g("mdone", C.c_int),
+                           g("nhis", C.c_int), g("his"), cap, g("Ainv"), g("moff", C.c_longlong), g("mlda", C.c_int), g("mrow0", C.c_int),
+                           g("row_member", C.c_int), g("b"), tol, done, ctrl_d, ctrl_i, g("r_his"), C.byref(bad))
+    assert rc == 0, L.smg_last_error()
+    assert bad.value == 0, "a guard region around a device buffer was overwritten"
+
+
+def union_sumsq_decide(L, rptr, rows, r, u, zsave, ss, mdone, nhis, his, tol, done=0, status=0, n_his=0, his_cap=None, r_last=-1.0, r_his=None):
+    """launch_union_sumsq_decide on n x k blocks r, u, zsave and the members' state (his: m x cap); the control block starts from the given
+    done / status / n_his / his_cap / r_last and a history r_his (default: his_cap sentinels).  Returns a dict of everything after the launches:
+    r, u, zsave, ss, mdone, nhis, his, r_his and the control block's done, status, n_his, r_last, r_prev, sumsq."""
+    r, u, zsave = _c(r).copy(), _c(u).copy(), _c(zsave).copy()
+    n, k = r.shape
+    his = _c(his).copy()
+    m, cap = his.shape
+    his_cap = cap if his_cap is None else his_cap
+    a = dict(rptr=_c(rptr, np.int32), rows=_c(rows, np.int32), r=r, u=u, zsave=zsave, ss=_c(ss).copy(), mdone=_c(mdone, np.int32).copy(),
+             nhis=_c(nhis, np.int32).copy(), his=his, r_his=sentinel(max(his_cap, 1)) if r_his is None else _c(r_his).copy())
+    assert len(a["rptr"]) == m + 1 and len(a["ss"]) == len(a["mdone"]) == len(a["nhis"]) == m and len(a["r_his"]) >= his_cap
+    ci, cd = (C.c_int * 4)(n_his, status, his_cap, -7), (C.c_double * 3)(r_last, 7.0, 7.0)
+    _union_call(L, "SUMSQ_DECIDE", m, n, k, a, tol, done, cap, cd, ci)
+    a.update(n_his=ci[0], status=ci[1], done=ci[3], r_last=cd[0], r_prev=cd[1], sumsq=cd[2])
+    return a
+
+
+def union_restore(L, rptr, rows, u, zsave, mdone, done=0):
+    """launch_union_restore: returns (u, zsave, mdone) after the launch"""
+    u, zsave = _c(u).copy(), _c(zsave).copy()
+    n, k = u.shape
+    a = dict(rptr=_c(rptr, np.int32), rows=_c(rows, np.int32), u=u, zsave=zsave, mdone=_c(mdone, np.int32).copy())
+    _union_call(L, "RESTORE", len(a["mdone"]), n, k, a, done=done)
+    return a["u"], a["zsave"], a["mdone"]
+
+
+def union_coarse(L, blocks, members, b, u, done=0):
+    """launch_blockdiag_gemv_add on the members' dense blocks (blocks[i]: lda_i x lda_i with the matrix of member i's members[i] rows in the
+    leading part), laid side by side as the handle lays them: returns (u, b) after the launches"""
+    b, u = _c(b).copy(), _c(u).copy()
+    n, k = u.shape
+    sizes = [int(np.asarray(B).shape[0]) for B in blocks]
+    moff = np.concatenate([[0], np.cumsum([s * s for s in sizes])[:-1]]).astype(np.int64)
+    mrow0 = np.concatenate([[0], np.cumsum(members)]).astype(np.int32)
+    assert mrow0[-1] == n and len(members) == len(blocks)
+    a = dict(Ainv=np.concatenate([_c(B).ravel() for B in blocks]), moff=moff, mlda=np.asarray(sizes, np.int32), mrow0=mrow0,
+             row_member=np.repeat(np.arange(len(blocks), dtype=np.int32), members), b=b, u=u)
+    _union_call(L, "COARSE", len(blocks), n, k, a, done=done)
+    return a["u"], a["b"]
 
 
 F32_OPS = dict(A=0, RESID=1, RESTRICT=2, PROLONG_ADD=3, RELAX=4, COARSE=5, VCYCLE=6)

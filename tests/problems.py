@@ -69,3 +69,20 @@ def random_spd_hierarchy(rng, n, levels, hub):
         P.sum_duplicates(); P.sort_indices()
         Ps.append(P); m = mc
     return A, Ps
+
+
+def _path_matrix(n):
+    """the tiny and ragged systems: a path graph's diagonally dominant matrix"""
+    return sp.diags([-1.0, 2.5, -1.0], [-1, 0, 1], shape=(n, n)).tocsr()
+
+
+def _path_interp(n):
+    """linear interpolation from every second vertex of the path"""
+    nc = (n + 1) // 2
+    rows, cols, vals = [], [], []
+    for i in range(n):
+        if i % 2 == 0:
+            rows.append(i); cols.append(i // 2); vals.append(1.0)
+        else:
+            rows += [i, i]; cols += [i // 2, min(i // 2 + 1, nc - 1)]; vals += [0.5, 0.5]
+    return sp.csr_matrix((vals, (rows, cols)), shape=(n, nc))

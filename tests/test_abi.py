@@ -69,7 +69,8 @@ def test_compute_fails_loudly_without_gpu(smg_mod):
 
 def _kernel_hook_calls(L, n=4, m=2, nb=1, op=0, k=2):
     """one call of each handle-free kernel hook (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine, smg_debug_eig_residual,
-    smg_debug_krylov) on arrays large enough for the largest legal shape among the arguments"""
+    smg_debug_krylov, and the three ops of smg_debug_union on a well-formed two-member problem) on arrays large enough for the largest legal
+    shape among the arguments"""
     dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
     big = max(n, 1) * max(m, 1, k) * 3
     D = [np.zeros(big * max(m, 1) * 6) for _ in range(8)]
@@ -83,12 +84,28 @@ def _kernel_hook_calls(L, n=4, m=2, nb=1, op=0, k=2):
         "combine": L.smg_debug_eig_combine(n, m, nb, d[0], d[1], d[2], 1, 0, d[3], d[4], d[5], d[6], C.byref(bad)),
         "residual": L.smg_debug_eig_residual(n, m, d[0], d[1], d[2], d[3], 1, 0, d[4], d[5], f[0], f[1], d[6], C.byref(gi), C.byref(bad)),
         "krylov": L.smg_debug_krylov(op, n, k, d[0], d[1], d[2], d[3], f[0], d[4], C.byref(rs), 0.0, 0, cd, ci, C.byref(gi), C.byref(bad)),
+        **{"union%d" % uop: _union_hook_call(L, uop) for uop in range(3)},
     }
+
+
+def _union_hook_call(L, op, m=2, n=4, k=2, **over):
+    """smg_debug_union on two members of two rows each (one 64 x 64 block each); over: arrays or scalars that replace the well-formed ones"""
+    ip, dp, lp = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_longlong)
+    a = dict(rptr=np.array([0, 2, 4], np.int32), rows=np.array([3, 0, 2, 1], np.int32), mdone=np.zeros(8, np.int32), nhis=np.zeros(8, np.int32),
+             moff=np.array([0, 4096], np.int64), mlda=np.array([64, 64], np.int32), mrow0=np.array([0, 2, 4], np.int32),
+             row_member=np.array([0, 0, 1, 1], np.int32), ci=np.array([0, 0, 3, 0], np.int32), cap=3)
+    a.update(over)
+    D = [np.zeros(2 * 4096) for _ in range(8)]
+    d = [x.ctypes.data_as(dp) for x in D]
+    q = lambda name, t: None if a[name] is None else a[name].ctypes.data_as(t)
+    bad, cd = C.c_int(0), (C.c_double * 3)()
+    return L.smg_debug_union(op, m, n, k, q("rptr", ip), q("rows", ip), d[0], d[1], d[2], d[3], q("mdone", ip), q("nhis", ip), d[4], a["cap"], d[5],
+                             q("moff", lp), q("mlda", ip), q("mrow0", ip), q("row_member", ip), d[6], 0.0, 0, cd, q("ci", ip), d[7], C.byref(bad))
 
 
 def test_kernel_hooks_refuse_bad_shapes(smg_mod):
     """SMG_ERR_INVALID before any device work: n < 1, m outside 1..64, nb outside 1..3, an unknown Krylov op, k < 1; the fp32 cycle's hooks:
-    no handle, an unknown op, a missing array, a handle without a precomputed system"""
+    no handle, an unknown op, a missing array, a handle without a precomputed system; the union hook: what its launchers cannot take"""
     L = smg_mod._lib.load()
     hooks = dict(n=["gram", "combine", "residual", "krylov"], m=["gram", "combine", "residual"], nb=["gram", "combine"], op=["krylov"],
                  k=["krylov"])
@@ -100,6 +117,24 @@ def test_kernel_hooks_refuse_bad_shapes(smg_mod):
     # a missing array is refused the same way
     assert L.smg_debug_eig_gram(4, 2, 1, None, 1, None, None, 0, 0, None, None, None) == -1
     assert L.smg_debug_krylov(0, 4, 2, None, None, None, None, None, None, None, 0.0, 0, None, None, None, None) == -1
+    # the union hook: an unknown op, m < 1, n < 1, k < 1, a missing array, lists and blocks that the launchers would index out of place
+    i32 = lambda *v: np.array(v, np.int32)
+    for op in (-1, 3):
+        assert _union_hook_call(L, op) == -1
+    for op in range(3):
+        for bad_shape in (dict(m=0), dict(n=0), dict(k=0)):
+            assert _union_hook_call(L, op, **bad_shape) == -1, (op, bad_shape)
+    for op in (0, 1):
+        for bad_list in (dict(rows=i32(3, 0, 2, 4)), dict(rows=i32(3, 0, -1, 1)), dict(rows=i32(3, 0, 3, 1)), dict(rptr=i32(0, 3, 2)), dict(rptr=i32(1, 2, 4)),
+                         dict(rptr=i32(0, 2, 5)), dict(rptr=None), dict(rows=None), dict(mdone=None)):
+            assert _union_hook_call(L, op, **bad_list) == -1 and b"smg_debug_union" in L.smg_last_error(), (op, bad_list)
+    for bad_state in (dict(cap=0), dict(nhis=None), dict(ci=None), dict(ci=i32(0, 0, -1, 0))):
+        assert _union_hook_call(L, 0, **bad_state) == -1, bad_state
+    for bad_block in (dict(mlda=i32(64, 32)), dict(mlda=i32(64, 96)), dict(mlda=i32(0, 64)), dict(mrow0=i32(0, 3, 2)), dict(mrow0=i32(1, 2, 4)),
+                      dict(mrow0=i32(0, 2, 3)), dict(row_member=i32(0, 1, 1, 1)), dict(row_member=i32(0, 0, 1, 2)), dict(moff=np.array([0, 4097], np.int64)),
+                      dict(moff=np.array([-2, 4096], np.int64)), dict(moff=None), dict(mlda=None), dict(mrow0=None), dict(row_member=None)):
+        assert _union_hook_call(L, 2, **bad_block) == -1 and b"smg_debug_union" in L.smg_last_error(), bad_block
+    assert _union_hook_call(L, 2, m=1, n=65, mrow0=i32(0, 65), row_member=np.zeros(65, np.int32), mlda=i32(64), moff=np.array([0], np.int64)) == -1   # lda < the member
     # the hooks of the fp32 cycle work on a handle: no handle, an unknown op, a missing array and a handle that was never precomputed are refused
     fp = C.POINTER(C.c_float)
     f = [np.zeros(64, np.float32).ctypes.data_as(fp) for _ in range(3)]

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from problems import random_spd_hierarchy as _random_spd_hierarchy, subdiv_problem
+from problems import _path_interp, _path_matrix, random_spd_hierarchy as _random_spd_hierarchy, subdiv_problem
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -585,21 +585,6 @@ def test_compact_and_fixed_pitch_panels_give_the_same_bits(smg, oracle_mod, kind
 
 
 # ----------------------------------------------------------------------------------------------- tiny and ragged systems
-def _path_matrix(n):
-    return sp.diags([-1.0, 2.5, -1.0], [-1, 0, 1], shape=(n, n)).tocsr()
-
-
-def _path_interp(n):
-    nc = (n + 1) // 2
-    rows, cols, vals = [], [], []
-    for i in range(n):
-        if i % 2 == 0:
-            rows.append(i); cols.append(i // 2); vals.append(1.0)
-        else:
-            rows += [i, i]; cols += [i // 2, min(i // 2 + 1, nc - 1)]; vals += [0.5, 0.5]
-    return sp.csr_matrix((vals, (rows, cols)), shape=(n, nc))
-
-
 @pytest.mark.parametrize("n,levels,k,known", [(3, 2, 1, None), (10, 2, 1, None), (63, 2, 1, None), (64, 2, 2, None), (65, 2, 1, None),
                                               (129, 2, 3, None), (37, 3, 5, None), (50, 2, 2, [0, 7, 49]), (30, 2, 1, "all but 3")])
 def test_tiny_and_ragged_systems(smg, oracle_mod, n, levels, k, known):

@@ -30,7 +30,7 @@ def members(smg, k, seed=0):
     return ms, As, Bs
 
 
-@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("k", [1, 3, 5, 8])
 def test_every_member_of_a_union_runs_its_own_loop(smg, oracle_mod, k):
     ms, As, Bs = members(smg, k)
     tol = 1e-9
@@ -136,3 +136,22 @@ def test_a_failing_member_does_not_touch_its_neighbours_and_mixed_precision_is_r
             assert cvi and np.array_equal(rhi, clean[i][1]), i
             assert np.array_equal(z2[f:f + c], z[f:f + c]), i
     assert np.isfinite(rh2).all()                                            # the handle's norm: over the members still in the running
+    # the same at k = 5 (a width the union runs raw: its columns are not padded) with the NaN in column 3 only
+    rng = np.random.default_rng(5)
+    B5 = np.asfortranarray(np.concatenate([A_ @ rng.uniform(-1, 1, (A_.shape[0], 5)) for A_ in As], axis=0))
+    conv5, z5, rh5 = u.solve(B5, np.zeros_like(B5), None, o)
+    clean5 = [u.union_history(i) for i in range(len(ms))]
+    assert conv5 and all(c for c, _ in clean5)
+    Bn5 = B5.copy()
+    Bn5[first + cnt // 2, 3] = np.nan
+    conv6, z6, rh6 = u.solve(Bn5, np.zeros_like(Bn5), None, o)
+    assert not conv6 and np.isfinite(rh6).all()
+    for i in range(len(ms)):
+        f, c = u.union_member_rows(i)
+        cvi, rhi = u.union_history(i)
+        if i == bad:
+            assert not cvi and len(rhi) == 1 and not np.isfinite(rhi[-1])
+            assert np.array_equal(z6[f:f + c], np.zeros((c, 5)))             # frozen at the iterate it failed on, all five columns
+        else:
+            assert cvi and np.array_equal(rhi, clean5[i][1]), i
+            assert np.array_equal(z6[f:f + c], z5[f:f + c]), i
