@@ -3,7 +3,8 @@
 // hierarchy (mg_precompute_block).  Energy, gradient, Hessian, the per-face eigenvalue fix, assembly and the line search run on the device;
 // the matrix keeps its sparsity, so every precompute after the first is value-only.
 //
-//   ./06_balloon_sim tests/golden/meshes/bunny_15K_init.smgm [steps]
+//   ./06_balloon_sim tests/golden/meshes/bunny_15K_init.smgm [steps] [matid]      matid (main.cpp:92-101): 0 neo-Hookean (default), 1 StVK,
+//                                                                               2 tension-field StVK
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +28,7 @@ int main(int argc, char* argv[])
     std::printf("numLv: %d\n", (int)mg.size());
 
     balloon_sim_data sim;                                       // thickness 0.1, poisson 0.5, young 6e6, M = 1000 * lumped mass, dt = 1e-3
+    if (argc > 3) sim.material = std::atoi(argv[3]);
     balloon_sim_precompute(origV, F, mg, sim);
     const double mg_tolerance = 2e-1;
     smgDense curPos = origV;

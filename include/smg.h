@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 509
+#define SMG_VERSION 510
 
 enum {
     SMG_OK = 0,
@@ -475,7 +475,7 @@ long long smg_arap_device_bytes(const smg_arap *a);
 int smg_arap_solve(smg_arap *a, const double *handle_pos, int ld_hp, const double *U0, int ld_u0, int memspace, int max_iter, double rel_tol,
                    const smg_solve_opts *opts, double *U, int ld_u, double *energy_his, int *cycles, int *n_iter);
 
-/* ---- implicit-Euler steps of a pressurised neo-Hookean membrane (the reference's 06_example_balloon_sim: main.cpp:109-134,
+/* ---- implicit-Euler steps of a pressurised membrane, neo-Hookean by default (the reference's 06_example_balloon_sim: main.cpp:109-134,
  * implicit_euler_mg_balloon.h:35-121, stretching energy only, no constraints) -- an application object on the BLOCK V-cycle -----------------
  * Per face with corners q0, q1, q2 (order of F), e1 = q1 - q0, e2 = q2 - q0:  a = [[e1.e1, e1.e2], [e1.e2, e2.e2]], abar = a of the rest pose,
  *     lnJ = log(det a / det abar) / 2,   W_f = coeff (beta (tr(abar^-1 a) - 2 - 2 lnJ) + alpha lnJ^2),   coeff = thickness sqrt(det abar) / 4,
@@ -501,6 +501,15 @@ int smg_arap_solve(smg_arap *a, const double *handle_pos, int ld_hp, const doubl
  *   connected component, dt <= 0, |poisson| >= 1, young <= 0, thickness <= 0, mass_scale <= 0, newton_iters < 0, eig_value <= 0.
  * smg_membrane_set_state / get_state: nV x 3 row-major blocks (host or device); set: NULL pos = the rest pose, NULL qdot = 0; get: NULL = skip.
  * smg_membrane_set_solver: 0 (default) smg_solve, the reference's loop; 1 smg_solve_pcg.
+ * smg_membrane_set_material: 0 (default) the neo-Hookean energy above, 1 StVK (StVKMaterial.cpp:11-60), 2 tension-field StVK
+ *   (TensionFieldStVKMaterial.cpp:11-171): the materials of the reference's runSimulation (main.cpp:92-101).  With M = abar^-1 (a - abar),
+ *   c = thickness sqrt(det abar) / 8:  StVK is W_f = c (alpha / 2 tr(M)^2 + beta tr(M^2)); it is finite for inverted faces.  Tension field:
+ *   l1 >= l2 the eigenvalues of M, k1 = thickness alpha / 8, k2 = thickness beta / 4;  l1 >= 0 and l2 >= -k1 / (k1 + k2) l1: StVK (pure
+ *   tension, the rest pose included);  else l1 < 0: W_f = 0, G_f = 0, H_f = 0 (slack; the fixed block is eig_value I_9);  else
+ *   W_f = (k1 + k2 - k1^2 / (k1 + k2)) sqrt(det abar) / 2 l1^2 (wrinkled: no resistance to compression across the wrinkles).  Everything
+ *   else of the step is the same.  The int is latched: legal between any two steps, the state is kept, nothing is rebuilt (every Newton
+ *   iteration re-precomputes the values anyway).  Any other value, or a null object: SMG_ERR_INVALID.  smg_membrane_material returns the
+ *   current one (0 for a null object).
  * smg_membrane_step: opts == NULL selects smg_solve_opts_default with tol = 2e-1 (the reference's mg_tolerance; the tolerance is absolute).
  *   Outputs (NULL ok): objective_his[i] = f(qdot) before Newton iteration i plus one final entry (newton_iters + 1 doubles), alpha[i] the
  *   accepted step (0 when the search gave up), cycles[i] the loop entries of solve i, *n_newton the iterations completed.  A non-finite
@@ -511,7 +520,8 @@ int smg_arap_solve(smg_arap *a, const double *handle_pos, int ld_hp, const doubl
  *   Query the sizes with NULL arrays first.  Scalar row 3 i + l of H holds, for the blocks q of block row i in order, the columns
  *   3 bcol[q] + m, m = 0 .. 2.
  * smg_membrane_faces_host: the per-face maths of the device kernel compiled for the host (no device needed): W[nF], G (9 planes, entry e of
- *   face f at G[e nF + f], may be NULL with H), H (the 45 entries of the upper triangle row by row, same planes, may be NULL), fixed when fix != 0. */
+ *   face f at G[e nF + f], may be NULL with H), H (the 45 entries of the upper triangle row by row, same planes, may be NULL), fixed when fix != 0.
+ * smg_membrane_faces_host_material: the same for a material (0: the bits of smg_membrane_faces_host; another value: SMG_ERR_INVALID). */
 typedef struct {
     double young, poisson, thickness, mass_scale, dt, pressure;
     int newton_iters;
@@ -525,10 +535,14 @@ long long smg_membrane_device_bytes(const smg_membrane *m);
 int smg_membrane_set_state(smg_membrane *m, const double *pos, const double *qdot, int memspace);
 int smg_membrane_get_state(smg_membrane *m, double *pos, double *qdot, int memspace);
 int smg_membrane_set_solver(smg_membrane *m, int pcg);
+int smg_membrane_set_material(smg_membrane *m, int material);
+int smg_membrane_material(const smg_membrane *m);
 int smg_membrane_step(smg_membrane *m, const smg_solve_opts *opts, double *objective_his, double *alpha, int *cycles, int *n_newton);
 int smg_membrane_lists(const int *F, int nF, int nV, int *n_blocks, int *n_contrib, int *bptr, int *bcol, int *c_ptr, int *c_src);
 int smg_membrane_faces_host(const double *V0, const double *P, int nV, const int *F, int nF, const smg_membrane_params *p, int fix, double *W,
                             double *G, double *H);
+int smg_membrane_faces_host_material(const double *V0, const double *P, int nV, const int *F, int nF, const smg_membrane_params *p, int material,
+                                     int fix, double *W, double *G, double *H);
 
 /* ---- harmonic and as-rigid-as-possible flattening of a disk mesh (Tutte / cotangent-weight harmonic map to a circle; the local / global
  * iteration of Liu, Zhang, Xu, Gotsman and Gortler 2008) -- an application object on a SCALAR hierarchy --------------------------------------
@@ -827,6 +841,9 @@ enum { SMG_MEM_REST = 0, SMG_MEM_FACES_RAW = 1, SMG_MEM_FACES = 2, SMG_MEM_ENERG
        SMG_MEM_GRADIENT = 6, SMG_MEM_OBJECTIVE = 7 };
 int smg_debug_membrane(int op, int nV, int nF, const int *F, const double *V0, const double *P, const double *in, const smg_membrane_params *p,
                        double *out, int *guard_hits);
+/* The same ops on the kernels of a material (smg_membrane_set_material: 0, 1, 2; another value: SMG_ERR_INVALID). */
+int smg_debug_membrane_material(int material, int op, int nV, int nF, const int *F, const double *V0, const double *P, const double *in,
+                                const smg_membrane_params *p, double *out, int *guard_hits);
 
 /* One launcher of the disk parameterization (csrc/smg_param_device.hip), handle-free and guarded like the hooks above.  F: nF x 3, V0: nV x 3
  * row-major, UV: nV x 2 column-major (leading dimension nV), R_in: the rotations as 2 planes (cos, sin); per-face results are planes (entry e

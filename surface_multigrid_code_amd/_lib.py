@@ -100,9 +100,13 @@ def load():
         "smg_membrane_set_state": (i, [vp, vp, vp, i]),
         "smg_membrane_get_state": (i, [vp, vp, vp, i]),
         "smg_membrane_set_solver": (i, [vp, i]),
+        "smg_membrane_set_material": (i, [vp, i]),
+        "smg_membrane_material": (i, [vp]),
         "smg_membrane_step": (i, [vp, C.POINTER(SolveOptsC), dp, dp, ip, ip]),
         "smg_membrane_lists": (i, [ip, i, i, ip, ip, ip, ip, ip, ip]),
         "smg_membrane_faces_host": (i, [dp, dp, i, ip, i, C.POINTER(MembraneParamsC), i, dp, dp, dp]),
+        "smg_membrane_faces_host_material": (i, [dp, dp, i, ip, i, C.POINTER(MembraneParamsC), i, i, dp, dp, dp]),
+        "smg_debug_membrane_material": (i, [i, i, i, i, ip, dp, dp, dp, C.POINTER(MembraneParamsC), dp, ip]),
         "smg_debug_param": (i, [i, i, i, ip, dp, dp, dp, dp, ip]),
         "smg_debug_union": (i, [i, i, i, i, ip, ip, dp, dp, dp, dp, ip, ip, dp, i, dp, C.POINTER(C.c_longlong), ip, ip, ip, dp, d, i, dp, ip, dp, ip]),
         "smg_param_create": (i, [vp, dp, i, ip, i, C.POINTER(vp)]),

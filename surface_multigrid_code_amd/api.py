@@ -788,22 +788,44 @@ class Parameterizer:
 
 
 class MembraneSim:
-    """Implicit-Euler steps of a pressurised neo-Hookean membrane on the block V-cycle (include/smg.h: smg_membrane_*), the time step of the
-    reference's 06_example_balloon_sim.
+    """Implicit-Euler steps of a pressurised membrane on the block V-cycle (include/smg.h: smg_membrane_*), the time step of the
+    reference's 06_example_balloon_sim.  material: "neo_hookean" (default), "stvk" or "tension_field" (or 0, 1, 2).
 
     hierarchy: a block Hierarchy (mg_precompute_block) whose level 0 is the mesh (V, F) with 3 DOFs per vertex; its prolongations are copied, it
     is not modified.  V: the rest pose.  params: the fields of smg_membrane_params (young, poisson, thickness, mass_scale, dt, pressure,
     newton_iters, ls_c, ls_shrink, ls_min_alpha, eig_floor, eig_value); the state starts as (V, 0)."""
 
-    def __init__(self, hierarchy, V, F, **params):
+    MATERIALS = ("neo_hookean", "stvk", "tension_field")
+
+    def __init__(self, hierarchy, V, F, material="neo_hookean", **params):
         self.L = _lib.load()
+        self.m = None
         V = np.ascontiguousarray(V, dtype=np.float64)
         F = np.ascontiguousarray(F, dtype=np.int32)
         self.n = V.shape[0]
         self.params = membrane_params(**params)
+        mat = self._material_id(material)
         out = C.c_void_p()
         _chk(self.L.smg_membrane_create(hierarchy.h, _dp(V), V.shape[0], _ip(F), F.shape[0], C.byref(self.params), C.byref(out)), "smg_membrane_create")
         self.m = C.c_void_p(out.value)
+        if mat != 0:
+            self.set_material(mat)
+
+    @classmethod
+    def _material_id(cls, material):
+        if isinstance(material, str):
+            if material not in cls.MATERIALS:
+                raise ValueError("unknown membrane material %r (one of %s)" % (material, ", ".join(cls.MATERIALS)))
+            return cls.MATERIALS.index(material)
+        return int(material)
+
+    def set_material(self, material):
+        """material: "neo_hookean" / 0, "stvk" / 1, "tension_field" / 2; legal between any two steps, the state is kept."""
+        _chk(self.L.smg_membrane_set_material(self.m, self._material_id(material)), "smg_membrane_set_material")
+
+    @property
+    def material(self):
+        return self.MATERIALS[self.L.smg_membrane_material(self.m)]
 
     def __del__(self):
         try:

@@ -338,7 +338,7 @@ inline void mg_precompute_block(const smgDense& Vf, const smgDenseI& Ff, const f
 inline void mg_precompute_block(const smgDense& Vf, const smgDenseI& Ff, std::vector<mg_data>& mg) { mg_precompute_block(Vf, Ff, 0.25f, 500, 1, mg); }
 
 // ---- implicit_euler_mg_balloon (reference 06_example_balloon_sim/sim_utils/implicit_euler_mg_balloon.h:35-121, with the pressure force of
-// main.cpp:113-122): one time step of the neo-Hookean membrane on the block V-cycle of `mg` (include/smg.h: smg_membrane_*).  The state
+// main.cpp:113-122): one time step of the membrane (neo-Hookean unless balloon_sim_data::material says otherwise) on the block V-cycle of `mg` (include/smg.h: smg_membrane_*).  The state
 // lives on the device between steps; curPos / qdot are read back after every step as the reference's arguments are.
 struct balloon_sim_data {
     std::shared_ptr<smg_membrane> m;
@@ -346,8 +346,15 @@ struct balloon_sim_data {
     int n = 0;                              // #V
     std::vector<double> objective, alpha;   // of the last step: f(qdot) before every Newton iteration and after the last; the accepted steps
     std::vector<int> cycles;                // ... and the loop entries of its solves
+    int material = 0;                       // 0 neo-Hookean, 1 StVK, 2 tension-field StVK (the reference's matid); balloon_sim_set_material after the precompute
     balloon_sim_data() { smg_membrane_params_default(&params); }
 };
+
+inline void balloon_sim_set_material(balloon_sim_data& data, int material)
+{
+    if (data.m) smg_detail::check(smg_membrane_set_material(data.m.get(), material), "balloon_sim_set_material");
+    data.material = material;
+}
 
 inline void balloon_sim_precompute(const smgDense& V, const smgDenseI& F, const std::vector<mg_data>& mg, balloon_sim_data& data)
 {
@@ -366,6 +373,7 @@ inline void balloon_sim_precompute(const smgDense& V, const smgDenseI& F, const 
     smg_detail::check(smg_membrane_create(h.get(), Vr.data(), V.rows, Fr.data(), F.rows, &data.params, &m), "balloon_sim_precompute");
     data.m.reset(m, smg_membrane_destroy);
     data.n = V.rows;
+    if (data.material != 0) smg_detail::check(smg_membrane_set_material(m, data.material), "balloon_sim_precompute");
 }
 
 // curPos (#V x 3) and qdot (3 #V, entry 3 v + d) are overwritten with the state after the step

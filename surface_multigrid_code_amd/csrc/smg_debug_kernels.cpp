@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane), of the parameterization kernels (smg_debug_param) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -375,15 +375,18 @@ extern "C" int smg_debug_arap(int op, int n, const int* rowptr, const int* col, 
     });
 }
 
-extern "C" int smg_debug_membrane(int op, int nV, int nF, const int* F, const double* V0, const double* P, const double* in,
-                                  const smg_membrane_params* p, double* out, int* guard_hits)
+// the body of smg_debug_membrane and smg_debug_membrane_material: the face ops run the kernels of `material`
+static int debug_membrane(const char* who, int material, int op, int nV, int nF, const int* F, const double* V0, const double* P, const double* in,
+                          const smg_membrane_params* p, double* out, int* guard_hits)
 {
-    return guarded("smg_debug_membrane", [&]() -> int {
-        if (op < SMG_MEM_REST || op > SMG_MEM_OBJECTIVE || nV < 1 || nF < 1 || !F || !p || !out) return fail(SMG_ERR_INVALID, "smg_debug_membrane: bad arguments");
+    return guarded(who, [&]() -> int {
+        if (material < 0 || material > 2)
+            return fail(SMG_ERR_INVALID, "%s: material %d is not 0 (neo-Hookean), 1 (StVK) or 2 (tension-field StVK)", who, material);
+        if (op < SMG_MEM_REST || op > SMG_MEM_OBJECTIVE || nV < 1 || nF < 1 || !F || !p || !out) return fail(SMG_ERR_INVALID, "%s: bad arguments", who);
         const bool needs_rest = op <= SMG_MEM_ENERGY || op == SMG_MEM_OBJECTIVE, needs_pose = (op >= SMG_MEM_FACES_RAW && op <= SMG_MEM_PRESSURE) || op == SMG_MEM_OBJECTIVE;
-        if ((needs_rest && !V0) || (needs_pose && !P) || (op >= SMG_MEM_MATRIX && !in)) return fail(SMG_ERR_INVALID, "smg_debug_membrane: op %d misses an operand", op);
-        if (int rc = check_faces("smg_debug_membrane", F, nF, nV)) return rc;
-        if (int rc = need_device("smg_debug_membrane")) return rc;
+        if ((needs_rest && !V0) || (needs_pose && !P) || (op >= SMG_MEM_MATRIX && !in)) return fail(SMG_ERR_INVALID, "%s: op %d misses an operand", who, op);
+        if (int rc = check_faces(who, F, nF, nV)) return rc;
+        if (int rc = need_device(who)) return rc;
         double alpha, beta;
         lame(*p, alpha, beta);
         std::vector<int> Fv(F, F + 3 * (size_t)nF), mp, mi;
@@ -417,10 +420,11 @@ extern "C" int smg_debug_membrane(int op, int nV, int nF, const int* F, const do
             case SMG_MEM_REST: HIPCHK(launch_membrane_rest(nF, dF, dV0, p->thickness, dout, st)); break;
             case SMG_MEM_FACES_RAW:
             case SMG_MEM_FACES:
-                HIPCHK(launch_membrane_faces(op == SMG_MEM_FACES ? 2 : 1, nF, dF, dP, drest, alpha, beta, p->eig_floor, p->eig_value, dout, dout + nf, dout + 10 * nf, st));
+                HIPCHK(launch_membrane_faces_material(material, op == SMG_MEM_FACES ? 2 : 1, nF, dF, dP, dV0, drest, p->thickness, alpha, beta, p->eig_floor, p->eig_value, dout,
+                                                      dout + nf, dout + 10 * nf, st));
                 break;
             case SMG_MEM_ENERGY:
-                HIPCHK(launch_membrane_faces(0, nF, dF, dP, drest, alpha, beta, p->eig_floor, p->eig_value, dout, nullptr, nullptr, st));
+                HIPCHK(launch_membrane_faces_material(material, 0, nF, dF, dP, dV0, drest, p->thickness, alpha, beta, p->eig_floor, p->eig_value, dout, nullptr, nullptr, st));
                 break;
             case SMG_MEM_PRESSURE:
                 HIPCHK(launch_membrane_pressure(nV, nF, dF, dP, dmp, dmi, p->pressure, dout, dout + 6 * nf, dout + 6 * nf + nv, st));
@@ -444,7 +448,7 @@ extern "C" int smg_debug_membrane(int op, int nV, int nF, const int* F, const do
                 double* terms = dout + 2 * n3;
                 HIPCHK(X.add(nullptr, nullptr, (size_t)fixed_sum_groups(nF + nV) * D, &dpart));
                 HIPCHK(launch_membrane_trial(nV, qdot, dx, in[nv + 4 * n3], qdot0, dP, fext, din, p->mass_scale, p->dt, dout, dout + n3, terms + nf, st));
-                HIPCHK(launch_membrane_faces(0, nF, dF, dout + n3, drest, alpha, beta, p->eig_floor, p->eig_value, terms, nullptr, nullptr, st));
+                HIPCHK(launch_membrane_faces_material(material, 0, nF, dF, dout + n3, dV0, drest, p->thickness, alpha, beta, p->eig_floor, p->eig_value, terms, nullptr, nullptr, st));
                 HIPCHK(launch_fixed_sum(terms, nF + nV, dpart, terms + nf + nv, st));
                 break;
             }
@@ -454,6 +458,18 @@ extern "C" int smg_debug_membrane(int op, int nV, int nF, const int* F, const do
         if (guard_hits) *guard_hits = bad;
         return SMG_OK;
     });
+}
+
+extern "C" int smg_debug_membrane(int op, int nV, int nF, const int* F, const double* V0, const double* P, const double* in,
+                                  const smg_membrane_params* p, double* out, int* guard_hits)
+{
+    return debug_membrane("smg_debug_membrane", 0, op, nV, nF, F, V0, P, in, p, out, guard_hits);
+}
+
+extern "C" int smg_debug_membrane_material(int material, int op, int nV, int nF, const int* F, const double* V0, const double* P, const double* in,
+                                           const smg_membrane_params* p, double* out, int* guard_hits)
+{
+    return debug_membrane("smg_debug_membrane_material", material, op, nV, nF, F, V0, P, in, p, out, guard_hits);
 }
 
 extern "C" int smg_debug_param(int op, int nV, int nF, const int* F, const double* V0, const double* UV, const double* R_in, double* out,

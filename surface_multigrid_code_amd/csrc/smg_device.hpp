@@ -475,6 +475,11 @@ hipError_t launch_membrane_rest(int nF, const int* F, const double* V0, double t
 // mode 0: W (nF) alone; 1: W, G (9 planes), the upper triangle of the unfixed H (45 planes); 2: the same with the eigenvalue fix (smg_membrane_inl.hpp)
 hipError_t launch_membrane_faces(int mode, int nF, const int* F, const double* P, const double* rest, double alpha, double beta, double floor,
                                  double value, double* W, double* G, double* H, hipStream_t st);
+// the same for a material: 0 neo-Hookean (launch_membrane_faces with rest), 1 StVK, 2 tension-field StVK (k_membrane_faces_mat, which reads
+// the rest pose V0 instead of rest); any other material is hipErrorInvalidValue
+hipError_t launch_membrane_faces_material(int material, int mode, int nF, const int* F, const double* P, const double* V0, const double* rest,
+                                          double thickness, double alpha, double beta, double floor, double value, double* W, double* G, double* H,
+                                          hipStream_t st);
 // val = M + dt2 K in the scalar CSR of the pattern (adjacency + I) (x) 1_3x3: block q of block row brow[q] (bptr: block rows, bcol: block
 // columns) sums the face sub-blocks c_src[c_ptr[q] .. c_ptr[q + 1]) = 9 f + 3 a + b in list order; M = mass_scale mass0 on the diagonal
 hipError_t launch_membrane_matrix(int nB, const int* brow, const int* bcol, const int* bptr, const int* c_ptr, const int* c_src, const double* H,

@@ -1,4 +1,4 @@
-// smg_membrane.cpp -- implicit-Euler steps of a pressurised neo-Hookean membrane on the block V-cycle (include/smg.h: smg_membrane_*;
+// smg_membrane.cpp -- implicit-Euler steps of a pressurised membrane (neo-Hookean, StVK or tension-field StVK) on the block V-cycle (include/smg.h: smg_membrane_*;
 // DESIGN.md section 20; the reference's 06_example_balloon_sim: main.cpp:109-134, implicit_euler_mg_balloon.h:35-121).
 // The object owns one handle built from the caller's block prolongations and precomputed with H = M + dt^2 K of the rest pose, the mesh and
 // its lists on the device (corner lists per vertex, contribution lists per 3 x 3 block), the rest constants per face, and the state
@@ -54,6 +54,7 @@ void membrane_lists(const int* F, int nF, int nV, MembraneLists& L)
 struct smg_membrane : MeshObject {             // handle[0]: H = M + dt^2 K, block
     int nV = 0, nF = 0, nB = 0;
     int pcg = 0;                               // the inner solver: 0 smg_solve (the reference's loop), 1 smg_solve_pcg
+    int material = 0;                          // 0 neo-Hookean, 1 StVK, 2 tension-field StVK (smg_membrane_set_material)
     smg_membrane_params p;
     double alpha = 0.0, beta = 0.0;            // the Lame parameters (main.cpp:63-67)
     DevBuf<int> F, m_ptr, m_idx, brow, bcol, bptr, c_ptr, c_src;
@@ -86,7 +87,8 @@ int assemble(smg_membrane* m, const double* P, const double* qdot, const double*
 {
     const smg_membrane_params& p = m->p;
     hipStream_t st = m->stream;
-    HIPCHK(launch_membrane_faces(2, m->nF, m->F.p, P, m->rest.p, m->alpha, m->beta, p.eig_floor, p.eig_value, m->terms.p, m->G.p, m->H.p, st));
+    HIPCHK(launch_membrane_faces_material(m->material, 2, m->nF, m->F.p, P, m->V0.p, m->rest.p, p.thickness, m->alpha, m->beta, p.eig_floor,
+                                          p.eig_value, m->terms.p, m->G.p, m->H.p, st));
     HIPCHK(launch_membrane_matrix(m->nB, m->brow.p, m->bcol.p, m->bptr.p, m->c_ptr.p, m->c_src.p, m->H.p, m->nF, p.dt * p.dt, m->mass0.p,
                                   p.mass_scale, m->Hval.p, st));
     HIPCHK(launch_membrane_gradient(m->nV, m->m_ptr.p, m->m_idx.p, m->G.p, m->nF, m->mass0.p, p.mass_scale, p.dt, qdot, qdot0, m->fext.p, nullptr,
@@ -101,7 +103,8 @@ int objective(smg_membrane* m, const double* dx, double step, double* f)
     hipStream_t st = m->stream;
     HIPCHK(launch_membrane_trial(m->nV, m->qdot.p, dx, step, m->qdot0.p, m->pos0.p, m->fext.p, m->mass0.p, p.mass_scale, p.dt, m->qdotT.p, m->posT.p,
                                  m->terms.p + m->nF, st));
-    HIPCHK(launch_membrane_faces(0, m->nF, m->F.p, m->posT.p, m->rest.p, m->alpha, m->beta, p.eig_floor, p.eig_value, m->terms.p, nullptr, nullptr, st));
+    HIPCHK(launch_membrane_faces_material(m->material, 0, m->nF, m->F.p, m->posT.p, m->V0.p, m->rest.p, p.thickness, m->alpha, m->beta, p.eig_floor,
+                                          p.eig_value, m->terms.p, nullptr, nullptr, st));
     HIPCHK(launch_fixed_sum(m->terms.p, m->nF + m->nV, m->part.p, m->E.p, st));
     HIPCHK(hipMemcpyAsync(f, m->E.p, sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -296,6 +299,17 @@ extern "C" int smg_membrane_set_solver(smg_membrane* m, int pcg)
     return SMG_OK;
 }
 
+extern "C" int smg_membrane_set_material(smg_membrane* m, int material)
+{
+    if (!m) return fail(SMG_ERR_INVALID, "smg_membrane_set_material: null object");
+    if (material < 0 || material > 2)
+        return fail(SMG_ERR_INVALID, "smg_membrane_set_material: material %d is not 0 (neo-Hookean), 1 (StVK) or 2 (tension-field StVK)", material);
+    m->material = material;
+    return SMG_OK;
+}
+
+extern "C" int smg_membrane_material(const smg_membrane* m) { return m ? m->material : 0; }
+
 extern "C" int smg_membrane_step(smg_membrane* m, const smg_solve_opts* opts, double* objective_his, double* alpha, int* cycles, int* n_newton)
 {
     return guarded("smg_membrane_step", [&]() { return step_impl(m, opts, objective_his, alpha, cycles, n_newton); });
@@ -344,6 +358,44 @@ extern "C" int smg_membrane_faces_host(const double* V0, const double* P, int nV
             r[0] = a11 / det; r[1] = -a01 / det; r[2] = a00 / det; r[3] = det; r[4] = p->thickness * std::sqrt(det) / 4.0;
             if (!G) { W[f] = membrane_face<false>(q, r, alpha, beta, g, h); continue; }
             W[f] = membrane_face<true>(q, r, alpha, beta, g, h);
+            for (int e = 0; e < 9; e++) G[e * nf + f] = g[e];
+            if (!H) continue;
+            if (fix) membrane_fix(h, p->eig_floor, p->eig_value);
+            for (int e = 0; e < 45; e++) H[e * nf + f] = h[e];
+        }
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_membrane_faces_host_material(const double* V0, const double* P, int nV, const int* F, int nF, const smg_membrane_params* p,
+                                                int material, int fix, double* W, double* G, double* H)
+{
+    return guarded("smg_membrane_faces_host_material", [&]() -> int {
+        const char* who = "smg_membrane_faces_host_material";
+        if (!V0 || !P || !F || !p || !W || nV <= 0 || nF <= 0 || (H && !G)) return fail(SMG_ERR_INVALID, "%s: bad arguments", who);
+        if (material < 0 || material > 2)
+            return fail(SMG_ERR_INVALID, "%s: material %d is not 0 (neo-Hookean), 1 (StVK) or 2 (tension-field StVK)", who, material);
+        if (const char* why = bad_params(*p)) return fail(SMG_ERR_INVALID, "%s: %s", who, why);
+        if (int rc = check_mesh(who, V0, nV, F, nF, false)) return rc;
+        if (material == 0) return smg_membrane_faces_host(V0, P, nV, F, nF, p, fix, W, G, H);
+        double alpha, beta;
+        lame(*p, alpha, beta);
+        const size_t nf = (size_t)nF;
+        for (int f = 0; f < nF; f++) {
+            double q0[9], q[9], r[8], g[9], h[45];
+            for (int j = 0; j < 3; j++)
+                for (int d = 0; d < 3; d++) {
+                    q0[3 * j + d] = V0[3 * (size_t)F[3 * (size_t)f + j] + d];
+                    q[3 * j + d] = P[3 * (size_t)F[3 * (size_t)f + j] + d];
+                }
+            mem_rest_consts(q0, p->thickness, r);
+            if (!G) {
+                W[f] = material == 1 ? membrane_face_mat<1, false>(q, r, p->thickness, alpha, beta, g, h)
+                                     : membrane_face_mat<2, false>(q, r, p->thickness, alpha, beta, g, h);
+                continue;
+            }
+            W[f] = material == 1 ? membrane_face_mat<1, true>(q, r, p->thickness, alpha, beta, g, h)
+                                 : membrane_face_mat<2, true>(q, r, p->thickness, alpha, beta, g, h);
             for (int e = 0; e < 9; e++) G[e * nf + f] = g[e];
             if (!H) continue;
             if (fix) membrane_fix(h, p->eig_floor, p->eig_value);

@@ -1,4 +1,4 @@
-// smg_membrane_device.hip -- the kernels of the neo-Hookean membrane time step (smg_membrane_step, include/smg.h; host side in
+// smg_membrane_device.hip -- the kernels of the membrane time step, neo-Hookean, StVK and tension-field StVK (smg_membrane_step, include/smg.h; host side in
 // smg_membrane.cpp; the per-face maths in smg_membrane_inl.hpp).
 //
 // Layout: positions, velocities, forces, gradients and right-hand sides are xyz rows (entry 3 v + l: the numbering of the 3-DOF system).
@@ -69,6 +69,31 @@ __global__ __launch_bounds__(MEM_FACE_THREADS) void k_membrane_faces(int nF, con
 #pragma unroll
     for (int e = 0; e < 5; e++) r[e] = rest[e * (size_t)nF + f];
     W[f] = membrane_face<MODE != 0>(q, r, alpha, beta, g, h);
+    if (MODE == 0) return;
+#pragma unroll
+    for (int e = 0; e < 9; e++) G[e * (size_t)nF + f] = g[e];
+    if (MODE == 2) membrane_fix(h, floor, value);
+#pragma unroll
+    for (int e = 0; e < 45; e++) H[e * (size_t)nF + f] = h[e];
+}
+
+// The same for the StVK (MAT 1) and tension-field StVK (MAT 2) materials, under a name of its own: k_membrane_faces stays the neo-Hookean
+// path.  The rest constants are recomputed from V0 by the expressions of k_membrane_rest, because M = abar^-1 (a - abar) needs abar itself
+// (recovered from abar^-1 it would leave M = O(eps) at the rest pose, where the tension-field branch test needs exactly 0).  The three
+// tension-field branches differ in ten scalars (membrane_face_mat), so the lanes of a wave diverge over those alone.
+template <int MODE, int MAT>
+__global__ __launch_bounds__(MEM_FACE_THREADS) void k_membrane_faces_mat(int nF, const int* __restrict__ F, const double* __restrict__ P,
+                                                                         const double* __restrict__ V0, double thickness, double alpha,
+                                                                         double beta, double floor, double value, double* __restrict__ W,
+                                                                         double* __restrict__ G, double* __restrict__ H)
+{
+    const int f = blockIdx.x * MEM_FACE_THREADS + threadIdx.x;
+    if (f >= nF) return;
+    double q[9], r[8], g[9], h[45];
+    load_corners(F, V0, f, q);
+    mem_rest_consts(q, thickness, r);
+    load_corners(F, P, f, q);
+    W[f] = membrane_face_mat<MAT, MODE != 0>(q, r, thickness, alpha, beta, g, h);
     if (MODE == 0) return;
 #pragma unroll
     for (int e = 0; e < 9; e++) G[e * (size_t)nF + f] = g[e];
@@ -252,6 +277,28 @@ hipError_t launch_membrane_faces(int mode, int nF, const int* F, const double* P
     else if (mode == 1) hipLaunchKernelGGL(k_membrane_faces<1>, grid, block, 0, st, nF, F, P, rest, alpha, beta, floor, value, W, G, H);
     else hipLaunchKernelGGL(k_membrane_faces<2>, grid, block, 0, st, nF, F, P, rest, alpha, beta, floor, value, W, G, H);
     return hipGetLastError();
+}
+
+template <int MAT>
+static hipError_t launch_faces_mat(int mode, int nF, const int* F, const double* P, const double* V0, double thickness, double alpha, double beta,
+                                   double floor, double value, double* W, double* G, double* H, hipStream_t st)
+{
+    const dim3 grid(mem_grid(nF, MEM_FACE_THREADS)), block(MEM_FACE_THREADS);
+    if (mode == 0) hipLaunchKernelGGL((k_membrane_faces_mat<0, MAT>), grid, block, 0, st, nF, F, P, V0, thickness, alpha, beta, floor, value, W, G, H);
+    else if (mode == 1) hipLaunchKernelGGL((k_membrane_faces_mat<1, MAT>), grid, block, 0, st, nF, F, P, V0, thickness, alpha, beta, floor, value, W, G, H);
+    else hipLaunchKernelGGL((k_membrane_faces_mat<2, MAT>), grid, block, 0, st, nF, F, P, V0, thickness, alpha, beta, floor, value, W, G, H);
+    return hipGetLastError();
+}
+
+hipError_t launch_membrane_faces_material(int material, int mode, int nF, const int* F, const double* P, const double* V0, const double* rest,
+                                          double thickness, double alpha, double beta, double floor, double value, double* W, double* G, double* H,
+                                          hipStream_t st)
+{
+    if (nF <= 0) return hipSuccess;
+    if (material == 0) return launch_membrane_faces(mode, nF, F, P, rest, alpha, beta, floor, value, W, G, H, st);
+    if (material == 1) return launch_faces_mat<1>(mode, nF, F, P, V0, thickness, alpha, beta, floor, value, W, G, H, st);
+    if (material == 2) return launch_faces_mat<2>(mode, nF, F, P, V0, thickness, alpha, beta, floor, value, W, G, H, st);
+    return hipErrorInvalidValue;      // a material without kernels is an error, never another material's path
 }
 
 hipError_t launch_membrane_matrix(int nB, const int* brow, const int* bcol, const int* bptr, const int* c_ptr, const int* c_src, const double* H,

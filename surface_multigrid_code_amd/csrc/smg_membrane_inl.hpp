@@ -1,6 +1,7 @@
-// smg_membrane_inl.hpp -- the neo-Hookean membrane energy of one triangle, its gradient, its Hessian and the Hessian's eigenvalue fix, in
-// registers (k_membrane_faces, csrc/smg_membrane_device.hip; smg_membrane_faces_host); and what smg_membrane.cpp shares
-// with the kernel hooks: the Lame parameters and the lists of the matrix kernel.
+// smg_membrane_inl.hpp -- the membrane energy of one triangle (neo-Hookean; StVK and tension-field StVK further down), its gradient, its
+// Hessian and the Hessian's eigenvalue fix, in registers (k_membrane_faces, k_membrane_faces_mat, csrc/smg_membrane_device.hip;
+// smg_membrane_faces_host, smg_membrane_faces_host_material); and what smg_membrane.cpp shares with the kernel hooks:
+// the Lame parameters and the lists of the matrix kernel.
 //
 // Corners q0, q1, q2, e1 = q1 - q0, e2 = q2 - q0, a = [[e1.e1, e1.e2], [e1.e2, e2.e2]], abar = a of the rest pose:
 //   lnJ = log(det a / det abar) / 2,   W = coeff (beta (tr(abar^-1 a) - 2 - 2 lnJ) + alpha lnJ^2),   coeff = h sqrt(det abar) / 4.
@@ -107,6 +108,130 @@ SMG_MEM_HD double membrane_face(const double (&q)[9], const double (&rest)[5], d
             if (r % 3 == c % 3) h += S2[r / 3][c / 3];
             H[mem_tri(r, c)] = coeff * h;
         }
+    return W;
+}
+
+// ---- the StVK and tension-field StVK materials (smg_membrane_set_material 1, 2; the reference's StVKMaterial.cpp:11-60 and
+// TensionFieldStVKMaterial.cpp:11-171).  Both are functions psi(a00, a01, a11) of the first fundamental form, so with t = d psi / d a
+// (symmetric 2 x 2) and the symmetric table of second derivatives over (r0, r1, r3)
+//   G = comb(t),   H = c00 r0 r0^T + c11 r1 r1^T + c33 r3 r3^T + c01 (r0 r1^T + r1 r0^T) + c03 (r0 r3^T + r3 r0^T) + c13 (r1 r3^T + r3 r1^T) + S(t) (x) I_3
+// with the S of the header.  A material supplies W, t (3) and the table (6); one tail builds G and the 45 entries.
+// With B = abar^-1, M = B (a - abar), tr = tr M, c = thickness sqrt(det abar) / 8 (= coeff / 2):
+//   StVK:  W = c (alpha / 2 tr^2 + beta tr(M^2)),  t = c (alpha tr B + 2 beta M B),  and the table is constant per face:
+//          c00 = c k B00^2, c33 = c k B11^2, c01 = 2 c k B00 B01, c13 = 2 c k B01 B11, k = alpha + 2 beta,
+//          c03 = c (alpha B00 B11 + 2 beta B01^2), c11 = 4 c (alpha B01^2 + beta (B01^2 + B00 B11)).
+//   tension field:  l1, l2 = tr / 2 +- sqrt(max(0, tr^2 / 4 - det M)), k1 = thickness alpha / 8, k2 = thickness beta / 4, tc = -k1 / (k1 + k2).
+//          l1 >= 0 and l2 >= tc l1: StVK (pure tension);  else l1 < 0: W = 0, t = 0, table 0 (slack);  else (wrinkled), with
+//          K = (k1 + k2 - k1^2 / (k1 + k2)) sqrt(det abar) / 2, den = sqrt(tr^2 / 4 - det M), adj = the adjugate of (a - abar),
+//          I = tr / 4 B - det B / 2 adj, m = B / 2 + (sign / den) I, s = sign l1 / den:
+//          W = K l1^2,  t = 2 K l1 m,  table = 2 K (m m^T + s / 4 B B^T - s / den^2 I I^T + s det B / 2 (2 r1 r1^T - r0 r3^T - r3 r0^T) in the places
+//          of the table), where x x^T of a symmetric 2 x 2 x stands for comb(x) comb(x)^T.
+// The comparisons are the reference's, >= included: at the rest pose M is exactly zero (a - abar is, abar being passed in exactly and not
+// recovered from B) and the face is in pure tension.  W is finite for inverted faces: there is no +inf rule.
+// rest: (abar^-1)00, 01, 11, det abar, coeff, abar00, abar01, abar11 (mem_rest_consts).
+SMG_MEM_HD void mem_rest_consts(const double (&q0)[9], double thickness, double (&rest)[8])
+{
+    double e1[3], e2[3];
+#pragma unroll
+    for (int d = 0; d < 3; d++) { e1[d] = q0[3 + d] - q0[d]; e2[d] = q0[6 + d] - q0[d]; }
+    const double a00 = (e1[0] * e1[0] + e1[1] * e1[1]) + e1[2] * e1[2];
+    const double a01 = (e1[0] * e2[0] + e1[1] * e2[1]) + e1[2] * e2[2];
+    const double a11 = (e2[0] * e2[0] + e2[1] * e2[1]) + e2[2] * e2[2];
+    const double det = a00 * a11 - a01 * a01;
+    rest[0] = a11 / det; rest[1] = -a01 / det; rest[2] = a00 / det; rest[3] = det; rest[4] = thickness * sqrt(det) / 4.0;
+    rest[5] = a00; rest[6] = a01; rest[7] = a11;
+}
+
+// MAT 1: StVK, 2: tension-field StVK.  Returns W; with DERIVS also G (9) and the upper triangle of the unfixed H (45).
+template <int MAT, bool DERIVS>
+SMG_MEM_HD double membrane_face_mat(const double (&q)[9], const double (&rest)[8], double thickness, double alpha, double beta, double (&G)[9],
+                                    double (&H)[45])
+{
+    double e1[3], e2[3];
+#pragma unroll
+    for (int d = 0; d < 3; d++) { e1[d] = q[3 + d] - q[d]; e2[d] = q[6 + d] - q[d]; }
+    const double a00 = (e1[0] * e1[0] + e1[1] * e1[1]) + e1[2] * e1[2];
+    const double a01 = (e1[0] * e2[0] + e1[1] * e2[1]) + e1[2] * e2[2];
+    const double a11 = (e2[0] * e2[0] + e2[1] * e2[1]) + e2[2] * e2[2];
+    const double b00 = rest[0], b01 = rest[1], b11 = rest[2];
+    const double d00 = a00 - rest[5], d01 = a01 - rest[6], d11 = a11 - rest[7];
+    const double M00 = b00 * d00 + b01 * d01, M01 = b00 * d01 + b01 * d11, M10 = b01 * d00 + b11 * d01, M11 = b01 * d01 + b11 * d11;
+    const double tr = M00 + M11;
+    const double c = 0.5 * rest[4];
+    double W = c * ((0.5 * alpha) * (tr * tr) + beta * ((M00 * M00 + 2.0 * (M01 * M10)) + M11 * M11));
+    double t00 = 0.0, t01 = 0.0, t11 = 0.0, c00 = 0.0, c01 = 0.0, c03 = 0.0, c11 = 0.0, c13 = 0.0, c33 = 0.0;
+    if (DERIVS) {
+        const double at = alpha * tr, k = alpha + 2.0 * beta;
+        t00 = c * (at * b00 + (2.0 * beta) * (M00 * b00 + M01 * b01));
+        t01 = c * (at * b01 + (2.0 * beta) * (M00 * b01 + M01 * b11));
+        t11 = c * (at * b11 + (2.0 * beta) * (M10 * b01 + M11 * b11));
+        c00 = c * (k * (b00 * b00));
+        c33 = c * (k * (b11 * b11));
+        c01 = c * ((2.0 * k) * (b00 * b01));
+        c13 = c * ((2.0 * k) * (b01 * b11));
+        c03 = c * (alpha * (b00 * b11) + (2.0 * beta) * (b01 * b01));
+        c11 = c * (4.0 * (alpha * (b01 * b01) + beta * (b01 * b01 + b00 * b11)));
+    }
+    if (MAT == 2) {
+        const double D = M00 * M11 - M01 * M10;
+        const double disc = tr * tr / 4.0 - D;
+        const double root = sqrt(fmax(0.0, disc));
+        double l1 = tr / 2.0 + root, l2 = tr / 2.0 - root, sign = 1.0;
+        if (l2 > l1) { const double x = l1; l1 = l2; l2 = x; sign = -1.0; }
+        const double k1 = 0.5 * (thickness / 4.0) * alpha, k2 = (thickness / 4.0) * beta;
+        const double tc = -k1 / (k1 + k2);
+        if (!(l1 >= 0.0 && l2 >= tc * l1)) {
+            if (l1 < 0.0) {
+                W = 0.0;
+                t00 = t01 = t11 = c00 = c01 = c03 = c11 = c13 = c33 = 0.0;
+            } else {
+                // wrinkled: disc > 0 here (disc <= 0 gives l1 == l2, which with l1 >= 0 and tc < 1 is pure tension), so den is the root above
+                const double K = ((k1 + k2) - k1 * k1 / (k1 + k2)) * (0.5 * sqrt(rest[3]));
+                W = (K * l1) * l1;
+                if (DERIVS) {
+                    const double den = root, detB = b00 * b11 - b01 * b01;
+                    const double i00 = (tr / 4.0) * b00 - (0.5 * detB) * d11, i01 = (tr / 4.0) * b01 + (0.5 * detB) * d01,
+                                 i11 = (tr / 4.0) * b11 - (0.5 * detB) * d00;
+                    const double sd = sign / den, s = sign * l1 / den, s4 = s / 4.0, s3 = s / (den * den), K2 = 2.0 * K, sB = s * detB;
+                    const double m00 = 0.5 * b00 + sd * i00, m01 = 0.5 * b01 + sd * i01, m11 = 0.5 * b11 + sd * i11;
+                    const double Kl = K2 * l1;
+                    t00 = Kl * m00; t01 = Kl * m01; t11 = Kl * m11;
+                    c00 = K2 * ((m00 * m00 + s4 * (b00 * b00)) - s3 * (i00 * i00));
+                    c33 = K2 * ((m11 * m11 + s4 * (b11 * b11)) - s3 * (i11 * i11));
+                    c03 = K2 * (((m00 * m11 + s4 * (b00 * b11)) - s3 * (i00 * i11)) - 0.5 * sB);
+                    c01 = K2 * (2.0 * ((m00 * m01 + s4 * (b00 * b01)) - s3 * (i00 * i01)));
+                    c13 = K2 * (2.0 * ((m01 * m11 + s4 * (b01 * b11)) - s3 * (i01 * i11)));
+                    c11 = K2 * (4.0 * ((m01 * m01 + s4 * (b01 * b01)) - s3 * (i01 * i01)) + sB);
+                }
+            }
+        }
+    }
+    if (!DERIVS) return W;
+
+    mem_comb(e1, e2, t00, t01, t11, G);
+    double r0[9], r1[9], r3[9];
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        r0[d] = -2.0 * e1[d]; r0[3 + d] = 2.0 * e1[d]; r0[6 + d] = 0.0;
+        r1[d] = -(e1[d] + e2[d]); r1[3 + d] = e2[d]; r1[6 + d] = e1[d];
+        r3[d] = -2.0 * e2[d]; r3[3 + d] = 0.0; r3[6 + d] = 2.0 * e2[d];
+    }
+    const double S2[3][3] = {{2.0 * ((t00 + 2.0 * t01) + t11), -2.0 * (t00 + t01), -2.0 * (t01 + t11)},
+                             {-2.0 * (t00 + t01), 2.0 * t00, 2.0 * t01},
+                             {-2.0 * (t01 + t11), 2.0 * t01, 2.0 * t11}};
+#pragma unroll
+    for (int cc = 0; cc < 9; cc++) {
+        // column cc of the table applied to the rows: y_k = sum_l c_kl r_l[cc]
+        const double y0 = (c00 * r0[cc] + c01 * r1[cc]) + c03 * r3[cc];
+        const double y1 = (c01 * r0[cc] + c11 * r1[cc]) + c13 * r3[cc];
+        const double y3 = (c03 * r0[cc] + c13 * r1[cc]) + c33 * r3[cc];
+#pragma unroll
+        for (int r = 0; r <= cc; r++) {
+            double h = (r0[r] * y0 + r1[r] * y1) + r3[r] * y3;
+            if (r % 3 == cc % 3) h += S2[r / 3][cc / 3];
+            H[mem_tri(r, cc)] = h;
+        }
+    }
     return W;
 }
 

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""Neo-Hookean membrane time steps (smg_membrane_step) on one GPU: ms per step, loop entries of the solves, and the same step on the path a block
+"""Membrane time steps (smg_membrane_step; neo-Hookean, StVK or tension-field StVK) on one GPU: ms per step, loop entries of the solves, and the same step on the path a block
 caller had before -- H assembled on the host (the numpy restatement of tests/test_membrane_host.py) and handed to smg_precompute.
 
-    python tools/membrane_time.py [--legs bunny,bunny2] [--reps 5] [--host-iters 2]
+    python tools/membrane_time.py [--legs bunny,bunny2] [--materials neo_hookean,stvk,tension_field] [--reps 5] [--host-iters 2]
+
+One process measures every requested material on one object per mesh (smg_membrane_set_material between the runs), so the neo-Hookean row of
+a session is the yardstick of the other two.  The host-assembly path is timed for the neo-Hookean material only.
 
 bunny: bunny_15K_init (15 804 vertices, the reference's mesh) with mg_precompute_block's defaults; bunny2: its 2 x mid-point subdivision
 (252 834 vertices), the same builder.  The reference's configuration: defaults of smg_membrane_params, tol = 2e-1, the stationary loop, ten
@@ -24,6 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default="bunny,bunny2")
+    ap.add_argument("--materials", default="neo_hookean", help="comma-separated: neo_hookean, stvk, tension_field")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-iters", type=int, default=2, help="Newton iterations of the host-assembly path to time (0: skip it)")
     args = ap.parse_args()
@@ -44,18 +48,22 @@ def main():
         nV, nF = V.shape[0], F.shape[0]
         print("%s: %d vertices, %d faces, %d levels; hierarchy %.2f s, create %.2f s, device memory of the object %.1f MB"
               % (name, nV, nF, mg.n_levels, t_h, t_c, sim.device_bytes() / 1e6), flush=True)
-        for pcg in (0, 1):
-            sim.set_solver(pcg)
-            ts, r = [], None
-            for rep in range(args.reps + 1):
-                sim.set_state()
-                t1 = time.perf_counter()
-                r = sim.step()
-                if rep:
-                    ts.append(1e3 * (time.perf_counter() - t1))
-            print("  %-10s %9.3f ms / step (min %.3f, max %.3f)  loop entries %s  alpha %s  objective %.10e -> %.10e"
-                  % ("PCG" if pcg else "stationary", np.median(ts), min(ts), max(ts), list(map(int, r["cycles"])), [float(a) for a in r["alpha"]],
-                     r["objective"][0], r["objective"][-1]), flush=True)
+        for material in args.materials.split(","):
+            sim.set_material(material)
+            for pcg in (0, 1):
+                sim.set_solver(pcg)
+                ts, r = [], None
+                for rep in range(args.reps + 1):
+                    sim.set_state()
+                    t1 = time.perf_counter()
+                    r = sim.step()
+                    if rep:
+                        ts.append(1e3 * (time.perf_counter() - t1))
+                n_it = len(r["cycles"])
+                print("  %-13s %-10s %9.3f ms / step (min %.3f, max %.3f), %.3f ms / Newton iteration  loop entries %s  alpha %s  objective %.10e -> %.10e"
+                      % (material, "PCG" if pcg else "stationary", np.median(ts), min(ts), max(ts), np.median(ts) / max(n_it, 1), list(map(int, r["cycles"])),
+                         [float(a) for a in r["alpha"]], r["objective"][0], r["objective"][-1]), flush=True)
+        sim.set_material("neo_hookean")
         sim.set_solver(0)
         # byte model of the eigen-fix kernel: F, nine corner coordinates, the rest constants in; W, G, H out
         faces = 12 * nF + 72 * nF + 40 * nF + 8 * nF * 55
