@@ -566,30 +566,69 @@ class Hierarchy:
         _chk(self.L.smg_synchronize(self.h), "smg_synchronize")
 
 
-class HeatGeodesics:
+class _MeshObject:
+    """What the objects built on a mesh and a caller's hierarchy share (csrc/smg_mesh_object.hpp): the library, the object of the smg_<name>_*
+    entry points (self.o; each class also shows it under the short attribute the C ABI's callers know), teardown, bytes, solver, the options
+    pointer and the arrays of a local / global iteration."""
+
+    _prefix = o = None
+
+    def _create(self, hierarchy, V, F, *args):
+        """smg_<name>_create(hierarchy, V, nV, F, nF, *args, &out); self.o stays None when anything raises, and __del__ then has nothing to do"""
+        self.L = _lib.load()
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        F = np.ascontiguousarray(F, dtype=np.int32)
+        self.n, self.nF = V.shape[0], F.shape[0]
+        out = C.c_void_p()
+        _chk(self._fn("create")(hierarchy.h, _dp(V), self.n, _ip(F), self.nF, *args, C.byref(out)), self._prefix + "create")
+        self.o = C.c_void_p(out.value)
+
+    def _fn(self, name):
+        return getattr(self.L, self._prefix + name)
+
+    def _call(self, name, *args):
+        _chk(self._fn(name)(self.o, *args), self._prefix + name)
+
+    def __del__(self):
+        try:
+            if self.o:
+                self._fn("destroy")(self.o)
+                self.o = None
+        except Exception:
+            pass
+
+    def set_solver(self, pcg=-1):
+        """1: the solves run smg_solve_pcg (default), 0: smg_solve's stationary loop, -1: unchanged."""
+        self._call("set_solver", int(pcg))
+
+    def device_bytes(self):
+        return self._fn("device_bytes")(self.o)
+
+    @staticmethod
+    def _opts(o):
+        return C.byref(o.c) if o is not None else None
+
+    def _iterate(self, name, max_iter, *args):
+        """smg_<name>(o, *args, energy_his, cycles, &n_iter) -> (E_0 .. E_n_iter, the loop entries of each inner solve)"""
+        E = np.zeros(max_iter + 1)
+        cyc = np.zeros(max(max_iter, 1), dtype=np.int32)
+        nit = C.c_int(0)
+        self._call(name, *args, _dp(E), _ip(cyc), C.byref(nit))
+        return E[:nit.value + 1].copy(), cyc[:nit.value].copy()
+
+
+class HeatGeodesics(_MeshObject):
     """Geodesic distance by the heat method on the V-cycle (include/smg.h: smg_geodesics_*), libigl's heat_geodesics_precompute / _solve.
 
     hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  t: None (or 0) for
     the default (bounding-box diagonal / 12)^2, else the heat step's time.  voronoi: the mass matrix of the heat step."""
 
-    def __init__(self, hierarchy, V, F, t=None, voronoi=False):
-        self.L = _lib.load()
-        V = np.ascontiguousarray(V, dtype=np.float64)
-        F = np.ascontiguousarray(F, dtype=np.int32)
-        self.n = V.shape[0]
-        out = C.c_void_p()
-        _chk(self.L.smg_geodesics_create(hierarchy.h, _dp(V), V.shape[0], _ip(F), F.shape[0], float(t or 0.0), int(bool(voronoi)),
-                                         C.byref(out)), "smg_geodesics_create")
-        self.g = C.c_void_p(out.value)
-        self.cycles = (0, 0)
+    _prefix = "smg_geodesics_"
+    g = property(lambda self: self.o)
 
-    def __del__(self):
-        try:
-            if self.g:
-                self.L.smg_geodesics_destroy(self.g)
-                self.g = None
-        except Exception:
-            pass
+    def __init__(self, hierarchy, V, F, t=None, voronoi=False):
+        self._create(hierarchy, V, F, float(t or 0.0), int(bool(voronoi)))
+        self.cycles = (0, 0)
 
     @property
     def t(self):
@@ -597,10 +636,7 @@ class HeatGeodesics:
 
     def set_solver(self, heat_pcg=-1, poisson_pcg=-1):
         """1: solve the stage by smg_solve_pcg (default), 0: by smg_solve's stationary loop, -1: unchanged."""
-        _chk(self.L.smg_geodesics_set_solver(self.g, int(heat_pcg), int(poisson_pcg)), "smg_geodesics_set_solver")
-
-    def device_bytes(self):
-        return self.L.smg_geodesics_device_bytes(self.g)
+        self._call("set_solver", int(heat_pcg), int(poisson_pcg))
 
     @staticmethod
     def _sources(sources):
@@ -613,71 +649,41 @@ class HeatGeodesics:
         src = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int32) for s in sets]) if sets else np.zeros(0), dtype=np.int32)
         return len(sets), ptr, src
 
-    @staticmethod
-    def _opts(o):
-        return C.byref(o.c) if o is not None else None
+    def _solve(self, k, ptr, src, memspace, heat_opts, poisson_opts, D_ptr, ld_d):
+        cyc = (C.c_int * 2)()
+        self._call("solve", k, _ip(ptr), _ip(src) if len(src) else None, memspace, self._opts(heat_opts), self._opts(poisson_opts), D_ptr, ld_d, cyc)
+        self.cycles = (cyc[0], cyc[1])
+        return self.cycles
 
     def distance(self, sources, heat_opts=None, poisson_opts=None):
         """Distances to each source set: sources = an int (one set of one vertex) or a list of sets (an int or a list of vertex indices
         each).  Returns the n x k array, column c = the distance to set c; self.cycles = the loop entries of the two solves."""
         k, ptr, src = self._sources(sources)
         D = np.zeros((self.n, max(k, 1)), order="F")
-        cyc = (C.c_int * 2)()
-        _chk(self.L.smg_geodesics_solve(self.g, k, _ip(ptr), _ip(src) if len(src) else None, SMG_HOST, self._opts(heat_opts),
-                                        self._opts(poisson_opts), D.ctypes.data, self.n, cyc), "smg_geodesics_solve")
-        self.cycles = (cyc[0], cyc[1])
+        self._solve(k, ptr, src, SMG_HOST, heat_opts, poisson_opts, D.ctypes.data, self.n)
         return D
 
     def distance_device(self, sources, D_ptr, ld_d=None, heat_opts=None, poisson_opts=None):
         """distance() into a column-major n x k block resident in HBM (device pointer, leading dimension ld_d, default n).  Returns the
         loop entries of the two solves."""
-        k, ptr, src = self._sources(sources)
-        cyc = (C.c_int * 2)()
-        _chk(self.L.smg_geodesics_solve(self.g, k, _ip(ptr), _ip(src) if len(src) else None, SMG_DEVICE, self._opts(heat_opts),
-                                        self._opts(poisson_opts), D_ptr, ld_d or self.n, cyc), "smg_geodesics_solve")
-        self.cycles = (cyc[0], cyc[1])
-        return self.cycles
+        return self._solve(*self._sources(sources), SMG_DEVICE, heat_opts, poisson_opts, D_ptr, ld_d or self.n)
 
 
-class ArapDeformer:
+class ArapDeformer(_MeshObject):
     """As-rigid-as-possible deformation on the V-cycle (include/smg.h: smg_arap_*), libigl's arap_precompute / arap_solve (spokes energy).
 
     hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  V: the rest pose,
     handles: the vertices whose positions deform() is given; the system -L of the rest pose is precomputed here, once."""
 
+    _prefix = "smg_arap_"
+    a = property(lambda self: self.o)
+
     def __init__(self, hierarchy, V, F, handles):
-        self.L = _lib.load()
-        V = np.ascontiguousarray(V, dtype=np.float64)
-        F = np.ascontiguousarray(F, dtype=np.int32)
         self.handles = np.ascontiguousarray(handles, dtype=np.int32).reshape(-1)
-        self.n = V.shape[0]
-        out = C.c_void_p()
-        _chk(self.L.smg_arap_create(hierarchy.h, _dp(V), V.shape[0], _ip(F), F.shape[0], _ip(self.handles), self.handles.shape[0], C.byref(out)),
-             "smg_arap_create")
-        self.a = C.c_void_p(out.value)
-
-    def __del__(self):
-        try:
-            if self.a:
-                self.L.smg_arap_destroy(self.a)
-                self.a = None
-        except Exception:
-            pass
-
-    def set_solver(self, pcg=-1):
-        """1: the global step runs smg_solve_pcg (default), 0: smg_solve's stationary loop, -1: unchanged."""
-        _chk(self.L.smg_arap_set_solver(self.a, int(pcg)), "smg_arap_set_solver")
-
-    def device_bytes(self):
-        return self.L.smg_arap_device_bytes(self.a)
+        self._create(hierarchy, V, F, _ip(self.handles), self.handles.shape[0])
 
     def _run(self, hp_ptr, ld_hp, U0_ptr, ld_u0, memspace, max_iter, rel_tol, opts, U_ptr, ld_u):
-        E = np.zeros(max_iter + 1)
-        cyc = np.zeros(max(max_iter, 1), dtype=np.int32)
-        nit = C.c_int(0)
-        _chk(self.L.smg_arap_solve(self.a, hp_ptr, ld_hp, U0_ptr, ld_u0, memspace, int(max_iter), float(rel_tol),
-                                   C.byref(opts.c) if opts is not None else None, U_ptr, ld_u, _dp(E), _ip(cyc), C.byref(nit)), "smg_arap_solve")
-        return E[:nit.value + 1].copy(), cyc[:nit.value].copy()
+        return self._iterate("solve", max_iter, hp_ptr, ld_hp, U0_ptr, ld_u0, memspace, int(max_iter), float(rel_tol), self._opts(opts), U_ptr, ld_u)
 
     def deform(self, handle_pos, U0=None, max_iter=10, rel_tol=0.0, opts=None):
         """handle_pos: n_handles x 3 (row r = the position of handles[r]); U0: the n x 3 start, None = the rest pose.  Returns
@@ -697,7 +703,7 @@ class ArapDeformer:
         return self._run(hp_ptr, ld_hp or self.handles.shape[0], U0_ptr, ld_u0 or self.n, SMG_DEVICE, max_iter, rel_tol, opts, U_ptr, ld_u or self.n)
 
 
-class Parameterizer:
+class Parameterizer(_MeshObject):
     """Harmonic and as-rigid-as-possible flattening of a disk mesh on the V-cycle (include/smg.h: smg_param_*): the cotangent-weight harmonic
     map to the circle of the mesh's area, and the local / global iteration of Liu et al. 2008 from it.
 
@@ -705,48 +711,25 @@ class Parameterizer:
     copied, it is not modified.  The system -L is precomputed here, twice: with the boundary loop known and with its first vertex known."""
 
     STATS = ("flipped", "max_aspect", "mean_aspect", "mean_area_ratio", "symmetric_dirichlet", "area")
+    _prefix = "smg_param_"
+    p = property(lambda self: self.o)
 
     def __init__(self, hierarchy, V, F):
-        self.L = _lib.load()
-        V = np.ascontiguousarray(V, dtype=np.float64)
-        F = np.ascontiguousarray(F, dtype=np.int32)
-        self.n, self.nF = V.shape[0], F.shape[0]
-        out = C.c_void_p()
-        _chk(self.L.smg_param_create(hierarchy.h, _dp(V), V.shape[0], _ip(F), F.shape[0], C.byref(out)), "smg_param_create")
-        self.p = C.c_void_p(out.value)
+        self._create(hierarchy, V, F)
         self.cycles = 0
-
-    def __del__(self):
-        try:
-            if self.p:
-                self.L.smg_param_destroy(self.p)
-                self.p = None
-        except Exception:
-            pass
-
-    def set_solver(self, pcg=-1):
-        """1: the solves run smg_solve_pcg (default), 0: smg_solve's stationary loop, -1: unchanged."""
-        _chk(self.L.smg_param_set_solver(self.p, int(pcg)), "smg_param_set_solver")
-
-    def device_bytes(self):
-        return self.L.smg_param_device_bytes(self.p)
 
     def boundary(self):
         """the boundary loop, in order; its first vertex is the one the global step pins"""
         n = C.c_int(0)
-        _chk(self.L.smg_param_boundary(self.p, C.byref(n), None), "smg_param_boundary")
+        self._call("boundary", C.byref(n), None)
         loop = np.zeros(n.value, dtype=np.int32)
-        _chk(self.L.smg_param_boundary(self.p, None, _ip(loop)), "smg_param_boundary")
+        self._call("boundary", None, _ip(loop))
         return loop
-
-    @staticmethod
-    def _opts(o):
-        return C.byref(o.c) if o is not None else None
 
     def harmonic_device(self, UV_ptr, ld_uv=None, opts=None, memspace=SMG_DEVICE):
         """harmonic() into a column-major n x 2 block resident in HBM (device pointer).  Returns the loop entries of the solve."""
         cyc = C.c_int(0)
-        _chk(self.L.smg_param_harmonic(self.p, memspace, self._opts(opts), UV_ptr, ld_uv or self.n, C.byref(cyc)), "smg_param_harmonic")
+        self._call("harmonic", memspace, self._opts(opts), UV_ptr, ld_uv or self.n, C.byref(cyc))
         self.cycles = cyc.value
         return self.cycles
 
@@ -759,12 +742,7 @@ class Parameterizer:
     def flatten_device(self, UV_ptr, ld_uv=None, UV0_ptr=None, ld_uv0=None, max_iter=10, rel_tol=0.0, opts=None, memspace=SMG_DEVICE):
         """flatten() between column-major n x 2 blocks resident in HBM (device pointers; leading dimensions default to n).  Returns
         (energy_his, cycles)."""
-        E = np.zeros(max_iter + 1)
-        cyc = np.zeros(max(max_iter, 1), dtype=np.int32)
-        nit = C.c_int(0)
-        _chk(self.L.smg_param_arap(self.p, UV0_ptr, ld_uv0 or self.n, memspace, int(max_iter), float(rel_tol), self._opts(opts), UV_ptr,
-                                   ld_uv or self.n, _dp(E), _ip(cyc), C.byref(nit)), "smg_param_arap")
-        return E[:nit.value + 1].copy(), cyc[:nit.value].copy()
+        return self._iterate("arap", max_iter, UV0_ptr, ld_uv0 or self.n, memspace, int(max_iter), float(rel_tol), self._opts(opts), UV_ptr, ld_uv or self.n)
 
     def flatten(self, UV0=None, max_iter=10, rel_tol=0.0, opts=None):
         """ARAP flattening from UV0 (n x 2; None = the harmonic map).  Returns (UV, energy_his, cycles): the map after the iterations run,
@@ -781,13 +759,13 @@ class Parameterizer:
         assert UV.shape == (self.n, 2)
         sigma = np.zeros((self.nF, 2), order="F")
         st = np.zeros(6)
-        _chk(self.L.smg_param_distortion(self.p, UV.ctypes.data, self.n, SMG_HOST, sigma.ctypes.data, _dp(st)), "smg_param_distortion")
+        self._call("distortion", UV.ctypes.data, self.n, SMG_HOST, sigma.ctypes.data, _dp(st))
         stats = dict(zip(self.STATS, st.tolist()))
         stats["flipped"] = int(stats["flipped"])
         return sigma, stats
 
 
-class MembraneSim:
+class MembraneSim(_MeshObject):
     """Implicit-Euler steps of a pressurised membrane on the block V-cycle (include/smg.h: smg_membrane_*), the time step of the
     reference's 06_example_balloon_sim.  material: "neo_hookean" (default), "stvk" or "tension_field" (or 0, 1, 2).
 
@@ -796,18 +774,13 @@ class MembraneSim:
     newton_iters, ls_c, ls_shrink, ls_min_alpha, eig_floor, eig_value); the state starts as (V, 0)."""
 
     MATERIALS = ("neo_hookean", "stvk", "tension_field")
+    _prefix = "smg_membrane_"
+    m = property(lambda self: self.o)
 
     def __init__(self, hierarchy, V, F, material="neo_hookean", **params):
-        self.L = _lib.load()
-        self.m = None
-        V = np.ascontiguousarray(V, dtype=np.float64)
-        F = np.ascontiguousarray(F, dtype=np.int32)
-        self.n = V.shape[0]
         self.params = membrane_params(**params)
         mat = self._material_id(material)
-        out = C.c_void_p()
-        _chk(self.L.smg_membrane_create(hierarchy.h, _dp(V), V.shape[0], _ip(F), F.shape[0], C.byref(self.params), C.byref(out)), "smg_membrane_create")
-        self.m = C.c_void_p(out.value)
+        self._create(hierarchy, V, F, C.byref(self.params))
         if mat != 0:
             self.set_material(mat)
 
@@ -821,42 +794,30 @@ class MembraneSim:
 
     def set_material(self, material):
         """material: "neo_hookean" / 0, "stvk" / 1, "tension_field" / 2; legal between any two steps, the state is kept."""
-        _chk(self.L.smg_membrane_set_material(self.m, self._material_id(material)), "smg_membrane_set_material")
+        self._call("set_material", self._material_id(material))
 
     @property
     def material(self):
         return self.MATERIALS[self.L.smg_membrane_material(self.m)]
 
-    def __del__(self):
-        try:
-            if self.m:
-                self.L.smg_membrane_destroy(self.m)
-                self.m = None
-        except Exception:
-            pass
-
     def set_solver(self, pcg=-1):
         """0: smg_solve's stationary loop (default, the reference), 1: smg_solve_pcg, -1: unchanged."""
-        _chk(self.L.smg_membrane_set_solver(self.m, int(pcg)), "smg_membrane_set_solver")
-
-    def device_bytes(self):
-        return self.L.smg_membrane_device_bytes(self.m)
+        self._call("set_solver", int(pcg))
 
     def set_state(self, pos=None, qdot=None):
         """pos, qdot: n x 3 (None: the rest pose / zero)"""
         pos = None if pos is None else np.ascontiguousarray(pos, dtype=np.float64).reshape(self.n, 3)
         qdot = None if qdot is None else np.ascontiguousarray(qdot, dtype=np.float64).reshape(self.n, 3)
-        _chk(self.L.smg_membrane_set_state(self.m, None if pos is None else pos.ctypes.data, None if qdot is None else qdot.ctypes.data, SMG_HOST),
-             "smg_membrane_set_state")
+        self._call("set_state", None if pos is None else pos.ctypes.data, None if qdot is None else qdot.ctypes.data, SMG_HOST)
 
     def set_state_device(self, pos_ptr, qdot_ptr):
         """the same from n x 3 row-major blocks resident in HBM (device pointers; 0 / None as above)"""
-        _chk(self.L.smg_membrane_set_state(self.m, pos_ptr or None, qdot_ptr or None, SMG_DEVICE), "smg_membrane_set_state")
+        self._call("set_state", pos_ptr or None, qdot_ptr or None, SMG_DEVICE)
 
     def state(self):
         """(pos, qdot), n x 3 each"""
         pos, qdot = np.zeros((self.n, 3)), np.zeros((self.n, 3))
-        _chk(self.L.smg_membrane_get_state(self.m, pos.ctypes.data, qdot.ctypes.data, SMG_HOST), "smg_membrane_get_state")
+        self._call("get_state", pos.ctypes.data, qdot.ctypes.data, SMG_HOST)
         return pos, qdot
 
     def step(self, opts=None):
@@ -866,8 +827,7 @@ class MembraneSim:
         obj, alpha = np.zeros(n_it + 1), np.zeros(max(n_it, 1))
         cyc = np.zeros(max(n_it, 1), dtype=np.int32)
         done = C.c_int(0)
-        _chk(self.L.smg_membrane_step(self.m, C.byref(opts.c) if opts is not None else None, _dp(obj), _dp(alpha), _ip(cyc), C.byref(done)),
-             "smg_membrane_step")
+        self._call("step", self._opts(opts), _dp(obj), _dp(alpha), _ip(cyc), C.byref(done))
         return {"objective": obj, "alpha": alpha[:n_it].copy(), "cycles": cyc[:n_it].copy()}
 
 

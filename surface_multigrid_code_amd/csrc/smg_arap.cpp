@@ -4,7 +4,7 @@
 // One iteration: rotations + energy terms (k_arap_rotations), the energy (fixed-order reduction), the right-hand side (k_arap_rhs), one
 // 3-column solve warm-started at the iterate, the new iterate as xyz rows.  All of it is enqueued on the object's stream, which the handle
 // uses too; per iteration the host reads one energy double beside the solve's own history.  Checks, stream, handle, the cotangent system and
-// the inner solve: smg_mesh_object.hpp; the energy's sum: launch_fixed_sum.
+// the inner solve: smg_mesh_object.hpp; the loop and its stopping rule: smg_local_global.hpp; the energy's sum: launch_fixed_sum.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "smg_device.hpp"
+#include "smg_local_global.hpp"
 #include "smg_mesh_object.hpp"
 
 using namespace smg;
@@ -90,56 +91,45 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
 int solve_impl(smg_arap* a, const double* handle_pos, int ld_hp, const double* U0, int ld_u0, int memspace, int max_iter, double rel_tol,
                const smg_solve_opts* opts, double* U, int ld_u, double* energy_his, int* cycles, int* n_iter)
 {
-    if (!a || !handle_pos || !U || (memspace != SMG_HOST && memspace != SMG_DEVICE) || max_iter < 0 || !(rel_tol >= 0.0) || !std::isfinite(rel_tol))
+    if (!a || !handle_pos || !U || bad_memspace(memspace) || max_iter < 0 || !(rel_tol >= 0.0) || !std::isfinite(rel_tol))
         return fail(SMG_ERR_INVALID, "smg_arap_solve: bad arguments");
     const int n = a->nV, nh = a->nh;
     if (ld_hp < nh || ld_u < n || (U0 && ld_u0 < n)) return fail(SMG_ERR_INVALID, "smg_arap_solve: a leading dimension is too small");
     DeviceScope dsc(a->device);
     hipStream_t st = a->stream;
-    const hipMemcpyKind in = memspace == SMG_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    const hipMemcpyKind back = memspace == SMG_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    const size_t col_n = (size_t)n * sizeof(double), col_h = (size_t)nh * sizeof(double);
-
-    smg_solve_opts so;
-    if (opts) so = *opts;
-    else { smg_solve_opts_default(&so); so.max_iter = 50; so.tol = 1e-8 * a->scale; }
+    const smg_solve_opts so = opts_or_default(opts, 1e-8 * a->scale, 50);
     HIPCHK(a->E.ensure((size_t)max_iter + 1));
+    int t_end = 0;
+    if (!n_iter) n_iter = &t_end;
+    *n_iter = 0;
 
     // the start: U0 or the rest pose, the handle rows from handle_pos; as the solve's column-major block (Ua) and as xyz rows (P)
-    HIPCHK(hipMemcpy2DAsync(a->hp.p, col_h, handle_pos, (size_t)ld_hp * sizeof(double), col_h, 3, in, st));
-    if (U0) HIPCHK(hipMemcpy2DAsync(a->Ua.p, col_n, U0, (size_t)ld_u0 * sizeof(double), col_n, 3, in, st));
+    HIPCHK(copy_columns(a->hp.p, nh, handle_pos, ld_hp, nh, 3, copy_in(memspace), st));
+    if (U0) HIPCHK(copy_columns(a->Ua.p, n, U0, ld_u0, n, 3, copy_in(memspace), st));
     else HIPCHK(launch_arap_columns(n, a->P0.p, a->Ua.p, n, st));
     HIPCHK(launch_arap_set_handles(nh, a->handles.p, a->hp.p, nh, a->Ua.p, n, st));
     HIPCHK(launch_arap_rows(n, a->Ua.p, n, a->P.p, st));
 
-    int t = 0;
-    double E_prev = 0.0;
-    for (;; t++) {
-        // local step: R_t from U_t, E_t = E(R_t, U_t); the right-hand side is enqueued ahead of the host's look at E_t
+    // local step: R_t from U_t, E_t = E(R_t, U_t); the right-hand side is enqueued ahead of the host's look at E_t
+    auto local = [&](int t, bool with_rhs, double* E_t) -> int {
         HIPCHK(launch_arap_rotations(n, a->rowptr.p, a->col.p, a->w.p, a->P0.p, a->P.p, a->R.p, a->eterm.p, st));
         HIPCHK(launch_fixed_sum(a->eterm.p, n, a->part.p, a->E.p + t, st));
-        double E_t = 0.0;
-        HIPCHK(hipMemcpyAsync(&E_t, a->E.p + t, sizeof(double), hipMemcpyDeviceToHost, st));
-        if (t < max_iter) HIPCHK(launch_arap_rhs(n, a->rowptr.p, a->col.p, a->w.p, a->P0.p, a->R.p, a->B.p, n, st));
+        HIPCHK(hipMemcpyAsync(E_t, a->E.p + t, sizeof(double), hipMemcpyDeviceToHost, st));
+        if (with_rhs) HIPCHK(launch_arap_rhs(n, a->rowptr.p, a->col.p, a->w.p, a->P0.p, a->R.p, a->B.p, n, st));
         HIPCHK(hipStreamSynchronize(st));
-        if (energy_his) energy_his[t] = E_t;
-        if (!std::isfinite(E_t)) {
-            if (n_iter) *n_iter = t;
-            return fail(SMG_ERR_NONFINITE, "smg_arap_solve: non-finite energy at iteration %d", t);
-        }
-        if (t == max_iter) break;
-        if (t > 0 && rel_tol > 0.0 && E_prev - E_t <= rel_tol * std::fabs(E_prev)) break;
-        E_prev = E_t;
-        // global step: (-L) U_{t+1} = b, handle rows known, from U_t
-        if (int rc = inner_solve(a->handle[0], a->pcg, a->B.p, n, a->hp.p, nh, a->Ua.p, n, 3, so, a->Ub.p, n, cycles ? cycles + t : nullptr)) {
-            if (n_iter) *n_iter = t;
-            return rc;
-        }
+        return SMG_OK;
+    };
+    // global step: (-L) U_{t+1} = b, handle rows known, from U_t
+    auto global = [&](int, int* entries) -> int {
+        if (int rc = inner_solve(a->handle[0], a->pcg, a->B.p, n, a->hp.p, nh, a->Ua.p, n, 3, so, a->Ub.p, n, entries)) return rc;
         std::swap(a->Ua, a->Ub);
         HIPCHK(launch_arap_rows(n, a->Ua.p, n, a->P.p, st));
-    }
-    if (n_iter) *n_iter = t;
-    HIPCHK(hipMemcpy2DAsync(U, (size_t)ld_u * sizeof(double), a->Ua.p, col_n, col_n, 3, back, st));
+        return SMG_OK;
+    };
+    const int rc = local_global(max_iter, rel_tol, local, global, energy_his, cycles, n_iter);
+    if (rc == LOCAL_GLOBAL_NONFINITE) return fail(SMG_ERR_NONFINITE, "smg_arap_solve: non-finite energy at iteration %d", *n_iter);
+    if (rc) return rc;
+    HIPCHK(copy_columns(U, ld_u, a->Ua.p, n, n, 3, copy_out(memspace), st));
     HIPCHK(hipStreamSynchronize(st));
     return SMG_OK;
 }

@@ -58,11 +58,7 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
     // the geometry of a query, then M - tL and L on the device and the two precomputes
     DevBuf<double> dV;
     HIPCHK(dV.upload(std::vector<double>(V, V + (size_t)nV * 3)));
-    std::vector<int> Fh(F, F + (size_t)nF * 3), mp, mi;
-    vertex_corner_lists(Fh, nV, mp, mi);
-    HIPCHK(g->F.upload(Fh));
-    HIPCHK(g->m_ptr.upload(mp));
-    HIPCHK(g->m_idx.upload(mi));
+    if (int rc = upload_faces(F, nF, nV, g->F, g->m_ptr, g->m_idx)) return rc;
     HIPCHK(g->W.alloc((size_t)nF * 9));
     HIPCHK(g->Af.alloc((size_t)nF));
     HIPCHK(launch_geo_basis(dV.p, g->F.p, nF, g->W.p, g->Af.p, g->stream));
@@ -79,7 +75,7 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
 int solve_impl(smg_geodesics* g, int k, const int* src_ptr, const int* src, int memspace, const smg_solve_opts* heat_opts,
                const smg_solve_opts* poisson_opts, double* D, int ld_d, int* cycles)
 {
-    if (!g || k < 1 || !src_ptr || !src || !D || ld_d < g->nV || (memspace != SMG_HOST && memspace != SMG_DEVICE))
+    if (!g || k < 1 || !src_ptr || !src || !D || ld_d < g->nV || bad_memspace(memspace))
         return fail(SMG_ERR_INVALID, "smg_geodesics_solve: bad arguments");
     const int n = g->nV;
     for (int c = 0; c < k; c++)
@@ -106,11 +102,8 @@ int solve_impl(smg_geodesics* g, int k, const int* src_ptr, const int* src, int 
     HIPCHK(hipMemcpyAsync(g->d_src_ptr.p, g->h_src_ptr.data(), ((size_t)k + 1) * sizeof(int), hipMemcpyHostToDevice, g->stream));
     HIPCHK(hipMemcpyAsync(g->d_src.p, g->h_src.data(), (size_t)total * sizeof(int), hipMemcpyHostToDevice, g->stream));
 
-    smg_solve_opts ho, po;
-    if (heat_opts) ho = *heat_opts;
-    else { smg_solve_opts_default(&ho); ho.max_iter = 100; ho.tol = 1e-11 * std::sqrt((double)total); }
-    if (poisson_opts) po = *poisson_opts;
-    else { smg_solve_opts_default(&po); po.max_iter = 100; po.tol = 1e-11 * std::sqrt((double)k * g->area); }
+    const smg_solve_opts ho = opts_or_default(heat_opts, 1e-11 * std::sqrt((double)total), 100);
+    const smg_solve_opts po = opts_or_default(poisson_opts, 1e-11 * std::sqrt((double)k * g->area), 100);
     smg_hierarchy *heat = g->handle[g->HEAT], *pois = g->handle[g->POIS];
 
     // 1. heat: (M - tL) U = indicator block B
@@ -126,8 +119,7 @@ int solve_impl(smg_geodesics* g, int k, const int* src_ptr, const int* src, int 
         HIPCHK(hipStreamSynchronize(g->stream));
     } else {
         HIPCHK(launch_geo_shift(n, k, g->d_src_ptr.p, g->d_src.p, g->U.p, n, g->mean.p, g->B.p, n, g->stream));
-        HIPCHK(hipMemcpy2DAsync(D, (size_t)ld_d * sizeof(double), g->B.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)k,
-                                hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(copy_columns(D, ld_d, g->B.p, n, n, k, hipMemcpyDeviceToHost, g->stream));
         HIPCHK(hipStreamSynchronize(g->stream));
     }
     return SMG_OK;

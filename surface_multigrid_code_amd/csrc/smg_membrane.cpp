@@ -129,12 +129,8 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
 
     MembraneLists L;
     membrane_lists(F, nF, nV, L);
-    std::vector<int> Fv(F, F + 3 * (size_t)nF), mp, mi;
-    vertex_corner_lists(Fv, nV, mp, mi);
     m->nB = (int)L.bcol.size();
-    HIPCHK(m->F.upload(Fv));
-    HIPCHK(m->m_ptr.upload(mp));
-    HIPCHK(m->m_idx.upload(mi));
+    if (int rc = upload_faces(F, nF, nV, m->F, m->m_ptr, m->m_idx)) return rc;
     HIPCHK(m->brow.upload(L.brow));
     HIPCHK(m->bcol.upload(L.bcol));
     HIPCHK(m->bptr.upload(L.bptr));
@@ -189,9 +185,7 @@ int step_impl(smg_membrane* m, const smg_solve_opts* opts, double* objective_his
     const smg_membrane_params& p = m->p;
     const int nV = m->nV, n3 = 3 * nV;
     const size_t vec = (size_t)n3 * sizeof(double);
-    smg_solve_opts so;
-    if (opts) so = *opts;
-    else { smg_solve_opts_default(&so); so.tol = 2e-1; }      // the reference's mg_tolerance (main.cpp)
+    const smg_solve_opts so = opts_or_default(opts, 2e-1);      // the reference's mg_tolerance (main.cpp)
 
     HIPCHK(hipMemcpyAsync(m->pos0.p, m->pos.p, vec, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(m->qdot0.p, m->qdot.p, vec, hipMemcpyDeviceToDevice, st));
@@ -241,17 +235,17 @@ int step_impl(smg_membrane* m, const smg_solve_opts* opts, double* objective_his
 
 int state_impl(smg_membrane* m, double* pos, double* qdot, const double* pos_in, const double* qdot_in, int memspace, bool set)
 {
-    if (!m || (memspace != SMG_HOST && memspace != SMG_DEVICE)) return fail(SMG_ERR_INVALID, "smg_membrane_%s_state: bad arguments", set ? "set" : "get");
+    if (!m || bad_memspace(memspace)) return fail(SMG_ERR_INVALID, "smg_membrane_%s_state: bad arguments", set ? "set" : "get");
     DeviceScope dsc(m->device);
     hipStream_t st = m->stream;
     const size_t vec = 3 * (size_t)m->nV * sizeof(double);
     if (set) {
-        const hipMemcpyKind in = memspace == SMG_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+        const hipMemcpyKind in = copy_in(memspace);
         HIPCHK(hipMemcpyAsync(m->pos.p, pos_in ? pos_in : m->V0.p, vec, pos_in ? in : hipMemcpyDeviceToDevice, st));
         if (qdot_in) HIPCHK(hipMemcpyAsync(m->qdot.p, qdot_in, vec, in, st));
         else HIPCHK(hipMemsetAsync(m->qdot.p, 0, vec, st));
     } else {
-        const hipMemcpyKind back = memspace == SMG_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        const hipMemcpyKind back = copy_out(memspace);
         if (pos) HIPCHK(hipMemcpyAsync(pos, m->pos.p, vec, back, st));
         if (qdot) HIPCHK(hipMemcpyAsync(qdot, m->qdot.p, vec, back, st));
     }
@@ -332,6 +326,43 @@ extern "C" int smg_membrane_lists(const int* F, int nF, int nV, int* n_blocks, i
     });
 }
 
+namespace {
+
+// W (and G, H: 9 and 45 planes of nF) of every face at P; material 0 reads the first five of the eight rest constants
+template <bool DERIVS>
+double face_host(int material, const double (&q)[9], const double (&r)[8], const smg_membrane_params& p, double alpha, double beta, double (&g)[9],
+                 double (&h)[45])
+{
+    if (material == 1) return membrane_face_mat<1, DERIVS>(q, r, p.thickness, alpha, beta, g, h);
+    if (material == 2) return membrane_face_mat<2, DERIVS>(q, r, p.thickness, alpha, beta, g, h);
+    const double r5[5] = {r[0], r[1], r[2], r[3], r[4]};
+    return membrane_face<DERIVS>(q, r5, alpha, beta, g, h);
+}
+
+void faces_host(const double* V0, const double* P, const int* F, int nF, const smg_membrane_params& p, int material, int fix, double* W, double* G, double* H)
+{
+    double alpha, beta;
+    lame(p, alpha, beta);
+    const size_t nf = (size_t)nF;
+    for (int f = 0; f < nF; f++) {
+        double q0[9], q[9], r[8], g[9], h[45];
+        for (int j = 0; j < 3; j++)
+            for (int d = 0; d < 3; d++) {
+                q0[3 * j + d] = V0[3 * (size_t)F[3 * (size_t)f + j] + d];
+                q[3 * j + d] = P[3 * (size_t)F[3 * (size_t)f + j] + d];
+            }
+        mem_rest_consts(q0, p.thickness, r);
+        if (!G) { W[f] = face_host<false>(material, q, r, p, alpha, beta, g, h); continue; }
+        W[f] = face_host<true>(material, q, r, p, alpha, beta, g, h);
+        for (int e = 0; e < 9; e++) G[e * nf + f] = g[e];
+        if (!H) continue;
+        if (fix) membrane_fix(h, p.eig_floor, p.eig_value);
+        for (int e = 0; e < 45; e++) H[e * nf + f] = h[e];
+    }
+}
+
+}  // namespace
+
 extern "C" int smg_membrane_faces_host(const double* V0, const double* P, int nV, const int* F, int nF, const smg_membrane_params* p, int fix,
                                        double* W, double* G, double* H)
 {
@@ -339,30 +370,7 @@ extern "C" int smg_membrane_faces_host(const double* V0, const double* P, int nV
         if (!V0 || !P || !F || !p || !W || nV <= 0 || nF <= 0 || (H && !G)) return fail(SMG_ERR_INVALID, "smg_membrane_faces_host: bad arguments");
         if (const char* why = bad_params(*p)) return fail(SMG_ERR_INVALID, "smg_membrane_faces_host: %s", why);
         if (int rc = check_mesh("smg_membrane_faces_host", V0, nV, F, nF, false)) return rc;
-        double alpha, beta;
-        lame(*p, alpha, beta);
-        const size_t nf = (size_t)nF;
-        for (int f = 0; f < nF; f++) {
-            double q0[9], q[9], r[5], g[9], h[45];
-            for (int j = 0; j < 3; j++)
-                for (int d = 0; d < 3; d++) {
-                    q0[3 * j + d] = V0[3 * (size_t)F[3 * (size_t)f + j] + d];
-                    q[3 * j + d] = P[3 * (size_t)F[3 * (size_t)f + j] + d];
-                }
-            double e1[3], e2[3];
-            for (int d = 0; d < 3; d++) { e1[d] = q0[3 + d] - q0[d]; e2[d] = q0[6 + d] - q0[d]; }
-            const double a00 = (e1[0] * e1[0] + e1[1] * e1[1]) + e1[2] * e1[2];
-            const double a01 = (e1[0] * e2[0] + e1[1] * e2[1]) + e1[2] * e2[2];
-            const double a11 = (e2[0] * e2[0] + e2[1] * e2[1]) + e2[2] * e2[2];
-            const double det = a00 * a11 - a01 * a01;
-            r[0] = a11 / det; r[1] = -a01 / det; r[2] = a00 / det; r[3] = det; r[4] = p->thickness * std::sqrt(det) / 4.0;
-            if (!G) { W[f] = membrane_face<false>(q, r, alpha, beta, g, h); continue; }
-            W[f] = membrane_face<true>(q, r, alpha, beta, g, h);
-            for (int e = 0; e < 9; e++) G[e * nf + f] = g[e];
-            if (!H) continue;
-            if (fix) membrane_fix(h, p->eig_floor, p->eig_value);
-            for (int e = 0; e < 45; e++) H[e * nf + f] = h[e];
-        }
+        faces_host(V0, P, F, nF, *p, 0, fix, W, G, H);
         return SMG_OK;
     });
 }
@@ -377,30 +385,7 @@ extern "C" int smg_membrane_faces_host_material(const double* V0, const double* 
             return fail(SMG_ERR_INVALID, "%s: material %d is not 0 (neo-Hookean), 1 (StVK) or 2 (tension-field StVK)", who, material);
         if (const char* why = bad_params(*p)) return fail(SMG_ERR_INVALID, "%s: %s", who, why);
         if (int rc = check_mesh(who, V0, nV, F, nF, false)) return rc;
-        if (material == 0) return smg_membrane_faces_host(V0, P, nV, F, nF, p, fix, W, G, H);
-        double alpha, beta;
-        lame(*p, alpha, beta);
-        const size_t nf = (size_t)nF;
-        for (int f = 0; f < nF; f++) {
-            double q0[9], q[9], r[8], g[9], h[45];
-            for (int j = 0; j < 3; j++)
-                for (int d = 0; d < 3; d++) {
-                    q0[3 * j + d] = V0[3 * (size_t)F[3 * (size_t)f + j] + d];
-                    q[3 * j + d] = P[3 * (size_t)F[3 * (size_t)f + j] + d];
-                }
-            mem_rest_consts(q0, p->thickness, r);
-            if (!G) {
-                W[f] = material == 1 ? membrane_face_mat<1, false>(q, r, p->thickness, alpha, beta, g, h)
-                                     : membrane_face_mat<2, false>(q, r, p->thickness, alpha, beta, g, h);
-                continue;
-            }
-            W[f] = material == 1 ? membrane_face_mat<1, true>(q, r, p->thickness, alpha, beta, g, h)
-                                 : membrane_face_mat<2, true>(q, r, p->thickness, alpha, beta, g, h);
-            for (int e = 0; e < 9; e++) G[e * nf + f] = g[e];
-            if (!H) continue;
-            if (fix) membrane_fix(h, p->eig_floor, p->eig_value);
-            for (int e = 0; e < 45; e++) H[e * nf + f] = h[e];
-        }
+        faces_host(V0, P, F, nF, *p, material, fix, W, G, H);
         return SMG_OK;
     });
 }

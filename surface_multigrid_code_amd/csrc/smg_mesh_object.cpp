@@ -162,4 +162,26 @@ int inner_solve(smg_hierarchy* h, int pcg, const double* B, int ldb, const doubl
     return rc;
 }
 
+smg_solve_opts opts_or_default(const smg_solve_opts* opts, double tol, int max_iter)
+{
+    if (opts) return *opts;
+    smg_solve_opts so;
+    smg_solve_opts_default(&so);
+    so.tol = tol;
+    if (max_iter > 0) so.max_iter = max_iter;
+    return so;
+}
+
+int upload_faces(const int* F, int nF, int nV, DevBuf<int>& d_F, DevBuf<int>& d_ptr, DevBuf<int>& d_idx, std::vector<int>* mp, std::vector<int>* mi)
+{
+    std::vector<int> Fv(F, F + 3 * (size_t)nF), ptr, idx;
+    vertex_corner_lists(Fv, nV, ptr, idx);
+    HIPCHK(d_F.upload(Fv));
+    HIPCHK(d_ptr.upload(ptr));
+    HIPCHK(d_idx.upload(idx));
+    if (mp) mp->swap(ptr);
+    if (mi) mi->swap(idx);
+    return SMG_OK;
+}
+
 }  // namespace smg

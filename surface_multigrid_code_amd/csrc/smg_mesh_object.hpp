@@ -1,6 +1,7 @@
 // smg_mesh_object.hpp -- what an object built on a triangle mesh and a caller's hierarchy starts from (smg_geodesics.cpp, smg_arap.cpp,
 // smg_membrane.cpp, smg_param.cpp): the checks of a create call, the object's stream, device and cloned handles, the cotangent system
-// assembled on the device, the inner solve, and the byte total.  `who` is the entry point's name, the prefix of every message.
+// assembled on the device, the inner solve and its default options, the copies of a call's blocks, and the byte total.  `who` is the entry
+// point's name, the prefix of every message.  The local / global loop of smg_arap_solve and smg_param_arap: smg_local_global.hpp.
 #pragma once
 #include <vector>
 
@@ -51,5 +52,19 @@ int cotan_system(const int* F, int nF, int nV, const double* d_V, int voronoi, d
 int inner_solve(smg_hierarchy* h, int pcg, const double* B, int ldb, const double* known, int ld_kv, const double* z0, int ld_z0, int k,
                 const smg_solve_opts& o, double* z, int ld_z, int* entries);
 inline void latch_solver(int& pcg, int v) { if (v >= 0) pcg = v ? 1 : 0; }
+// the caller's options, or smg_solve_opts_default with this tol and (max_iter > 0) this max_iter
+smg_solve_opts opts_or_default(const smg_solve_opts* opts, double tol, int max_iter = 0);
+
+// ---- the blocks a call moves: the memspace argument and its two copy kinds; rows x k doubles between column-major blocks with leading
+// dimensions ld_dst, ld_src; F (nF x 3) and the corner lists t = 3 f + i of every vertex, faces ascending, onto the device (mp, mi: kept on the host too)
+inline bool bad_memspace(int memspace) { return memspace != SMG_HOST && memspace != SMG_DEVICE; }
+inline hipMemcpyKind copy_in(int memspace) { return memspace == SMG_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice; }
+inline hipMemcpyKind copy_out(int memspace) { return memspace == SMG_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice; }
+inline hipError_t copy_columns(double* dst, int ld_dst, const double* src, int ld_src, int rows, int k, hipMemcpyKind kind, hipStream_t st)
+{
+    return hipMemcpy2DAsync(dst, (size_t)ld_dst * sizeof(double), src, (size_t)ld_src * sizeof(double), (size_t)rows * sizeof(double), (size_t)k, kind, st);
+}
+int upload_faces(const int* F, int nF, int nV, DevBuf<int>& d_F, DevBuf<int>& d_ptr, DevBuf<int>& d_idx, std::vector<int>* mp = nullptr,
+                 std::vector<int>* mi = nullptr);
 
 }  // namespace smg

@@ -5,7 +5,7 @@
 // One ARAP iteration: rotations + energy terms (k_param_local), the energy (fixed-order reduction), the right-hand side (k_param_rhs), one
 // 2-column solve warm-started at the iterate.  All of it is enqueued on the object's stream, which the handles use too; per iteration the host
 // reads one energy double beside the solve's own history.  Checks, stream, handles, the cotangent system and the inner solve:
-// smg_mesh_object.hpp; the sums: launch_fixed_sum / launch_fixed_max.
+// smg_mesh_object.hpp; the loop and its stopping rule: smg_local_global.hpp; the sums: launch_fixed_sum / launch_fixed_max.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "smg_device.hpp"
+#include "smg_local_global.hpp"
 #include "smg_mesh.hpp"
 #include "smg_mesh_object.hpp"
 #include "smg_param_inl.hpp"
@@ -119,9 +120,15 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
     p->nl = (int)p->loop.size();
     if (p->nl >= nV) return fail(SMG_ERR_INVALID, "%s: every vertex is on the boundary: nothing to solve", who);
 
+    const std::vector<double> circle = circle_positions(V, p->loop, 0.5 * area2);
+
+    if (int rc = p->open(who)) return rc;
+    if (int rc = p->clone(who, h, 0)) return rc;
+    if (int rc = p->clone(who, h, 1)) return rc;
+
     // the rest constants on the host (the text the device compiles): the scale of the ARAP right-hand side
     std::vector<int> mp, mi;
-    vertex_corner_lists(m.F, nV, mp, mi);
+    if (int rc = upload_faces(F, nF, nV, p->F, p->m_ptr, p->m_idx, &mp, &mi)) return rc;
     {
         std::vector<double> bound(3 * (size_t)nF);
         for (size_t f = 0; f < (size_t)nF; f++) {
@@ -137,11 +144,6 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
         }
         p->scale_arap = std::sqrt(ss);
     }
-    const std::vector<double> circle = circle_positions(V, p->loop, 0.5 * area2);
-
-    if (int rc = p->open(who)) return rc;
-    if (int rc = p->clone(who, h, 0)) return rc;
-    if (int rc = p->clone(who, h, 1)) return rc;
 
     // -L on the host as CSR (assembled on the device): the matrix of both handles
     DevBuf<double> dV;
@@ -166,9 +168,6 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
     if (int rc = smg_precompute(p->handle[0], nV, S.ptr.data(), S.col.data(), S.L.data(), p->loop.data(), p->nl)) return rc;
     if (int rc = smg_precompute(p->handle[1], nV, S.ptr.data(), S.col.data(), S.L.data(), p->loop.data(), 1)) return rc;
 
-    HIPCHK(p->F.upload(m.F));
-    HIPCHK(p->m_ptr.upload(mp));
-    HIPCHK(p->m_idx.upload(mi));
     HIPCHK(p->circle.upload(circle));
     const size_t n = (size_t)nV, nf = (size_t)nF;
     HIPCHK(p->rest.alloc(6 * nf));
@@ -188,15 +187,11 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
     return SMG_OK;
 }
 
-bool bad_memspace(int memspace) { return memspace != SMG_HOST && memspace != SMG_DEVICE; }
-
 // Ub = the harmonic map: (-L)_uu u = -(-L)_ub u_b from zero, the loop on the circle; then Ua <-> Ub
 int harmonic_into_Ua(smg_param* p, const smg_solve_opts* opts, int* cycles)
 {
     const size_t n = (size_t)p->nV;
-    smg_solve_opts so;
-    if (opts) so = *opts;
-    else { smg_solve_opts_default(&so); so.max_iter = 50; so.tol = 1e-8 * p->scale_harmonic; }
+    const smg_solve_opts so = opts_or_default(opts, 1e-8 * p->scale_harmonic, 50);
     HIPCHK(hipMemsetAsync(p->B.p, 0, 2 * n * sizeof(double), p->stream));
     HIPCHK(hipMemsetAsync(p->Ua.p, 0, 2 * n * sizeof(double), p->stream));
     if (int rc = inner_solve(p->handle[0], p->pcg, p->B.p, p->nV, p->circle.p, p->nl, p->Ua.p, p->nV, 2, so, p->Ub.p, p->nV, cycles)) return rc;
@@ -210,9 +205,7 @@ int harmonic_impl(smg_param* p, int memspace, const smg_solve_opts* opts, double
     if (ld_uv < p->nV) return fail(SMG_ERR_INVALID, "smg_param_harmonic: a leading dimension is too small");
     DeviceScope dsc(p->device);
     if (int rc = harmonic_into_Ua(p, opts, cycles)) return rc;
-    const size_t col_n = (size_t)p->nV * sizeof(double);
-    HIPCHK(hipMemcpy2DAsync(UV, (size_t)ld_uv * sizeof(double), p->Ua.p, col_n, col_n, 2, memspace == SMG_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                            p->stream));
+    HIPCHK(copy_columns(UV, ld_uv, p->Ua.p, p->nV, p->nV, 2, copy_out(memspace), p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
     return SMG_OK;
 }
@@ -226,51 +219,39 @@ int arap_impl(smg_param* p, const double* UV0, int ld_uv0, int memspace, int max
     if (ld_uv < n || (UV0 && ld_uv0 < n)) return fail(SMG_ERR_INVALID, "smg_param_arap: a leading dimension is too small");
     DeviceScope dsc(p->device);
     hipStream_t st = p->stream;
-    const hipMemcpyKind in = memspace == SMG_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    const hipMemcpyKind back = memspace == SMG_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    const size_t col_n = (size_t)n * sizeof(double);
-
-    smg_solve_opts so;
-    if (opts) so = *opts;
-    else { smg_solve_opts_default(&so); so.max_iter = 50; so.tol = 1e-8 * p->scale_arap; }
+    const smg_solve_opts so = opts_or_default(opts, 1e-8 * p->scale_arap, 50);
     HIPCHK(p->E.ensure((size_t)max_iter + 1));
-    if (n_iter) *n_iter = 0;
+    int t_end = 0;
+    if (!n_iter) n_iter = &t_end;
+    *n_iter = 0;
 
     // the start: UV0, or the harmonic map with the same options
-    if (UV0) HIPCHK(hipMemcpy2DAsync(p->Ua.p, col_n, UV0, (size_t)ld_uv0 * sizeof(double), col_n, 2, in, st));
+    if (UV0) HIPCHK(copy_columns(p->Ua.p, n, UV0, ld_uv0, n, 2, copy_in(memspace), st));
     else if (int rc = harmonic_into_Ua(p, opts, nullptr)) return rc;
 
-    int t = 0;
-    double E_prev = 0.0;
-    for (;; t++) {
-        // local step: R_t from U_t, E_t = E(R_t, U_t); the right-hand side is enqueued ahead of the host's look at E_t
+    // local step: R_t from U_t, E_t = E(R_t, U_t); the right-hand side is enqueued ahead of the host's look at E_t
+    auto local = [&](int t, bool with_rhs, double* E_t) -> int {
         HIPCHK(launch_param_local(nF, p->F.p, p->rest.p, p->Ua.p, n, p->R.p, p->eterm.p, st));
         HIPCHK(launch_fixed_sum(p->eterm.p, nF, p->part.p, p->E.p + t, st));
-        double E_t = 0.0;
-        HIPCHK(hipMemcpyAsync(&E_t, p->E.p + t, sizeof(double), hipMemcpyDeviceToHost, st));
-        if (t < max_iter) {
+        HIPCHK(hipMemcpyAsync(E_t, p->E.p + t, sizeof(double), hipMemcpyDeviceToHost, st));
+        if (with_rhs) {
             HIPCHK(launch_param_rhs(n, nF, p->m_ptr.p, p->m_idx.p, p->rest.p, p->R.p, p->B.p, n, st));
             // the pinned row: loop[0] keeps the value it has in the iterate
-            HIPCHK(hipMemcpy2DAsync(p->pin.p, sizeof(double), p->Ua.p + p->loop[0], col_n, sizeof(double), 2, hipMemcpyDeviceToDevice, st));
+            HIPCHK(copy_columns(p->pin.p, 1, p->Ua.p + p->loop[0], n, 1, 2, hipMemcpyDeviceToDevice, st));
         }
         HIPCHK(hipStreamSynchronize(st));
-        if (energy_his) energy_his[t] = E_t;
-        if (!std::isfinite(E_t)) {
-            if (n_iter) *n_iter = t;
-            return fail(SMG_ERR_NONFINITE, "smg_param_arap: non-finite energy at iteration %d", t);
-        }
-        if (t == max_iter) break;
-        if (t > 0 && rel_tol > 0.0 && E_prev - E_t <= rel_tol * std::fabs(E_prev)) break;
-        E_prev = E_t;
-        // global step: (-L) U_{t+1} = rhs, loop[0] known, from U_t
-        if (int rc = inner_solve(p->handle[1], p->pcg, p->B.p, n, p->pin.p, 1, p->Ua.p, n, 2, so, p->Ub.p, n, cycles ? cycles + t : nullptr)) {
-            if (n_iter) *n_iter = t;
-            return rc;
-        }
+        return SMG_OK;
+    };
+    // global step: (-L) U_{t+1} = rhs, loop[0] known, from U_t
+    auto global = [&](int, int* entries) -> int {
+        if (int rc = inner_solve(p->handle[1], p->pcg, p->B.p, n, p->pin.p, 1, p->Ua.p, n, 2, so, p->Ub.p, n, entries)) return rc;
         std::swap(p->Ua, p->Ub);
-    }
-    if (n_iter) *n_iter = t;
-    HIPCHK(hipMemcpy2DAsync(UV, (size_t)ld_uv * sizeof(double), p->Ua.p, col_n, col_n, 2, back, st));
+        return SMG_OK;
+    };
+    const int rc = local_global(max_iter, rel_tol, local, global, energy_his, cycles, n_iter);
+    if (rc == LOCAL_GLOBAL_NONFINITE) return fail(SMG_ERR_NONFINITE, "smg_param_arap: non-finite energy at iteration %d", *n_iter);
+    if (rc) return rc;
+    HIPCHK(copy_columns(UV, ld_uv, p->Ua.p, n, n, 2, copy_out(memspace), st));
     HIPCHK(hipStreamSynchronize(st));
     return SMG_OK;
 }
@@ -282,11 +263,11 @@ int distortion_impl(smg_param* p, const double* UV, int ld_uv, int memspace, dou
     if (ld_uv < n) return fail(SMG_ERR_INVALID, "smg_param_distortion: a leading dimension is too small");
     DeviceScope dsc(p->device);
     hipStream_t st = p->stream;
-    const size_t col_n = (size_t)n * sizeof(double), nf = (size_t)nF;
+    const size_t nf = (size_t)nF;
     const double* dUV = UV;
     int ld = ld_uv;
     if (memspace == SMG_HOST) {      // the map through the right-hand side's block: no iteration is in flight between two calls
-        HIPCHK(hipMemcpy2DAsync(p->B.p, col_n, UV, (size_t)ld_uv * sizeof(double), col_n, 2, hipMemcpyHostToDevice, st));
+        HIPCHK(copy_columns(p->B.p, n, UV, ld_uv, n, 2, hipMemcpyHostToDevice, st));
         dUV = p->B.p;
         ld = n;
     }
@@ -295,7 +276,7 @@ int distortion_impl(smg_param* p, const double* UV, int ld_uv, int memspace, dou
     HIPCHK(launch_fixed_max(p->terms.p + 6 * nf, nF, p->part.p, p->stats.p + 6, st));
     double s[7];
     HIPCHK(hipMemcpyAsync(s, p->stats.p, sizeof s, hipMemcpyDeviceToHost, st));
-    if (sigma) HIPCHK(hipMemcpyAsync(sigma, p->sigma.p, 2 * nf * sizeof(double), memspace == SMG_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    if (sigma) HIPCHK(hipMemcpyAsync(sigma, p->sigma.p, 2 * nf * sizeof(double), copy_out(memspace), st));
     HIPCHK(hipStreamSynchronize(st));
     stats[0] = s[0];                // flipped faces
     stats[1] = s[6];                // max sigma1 / sigma2 over the unflipped faces

@@ -268,6 +268,26 @@ def test_solve_refusals(smg, sphere_case):
     assert L.smg_arap_solve(arap.a, hpf.ctypes.data, handles.size, None, 0, 7, 1, 0.0, None, U.ctypes.data, V.shape[0], None, None, None) == -1
 
 
+def test_non_finite_start_is_refused_at_iteration_0(smg, sphere_case):
+    """one NaN in U0 at a vertex that is no handle: E_0 is NaN, so the call ends before any inner solve with SMG_ERR_NONFINITE, n_iter = 0 and
+    nothing written past energy_his[0]; the object is as usable afterwards as before (the same bits)"""
+    import ctypes as C
+    V, F, mg, handles, hp, arap = sphere_case
+    n, nh, L = V.shape[0], handles.size, smg._lib.load()
+    before = arap.deform(hp, max_iter=2)
+    v = int(np.setdiff1d(np.arange(n), handles)[n // 2])
+    U0 = np.asfortranarray(V.copy())
+    U0[v, 1] = np.nan
+    hpf, U = np.asfortranarray(hp), np.zeros((n, 3), order="F")
+    E, cyc, nit = np.full(4, -7.0), np.full(3, -7, dtype=np.int32), C.c_int(-7)
+    rc = L.smg_arap_solve(arap.a, hpf.ctypes.data, nh, U0.ctypes.data, n, 0, 3, 0.0, None, U.ctypes.data, n, E.ctypes.data_as(C.POINTER(C.c_double)),
+                          cyc.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nit))
+    assert rc == -4 and L.smg_last_error() == b"smg_arap_solve: non-finite energy at iteration 0"
+    assert nit.value == 0 and np.isnan(E[0]) and np.all(E[1:] == -7.0) and np.all(cyc == -7)
+    after = arap.deform(hp, max_iter=2)
+    assert all(np.array_equal(x, y) for x, y in zip(before, after))
+
+
 def test_stationary_loop_option(smg, bunny_case):
     V, F, mg, handles, hp, arap = bunny_case
     U_pcg, E_pcg, c_pcg = arap.deform(hp, max_iter=4)

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): what the three objects built on a mesh and a caller's hierarchy hold in HBM (csrc/smg_mesh_object.hpp).  Per object: create,
+"""GPU (-m gpu): what the four objects built on a mesh and a caller's hierarchy hold in HBM (csrc/smg_mesh_object.hpp).  Per object: create,
 use once, read device_bytes() and the library's count of live DevBuf bytes, destroy.  Everything device_bytes() counts is a live buffer and
 nothing is counted twice, and the teardown -- which names no buffer -- gives every byte back."""
 import gc
@@ -34,10 +34,16 @@ def _membrane(smg):
     return mg, lambda: smg.MembraneSim(mg, V, F, newton_iters=2), lambda m: m.step()
 
 
-@pytest.mark.parametrize("which", ["geodesics", "arap", "membrane"])
+def _param(smg):
+    V, F = load_mesh("ogre_sim.smgm")                                              # 2 612 vertices, a disk
+    mg = smg.mg_precompute(V, F, 0.25, 500, 1)
+    return mg, lambda: smg.Parameterizer(mg, V, F), lambda p: p.distortion(p.flatten(max_iter=2)[0])
+
+
+@pytest.mark.parametrize("which", ["geodesics", "arap", "membrane", "param"])
 def test_device_bytes_are_live_buffers_and_destroy_frees_them(smg, which):
     live = smg._lib.load().smg_device_bytes_live
-    mg, create, use = {"geodesics": _geodesics, "arap": _arap, "membrane": _membrane}[which](smg)    # the caller's hierarchy stays alive throughout
+    mg, create, use = {"geodesics": _geodesics, "arap": _arap, "membrane": _membrane, "param": _param}[which](smg)    # the caller's hierarchy stays alive throughout
     gc.collect()
     before = live()
     obj = create()
