@@ -717,6 +717,17 @@ int smg_debug_check_block_gs_plan(smg_hierarchy *h, int lv, int block_rows, int 
  * stats[3] as smg_level_get_wave_gs_order.  Checks the plan's invariants on the way.  Needs no GPU (after the host half of smg_precompute).
  * *n_pieces = 0: the level does not qualify (a row of more than 64 off-diagonal entries). */
 int smg_debug_check_wave_gs_plan(smg_hierarchy *h, int lv, int piece_rows, int pieces_mode, int *n_pieces, int *n_colors, double *stats, double *max_abs_diff);
+/* Test hook: the copies of the level values a sweep plan of level lv holds, and the maps that refresh them after a value-only smg_precompute
+ * (which: 0 the overlapped tiling of relax(sweeps), sweeps 1 .. 3; 1 wave; 2 block Gauss-Seidel; sweeps is ignored for 1 and 2).  The plan is built on the
+ * host from the matrix the level sweeps on -- A_lv, or its transpose where A_lv is not bit-symmetric -- exactly as the solves build it, and checked bit for
+ * bit: a slot with a map holds the level value the map names, an entry slot without one +0.0 (sign bit clear), a diagonal slot without one 1.0 -- the
+ * padding the refresh leaves untouched.  *n_slots: entry and diagonal slots, *n_padding: those without a map, *bad: slots that fail (must be 0).
+ * against_transpose != 0: every mapped slot is compared with the MIRRORED level value (a_ji for a slot of a_ij), the comparison the map of the wrong one
+ * of A_lv / A_lv^T would pass: *bad then counts the slots whose entry is not bit-symmetric.  *on_transpose: 1 when the plan was built from A_lv^T.
+ * Needs no GPU (after the host half of smg_precompute; which of A_lv / A_lv^T the level sweeps on is decided with the level's images, so without a
+ * GPU the hook applies that rule itself: A_lv^T wherever the two differ in any bit).  *n_slots = 0: the level has no such plan. */
+int smg_debug_check_plan_value_maps(smg_hierarchy *h, int lv, int which, int sweeps, int against_transpose, int *n_slots, int *n_padding, int *bad,
+                                    int *on_transpose);
 /* Test hook: raises the stall flag of the sparse triangular solves on the device, as a wait that gave up would (csrc/smg_coarse_device.hip).
  * The next solve's waits then give up at once, its coarse corrections are NaN, and the next synchronising entry point returns SMG_ERR_HIP
  * and clears the flag.  Fails unless the handle holds a sparse coarse factorisation. */

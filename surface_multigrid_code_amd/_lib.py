@@ -163,6 +163,7 @@ def load():
         "smg_debug_device_bytes": (i, [vp, C.c_char_p, i]),
         "smg_level_get_wave_gs_order": (i, [vp, i, i, ip, ip, ip, ip, ip, dp]),
         "smg_debug_check_wave_gs_plan": (i, [vp, i, i, i, ip, ip, dp, dp]),
+        "smg_debug_check_plan_value_maps": (i, [vp, i, i, i, i, ip, ip, ip, ip]),
         "smg_debug_raise_coarse_stall": (i, [vp]),
         "smg_debug_check_block_gs_plan": (i, [vp, i, i, ip, ip, dp, dp, dp]),
         "smg_level_get_block_gs_order": (i, [vp, i, i, ip, ip, ip, ip, ip, dp]),

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "smg_internal.hpp"
@@ -99,23 +100,28 @@ SweepPlan smg::sweep_plan(const smg_hierarchy* h, int lv, int k, int sweeps, boo
 // entries the index into Level::d_Aval: what every plan is built from.
 struct SweepMatrix {
     const Level* Lv = nullptr;
-    Csr AT;                        // (where the level sweeps on A^T)
+    bool on_transpose = false;     // the level sweeps on A^T (Level::gs_on_transpose)
+    Csr AT;                        // (then)
     std::vector<int> tsrc;         // ... entry of AT -> entry of A_int
     const Csr* G = nullptr;        // A_int or AT
     std::vector<int> to_level_value(const std::vector<int>& entries) const      // plan slots -> Level::d_Aval (-1: padding)
     {
         std::vector<int> m(entries.size());
-        for (size_t i = 0; i < m.size(); i++) m[i] = entries[i] < 0 ? -1 : Lv->A_int_src[(size_t)(Lv->gs_on_transpose ? tsrc[(size_t)entries[i]] : entries[i])];
+        for (size_t i = 0; i < m.size(); i++) m[i] = entries[i] < 0 ? -1 : Lv->A_int_src[(size_t)(on_transpose ? tsrc[(size_t)entries[i]] : entries[i])];
         return m;
     }
 };
-static int sweep_matrix(smg_hierarchy* h, int lv, SweepMatrix* M)
+// by_bits: a handle whose device half never ran (the self-checks on a machine without a GPU) has no images and no Level::gs_on_transpose yet --
+// the rule of the first precompute (level_images: A^T wherever the two differ in any bit) is applied here
+static int sweep_matrix(smg_hierarchy* h, int lv, SweepMatrix* M, bool by_bits = false)
 {
     int rc = ensure_A_int(h, lv);
     if (rc) return rc;
     M->Lv = &h->lv[lv];
-    if (M->Lv->gs_on_transpose) M->AT = transpose(M->Lv->A_int, &M->tsrc);
-    M->G = M->Lv->gs_on_transpose ? &M->AT : &M->Lv->A_int;
+    M->on_transpose = M->Lv->gs_on_transpose;
+    if (M->on_transpose || by_bits) M->AT = transpose(M->Lv->A_int, &M->tsrc);
+    if (by_bits && !M->on_transpose) M->on_transpose = !(M->AT.ptr == M->Lv->A_int.ptr && M->AT.col == M->Lv->A_int.col && M->AT.val == M->Lv->A_int.val);
+    M->G = M->on_transpose ? &M->AT : &M->Lv->A_int;
     return SMG_OK;
 }
 
@@ -128,14 +134,63 @@ static int gather_plan_values(smg_hierarchy* h, const Level& Lv, PlanValues& V)
     HIPCHK(launch_gather_vals(V.diag.p, Lv.d_Aval.p, V.mapd.p, V.diag.n, h->stream));
     return SMG_OK;
 }
-// a new plan's values as its builder read them from the host copy, and their maps (kept on the host); after a value-only re-precompute that copy is
-// stale: the values are gathered from the device copy at once
-static int set_plan_values(smg_hierarchy* h, const Level& Lv, const SweepMatrix& M, PlanValues& V, const std::vector<double>& val, const std::vector<int>& entry,
-                           const std::vector<double>& diag, const std::vector<int>& dentry)
+// A plan's copies of the level values on the host: the values as its builder read them from the host copy, and for every slot the index into
+// Level::d_Aval (-1: padding the builder wrote -- +0.0 in an entry slot, 1.0 on the diagonal of a lane without a row; refresh_plan_values keeps it).
+// What set_plan_values uploads and smg_debug_check_plan_value_maps checks.
+struct PlanSlots {
+    const std::vector<double> *val = nullptr, *diag = nullptr;
+    std::vector<int> map, mapd;
+};
+static PlanSlots plan_slots(const SweepMatrix& M, const std::vector<double>& val, const std::vector<int>& entry, const std::vector<double>& diag,
+                            const std::vector<int>& dentry)
 {
-    HIPCHK(V.val.upload(val)); HIPCHK(V.diag.upload(diag));
-    V.host_map = M.to_level_value(entry); V.host_mapd = M.to_level_value(dentry);
+    PlanSlots S;
+    S.val = &val; S.diag = &diag; S.map = M.to_level_value(entry); S.mapd = M.to_level_value(dentry);
+    return S;
+}
+static PlanSlots plan_slots(const SweepMatrix& M, const TiledGs& P) { return plan_slots(M, P.pval, P.pentry, P.pdiag, P.pdentry); }
+static PlanSlots plan_slots(const SweepMatrix& M, const BgsPlan& P) { return plan_slots(M, P.eval, P.eentry, P.udiag, P.dentry); }
+static PlanSlots plan_slots(const SweepMatrix& M, const WgsPlan& P) { return plan_slots(M, P.eval, P.eentry, P.diag, P.dentry); }
+// a new plan's values and their maps (kept on the host); after a value-only re-precompute the host copy the builder read is stale: the values are
+// gathered from the device copy at once
+static int set_plan_values(smg_hierarchy* h, const Level& Lv, PlanSlots&& S, PlanValues& V)
+{
+    HIPCHK(V.val.upload(*S.val)); HIPCHK(V.diag.upload(*S.diag));
+    V.host_map = std::move(S.map); V.host_mapd = std::move(S.mapd);
     return h->host_stale && Lv.d_Aval.p ? gather_plan_values(h, Lv, V) : SMG_OK;
+}
+
+// ---- the plans of a level as the host builds them (ensure_* below; smg_debug_check_plan_value_maps)
+// Tile size (measured at C3, tools/tiled_sweep.sh): parts of 128 .. 256 rows, 512 threads (one row of every colour per thread).
+// Smaller tiles put more CUs to work but the halo of P rings then dominates (6x redundant row updates at 64 rows: slower);
+// larger ones run too few workgroups.
+// Beyond 65 536 rows parts of 256 rows are more workgroups than the part has compute units (a second round of them: tools/size_sweep.py, a
+// 69 120-row level 45.8 us per visit against 28 us at 56 320 rows): the parts grow to 512 rows so that the level stays one round up to 122 880
+// rows (69 120 rows: 34.2 us, 77 824: 43.4 -> 32.2, 101 376: 47.5 (colour launches) -> 36.7; at 30 720 rows parts of 512 rows lose: 25.1 -> 28.0).
+static TiledGs host_tiled_plan(const SweepMatrix& M, int sweeps, int* threads)
+{
+    static const int rows_env = env_int("SMG_TILED_ROWS", 0), nt_env = env_int("SMG_TILED_NT", 0);
+    const Level& Lv = *M.Lv;
+    const int tile_rows0 = rows_env > 0 ? rows_env : std::min(512, std::max(256, (Lv.n + 239) / 240));
+    constexpr int max_ext = (64 * 1024 - TILED_LDS_STATIC) / 8;    // 64 KB of LDS, the kernel's static header included
+    // a tile whose halo makes a colour's panel longer than the workgroup gets smaller tiles
+    TiledGs P;
+    *threads = 512;
+    for (int tile_rows = tile_rows0, tries = 0; tries < 3 && P.empty(); tile_rows = tile_rows * 2 / 3, tries++) {
+        *threads = nt_env > 0 ? nt_env : 512;
+        P = build_tiled_gs(*M.G, Lv.ord.color_ptr, sweeps, tile_rows, max_ext, *threads);
+    }
+    return P;
+}
+static BgsPlan host_bgs_plan(const SweepMatrix& M)
+{
+    static const int rows_env = env_int("SMG_BGS_ROWS", 64);
+    return build_bgs(*M.G, M.Lv->ord.color_ptr, std::min(std::max(rows_env, 8), (int)BGS_ROWS));
+}
+static WgsPlan host_wgs_plan(const SweepMatrix& M)
+{
+    static const int rows_env = env_int("SMG_WGS_ROWS", WGS_ROWS), mode_env = env_int("SMG_WGS_PIECES", 1);
+    return build_wgs(*M.G, std::min(std::max(rows_env, 8), (int)WGS_ROWS), mode_env);
 }
 
 static int ensure_tiled(smg_hierarchy* h, int lv, int sweeps)
@@ -144,27 +199,13 @@ static int ensure_tiled(smg_hierarchy* h, int lv, int sweeps)
     TiledBuf& B = Lv.tiled[sweeps];
     if (B.tried) return SMG_OK;
     B.tried = true;
-    // Tile size (measured at C3, tools/tiled_sweep.sh): parts of 128 .. 256 rows, 512 threads (one row of every colour per thread).
-    // Smaller tiles put more CUs to work but the halo of P rings then dominates (6x redundant row updates at 64 rows: slower);
-    // larger ones run too few workgroups.
-    // Beyond 65 536 rows parts of 256 rows are more workgroups than the part has compute units (a second round of them: tools/size_sweep.py, a
-    // 69 120-row level 45.8 us per visit against 28 us at 56 320 rows): the parts grow to 512 rows so that the level stays one round up to 122 880
-    // rows (69 120 rows: 34.2 us, 77 824: 43.4 -> 32.2, 101 376: 47.5 (colour launches) -> 36.7; at 30 720 rows parts of 512 rows lose: 25.1 -> 28.0).
-    static const int rows_env = env_int("SMG_TILED_ROWS", 0), nt_env = env_int("SMG_TILED_NT", 0);
-    const int tile_rows0 = rows_env > 0 ? rows_env : std::min(512, std::max(256, (Lv.n + 239) / 240));
-    constexpr int max_ext = (64 * 1024 - TILED_LDS_STATIC) / 8;    // 64 KB of LDS, the kernel's static header included
     SweepMatrix M;
     { int rc = sweep_matrix(h, lv, &M); if (rc) return rc; }
-    // a tile whose halo makes a colour's panel longer than the workgroup gets smaller tiles
-    TiledGs P;
     int threads = 512;
-    for (int tile_rows = tile_rows0, tries = 0; tries < 3 && P.empty(); tile_rows = tile_rows * 2 / 3, tries++) {
-        threads = nt_env > 0 ? nt_env : 512;
-        P = build_tiled_gs(*M.G, Lv.ord.color_ptr, sweeps, tile_rows, max_ext, threads);
-    }
+    const TiledGs P = host_tiled_plan(M, sweeps, &threads);
     if (P.empty()) return SMG_OK;
     HIPCHK(B.hdr.upload(P.hdr)); HIPCHK(B.ext_rows.upload(P.ext_rows)); HIPCHK(B.pcol.upload(P.pcol)); HIPCHK(B.prow.upload(P.prow));
-    { int rc = set_plan_values(h, Lv, M, B.v, P.pval, P.pentry, P.pdiag, P.pdentry); if (rc) return rc; }
+    { int rc = set_plan_values(h, Lv, plan_slots(M, P), B.v); if (rc) return rc; }
     HIPCHK(tiled_gs_prepare(P.max_ext));
     int wmax = 0;
     for (int t = 0; t < P.n_tiles; t++) wmax = std::max(wmax, P.hdr[(size_t)t * TILED_HDR + 2]);
@@ -183,15 +224,14 @@ static int ensure_bgs(smg_hierarchy* h, int lv)
     BgsBuf& B = Lv.bgs;
     if (B.tried) return SMG_OK;
     B.tried = true;
-    static const int rows_env = env_int("SMG_BGS_ROWS", 64);
     SweepMatrix M;
     { int rc = sweep_matrix(h, lv, &M); if (rc) return rc; }
     const auto t_plan0 = std::chrono::steady_clock::now();
-    BgsPlan P = build_bgs(*M.G, Lv.ord.color_ptr, std::min(std::max(rows_env, 8), (int)BGS_ROWS));
+    const BgsPlan P = host_bgs_plan(M);
     const double plan_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_plan0).count();
     if (P.empty()) return SMG_OK;
     HIPCHK(B.hdr.upload(P.hdr)); HIPCHK(B.xrow.upload(P.xrow)); HIPCHK(B.ugrow.upload(P.ugrow)); HIPCHK(B.ulrow.upload(P.ulrow)); HIPCHK(B.eidx.upload(P.eidx));
-    { int rc = set_plan_values(h, Lv, M, B.v, P.eval, P.eentry, P.udiag, P.dentry); if (rc) return rc; }
+    { int rc = set_plan_values(h, Lv, plan_slots(M, P), B.v); if (rc) return rc; }
     B.view.n_blocks = P.n_blocks; B.view.n_colors = P.n_colors; B.view.xrows = P.xrows;
     B.view.hdr = B.hdr.p; B.view.xrow = B.xrow.p; B.view.ugrow = B.ugrow.p; B.view.ulrow = B.ulrow.p; B.view.udiag = B.v.diag.p; B.view.eidx = B.eidx.p; B.view.eval = B.v.val.p;
     B.color_ptr = P.color_ptr; B.host_rows = P.rows; B.host_blk_ptr = P.blk_ptr; B.rim = P.rim; B.fill = P.fill;
@@ -207,15 +247,14 @@ static int ensure_wgs(smg_hierarchy* h, int lv)
     WgsBuf& B = Lv.wgs;
     if (B.tried) return SMG_OK;
     B.tried = true;
-    static const int rows_env = env_int("SMG_WGS_ROWS", WGS_ROWS), mode_env = env_int("SMG_WGS_PIECES", 1);
     SweepMatrix M;
     { int rc = sweep_matrix(h, lv, &M); if (rc) return rc; }
     const auto t_plan0 = std::chrono::steady_clock::now();
-    WgsPlan P = build_wgs(*M.G, std::min(std::max(rows_env, 8), (int)WGS_ROWS), mode_env);
+    const WgsPlan P = host_wgs_plan(M);
     const double plan_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_plan0).count();
     if (P.empty()) return SMG_OK;
     HIPCHK(B.hdr.upload(P.hdr)); HIPCHK(B.grow.upload(P.grow)); HIPCHK(B.meta.upload(P.meta)); HIPCHK(B.rim.upload(P.rim)); HIPCHK(B.eoff.upload(P.eoff));
-    { int rc = set_plan_values(h, Lv, M, B.v, P.eval, P.eentry, P.diag, P.dentry); if (rc) return rc; }
+    { int rc = set_plan_values(h, Lv, plan_slots(M, P), B.v); if (rc) return rc; }
     B.view.n_pieces = P.n_pieces; B.view.n_colors = P.n_colors; B.view.rim_pitch = P.rim_pitch; B.view.nb_max = P.nb_max;
     B.view.hdr = B.hdr.p; B.view.grow = B.grow.p; B.view.meta = B.meta.p; B.view.diag = B.v.diag.p; B.view.rim = B.rim.p; B.view.eoff = B.eoff.p; B.view.eval = B.v.val.p;
     B.color_ptr = P.color_ptr; B.host_rows = P.rows; B.host_piece_ptr = P.piece_ptr; B.rim_ratio = P.rim_ratio; B.phases_mean = P.phases_mean; B.phases_max = P.phases_max;
@@ -493,6 +532,62 @@ extern "C" int smg_debug_check_block_gs_plan(smg_hierarchy* h, int lv, int block
         const long bad = bgs_sweep_host(P, b.data(), y.data());
         if (bad >= 0) return fail(SMG_ERR_INVALID, "block plan: local index %d outside the image of %d rows", P.eidx[(size_t)bad], P.xrows);
         if (max_abs_diff) *max_abs_diff = max_diff(y, ref);
+        return SMG_OK;
+    });
+}
+
+// The value maps of a plan of level lv (which: 0 the overlapped tiling of relax(sweeps), 1 wave, 2 block Gauss-Seidel), built from sweep_matrix()
+// as ensure_tiled / ensure_wgs / ensure_bgs build it: every slot with a map holds, bit for bit, the level value the map names (Level::A.val, what
+// Level::d_Aval is uploaded from), every entry slot without one +0.0, every diagonal slot without one 1.0 -- what refresh_plan_values relies on.
+// against_transpose: the comparison a map of A would pass where the level sweeps on A^T and the reverse (entry (i, j) against a_ji): tests show with
+// it that a wrong map is counted.  *on_transpose: the plan was built from A^T -- the level's choice, or on a handle whose device half never ran
+// (no GPU) the choice of the first precompute, from the bits.  *n_slots = 0: the level has no such plan.
+extern "C" int smg_debug_check_plan_value_maps(smg_hierarchy* h, int lv, int which, int sweeps, int against_transpose, int* n_slots, int* n_padding, int* bad,
+                                               int* on_transpose)
+{
+    return guarded("smg_debug_check_plan_value_maps", [&]() -> int {
+        const Csr* A_int = nullptr;
+        int rc = check_level(h, lv, which >= 0 && which <= 2 && (which != 0 || (sweeps >= 1 && sweeps <= 3)), "smg_debug_check_plan_value_maps", &A_int);
+        if (rc) return rc;
+        SweepMatrix M;
+        if ((rc = sweep_matrix(h, lv, &M, !h->lv[lv].dA.view.val))) return rc;
+        if (on_transpose) *on_transpose = M.on_transpose ? 1 : 0;
+        TiledGs T; WgsPlan W; BgsPlan Bp;
+        PlanSlots S;
+        int threads = 0;
+        if (which == 0) { T = host_tiled_plan(M, sweeps, &threads); if (!T.empty()) S = plan_slots(M, T); }
+        else if (which == 1) { W = host_wgs_plan(M); if (!W.empty()) S = plan_slots(M, W); }
+        else { Bp = host_bgs_plan(M); if (!Bp.empty()) S = plan_slots(M, Bp); }
+        if (n_slots) *n_slots = 0;
+        if (n_padding) *n_padding = 0;
+        if (bad) *bad = 0;
+        if (!S.val) return SMG_OK;
+        const Csr& A = h->lv[lv].A;
+        std::vector<double> mirrored;
+        if (against_transpose) {
+            std::vector<int> tsrc;
+            const Csr AT = transpose(A, &tsrc);
+            if (!(AT.ptr == A.ptr && AT.col == A.col)) return fail(SMG_ERR_INVALID, "smg_debug_check_plan_value_maps: level %d is not structurally symmetric", lv);
+            mirrored.resize(A.val.size());
+            for (size_t e = 0; e < mirrored.size(); e++) mirrored[e] = A.val[(size_t)tsrc[e]];
+        }
+        const double* level_val = against_transpose ? mirrored.data() : A.val.data();
+        const size_t n_level_val = A.val.size();
+        auto same_bits = [](double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; };
+        int slots = 0, padding = 0, wrong = 0;
+        auto check = [&](const std::vector<double>& val, const std::vector<int>& map, double pad) {
+            if (val.size() != map.size()) { wrong += (int)std::max(val.size(), map.size()); return; }
+            for (size_t i = 0; i < val.size(); i++) {
+                slots++;
+                if (map[i] < 0) { padding++; wrong += !same_bits(val[i], pad); }
+                else wrong += (size_t)map[i] >= n_level_val || !same_bits(val[i], level_val[(size_t)map[i]]);
+            }
+        };
+        check(*S.val, S.map, 0.0);
+        check(*S.diag, S.mapd, 1.0);
+        if (n_slots) *n_slots = slots;
+        if (n_padding) *n_padding = padding;
+        if (bad) *bad = wrong;
         return SMG_OK;
     });
 }

@@ -44,6 +44,23 @@ def subdiv_problem(mesh="ogre_sim.smgm", n_sub=2, kind="mcf", k=1, seed=0, n_pin
     return out
 
 
+def value_step(A, seed):
+    """What a time-stepping caller hands to its next smg_precompute: the pattern of A, new values, still SPD, and NOT bit-symmetric.
+    D A D + diag(u diag A) with D = 1 + 0.01 U(0,1) and u ~ U(0, 0.5) -- which differs from its transpose in the last bits only -- and then every
+    stored entry moved independently of its mirror image by 1 + 1e-5 U(-1,1), so that a sweep on A where A^T is due (the reference walks
+    column i) gives other bits in every row."""
+    A = sp.csr_matrix(A)
+    A.sort_indices()
+    rng = np.random.default_rng(seed)
+    n = A.shape[0]
+    D = sp.diags(1.0 + 0.01 * rng.uniform(size=n))
+    B = (D @ A @ D + sp.diags(rng.uniform(0, 0.5, n) * A.diagonal())).tocsr()
+    B.sort_indices()
+    assert np.array_equal(B.indptr, A.indptr) and np.array_equal(B.indices, A.indices)
+    B.data = B.data * (1.0 + 1e-5 * rng.uniform(-1, 1, B.nnz))
+    return B
+
+
 def random_spd_hierarchy(rng, n, levels, hub):
     """A random sparse SPD matrix (irregular degrees; optionally a few hub rows so that SELL slices get very wide and the
     compact-panel fallback and > 4 colours are exercised) with a random aggregation-type prolongation hierarchy."""

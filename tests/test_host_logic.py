@@ -681,6 +681,72 @@ def test_wave_gauss_seidel_plan_is_the_lexicographic_sweep_in_its_order(smg_mod)
                 assert diff.value == 0.0, "level %d, pieces of %d rows (mode %d): the piece sweep differs by %g" % (lv, piece_rows, mode, diff.value)
 
 
+def test_sweep_plans_copy_the_level_values_their_maps_name_and_pad_with_zero_and_one(smg_mod):
+    """The three plan-based sweeps keep copies of the level's values and diagonals; a value-only re-precompute gathers them anew through the plans'
+    maps and leaves every slot without a map untouched (csrc/smg_sweep_plans.cpp: refresh_plan_values).  So, for every plan as the solves build it:
+    a mapped slot holds the bits of the level value its map names -- of A_lv^T where the level sweeps on the transpose --, an unmapped entry slot
+    +0.0 and an unmapped diagonal slot 1.0.  Torus subdivision levels (tiled, wave and block plans) and the decimated bunny (level 0 tiled, its
+    Galerkin levels wave), with A1 = M - 0.01 L (level 0 bit-symmetric: sweeps on A; Galerkin levels on A^T) and with value_step(A1, 1) (no level
+    bit-symmetric: every level on A^T; without a GPU the hook applies the first precompute's rule from the bits, and reports its choice).  The comparison against the mirrored values -- what the map of the wrong one of A / A^T
+    would pass -- must count mismatches wherever the level's matrix is not bit-symmetric, and none on the bit-symmetric level 0 of A1."""
+    import ctypes as C
+    from problems import value_step
+    smg = smg_mod
+    L = smg._lib.load()
+
+    def check(mg, lv, which, sweeps, against_transpose=0):
+        ns, npad, bad, on_t = C.c_int(-1), C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        rc = L.smg_debug_check_plan_value_maps(mg.h, lv, which, sweeps, against_transpose, C.byref(ns), C.byref(npad), C.byref(bad), C.byref(on_t))
+        assert rc == 0, L.smg_last_error()
+        assert on_t.value == int(stepped or lv > 0), "level %d: built from %s" % (lv, "A^T" if on_t.value else "A")
+        return ns.value, npad.value, bad.value
+
+    def torus():
+        V, F = smg.mesh.torus(8, 8)
+        mg, Vf, Ff = smg.mg_precompute_subdiv(V, F, 3, n_extra_levels=0)
+        Vf = M.normalize_unit_area(Vf, Ff)
+        return mg, (M.massmatrix(Vf, Ff, "barycentric") - 0.01 * M.cotmatrix(Vf, Ff)).tocsr(), {0: (0, 1, 2), 1: (0, 1, 2), 2: (0, 1, 2)}, 3
+
+    def bunny():
+        V, F = M.read_smgm("bunny.smgm")
+        V = M.normalize_unit_area(V, F)
+        return smg.mg_precompute(V, F, 0.25, 200, 1), (M.massmatrix(V, F, "barycentric") - 0.01 * M.cotmatrix(V, F)).tocsr(), {0: (0,), 1: (0, 1), 2: (0,)}, 2
+
+    for make in (torus, bunny):
+        for stepped in (False, True):
+            mg, A1, must_have, n_smoothed = make()      # must_have: plan kind -> the levels that have such a plan
+            A1.sort_indices()
+            assert (A1 != A1.T).nnz == 0
+            A = value_step(A1, 1) if stepped else A1
+            _host_precompute(smg, mg, A)
+            assert mg.n_levels - 1 == n_smoothed
+            for lv in range(n_smoothed):
+                Al = mg.matrix(lv, "A")
+                unsym = (Al != Al.T).nnz
+                assert (unsym > 0) == (stepped or lv > 0), "level %d: %d entries differ from their mirror image" % (lv, unsym)
+                plans = [(1, 0), (2, 0)] + [(0, s) for s in (1, 2, 3)]
+                for which, sweeps in plans:
+                    ns, npad, bad = check(mg, lv, which, sweeps)
+                    if ns == 0:      # the level does not qualify: more than 5 colours or 12 entries per row (tiling), too wide a rim (block)
+                        assert lv not in must_have[which], "level %d has no plan of kind %d (%d sweeps)" % (lv, which, sweeps)
+                        continue
+                    assert bad == 0, "level %d, plan kind %d, %d sweeps: %d of %d slots do not hold the value their map names" % (lv, which, sweeps, bad, ns)
+                    assert npad > 0 and ns > npad
+                    # the same comparison fed the values of the other one of A / A^T
+                    ns2, npad2, bad2 = check(mg, lv, which, sweeps, against_transpose=1)
+                    assert (ns2, npad2) == (ns, npad)
+                    if unsym:
+                        assert bad2 > 0, "level %d, plan kind %d: the check passes with the map of A where A^T is due" % (lv, which)
+                        assert bad2 >= unsym      # every entry that differs from its mirror image sits in at least one slot
+                    else:
+                        assert bad2 == 0
+    # refusals: no handle, an unknown plan kind, a sweep count the tiling has no plan for, a level that is not smoothed
+    z = C.c_int()
+    assert L.smg_debug_check_plan_value_maps(None, 0, 0, 1, 0, C.byref(z), C.byref(z), C.byref(z), C.byref(z)) == -1
+    for lv, which, sweeps in ((0, 3, 1), (0, -1, 1), (0, 0, 0), (0, 0, 4), (mg.n_levels - 1, 1, 1), (-1, 1, 1)):
+        assert L.smg_debug_check_plan_value_maps(mg.h, lv, which, sweeps, 0, C.byref(z), C.byref(z), C.byref(z), C.byref(z)) == -1, (lv, which, sweeps)
+
+
 def test_union_of_hierarchies_is_block_diagonal(smg_mod):
     """smg_hierarchy_create_union (independent meshes in one handle, csrc/smg_union.cpp): P_full of every level is diag(P_full of the members), member row
     ranges are reported, the Galerkin operators of the union are the members' (bit for bit: block-diagonal products add nothing), members of unequal depth
