@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 510
+#define SMG_VERSION 511
 
 enum {
     SMG_OK = 0,
@@ -610,6 +610,58 @@ int smg_param_arap(smg_param *p, const double *UV0, int ld_uv0, int memspace, in
                    double *UV, int ld_uv, double *energy_his, int *cycles, int *n_iter);
 int smg_param_distortion(smg_param *p, const double *UV, int ld_uv, int memspace, double *sigma, double *stats);
 
+/* ---- projective-dynamics membrane steps on the scalar V-cycle (csrc/smg_pd.cpp; Bouaziz, Martin, Liu, Kavan, Pauly
+ * 2014, triangle-strain constraints).  The global matrix (density / dt^2) M0 - stiffness L of the rest pose (Voronoi mass) is the same for x, y
+ * and z and constant for the life of the object: one precompute at create, none afterwards.  The per-face maths (rest frame, deformation
+ * gradient, the closed-form 3 x 2 singular-value projection onto the band [sigma_min, sigma_max], its two guards) is stated in
+ * csrc/smg_pd_inl.hpp.  One step of size h = dt from (x, v), n_pins >= 0 pinned vertices:
+ *   f_v = pressure m_v(x) n_v(x) + density m0_v g (m_v the mixed Voronoi mass of the start pose, n_v the unit vector along the sum of e1 x e2
+ *   over the vertex's corners, m0 the mass of the rest pose); s_v = x_v + h v_v + h^2 f_v / (density m0_v), a pinned row takes its pin position;
+ *   q_0 = s; iteration t: T_f = the projection of F_f(q_t), E_t = sum_v (density m0_v / (2 h^2)) |q_v - s_v|^2 + sum_f (stiffness A_f / 2)
+ *   |F_f(q_t) - T_f|_F^2, then ((density / h^2) M0 - stiffness L) q_{t+1} = b, b_v = (density m0_v / h^2) s_v + the sum over v's corners (f, i),
+ *   list order, of stiffness A_f (T_f g_{f,i}), pinned rows known: one 3-column solve warm-started at q_t.  Then v = (q - x) / h, x = q.
+ *   With exact solves E_{t+1} <= E_t.  sigma_min = sigma_max = 1 is the ARAP membrane; a wider band limits strain.
+ * smg_pd_create: h gives the prolongations (any scalar hierarchy on this mesh); they are copied into one internal handle, h is not modified.
+ *   dt, density and stiffness are in the matrix and fixed at create.  pins (n_pins >= 0 distinct vertices; NULL when 0) are held at rest until
+ *   a step moves them.  The state starts as (V, 0).  SMG_ERR_INVALID, before any device work, for: a union or block hierarchy, nV that is not the
+ *   hierarchy's level-0 rows, a face index out of range, a face of zero area, a non-finite coordinate, more than one connected component;
+ *   then dt, density or stiffness non-finite or <= 0; strain limits non-finite or not 0 <= sigma_min <= sigma_max; non-finite pressure or
+ *   gravity; a pin out of range or repeated; every vertex pinned.  SMG_ERR_NO_DEVICE comes after all of them.
+ * smg_pd_set_solver: pcg = 1 the solves run smg_solve_pcg (the default), 0 smg_solve's stationary loop; < 0 keeps.
+ * smg_pd_set_state / smg_pd_get_state: pos, vel are nV x 3 xyz rows in memspace; NULL keeps (set) or is skipped (get).
+ * smg_pd_set_forces (gravity: 3 doubles on the host, NULL keeps) and smg_pd_set_strain_limits: legal between any two steps; nothing is rebuilt.
+ * smg_pd_step: pin_pos (n_pins x 3 xyz rows in memspace; NULL keeps the pins where they are) are the pin positions at the END of the step.
+ *   The loop and its stopping rule are those of smg_arap_solve: max_iter iterations (>= 0), rel_tol > 0 ends earlier when
+ *   E_{t-1} - E_t <= rel_tol |E_{t-1}|; energy_his (max_iter + 1 doubles), cycles (max_iter ints: the loop entries of each inner solve) and
+ *   n_iter may be NULL.  opts: the options of the inner solves (tol is absolute); NULL selects smg_solve_opts_default with max_iter = 50 and
+ *   tol = 1e-8 |b_0|_F of this step (all rows).  An unconverged inner solve is not an error; a failing solve's code is returned unchanged.  A
+ *   non-finite energy returns SMG_ERR_NONFINITE and leaves the state and the pins as they were before the call.  The same inputs give the
+ *   same bits with graphs on or off and with SMG_HOST or SMG_DEVICE.
+ * smg_pd_strain: of the current state.  sigma (NULL ok; in memspace) holds 2 nF doubles in planes, sigma1 then sigma2.  stats is a host array
+ *   of 4 doubles: max sigma1, min sigma2, the number of faces outside the band (sigma1 > sigma_max or sigma2 < sigma_min), the
+ *   rest-area-weighted mean of |F - T|_F^2.  The sums are fixed-order reductions, max and min go through a tree of the same shape.
+ * smg_pd_project_host: the host twin of the face maths (no GPU): of the pose P (nV x 3 xyz rows) against the rest pose V0, the planes Fg (6:
+ *   f1x, f1y, f1z, f2x, f2y, f2z), sigma (2) and T (6, as Fg), each NULL ok; *guard_hits (NULL ok) = the faces on which a guard fired.
+ * Not covered: bending, collisions, per-face stiffness or thickness, volume constraints, several components, union / block / sharded forms,
+ * Chebyshev or other acceleration of the outer iteration. */
+typedef struct smg_pd smg_pd;
+typedef struct { double dt, density, stiffness, sigma_min, sigma_max, pressure, gravity[3]; } smg_pd_params;
+void smg_pd_params_default(smg_pd_params *p);              /* 1e-2, 1, 1, 1, 1, 0, {0,0,0} */
+int smg_pd_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const int *pins, int n_pins, const smg_pd_params *p,
+                  smg_pd **out);
+void smg_pd_destroy(smg_pd *d);
+long long smg_pd_device_bytes(const smg_pd *d);
+int smg_pd_set_solver(smg_pd *d, int pcg);
+int smg_pd_set_state(smg_pd *d, const double *pos, const double *vel, int memspace);
+int smg_pd_get_state(smg_pd *d, double *pos, double *vel, int memspace);
+int smg_pd_set_forces(smg_pd *d, double pressure, const double *gravity);
+int smg_pd_set_strain_limits(smg_pd *d, double sigma_min, double sigma_max);
+int smg_pd_step(smg_pd *d, const double *pin_pos, int memspace, int max_iter, double rel_tol, const smg_solve_opts *opts, double *energy_his,
+                int *cycles, int *n_iter);
+int smg_pd_strain(smg_pd *d, int memspace, double *sigma, double *stats);
+int smg_pd_project_host(const double *V0, const double *P, int nV, const int *F, int nF, double sigma_min, double sigma_max, double *Fg,
+                        double *sigma, double *T, int *guard_hits);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -870,6 +922,25 @@ int smg_debug_membrane_material(int material, int op, int nV, int nF, const int 
 enum { SMG_PARAM_REST = 0, SMG_PARAM_COVARIANCE = 1, SMG_PARAM_ROTATIONS = 2, SMG_PARAM_RHS = 3, SMG_PARAM_FACE_ENERGY = 4, SMG_PARAM_ENERGY = 5,
        SMG_PARAM_DISTORTION = 6 };
 int smg_debug_param(int op, int nV, int nF, const int *F, const double *V0, const double *UV, const double *R_in, double *out, int *guard_hits);
+
+/* One launcher of the projective-dynamics step (csrc/smg_pd_device.hip), handle-free and guarded like the hooks above.  F: nF x 3; V0 (the rest
+ * pose) and P (a pose): nV x 3 xyz rows; p: dt, density, stiffness, the band, pressure and gravity of the op; per-face results are planes (entry e
+ * of face f at [e nF + f]); column-major blocks are nV x 3 with leading dimension nV; in / out are concatenations in the order given.
+ *   SMG_PD_REST       V0              -> out = the rest constants (4 planes): a, b, c, A_f
+ *   SMG_PD_FACES      V0, P           -> out = Fg (6 planes), sigma (2), T (6), the energy terms (1), the corner shares (9): k_pd_faces<1>
+ *   SMG_PD_FACES_STEP V0, P           -> out = the energy terms (1), the corner shares (9): k_pd_faces<0>, the pose read as a column-major block
+ *   SMG_PD_MASS       V0              -> out = m0 (nV), the Voronoi mass of the rest pose as the object computes it
+ *   SMG_PD_PREDICT    V0, P = x, in = vel (3 nV xyz rows) -> out = fext (3 nV xyz rows), S (column-major)
+ *   SMG_PD_VERTICES   in = the corner shares (9 planes), m0 (nV), S, Q (column-major each)
+ *                                     -> out = B (column-major), the inertia terms (nV), |B_v|^2 (nV)
+ *   SMG_PD_ENERGY     in = terms (nF + nV) -> out[0] = their sum (fixed row chunks, fixed-order finalize)
+ *   SMG_PD_FINISH     P = x, in = Q (column-major) -> out = vel = (Q - x) / dt (3 nV xyz rows), the new x (3 nV xyz rows)
+ *   SMG_PD_STRAIN     V0, P           -> out = the statistics' terms (5 planes): sigma1, -sigma2, outside the band, A_f |F - T|_F^2, A_f
+ * SMG_ERR_INVALID for an unknown op, a missing operand or a face index out of range; SMG_ERR_NO_DEVICE without a GPU. */
+enum { SMG_PD_REST = 0, SMG_PD_FACES = 1, SMG_PD_FACES_STEP = 2, SMG_PD_MASS = 3, SMG_PD_PREDICT = 4, SMG_PD_VERTICES = 5, SMG_PD_ENERGY = 6,
+       SMG_PD_FINISH = 7, SMG_PD_STRAIN = 8 };
+int smg_debug_pd(int op, int nV, int nF, const int *F, const double *V0, const double *P, const double *in, const smg_pd_params *p, double *out,
+                 int *guard_hits);
 
 /* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
  * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.

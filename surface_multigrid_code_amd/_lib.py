@@ -20,6 +20,11 @@ class MembraneParamsC(C.Structure):
                 ("ls_min_alpha", C.c_double), ("eig_floor", C.c_double), ("eig_value", C.c_double)]
 
 
+class PdParamsC(C.Structure):
+    _fields_ = [("dt", C.c_double), ("density", C.c_double), ("stiffness", C.c_double), ("sigma_min", C.c_double), ("sigma_max", C.c_double),
+                ("pressure", C.c_double), ("gravity", C.c_double * 3)]
+
+
 _lib = None
 
 
@@ -117,6 +122,19 @@ def load():
         "smg_param_harmonic": (i, [vp, i, C.POINTER(SolveOptsC), vp, i, ip]),
         "smg_param_arap": (i, [vp, vp, i, i, i, d, C.POINTER(SolveOptsC), vp, i, dp, ip, ip]),
         "smg_param_distortion": (i, [vp, vp, i, i, vp, dp]),
+        "smg_pd_params_default": (None, [C.POINTER(PdParamsC)]),
+        "smg_pd_create": (i, [vp, dp, i, ip, i, ip, i, C.POINTER(PdParamsC), C.POINTER(vp)]),
+        "smg_pd_destroy": (None, [vp]),
+        "smg_pd_device_bytes": (C.c_longlong, [vp]),
+        "smg_pd_set_solver": (i, [vp, i]),
+        "smg_pd_set_state": (i, [vp, vp, vp, i]),
+        "smg_pd_get_state": (i, [vp, vp, vp, i]),
+        "smg_pd_set_forces": (i, [vp, d, dp]),
+        "smg_pd_set_strain_limits": (i, [vp, d, d]),
+        "smg_pd_step": (i, [vp, vp, i, i, d, C.POINTER(SolveOptsC), dp, ip, ip]),
+        "smg_pd_strain": (i, [vp, i, vp, dp]),
+        "smg_pd_project_host": (i, [dp, dp, i, ip, i, d, d, dp, dp, dp, ip]),
+        "smg_debug_pd": (i, [i, i, i, ip, dp, dp, dp, C.POINTER(PdParamsC), dp, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

@@ -831,6 +831,86 @@ class MembraneSim(_MeshObject):
         return {"objective": obj, "alpha": alpha[:n_it].copy(), "cycles": cyc[:n_it].copy()}
 
 
+class ProjectiveDynamics(_MeshObject):
+    """Projective-dynamics steps of a membrane with triangle-strain constraints on the scalar V-cycle (include/smg.h: smg_pd_*; Bouaziz et al.
+    2014).  The global matrix (density / dt^2) M0 - stiffness L is precomputed here, once; a step is a handful of 3-column warm-started solves.
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  V: the rest pose.
+    pins: the vertices a step holds at given positions (none is legal).  params: the fields of smg_pd_params (dt, density, stiffness,
+    sigma_min, sigma_max, pressure, gravity); the state starts as (V, 0)."""
+
+    STATS = ("max_sigma1", "min_sigma2", "outside_band", "mean_distance2")
+    _prefix = "smg_pd_"
+    d = property(lambda self: self.o)
+
+    def __init__(self, hierarchy, V, F, pins=(), **params):
+        self.params = pd_params(**params)
+        self.pins = np.ascontiguousarray(pins, dtype=np.int32).reshape(-1)
+        self._create(hierarchy, V, F, _ip(self.pins) if self.pins.size else None, self.pins.shape[0], C.byref(self.params))
+
+    def set_state(self, pos=None, vel=None):
+        """pos, vel: n x 3 (None keeps)"""
+        pos = None if pos is None else np.ascontiguousarray(pos, dtype=np.float64).reshape(self.n, 3)
+        vel = None if vel is None else np.ascontiguousarray(vel, dtype=np.float64).reshape(self.n, 3)
+        self._call("set_state", None if pos is None else pos.ctypes.data, None if vel is None else vel.ctypes.data, SMG_HOST)
+
+    def set_state_device(self, pos_ptr, vel_ptr):
+        """the same from n x 3 row-major blocks resident in HBM (device pointers; 0 / None keeps)"""
+        self._call("set_state", pos_ptr or None, vel_ptr or None, SMG_DEVICE)
+
+    def state(self):
+        """(pos, vel), n x 3 each"""
+        pos, vel = np.zeros((self.n, 3)), np.zeros((self.n, 3))
+        self._call("get_state", pos.ctypes.data, vel.ctypes.data, SMG_HOST)
+        return pos, vel
+
+    def state_device(self, pos_ptr, vel_ptr):
+        """state() into n x 3 row-major blocks resident in HBM (device pointers; 0 / None skips)"""
+        self._call("get_state", pos_ptr or None, vel_ptr or None, SMG_DEVICE)
+
+    def set_forces(self, pressure, gravity=None):
+        """legal between any two steps; gravity: 3 numbers, None keeps"""
+        g = None if gravity is None else np.ascontiguousarray(gravity, dtype=np.float64).reshape(3)
+        self._call("set_forces", float(pressure), None if g is None else _dp(g))
+
+    def set_strain_limits(self, sigma_min, sigma_max):
+        """legal between any two steps; (1, 1) is the ARAP membrane"""
+        self._call("set_strain_limits", float(sigma_min), float(sigma_max))
+
+    def step(self, pin_pos=None, max_iter=10, rel_tol=0.0, opts=None):
+        """One time step.  pin_pos: n_pins x 3, the pins at the end of the step (None keeps them).  Returns (energy_his, cycles): E_0 .. E_n_iter
+        and the loop entries of each inner solve."""
+        hp = None if pin_pos is None else np.ascontiguousarray(pin_pos, dtype=np.float64).reshape(self.pins.shape[0], 3)
+        return self._iterate("step", max_iter, None if hp is None else hp.ctypes.data, SMG_HOST, int(max_iter), float(rel_tol), self._opts(opts))
+
+    def step_device(self, pin_pos_ptr=None, max_iter=10, rel_tol=0.0, opts=None):
+        """step() with the pin positions (n_pins x 3 xyz rows) resident in HBM (device pointer; 0 / None keeps)"""
+        return self._iterate("step", max_iter, pin_pos_ptr or None, SMG_DEVICE, int(max_iter), float(rel_tol), self._opts(opts))
+
+    def strain(self):
+        """(sigma, stats) of the current state: sigma nF x 2 (the singular values of every face's deformation gradient, larger first) and the
+        dict of STATS."""
+        sigma = np.zeros((self.nF, 2), order="F")
+        st = np.zeros(4)
+        self._call("strain", SMG_HOST, sigma.ctypes.data, _dp(st))
+        stats = dict(zip(self.STATS, st.tolist()))
+        stats["outside_band"] = int(stats["outside_band"])
+        return sigma, stats
+
+
+def pd_params(**params):
+    """smg_pd_params with the library's defaults and the given fields (gravity: 3 numbers)"""
+    p = _lib.PdParamsC()
+    _lib.load().smg_pd_params_default(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError("unknown projective-dynamics parameter %r" % k)
+        if k == "gravity":
+            v = (C.c_double * 3)(*[float(x) for x in v])
+        setattr(p, k, v)
+    return p
+
+
 def membrane_params(**params):
     """smg_membrane_params with the library's defaults and the given fields"""
     p = _lib.MembraneParamsC()

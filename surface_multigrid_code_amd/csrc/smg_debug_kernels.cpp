@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -517,6 +517,95 @@ extern "C" int smg_debug_param(int op, int nV, int nF, const int* F, const doubl
                 HIPCHK(launch_fixed_sum(dterm, nF, dpart, dout, st));
                 break;
             default: HIPCHK(launch_param_distortion(nF, dF, drest, dUV, nV, dout, nullptr, nullptr, st)); break;
+        }
+        int bad = 0;
+        HIPCHK(X.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_pd(int op, int nV, int nF, const int* F, const double* V0, const double* P, const double* in, const smg_pd_params* p,
+                            double* out, int* guard_hits)
+{
+    return guarded("smg_debug_pd", [&]() -> int {
+        if (op < SMG_PD_REST || op > SMG_PD_STRAIN || nV < 1 || nF < 1 || !F || !p || !out) return fail(SMG_ERR_INVALID, "smg_debug_pd: bad arguments");
+        const bool needs_rest = op != SMG_PD_ENERGY && op != SMG_PD_FINISH && op != SMG_PD_VERTICES;
+        const bool needs_pose = op == SMG_PD_FACES || op == SMG_PD_FACES_STEP || op == SMG_PD_PREDICT || op == SMG_PD_FINISH || op == SMG_PD_STRAIN;
+        const bool needs_in = op == SMG_PD_PREDICT || op == SMG_PD_VERTICES || op == SMG_PD_ENERGY || op == SMG_PD_FINISH;
+        if ((needs_rest && !V0) || (needs_pose && !P) || (needs_in && !in)) return fail(SMG_ERR_INVALID, "smg_debug_pd: op %d misses an operand", op);
+        if (int rc = check_faces("smg_debug_pd", F, nF, nV)) return rc;
+        if (int rc = need_device("smg_debug_pd")) return rc;
+        const size_t D = sizeof(double), nf = (size_t)nF, nv = (size_t)nV, n3 = 3 * nv;
+        const size_t out_n = op == SMG_PD_REST ? 4 * nf : op == SMG_PD_FACES ? 24 * nf : op == SMG_PD_FACES_STEP ? 10 * nf : op == SMG_PD_MASS ? nv
+                             : op == SMG_PD_PREDICT ? 2 * n3 : op == SMG_PD_VERTICES ? n3 + 2 * nv : op == SMG_PD_ENERGY ? 1 : op == SMG_PD_FINISH ? 2 * n3 : 5 * nf;
+        const size_t in_n = op == SMG_PD_PREDICT ? n3 : op == SMG_PD_VERTICES ? 9 * nf + nv + 2 * n3 : op == SMG_PD_ENERGY ? nf + nv : op == SMG_PD_FINISH ? n3 : 0;
+        Scratch X;
+        HIPCHK(X.init());
+        hipStream_t st = X.stream();
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr;
+        double *dV0 = nullptr, *dP = nullptr, *din = nullptr, *dout = nullptr, *drest = nullptr, *dQ = nullptr, *dQn = nullptr, *dm0 = nullptr, *dpart = nullptr;
+        HIPCHK(X.add(F, nullptr, 3 * nf * sizeof(int), &dF));
+        if (V0) HIPCHK(X.add(V0, nullptr, n3 * D, &dV0));
+        if (P) HIPCHK(X.add(P, nullptr, n3 * D, &dP));
+        if (in_n) HIPCHK(X.add(in, nullptr, in_n * D, &din));
+        HIPCHK(X.add(out, out, out_n * D, &dout));
+        if (op == SMG_PD_FACES || op == SMG_PD_FACES_STEP || op == SMG_PD_STRAIN) {
+            HIPCHK(X.add(nullptr, nullptr, 4 * nf * D, &drest));
+            HIPCHK(launch_pd_rest(nF, dF, dV0, drest, st));
+        }
+        std::vector<int> mp, mi;
+        if (op == SMG_PD_MASS || op == SMG_PD_PREDICT || op == SMG_PD_VERTICES) {
+            vertex_corner_lists(std::vector<int>(F, F + 3 * nf), nV, mp, mi);
+            HIPCHK(X.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+            HIPCHK(X.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+        }
+        switch (op) {
+            case SMG_PD_REST: HIPCHK(launch_pd_rest(nF, dF, dV0, dout, st)); break;
+            case SMG_PD_FACES:
+                HIPCHK(launch_pd_faces(nF, dF, drest, dP, 3, 1, p->stiffness, p->sigma_min, p->sigma_max, dout + 14 * nf, dout + 15 * nf, dout, dout + 6 * nf,
+                                       dout + 8 * nf, st));
+                break;
+            case SMG_PD_FACES_STEP:
+                HIPCHK(X.add(nullptr, nullptr, n3 * D, &dQ));
+                HIPCHK(launch_arap_columns(nV, dP, dQ, nV, st));
+                HIPCHK(launch_pd_faces(nF, dF, drest, dQ, 1, nv, p->stiffness, p->sigma_min, p->sigma_max, dout, dout + nf, nullptr, nullptr, nullptr, st));
+                break;
+            case SMG_PD_MASS:
+                HIPCHK(X.add(nullptr, nullptr, 6 * nf * D, &dQn));
+                HIPCHK(launch_membrane_pressure(nV, nF, dF, dV0, dmp, dmi, 0.0, dQn, dout, nullptr, st));
+                break;
+            case SMG_PD_PREDICT:
+                HIPCHK(X.add(nullptr, nullptr, 6 * nf * D, &dQn));
+                HIPCHK(X.add(nullptr, nullptr, nv * D, &dm0));
+                HIPCHK(launch_membrane_pressure(nV, nF, dF, dV0, dmp, dmi, 0.0, dQn, dm0, nullptr, st));
+                HIPCHK(launch_membrane_pressure(nV, nF, dF, dP, dmp, dmi, p->pressure, dQn, nullptr, dout, st));
+                HIPCHK(launch_pd_predict(nV, dP, din, dout, dm0, p->dt, p->density, p->gravity, dout + n3, nV, st));
+                break;
+            case SMG_PD_VERTICES: {
+                const double *m0 = din + 9 * nf, *S = m0 + nv, *Q = S + n3;
+                HIPCHK(launch_pd_vertices(nV, nF, dmp, dmi, din, m0, p->density / (p->dt * p->dt), S, Q, nV, dout, nV, dout + n3, dout + n3 + nv, st));
+                break;
+            }
+            case SMG_PD_ENERGY:
+                HIPCHK(X.add(nullptr, nullptr, (size_t)fixed_sum_groups(nF + nV) * D, &dpart));
+                HIPCHK(launch_fixed_sum(din, nF + nV, dpart, dout, st));
+                break;
+            case SMG_PD_FINISH:
+                HIPCHK(hipMemcpyAsync(dout + n3, dP, n3 * D, hipMemcpyDeviceToDevice, st));
+                HIPCHK(launch_pd_finish(nV, din, nV, p->dt, dout + n3, dout, st));
+                break;
+            default: {
+                double *dFg = nullptr, *dsig = nullptr, *dT = nullptr, *det = nullptr, *dsh = nullptr;
+                HIPCHK(X.add(nullptr, nullptr, 6 * nf * D, &dFg));
+                HIPCHK(X.add(nullptr, nullptr, 2 * nf * D, &dsig));
+                HIPCHK(X.add(nullptr, nullptr, 6 * nf * D, &dT));
+                HIPCHK(X.add(nullptr, nullptr, nf * D, &det));
+                HIPCHK(X.add(nullptr, nullptr, 9 * nf * D, &dsh));
+                HIPCHK(launch_pd_faces(nF, dF, drest, dP, 3, 1, p->stiffness, p->sigma_min, p->sigma_max, det, dsh, dFg, dsig, dT, st));
+                HIPCHK(launch_pd_strain_terms(nF, drest, dFg, dsig, dT, p->sigma_min, p->sigma_max, dout, st));
+                break;
+            }
         }
         int bad = 0;
         HIPCHK(X.finish(&bad));

@@ -498,4 +498,24 @@ hipError_t launch_membrane_trial(int nV, const double* qdot, const double* dx, d
 // term[v] = a_v . b_v
 hipError_t launch_membrane_dot3(int nV, const double* a, const double* b, double* term, hipStream_t st);
 
+// projective-dynamics membrane step (smg_pd_device.hip; the maths in smg_pd_inl.hpp).  x, vel, fext, V0: xyz rows (entry 3 v + l); S, Q, B:
+// column-major nV x 3; per-face arrays are face-major planes (plane e at [e * nF + f]): rest (4: a, b, c, A_f), share (9: 3 i + l), Fg and T (6),
+// sigma (2); m_ptr / m_idx: the corner lists t = 3 f + i of every vertex, faces ascending ------------------------------------------------
+hipError_t launch_pd_rest(int nF, const int* F, const double* V0, double* rest, hipStream_t st);
+// per face of the pose Q (coordinate l of vertex v at Q[v * sv + l * sl]): eterm[f] = (k A_f / 2) |F - T|_F^2 and share = k A_f (T g_i); Fg, sigma, T:
+// all three or none (nullptr): the planes of the deformation gradient, its singular values and its projection onto the band [smin, smax]
+hipError_t launch_pd_faces(int nF, const int* F, const double* rest, const double* Q, size_t sv, size_t sl, double k, double smin, double smax,
+                           double* eterm, double* share, double* Fg, double* sigma, double* T, hipStream_t st);
+// terms (5 planes): sigma1, -sigma2, outside the band (0 / 1), A_f |F - T|_F^2, A_f
+hipError_t launch_pd_strain_terms(int nF, const double* rest, const double* Fg, const double* sigma, const double* T, double smin, double smax,
+                                  double* terms, hipStream_t st);
+// S_v = (x_v + h vel_v) + (h^2 (-fext_v + (rho m0_v) g)) / (rho m0_v); g: 3 doubles on the host
+hipError_t launch_pd_predict(int nV, const double* x, const double* vel, const double* fext, const double* m0, double h, double rho, const double* g,
+                             double* S, int ld, hipStream_t st);
+// B_v = (c_mass m0_v) S_v + the corner shares of v in list order, iterm[v] = (c_mass m0_v / 2) |Q_v - S_v|^2, bsq[v] = |B_v|^2
+hipError_t launch_pd_vertices(int nV, int nF, const int* m_ptr, const int* m_idx, const double* share, const double* m0, double c_mass, const double* S,
+                              const double* Q, int ld, double* B, int ldb, double* iterm, double* bsq, hipStream_t st);
+// vel = (Q - x) / h, x = Q
+hipError_t launch_pd_finish(int nV, const double* Q, int ld, double h, double* x, double* vel, hipStream_t st);
+
 }  // namespace smg
