@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 511
+#define SMG_VERSION 512
 
 enum {
     SMG_OK = 0,
@@ -662,6 +662,64 @@ int smg_pd_strain(smg_pd *d, int memspace, double *sigma, double *stats);
 int smg_pd_project_host(const double *V0, const double *P, int nV, const int *F, int nF, double sigma_min, double sigma_max, double *Fg,
                         double *sigma, double *T, int *guard_hits);
 
+/* ---- feature-preserving denoising on the scalar V-cycle (csrc/smg_denoise.cpp): the bilateral normal filter of Zheng,
+ * Fu, Au, Tai 2011 (local scheme), then vertex positions that follow the filtered normals.  The global matrix fidelity M - L of the input mesh
+ * (Voronoi mass) is the same for x, y and z and constant for the life of the object: one precompute at create, none afterwards.  All of the
+ * following are taken from the input mesh (V, F) and stay fixed: the unit face normals n_f, the areas A_f, the centroids c_f, w_{f,k} = half the
+ * cotangent at corner k (the weight of the edge opposite corner k, the convention of smg_mesh_cotmatrix), the mass M, and N(f) = the faces that
+ * share at least one vertex with f, without f, ascending (smg_mesh_face_neighbours).  The per-face maths is stated in csrc/smg_denoise_inl.hpp.
+ *   Filter: from m^0 (the argument; NULL: n), normal_iters times: s_f = sum over g in N(f), list order, of A_g exp(-|c_f - c_g|^2 / (2 sigma_s^2))
+ *   exp(-|m_f - m_g|^2 / (2 sigma_r^2)) m_g (one exponential of the summed arguments), m_f <- s_f / |s_f|; |s_f| zero or not finite: m_f stays.
+ *   Every face reads the old normals.
+ *   Update: the alternating minimisation of E(X, t) = (1/2) sum_f sum_k w_{f,k} |(x_i - x_j) - t_{f,k}|^2 + (fidelity / 2) sum_v M_v |x_v - V_v|^2
+ *   with every t_{f,k} orthogonal to m_f, (i, j) the two corners after k in cyclic order.  Iteration t: h_{f,k} = (x_i - x_j) . m_f,
+ *   t_{f,k} = (x_i - x_j) - h_{f,k} m_f, E_t = sum_f (1/2) sum_k w_{f,k} h_{f,k}^2 + the fidelity term; then (fidelity M - L) x_{t+1} =
+ *   fidelity M V + b, b_v = the sum over v's corners, list order, of +w_{f,k} t_{f,k} where v is i and -w_{f,k} t_{f,k} where v is j: one 3-column
+ *   solve warm-started at x_t.  With exact solves E_{t+1} <= E_t.
+ * smg_denoise_params: sigma_s <= 0 selects the rule sigma_s = the mean of |c_f - c_g| over all ordered pairs (f, g in N(f)), a fixed-order sum
+ *   computed once at create (a mesh of one face: 1); sigma_r is a distance between unit normals; fidelity has units 1 / length^2, so a value
+ *   tuned on one mesh carries over to another only at the same scale: bring the mesh to unit area first (smg_mesh_normalize_unit_area), which
+ *   is the scale the default 1 is meant for.  fidelity is in the matrix and fixed at create.
+ * smg_denoise_create: h gives the prolongations (any scalar hierarchy on this mesh); they are copied into one internal handle, h is not
+ *   modified.  SMG_ERR_INVALID, before any device work, for: a union or block hierarchy, nV that is not the hierarchy's level-0 rows, a face
+ *   index out of range, a face of zero area, a non-finite coordinate, more than one connected component; then sigma_r or fidelity non-finite
+ *   or <= 0, a non-finite sigma_s, normal_iters < 0.  SMG_ERR_NO_DEVICE comes after all of them.  Sharded solves are not offered.
+ * smg_denoise_set_solver: pcg = 1 the solves run smg_solve_pcg (the default), 0 smg_solve's stationary loop; < 0 keeps.
+ * smg_denoise_sigma_s: the value in use.  smg_denoise_set_filter: legal between any two calls, nothing is rebuilt; sigma_s <= 0, sigma_r <= 0
+ *   or normal_iters < 0 keeps the current value (normal_iters = 0 is legal: the filter returns its input); a non-finite value is refused.
+ * smg_denoise_filter: runs the filter from normals_in (nF x 3 xyz rows in memspace; NULL: n) and latches the result as m; normals_out (nF x 3
+ *   xyz rows in memspace) may be NULL.  A failing call leaves m as it was.
+ * smg_denoise_update: runs the update against the latched m (before any filter: m = n) from X0 (nV x 3 xyz rows in memspace; NULL: V) into X
+ *   (nV x 3 xyz rows in memspace).  The loop and its stopping rule are those of smg_arap_solve and smg_pd_step: max_iter iterations (>= 0),
+ *   rel_tol > 0 ends earlier when E_{t-1} - E_t <= rel_tol |E_{t-1}|; energy_his (max_iter + 1 doubles), cycles (max_iter ints: the loop
+ *   entries of each inner solve) and n_iter may be NULL.  opts: the options of the inner solves (tol is absolute); NULL selects
+ *   smg_solve_opts_default with max_iter = 50 and tol = 1e-8 |b_0|_F of this call.  An unconverged inner solve is not an error; a failing
+ *   solve's code is returned unchanged.  A non-finite energy returns SMG_ERR_NONFINITE: X is not written, nothing is latched, nothing is
+ *   written past energy_his[*n_iter].  The object keeps no positions: the next call starts from its own X0.
+ * smg_denoise_run: smg_denoise_filter(NULL, NULL), then smg_denoise_update(NULL) in one call.
+ *   The same inputs give the same bits with graphs on or off and with SMG_HOST or SMG_DEVICE.
+ * smg_denoise_faces_host: the host twin of the per-face pieces (no GPU), with the operands of the ops SMG_DN_REST .. SMG_DN_PROJECT of
+ *   smg_debug_denoise below.
+ * Not covered: collapse prevention (the energy does not resist slivers at high noise), anisotropic or guided filters, the edge-neighbour
+ * variant of N(f), union / block / sharded forms, moving connectivity. */
+typedef struct smg_denoise smg_denoise;
+typedef struct { double sigma_s, sigma_r, fidelity; int normal_iters; } smg_denoise_params;
+enum { SMG_DN_REST = 0, SMG_DN_SPACING = 1, SMG_DN_FILTER = 2, SMG_DN_PROJECT = 3, SMG_DN_RHS = 4, SMG_DN_ENERGY = 5 };
+void smg_denoise_params_default(smg_denoise_params *p);    /* 0, 0.35, 1, 20 */
+int smg_denoise_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const smg_denoise_params *p, smg_denoise **out);
+void smg_denoise_destroy(smg_denoise *d);
+long long smg_denoise_device_bytes(const smg_denoise *d);
+int smg_denoise_set_solver(smg_denoise *d, int pcg);
+double smg_denoise_sigma_s(const smg_denoise *d);
+int smg_denoise_set_filter(smg_denoise *d, double sigma_s, double sigma_r, int normal_iters);
+int smg_denoise_filter(smg_denoise *d, const double *normals_in, int memspace, double *normals_out);
+int smg_denoise_update(smg_denoise *d, const double *X0, int memspace, int max_iter, double rel_tol, const smg_solve_opts *opts, double *X,
+                       double *energy_his, int *cycles, int *n_iter);
+int smg_denoise_run(smg_denoise *d, int memspace, int max_iter, double rel_tol, const smg_solve_opts *opts, double *X, double *energy_his,
+                    int *cycles, int *n_iter);
+int smg_denoise_faces_host(int op, int nV, int nF, const int *F, const double *V0, const double *P, const double *in,
+                           const smg_denoise_params *p, double *out);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -942,6 +1000,21 @@ enum { SMG_PD_REST = 0, SMG_PD_FACES = 1, SMG_PD_FACES_STEP = 2, SMG_PD_MASS = 3
 int smg_debug_pd(int op, int nV, int nF, const int *F, const double *V0, const double *P, const double *in, const smg_pd_params *p, double *out,
                  int *guard_hits);
 
+/* One launcher of the denoiser (csrc/smg_denoise_device.hip), handle-free and guarded like the hooks above.  F: nF x 3; V0 (the input mesh) and P
+ * (a pose): nV x 3 xyz rows; p: sigma_s, sigma_r, normal_iters and fidelity of the op; per-face arrays are planes (entry e of face f at
+ * [e nF + f]); column-major blocks are nV x 3 with leading dimension nV; in / out are concatenations in the order given.  N(f) is built from F.
+ *   SMG_DN_REST     V0                       -> out = the rest constants (10 planes): n (3), A, c (3), w (3)
+ *   SMG_DN_SPACING  V0                       -> out[f] = the sum over N(f), list order, of |c_f - c_g|
+ *   SMG_DN_FILTER   V0, in = normals (3 planes) -> out = the normals after normal_iters iterations (3 planes); sigma_s must be > 0 here
+ *   SMG_DN_PROJECT  V0, P, in = m (3 planes) -> out = the energy terms (1), the corner shares (9); the pose read as a column-major block
+ *   SMG_DN_RHS      V0, in = the corner shares (9 planes), X (column-major)
+ *                                            -> out = B (column-major), the fidelity terms (nV), |B_v|^2 (nV), the mass M (nV)
+ *   SMG_DN_ENERGY   in = terms (nF + nV)     -> out[0] = their sum (fixed row chunks, fixed-order finalize)
+ * SMG_ERR_INVALID for an unknown op, a missing operand, a face index out of range or a filter without sigma_s > 0; SMG_ERR_NO_DEVICE without a
+ * GPU. */
+int smg_debug_denoise(int op, int nV, int nF, const int *F, const double *V0, const double *P, const double *in, const smg_denoise_params *p,
+                      double *out, int *guard_hits);
+
 /* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
  * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.
  *   SMG_UNION_SUMSQ_DECIDE  rptr[m + 1], rows (member i's rows of the block: rows[rptr[i] .. rptr[i + 1]), each row at most once), r, u, zsave,
@@ -975,6 +1048,9 @@ int smg_mesh_normalize_unit_area(double *V, int nV, const int *F, int nF);      
 int smg_mesh_cotmatrix(const double *V, int nV, const int *F, int nF, int *nnz, int *rowptr, int *col, double *val);
 int smg_mesh_massmatrix(const double *V, int nV, const int *F, int nF, int voronoi, double *diag);
 int smg_mesh_boundary_loop(const int *F, int nF, int nV, int *loop, int *n_loop); /* longest loop; loop holds <= nV */
+/* N(f): per face the faces that share at least one vertex with it, without f, as CSR with ascending, duplicate-free rows (ptr: nF + 1 ints).
+ * Returns the number of entries (>= 0; with ptr and idx NULL only that: the size query) or a negative error code. */
+int smg_mesh_face_neighbours(const int *F, int nF, int nV, int *ptr, int *idx);
 /* one mid-point upsampling step: S is (nV+nE) x nV in CSR (nV + 2 nE entries), NF is 4 nF x 3 */
 int smg_mesh_midpoint_upsample(int nV, const int *F, int nF, int *nE, int *S_rowptr, int *S_col, double *S_val,
                                int *NF);

@@ -25,6 +25,10 @@ class PdParamsC(C.Structure):
                 ("pressure", C.c_double), ("gravity", C.c_double * 3)]
 
 
+class DenoiseParamsC(C.Structure):
+    _fields_ = [("sigma_s", C.c_double), ("sigma_r", C.c_double), ("fidelity", C.c_double), ("normal_iters", C.c_int)]
+
+
 _lib = None
 
 
@@ -135,6 +139,18 @@ def load():
         "smg_pd_strain": (i, [vp, i, vp, dp]),
         "smg_pd_project_host": (i, [dp, dp, i, ip, i, d, d, dp, dp, dp, ip]),
         "smg_debug_pd": (i, [i, i, i, ip, dp, dp, dp, C.POINTER(PdParamsC), dp, ip]),
+        "smg_denoise_params_default": (None, [C.POINTER(DenoiseParamsC)]),
+        "smg_denoise_create": (i, [vp, dp, i, ip, i, C.POINTER(DenoiseParamsC), C.POINTER(vp)]),
+        "smg_denoise_destroy": (None, [vp]),
+        "smg_denoise_device_bytes": (C.c_longlong, [vp]),
+        "smg_denoise_set_solver": (i, [vp, i]),
+        "smg_denoise_sigma_s": (d, [vp]),
+        "smg_denoise_set_filter": (i, [vp, d, d, i]),
+        "smg_denoise_filter": (i, [vp, vp, i, vp]),
+        "smg_denoise_update": (i, [vp, vp, i, i, d, C.POINTER(SolveOptsC), vp, dp, ip, ip]),
+        "smg_denoise_run": (i, [vp, i, i, d, C.POINTER(SolveOptsC), vp, dp, ip, ip]),
+        "smg_denoise_faces_host": (i, [i, i, i, ip, dp, dp, dp, C.POINTER(DenoiseParamsC), dp]),
+        "smg_debug_denoise": (i, [i, i, i, ip, dp, dp, dp, C.POINTER(DenoiseParamsC), dp, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),
@@ -202,6 +218,7 @@ def load():
         "smg_mesh_cotmatrix": (i, [dp, i, ip, i, ip, ip, ip, dp]),
         "smg_mesh_massmatrix": (i, [dp, i, ip, i, i, dp]),
         "smg_mesh_boundary_loop": (i, [ip, i, i, ip, ip]),
+        "smg_mesh_face_neighbours": (i, [ip, i, i, ip, ip]),
         "smg_mesh_midpoint_upsample": (i, [i, ip, i, ip, ip, ip, dp, ip]),
         "smg_mesh_torus": (i, [i, i, d, d, dp, ip]),
     }

@@ -898,6 +898,76 @@ class ProjectiveDynamics(_MeshObject):
         return sigma, stats
 
 
+class Denoiser(_MeshObject):
+    """Feature-preserving denoising of a triangle mesh on the scalar V-cycle (include/smg.h: smg_denoise_*): the bilateral normal filter of
+    Zheng et al. 2011 over the faces that share a vertex, then positions that follow the filtered normals.  The global matrix fidelity M - L
+    is precomputed here, once; an update is a handful of 3-column warm-started solves.
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  V: the noisy positions.
+    params: the fields of smg_denoise_params (sigma_s, sigma_r, fidelity, normal_iters); sigma_s <= 0 selects the mean centroid distance of
+    the neighbourhoods.  fidelity has units 1 / length^2: normalise the mesh to unit area first."""
+
+    _prefix = "smg_denoise_"
+    d = property(lambda self: self.o)
+
+    def __init__(self, hierarchy, V, F, **params):
+        self.params = denoise_params(**params)
+        self._create(hierarchy, V, F, C.byref(self.params))
+
+    @property
+    def sigma_s(self):
+        """the value in use"""
+        return self.L.smg_denoise_sigma_s(self.d)
+
+    def set_filter(self, sigma_s=0.0, sigma_r=0.0, normal_iters=-1):
+        """legal between any two calls; sigma_s <= 0, sigma_r <= 0 or normal_iters < 0 keeps the current value"""
+        self._call("set_filter", float(sigma_s), float(sigma_r), int(normal_iters))
+
+    def filter(self, normals=None):
+        """The filter from normals (nF x 3; None: the input mesh's own); the result (nF x 3) is returned and latched for update()."""
+        m0 = None if normals is None else np.ascontiguousarray(normals, dtype=np.float64).reshape(self.nF, 3)
+        out = np.zeros((self.nF, 3))
+        self._call("filter", None if m0 is None else m0.ctypes.data, SMG_HOST, out.ctypes.data)
+        return out
+
+    def filter_device(self, normals_ptr=None, out_ptr=None):
+        """filter() between nF x 3 row-major blocks resident in HBM (device pointers; 0 / None: the mesh's normals / no output)"""
+        self._call("filter", normals_ptr or None, SMG_DEVICE, out_ptr or None)
+
+    def update(self, X0=None, max_iter=10, rel_tol=0.0, opts=None):
+        """The vertex update against the latched normals from X0 (n x 3; None: V).  Returns (X, energy_his, cycles)."""
+        X0 = None if X0 is None else np.ascontiguousarray(X0, dtype=np.float64).reshape(self.n, 3)
+        X = np.zeros((self.n, 3))
+        E, cyc = self._iterate("update", max_iter, None if X0 is None else X0.ctypes.data, SMG_HOST, int(max_iter), float(rel_tol), self._opts(opts),
+                               X.ctypes.data)
+        return X, E, cyc
+
+    def update_device(self, X_ptr, X0_ptr=None, max_iter=10, rel_tol=0.0, opts=None):
+        """update() between n x 3 row-major blocks resident in HBM (device pointers).  Returns (energy_his, cycles)."""
+        return self._iterate("update", max_iter, X0_ptr or None, SMG_DEVICE, int(max_iter), float(rel_tol), self._opts(opts), X_ptr)
+
+    def run(self, max_iter=10, rel_tol=0.0, opts=None):
+        """filter(), then update() from V, in one call.  Returns (X, energy_his, cycles)."""
+        X = np.zeros((self.n, 3))
+        E, cyc = self._iterate("run", max_iter, SMG_HOST, int(max_iter), float(rel_tol), self._opts(opts), X.ctypes.data)
+        return X, E, cyc
+
+    def run_device(self, X_ptr, max_iter=10, rel_tol=0.0, opts=None):
+        """run() into an n x 3 row-major block resident in HBM (device pointer).  Returns (energy_his, cycles)."""
+        return self._iterate("run", max_iter, SMG_DEVICE, int(max_iter), float(rel_tol), self._opts(opts), X_ptr)
+
+
+def denoise_params(**params):
+    """smg_denoise_params with the library's defaults and the given fields"""
+    p = _lib.DenoiseParamsC()
+    _lib.load().smg_denoise_params_default(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError("unknown denoising parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 def pd_params(**params):
     """smg_pd_params with the library's defaults and the given fields (gravity: 3 numbers)"""
     p = _lib.PdParamsC()

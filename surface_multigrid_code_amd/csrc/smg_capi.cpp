@@ -820,6 +820,21 @@ extern "C" int smg_mesh_boundary_loop(const int* F, int nF, int nV, int* loop, i
     return SMG_OK;
 }
 
+extern "C" int smg_mesh_face_neighbours(const int* F, int nF, int nV, int* ptr, int* idx)
+{
+    return guarded("smg_mesh_face_neighbours", [&]() -> int {
+        if (!F || nF <= 0 || nV <= 0) return fail(SMG_ERR_INVALID, "smg_mesh_face_neighbours: bad arguments");
+        for (size_t i = 0; i < 3 * (size_t)nF; i++)
+            if (F[i] < 0 || F[i] >= nV) return fail(SMG_ERR_INVALID, "smg_mesh_face_neighbours: face index out of range");
+        std::vector<int> Fv(F, F + 3 * (size_t)nF), mp, mi, np, ni;
+        vertex_corner_lists(Fv, nV, mp, mi);
+        if (!face_neighbours(Fv, mp, mi, np, ni)) return fail(SMG_ERR_INVALID, "smg_mesh_face_neighbours: more than 2^31 - 1 entries");
+        if (ptr) std::copy(np.begin(), np.end(), ptr);
+        if (idx) std::copy(ni.begin(), ni.end(), idx);
+        return (int)ni.size();
+    });
+}
+
 static int smg_mesh_midpoint_upsample_impl(int nV, const int* F, int nF, int* nE, int* S_rowptr, int* S_col, double* S_val, int* NF)
 {
     if (!F) return fail(SMG_ERR_INVALID, "smg_mesh_midpoint_upsample: bad arguments");

@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -11,6 +11,7 @@
 #include "smg_device.hpp"
 #include "smg_internal.hpp"
 #include "smg_membrane_inl.hpp"
+#include "smg_mesh.hpp"
 #include "smg_mesh_object.hpp"
 
 using namespace smg;
@@ -606,6 +607,88 @@ extern "C" int smg_debug_pd(int op, int nV, int nF, const int* F, const double* 
                 HIPCHK(launch_pd_strain_terms(nF, drest, dFg, dsig, dT, p->sigma_min, p->sigma_max, dout, st));
                 break;
             }
+        }
+        int bad = 0;
+        HIPCHK(X.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_denoise(int op, int nV, int nF, const int* F, const double* V0, const double* P, const double* in, const smg_denoise_params* p,
+                                 double* out, int* guard_hits)
+{
+    return guarded("smg_debug_denoise", [&]() -> int {
+        if (op < SMG_DN_REST || op > SMG_DN_ENERGY || nV < 1 || nF < 1 || !F || !p || !out) return fail(SMG_ERR_INVALID, "smg_debug_denoise: bad arguments");
+        const bool needs_rest = op != SMG_DN_ENERGY, needs_pose = op == SMG_DN_PROJECT, needs_in = op >= SMG_DN_FILTER;
+        if ((needs_rest && !V0) || (needs_pose && !P) || (needs_in && !in)) return fail(SMG_ERR_INVALID, "smg_debug_denoise: op %d misses an operand", op);
+        if (op == SMG_DN_FILTER && (!(p->sigma_s > 0.0) || !(p->sigma_r > 0.0) || p->normal_iters < 0))
+            return fail(SMG_ERR_INVALID, "smg_debug_denoise: the filter takes sigma_s > 0, sigma_r > 0 and normal_iters >= 0");
+        if (int rc = check_faces("smg_debug_denoise", F, nF, nV)) return rc;
+        if (int rc = need_device("smg_debug_denoise")) return rc;
+        const size_t D = sizeof(double), nf = (size_t)nF, nv = (size_t)nV, n3 = 3 * nv;
+        const size_t out_n = op == SMG_DN_REST ? 10 * nf : op == SMG_DN_SPACING ? nf : op == SMG_DN_FILTER ? 3 * nf : op == SMG_DN_PROJECT ? 10 * nf
+                             : op == SMG_DN_RHS ? 2 * n3 : 1;
+        const size_t in_n = op == SMG_DN_FILTER || op == SMG_DN_PROJECT ? 3 * nf : op == SMG_DN_RHS ? 9 * nf + n3 : op == SMG_DN_ENERGY ? nf + nv : 0;
+        Scratch X;
+        HIPCHK(X.init());
+        hipStream_t st = X.stream();
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr, *dnp = nullptr, *dni = nullptr;
+        double *dV0 = nullptr, *dP = nullptr, *din = nullptr, *dout = nullptr, *drest = nullptr, *dQ = nullptr, *dQn = nullptr, *dm2 = nullptr, *dpart = nullptr;
+        HIPCHK(X.add(F, nullptr, 3 * nf * sizeof(int), &dF));
+        if (V0) HIPCHK(X.add(V0, nullptr, n3 * D, &dV0));
+        if (P) HIPCHK(X.add(P, nullptr, n3 * D, &dP));
+        if (in_n) HIPCHK(X.add(in, nullptr, in_n * D, &din));
+        HIPCHK(X.add(out, out, out_n * D, &dout));
+        if (op == SMG_DN_SPACING || op == SMG_DN_FILTER || op == SMG_DN_PROJECT) {
+            HIPCHK(X.add(nullptr, nullptr, 10 * nf * D, &drest));
+            HIPCHK(launch_denoise_rest(nF, dF, dV0, drest, st));
+        }
+        std::vector<int> mp, mi, np, ni;
+        if (op == SMG_DN_SPACING || op == SMG_DN_FILTER || op == SMG_DN_RHS) {
+            const std::vector<int> Fv(F, F + 3 * nf);
+            vertex_corner_lists(Fv, nV, mp, mi);
+            if (op == SMG_DN_RHS) {
+                HIPCHK(X.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+                HIPCHK(X.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+            } else {
+                if (!face_neighbours(Fv, mp, mi, np, ni)) return fail(SMG_ERR_INVALID, "smg_debug_denoise: the neighbourhoods have more than 2^31 - 1 entries");
+                HIPCHK(X.add(np.data(), nullptr, np.size() * sizeof(int), &dnp));
+                HIPCHK(X.add(ni.data(), nullptr, ni.size() * sizeof(int), &dni));
+            }
+        }
+        switch (op) {
+            case SMG_DN_REST: HIPCHK(launch_denoise_rest(nF, dF, dV0, dout, st)); break;
+            case SMG_DN_SPACING: HIPCHK(launch_denoise_spacing(nF, dnp, dni, drest, dout, st)); break;
+            case SMG_DN_FILTER: {
+                // the object's ping-pong: the host swaps the pair between the launches; the result is copied into the guarded output
+                double *a = din, *b = nullptr;
+                HIPCHK(X.add(nullptr, nullptr, 3 * nf * D, &b));
+                for (int it = 0; it < p->normal_iters; it++) {
+                    HIPCHK(launch_denoise_filter(nF, dnp, dni, drest, a, p->sigma_s, p->sigma_r, b, st));
+                    std::swap(a, b);
+                }
+                HIPCHK(hipMemcpyAsync(dout, a, 3 * nf * D, hipMemcpyDeviceToDevice, st));
+                break;
+            }
+            case SMG_DN_PROJECT:
+                HIPCHK(X.add(nullptr, nullptr, n3 * D, &dQ));
+                HIPCHK(launch_arap_columns(nV, dP, dQ, nV, st));
+                HIPCHK(launch_denoise_project(nF, dF, drest, din, dQ, 1, nv, dout, dout + nf, st));
+                break;
+            case SMG_DN_RHS: {
+                HIPCHK(X.add(nullptr, nullptr, 6 * nf * D, &dQn));
+                HIPCHK(X.add(nullptr, nullptr, n3 * D, &dQ));
+                dm2 = dout + n3 + 2 * nv;
+                HIPCHK(launch_membrane_pressure(nV, nF, dF, dV0, dmp, dmi, 0.0, dQn, dm2, nullptr, st));
+                HIPCHK(launch_arap_columns(nV, dV0, dQ, nV, st));
+                HIPCHK(launch_pd_vertices(nV, nF, dmp, dmi, din, dm2, p->fidelity, dQ, din + 9 * nf, nV, dout, nV, dout + n3, dout + n3 + nv, st));
+                break;
+            }
+            default:
+                HIPCHK(X.add(nullptr, nullptr, (size_t)fixed_sum_groups(nF + nV) * D, &dpart));
+                HIPCHK(launch_fixed_sum(din, nF + nV, dpart, dout, st));
+                break;
         }
         int bad = 0;
         HIPCHK(X.finish(&bad));

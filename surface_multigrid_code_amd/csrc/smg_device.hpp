@@ -518,4 +518,17 @@ hipError_t launch_pd_vertices(int nV, int nF, const int* m_ptr, const int* m_idx
 // vel = (Q - x) / h, x = Q
 hipError_t launch_pd_finish(int nV, const double* Q, int ld, double h, double* x, double* vel, hipStream_t st);
 
+// feature-preserving denoising (smg_denoise_device.hip; the maths in smg_denoise_inl.hpp).  V0: xyz rows; per-face arrays are face-major planes
+// (plane e at [e * nF + f]): rest (10: n, A, c, w), a normal field (3), share (9: 3 i + l); nb_ptr / nb_idx: N(f), the faces that share a vertex
+// with f, ascending.  The right-hand side of the global step is launch_pd_vertices' (S = the input positions, c_mass = fidelity) -------------
+hipError_t launch_denoise_rest(int nF, const int* F, const double* V0, double* rest, hipStream_t st);
+// term[f] = sum over N(f), in list order, of |c_f - c_g|
+hipError_t launch_denoise_spacing(int nF, const int* nb_ptr, const int* nb_idx, const double* rest, double* term, hipStream_t st);
+// one iteration of the bilateral normal filter: m_out (another buffer than m_in) from m_in
+hipError_t launch_denoise_filter(int nF, const int* nb_ptr, const int* nb_idx, const double* rest, const double* m_in, double sigma_s, double sigma_r,
+                                 double* m_out, hipStream_t st);
+// per face of the pose X (coordinate l of vertex v at X[v * sv + l * sl]) against the normals m: eterm[f] = (1/2) sum_k w_k h_k^2 and the corner shares
+hipError_t launch_denoise_project(int nF, const int* F, const double* rest, const double* m, const double* X, size_t sv, size_t sl, double* eterm,
+                                  double* share, hipStream_t st);
+
 }  // namespace smg

@@ -338,6 +338,29 @@ void vertex_corner_lists(const std::vector<int>& F, int nV, std::vector<int>& m_
     for (int f = 0; f < nF; f++) for (int c = 0; c < 3; c++) m_idx[mn[F[3 * f + c]]++] = 3 * f + c;
 }
 
+bool face_neighbours(const std::vector<int>& F, const std::vector<int>& m_ptr, const std::vector<int>& m_idx, std::vector<int>& nb_ptr,
+                     std::vector<int>& nb_idx)
+{
+    const int nF = (int)(F.size() / 3);
+    nb_ptr.assign((size_t)nF + 1, 0);
+    nb_idx.clear();
+    std::vector<int> row;
+    for (int f = 0; f < nF; f++) {
+        row.clear();
+        for (int c = 0; c < 3; c++) {
+            const int v = F[3 * (size_t)f + c];
+            for (int p = m_ptr[v]; p < m_ptr[v + 1]; p++)
+                if (m_idx[p] / 3 != f) row.push_back(m_idx[p] / 3);
+        }
+        std::sort(row.begin(), row.end());
+        row.erase(std::unique(row.begin(), row.end()), row.end());
+        if (nb_idx.size() + row.size() > (size_t)INT32_MAX) return false;
+        nb_idx.insert(nb_idx.end(), row.begin(), row.end());
+        nb_ptr[(size_t)f + 1] = (int)nb_idx.size();
+    }
+    return true;
+}
+
 Mesh make_torus(int nu, int nv, double R, double r)
 {
     Mesh m;

@@ -56,6 +56,10 @@ struct AssemblyPlan {
 AssemblyPlan make_assembly_plan(const std::vector<int>& F, int nV);
 // per vertex the corners t = 3f + c that touch it, faces ascending (AssemblyPlan::m_ptr / m_idx; the heat-method divergence gathers in this order)
 void vertex_corner_lists(const std::vector<int>& F, int nV, std::vector<int>& m_ptr, std::vector<int>& m_idx);
+// per face f the faces that share at least one vertex with it, without f, ascending and duplicate-free (CSR: nb_ptr has nF + 1 entries), from
+// the corner lists; false when the entries do not fit an int
+bool face_neighbours(const std::vector<int>& F, const std::vector<int>& m_ptr, const std::vector<int>& m_idx, std::vector<int>& nb_ptr,
+                     std::vector<int>& nb_idx);
 
 // What one coarsening step keeps about its collapses when asked to (the reference's decInfo / decIM, src/single_collapse_data.h and
 // src/SSP_collapse_edge.cpp:452-459): per successful collapse the faces of the pre-collapse one-ring with their flattened positions.
