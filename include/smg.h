@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 512
+#define SMG_VERSION 513
 
 enum {
     SMG_OK = 0,
@@ -720,6 +720,67 @@ int smg_denoise_run(smg_denoise *d, int memspace, int max_iter, double rel_tol, 
 int smg_denoise_faces_host(int op, int nV, int nF, const int *F, const double *V0, const double *P, const double *in,
                            const smg_denoise_params *p, double *out);
 
+/* ---- cubic and normal-driven stylization on the scalar V-cycle (csrc/smg_stylize.cpp): Liu and Jacobson 2019 ("Cubic
+ * stylization") and its closed-form sibling, Liu and Jacobson 2021 ("Normal-driven spherical shape analogies").  As-rigid-as-possible deformation
+ * with a penalty on each vertex's rotated normal.  Rest mesh (V, F); L, w_ij, e_ij, e'_ij, N(i) as for smg_arap above; n_i = the unit
+ * area-weighted vertex normal, the normalised sum of (p1 - p0) x (p2 - p0) over the vertex's faces, faces ascending; a_i = the barycentric vertex
+ * area, the sum of the double areas over 6 in the same order; lambda_i = a per-vertex weight (uniform lambda unless set); Q = a rotation holding
+ * the cube's axes (the identity unless set); t_i = caller-given unit target normals.
+ *     cubic:          E(R, U) = sum_i [ (1/2) sum_{j in N(i)} w_ij |e'_ij - R_i e_ij|^2 + lambda_i a_i |Q R_i n_i|_1 ]
+ *     normal-driven:  lambda_i a_i |R_i n_i - t_i|^2 in place of the L1 term (Q is not used)
+ *     global: (-L) U = b, b_i = sum_j (w_ij / 2) (R_i + R_j) e_ij, the pinned rows known: smg_arap's, the factor 1/2 cancels
+ *     local, cubic: S_i = sum_j w_ij e_ij e'_ij^T once, then at most admm_iters iterations from the state (z, u, rho) of the vertex:
+ *         M = S + rho n (Q^T (z - u))^T;  R = the closest rotation of M (smg_arap's fit);  y = Q R n;  z_old = z;  z = shrink(y + u, lambda_i a_i / rho);
+ *         u += y - z;  r = |z - y|;  s = rho |z - z_old|;  r > mu s: rho *= tau, u /= tau;  else s > mu r: rho /= tau, u *= tau;
+ *         stop when r < sqrt(3) abs_tol + rel_tol max(|y|, |z|) and s < sqrt(3) abs_tol + rel_tol rho |u| (the updated rho, u)
+ *       z = u = 0 and rho = rho0 at the start of every smg_stylize_run; the state is carried from outer iteration to outer iteration within the
+ *       call and nothing is kept between calls: the same inputs give the same bits.
+ *     local, normal-driven: R = the closest rotation of S + 2 lambda_i a_i n t_i^T; no state.
+ * The paper's edge sets are spokes and rims; this object uses smg_arap's spokes, so that the matrix, the weights and the right-hand side kernel
+ * are shared with it.  ADMM does not minimise the local problem exactly, so monotone descent of E is observed, not proved.
+ *
+ * smg_stylize_params: lambda >= 0; rho0, abs_tol, rel_tol > 0; mu > 1, tau > 1; all finite; admm_iters >= 1.
+ * smg_stylize_create: h gives the prolongations (any scalar hierarchy on this mesh); they are copied into one internal handle, precomputed here
+ *   with -L and known = pins; h is not modified.  pins: n_pins distinct vertices, their order is the row order of pin_pos.  SMG_ERR_INVALID,
+ *   before any device work, in this order: a null argument; a union or block hierarchy, nV != the rows of level 0; a face index out of range, a
+ *   face of zero area, a non-finite coordinate, more than one connected component; n_pins < 1, a pin out of range or repeated, every vertex
+ *   pinned; then the parameters in the order lambda, rho0, abs_tol, rel_tol, mu, tau, admm_iters.  SMG_ERR_NO_DEVICE comes after all of them.
+ * smg_stylize_set_solver: as smg_arap_set_solver.  smg_stylize_device_bytes: the internal handle and the object's own buffers.
+ * smg_stylize_set_params: legal between calls, nothing is rebuilt; the checks of create.
+ * smg_stylize_set_lambda: nV host values lambda_i, each finite and >= 0; NULL: back to the uniform lambda.
+ * smg_stylize_set_frame: 9 host doubles, Q row-major; NULL: the identity.  Refused unless |Q^T Q - I| <= 1e-12 entrywise and det Q > 0.
+ * smg_stylize_set_targets: nV x 3 host xyz rows of unit vectors select the normal-driven mode; NULL selects the cubic mode.  Refused unless
+ *   every row is finite with | |t| - 1 | <= 1e-8.
+ * smg_stylize_normals: n (nV x 3 xyz rows) and a (nV) to host arrays; either may be NULL.
+ * smg_stylize_run: the start iterate, the local / global loop and the copy out; arguments, memspace handling, stopping rule and
+ *   SMG_ERR_NONFINITE exactly as smg_arap_solve (pin_pos for handle_pos); pin_pos may be NULL = the rest positions of the pins.  opts NULL:
+ *   smg_solve_opts_default with max_iter = 50 and tol = 1e-8 s, smg_arap's s.
+ * smg_stylize_admm_stats: the minimum, mean and maximum of the ADMM iteration counts of the last local step (normal-driven: all 0) and the
+ *   number of vertices that used all admm_iters; iters (NULL ok): the nV counts.  Before any run: SMG_ERR_INVALID.
+ * smg_stylize_local_host: the host twin of one local step on caller arrays (no GPU, the text the kernels compile), with the operands and the
+ *   layout of smg_debug_stylize below; SMG_STY_ENERGY writes the nV terms only.
+ * Not covered: the spokes-and-rims energy, per-axis weights, union / block / sharded forms, a new pin SET without a new object. */
+typedef struct smg_stylize smg_stylize;
+typedef struct { double lambda, rho0, abs_tol, rel_tol, mu, tau; int admm_iters; } smg_stylize_params;
+enum { SMG_STY_NORMALS = 0, SMG_STY_ADMM_ONE = 1, SMG_STY_LOCAL = 2, SMG_STY_LOCAL_TARGETS = 3, SMG_STY_ENERGY = 4 };
+void smg_stylize_params_default(smg_stylize_params *p);    /* 0.2, 1e-4, 1e-5, 1e-3, 10, 2, 100 */
+int smg_stylize_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const int *pins, int n_pins,
+                       const smg_stylize_params *p, smg_stylize **out);
+void smg_stylize_destroy(smg_stylize *s);
+long long smg_stylize_device_bytes(const smg_stylize *s);
+int smg_stylize_set_solver(smg_stylize *s, int pcg);
+int smg_stylize_set_params(smg_stylize *s, const smg_stylize_params *p);
+int smg_stylize_set_lambda(smg_stylize *s, const double *lambda);
+int smg_stylize_set_frame(smg_stylize *s, const double *Q);
+int smg_stylize_set_targets(smg_stylize *s, const double *targets);
+int smg_stylize_normals(smg_stylize *s, double *normals, double *areas);
+int smg_stylize_run(smg_stylize *s, const double *pin_pos, int ld_pp, const double *U0, int ld_u0, int memspace, int max_iter, double rel_tol,
+                    const smg_solve_opts *opts, double *U, int ld_u, double *energy_his, int *cycles, int *n_iter);
+int smg_stylize_admm_stats(smg_stylize *s, int *min_iters, double *mean_iters, int *max_iters, int *at_cap, int *iters);
+int smg_stylize_local_host(int op, int nV, int nF, const int *F, const int *rowptr, const int *col, const double *w, const double *V0,
+                           const double *P, const double *lambda, const double *Q, const double *targets, const double *state_in,
+                           const double *R_in, const smg_stylize_params *p, double *out, int *iters);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -1014,6 +1075,22 @@ int smg_debug_pd(int op, int nV, int nF, const int *F, const double *V0, const d
  * GPU. */
 int smg_debug_denoise(int op, int nV, int nF, const int *F, const double *V0, const double *P, const double *in, const smg_denoise_params *p,
                       double *out, int *guard_hits);
+
+/* One launcher of the stylizer (csrc/smg_stylize_device.hip), handle-free and guarded like the hooks above.  F: nF x 3; rowptr[nV + 1], col, w: a
+ * CSR with the cotangent matrix's pattern (diagonal entries are skipped); V0 (the rest mesh) and P (a pose): nV x 3 xyz rows; lambda: nV values
+ * or NULL = p->lambda; Q: 9 doubles or NULL = the identity; targets: nV x 3 xyz rows; state_in: 7 planes of nV (z, u, rho) or NULL = the start
+ * state z = u = 0, rho = p->rho0; R_in: 9 doubles per vertex.  n_i and a_i are computed from F and V0 by k_stylize_normals first.
+ *   SMG_STY_NORMALS        V0                 -> out = n (nV x 3 xyz rows), a (nV)
+ *   SMG_STY_ADMM_ONE       V0, P, [state_in]  -> exactly one ADMM iteration: the layout of SMG_STY_LOCAL, iters all 1
+ *   SMG_STY_LOCAL          V0, P, [state_in]  -> out = R (9 nV), the energy terms (nV), the state (7 planes); iters[nV] = the iterations used
+ *   SMG_STY_LOCAL_TARGETS  V0, P, targets     -> out = R (9 nV), the energy terms (nV); iters all 0
+ *   SMG_STY_ENERGY         V0, P, R_in, [targets: the normal-driven term] -> out = the energy terms (nV), then their sum (fixed row chunks,
+ *                                                fixed-order finalize)
+ * SMG_ERR_INVALID for an unknown op, a missing operand, bad parameters, a face index out of range or a malformed CSR; SMG_ERR_NO_DEVICE without
+ * a GPU. */
+int smg_debug_stylize(int op, int nV, int nF, const int *F, const int *rowptr, const int *col, const double *w, const double *V0, const double *P,
+                      const double *lambda, const double *Q, const double *targets, const double *state_in, const double *R_in,
+                      const smg_stylize_params *p, double *out, int *iters, int *guard_hits);
 
 /* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
  * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.

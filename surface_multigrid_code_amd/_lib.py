@@ -29,6 +29,11 @@ class DenoiseParamsC(C.Structure):
     _fields_ = [("sigma_s", C.c_double), ("sigma_r", C.c_double), ("fidelity", C.c_double), ("normal_iters", C.c_int)]
 
 
+class StylizeParamsC(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("rho0", C.c_double), ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("mu", C.c_double),
+                ("tau", C.c_double), ("admm_iters", C.c_int)]
+
+
 _lib = None
 
 
@@ -151,6 +156,20 @@ def load():
         "smg_denoise_run": (i, [vp, i, i, d, C.POINTER(SolveOptsC), vp, dp, ip, ip]),
         "smg_denoise_faces_host": (i, [i, i, i, ip, dp, dp, dp, C.POINTER(DenoiseParamsC), dp]),
         "smg_debug_denoise": (i, [i, i, i, ip, dp, dp, dp, C.POINTER(DenoiseParamsC), dp, ip]),
+        "smg_stylize_params_default": (None, [C.POINTER(StylizeParamsC)]),
+        "smg_stylize_create": (i, [vp, dp, i, ip, i, ip, i, C.POINTER(StylizeParamsC), C.POINTER(vp)]),
+        "smg_stylize_destroy": (None, [vp]),
+        "smg_stylize_device_bytes": (C.c_longlong, [vp]),
+        "smg_stylize_set_solver": (i, [vp, i]),
+        "smg_stylize_set_params": (i, [vp, C.POINTER(StylizeParamsC)]),
+        "smg_stylize_set_lambda": (i, [vp, dp]),
+        "smg_stylize_set_frame": (i, [vp, dp]),
+        "smg_stylize_set_targets": (i, [vp, dp]),
+        "smg_stylize_normals": (i, [vp, dp, dp]),
+        "smg_stylize_run": (i, [vp, vp, i, vp, i, i, i, d, C.POINTER(SolveOptsC), vp, i, dp, ip, ip]),
+        "smg_stylize_admm_stats": (i, [vp, ip, dp, ip, ip, ip]),
+        "smg_stylize_local_host": (i, [i, i, i, ip, ip, ip, dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(StylizeParamsC), dp, ip]),
+        "smg_debug_stylize": (i, [i, i, i, ip, ip, ip, dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(StylizeParamsC), dp, ip, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

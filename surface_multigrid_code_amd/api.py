@@ -957,6 +957,90 @@ class Denoiser(_MeshObject):
         return self._iterate("run", max_iter, SMG_DEVICE, int(max_iter), float(rel_tol), self._opts(opts), X_ptr)
 
 
+class Stylizer(_MeshObject):
+    """Cubic and normal-driven stylization on the scalar V-cycle (include/smg.h: smg_stylize_*; Liu and Jacobson 2019 and 2021): as-rigid-as-possible
+    deformation with the penalty lambda a_i |Q R_i n_i|_1 (cubic) or lambda a_i |R_i n_i - t_i|^2 (normal-driven, after set_targets) on every
+    vertex's rotated normal.  The global matrix -L is smg_arap's and is precomputed here, once; the local step is an ADMM loop per vertex.
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  V: the rest pose; bring it
+    to a unit bounding box first: lambda is tuned at that scale.  pins: the vertices whose positions run() is given (None: vertex 0).
+    params: the fields of smg_stylize_params (lambda_, rho0, abs_tol, rel_tol, mu, tau, admm_iters)."""
+
+    _prefix = "smg_stylize_"
+    s = property(lambda self: self.o)
+
+    def __init__(self, hierarchy, V, F, pins=None, **params):
+        self.pins = np.ascontiguousarray([0] if pins is None else pins, dtype=np.int32).reshape(-1)
+        self.params = stylize_params(**params)
+        self._create(hierarchy, V, F, _ip(self.pins), self.pins.shape[0], C.byref(self.params))
+
+    def set_params(self, **params):
+        """legal between calls, nothing is rebuilt; fields not named keep their values"""
+        p = stylize_params(**{**{k: getattr(self.params, k) for k, _ in self.params._fields_}, **params})
+        self._call("set_params", C.byref(p))
+        self.params = p
+
+    def set_lambda(self, lam=None):
+        """per-vertex weights (n values, finite and >= 0); None: back to the uniform lambda"""
+        lam = None if lam is None else np.ascontiguousarray(lam, dtype=np.float64).reshape(self.n)
+        self._call("set_lambda", None if lam is None else _dp(lam))
+
+    def set_frame(self, Q=None):
+        """Q: the 3 x 3 rotation whose rows are the cube's axes; None: the identity"""
+        Q = None if Q is None else np.ascontiguousarray(Q, dtype=np.float64).reshape(9)
+        self._call("set_frame", None if Q is None else _dp(Q))
+
+    def set_targets(self, targets=None):
+        """n x 3 unit target normals select the normal-driven mode; None selects the cubic mode"""
+        T = None if targets is None else np.ascontiguousarray(targets, dtype=np.float64).reshape(self.n, 3)
+        self._call("set_targets", None if T is None else _dp(T))
+
+    def normals(self):
+        """(n_i as n x 3, a_i): the unit area-weighted vertex normals and the barycentric vertex areas of the rest pose"""
+        nrm, area = np.zeros((self.n, 3)), np.zeros(self.n)
+        self._call("normals", _dp(nrm), _dp(area))
+        return nrm, area
+
+    def admm_stats(self):
+        """the ADMM iteration counts of the last local step: dict(min, mean, max, at_cap, iters)"""
+        lo, hi, cap, mean = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0)
+        it = np.zeros(self.n, dtype=np.int32)
+        self._call("admm_stats", C.byref(lo), C.byref(mean), C.byref(hi), C.byref(cap), _ip(it))
+        return dict(min=lo.value, mean=mean.value, max=hi.value, at_cap=cap.value, iters=it)
+
+    def _run(self, pp_ptr, ld_pp, U0_ptr, ld_u0, memspace, max_iter, rel_tol, opts, U_ptr, ld_u):
+        return self._iterate("run", max_iter, pp_ptr, ld_pp, U0_ptr, ld_u0, memspace, int(max_iter), float(rel_tol), self._opts(opts), U_ptr, ld_u)
+
+    def run(self, pin_pos=None, U0=None, max_iter=10, rel_tol=0.0, opts=None):
+        """pin_pos: n_pins x 3 (row r = the position of pins[r]; None: the rest positions); U0: the n x 3 start, None = the rest pose.  Returns
+        (U, energy_his, cycles): the n x 3 positions after the iterations run, E_0 .. E_n_iter, the loop entries of each inner solve."""
+        pp = None if pin_pos is None else _colmajor(pin_pos)
+        assert pp is None or pp.shape == (self.pins.shape[0], 3)
+        U0 = None if U0 is None else _colmajor(U0)
+        assert U0 is None or U0.shape == (self.n, 3)
+        U = np.zeros((self.n, 3), order="F")
+        E, cyc = self._run(None if pp is None else pp.ctypes.data, self.pins.shape[0], None if U0 is None else U0.ctypes.data, self.n, SMG_HOST,
+                           max_iter, rel_tol, opts, U.ctypes.data, self.n)
+        return U, E, cyc
+
+    def run_device(self, U_ptr, pp_ptr=None, ld_u=None, U0_ptr=None, ld_u0=None, ld_pp=None, max_iter=10, rel_tol=0.0, opts=None):
+        """run() between column-major blocks resident in HBM (device pointers; leading dimensions default to n_pins and n).
+        Returns (energy_his, cycles)."""
+        return self._run(pp_ptr or None, ld_pp or self.pins.shape[0], U0_ptr or None, ld_u0 or self.n, SMG_DEVICE, max_iter, rel_tol, opts, U_ptr,
+                         ld_u or self.n)
+
+
+def stylize_params(**params):
+    """smg_stylize_params with the library's defaults and the given fields (lambda is spelled lambda_)"""
+    p = _lib.StylizeParamsC()
+    _lib.load().smg_stylize_params_default(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError("unknown stylization parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 def denoise_params(**params):
     """smg_denoise_params with the library's defaults and the given fields"""
     p = _lib.DenoiseParamsC()

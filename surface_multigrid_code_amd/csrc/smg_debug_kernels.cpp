@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -13,6 +13,7 @@
 #include "smg_membrane_inl.hpp"
 #include "smg_mesh.hpp"
 #include "smg_mesh_object.hpp"
+#include "smg_stylize_inl.hpp"
 
 using namespace smg;
 
@@ -689,6 +690,68 @@ extern "C" int smg_debug_denoise(int op, int nV, int nF, const int* F, const dou
                 HIPCHK(X.add(nullptr, nullptr, (size_t)fixed_sum_groups(nF + nV) * D, &dpart));
                 HIPCHK(launch_fixed_sum(din, nF + nV, dpart, dout, st));
                 break;
+        }
+        int bad = 0;
+        HIPCHK(X.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_stylize(int op, int nV, int nF, const int* F, const int* rowptr, const int* col, const double* w, const double* V0,
+                                 const double* P, const double* lambda, const double* Q, const double* targets, const double* state_in,
+                                 const double* R_in, const smg_stylize_params* p, double* out, int* iters, int* guard_hits)
+{
+    return guarded("smg_debug_stylize", [&]() -> int {
+        const char* who = "smg_debug_stylize";
+        if (int rc = stylize_check_operands(who, op, nV, nF, F, rowptr, col, w, V0, P, lambda, Q, targets, R_in, p, out, iters)) return rc;
+        if (int rc = need_device(who)) return rc;
+        std::vector<int> mp, mi;
+        vertex_corner_lists(std::vector<int>(F, F + 3 * (size_t)nF), nV, mp, mi);
+        Scratch X;
+        HIPCHK(X.init());
+        const size_t n = (size_t)nV, nnz = (size_t)rowptr[nV], vec = n * sizeof(double);
+        const bool cubic = op == SMG_STY_ADMM_ONE || op == SMG_STY_LOCAL;
+        const size_t out_bytes = op == SMG_STY_NORMALS ? 4 * vec : cubic ? (10 + STY_STATE) * vec : op == SMG_STY_LOCAL_TARGETS ? 10 * vec : vec + sizeof(double);
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr, *dptr = nullptr, *dcol = nullptr, *dit = nullptr;
+        double *dw = nullptr, *dV0 = nullptr, *dP = nullptr, *dlam = nullptr, *dtgt = nullptr, *dR = nullptr, *dn = nullptr, *da = nullptr, *dout = nullptr,
+               *dpart = nullptr;
+        HIPCHK(X.add(F, nullptr, 3 * (size_t)nF * sizeof(int), &dF));
+        HIPCHK(X.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+        HIPCHK(X.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+        HIPCHK(X.add(rowptr, nullptr, (n + 1) * sizeof(int), &dptr));
+        HIPCHK(X.add(col, nullptr, nnz * sizeof(int), &dcol));
+        HIPCHK(X.add(w, nullptr, nnz * sizeof(double), &dw));
+        HIPCHK(X.add(V0, nullptr, 3 * vec, &dV0));
+        if (P) HIPCHK(X.add(P, nullptr, 3 * vec, &dP));
+        if (lambda) HIPCHK(X.add(lambda, nullptr, vec, &dlam));
+        if (targets) HIPCHK(X.add(targets, nullptr, 3 * vec, &dtgt));
+        if (op == SMG_STY_ENERGY) HIPCHK(X.add(R_in, nullptr, 9 * vec, &dR));
+        HIPCHK(X.add(out, out, out_bytes, &dout));
+        if (op != SMG_STY_NORMALS) {
+            HIPCHK(X.add(nullptr, nullptr, 3 * vec, &dn));
+            HIPCHK(X.add(nullptr, nullptr, vec, &da));
+        }
+        if (iters && op != SMG_STY_NORMALS && op != SMG_STY_ENERGY) HIPCHK(X.add(iters, iters, n * sizeof(int), &dit));
+        if (op == SMG_STY_ENERGY) HIPCHK(X.add(nullptr, nullptr, (size_t)fixed_sum_groups(nV) * sizeof(double), &dpart));
+        hipStream_t st = X.stream();
+        StyFrame fr = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
+        if (Q) for (int e = 0; e < 9; e++) fr.q[e] = Q[e];
+        StyParams sp = sty_params(*p);
+        if (op == SMG_STY_ADMM_ONE) sp.admm_iters = 1;
+        if (op == SMG_STY_NORMALS) {
+            HIPCHK(launch_stylize_normals(nV, dF, dmp, dmi, dV0, dout, dout + 3 * n, st));
+        } else {
+            HIPCHK(launch_stylize_normals(nV, dF, dmp, dmi, dV0, dn, da, st));
+            if (cubic) {
+                if (state_in) HIPCHK(hipMemcpyAsync(dout + 10 * n, state_in, STY_STATE * vec, hipMemcpyHostToDevice, st));
+                HIPCHK(launch_stylize_cubic(nV, dptr, dcol, dw, dV0, dP, dn, da, dlam, fr, sp, state_in ? 0 : 1, dout + 10 * n, dout, dout + 9 * n, dit, st));
+            } else if (op == SMG_STY_LOCAL_TARGETS) {
+                HIPCHK(launch_stylize_targets(nV, dptr, dcol, dw, dV0, dP, dn, da, dlam, dtgt, sp, dout, dout + 9 * n, dit, st));
+            } else {
+                HIPCHK(launch_stylize_energy(nV, dptr, dcol, dw, dV0, dP, dn, da, dlam, fr, dtgt, sp, dR, dout, st));
+                HIPCHK(launch_fixed_sum(dout, nV, dpart, dout + n, st));
+            }
         }
         int bad = 0;
         HIPCHK(X.finish(&bad));

@@ -518,6 +518,26 @@ hipError_t launch_pd_vertices(int nV, int nF, const int* m_ptr, const int* m_idx
 // vel = (Q - x) / h, x = Q
 hipError_t launch_pd_finish(int nV, const double* Q, int ld, double h, double* x, double* vel, hipStream_t st);
 
+// cubic and normal-driven stylization (smg_stylize_device.hip; the maths in smg_stylize_inl.hpp).  The CSR, P0, P and R as for smg_arap; nrm, tgt: xyz
+// rows; area, lam (nullptr: the uniform p.lambda): one double per vertex; state: 7 planes of n (z, u, rho); iters: the ADMM iterations used -------
+struct StyParams;
+struct StyFrame;
+// n_i, a_i from the corner lists t = 3 f + i of every vertex (mp, mi), faces ascending
+hipError_t launch_stylize_normals(int n, const int* F, const int* mp, const int* mi, const double* V, double* nrm, double* area, hipStream_t st);
+// the cubic local step (k_stylize_local): at most p.admm_iters ADMM iterations per vertex from state (fresh != 0: from z = u = 0, rho = p.rho0), the
+// rotations, the state, eterm[i] = (1/2) sum_j w_ij |e'_ij - R_i e_ij|^2 + lambda_i a_i |Q R_i n_i|_1 and the iteration counts
+hipError_t launch_stylize_cubic(int n, const int* rowptr, const int* col, const double* w, const double* P0, const double* P, const double* nrm,
+                                const double* area, const double* lam, const StyFrame& Q, const StyParams& p, int fresh, double* state, double* R,
+                                double* eterm, int* iters, hipStream_t st);
+// the normal-driven local step: R_i = the closest rotation of S_i + 2 lambda_i a_i n_i t_i^T, eterm[i] with lambda_i a_i |R_i n_i - t_i|^2, iters[i] = 0
+hipError_t launch_stylize_targets(int n, const int* rowptr, const int* col, const double* w, const double* P0, const double* P, const double* nrm,
+                                  const double* area, const double* lam, const double* tgt, const StyParams& p, double* R, double* eterm, int* iters,
+                                  hipStream_t st);
+// eterm[i] with the given rotations (tgt != nullptr: the normal-driven term)
+hipError_t launch_stylize_energy(int n, const int* rowptr, const int* col, const double* w, const double* P0, const double* P, const double* nrm,
+                                 const double* area, const double* lam, const StyFrame& Q, const double* tgt, const StyParams& p, const double* R,
+                                 double* eterm, hipStream_t st);
+
 // feature-preserving denoising (smg_denoise_device.hip; the maths in smg_denoise_inl.hpp).  V0: xyz rows; per-face arrays are face-major planes
 // (plane e at [e * nF + f]): rest (10: n, A, c, w), a normal field (3), share (9: 3 i + l); nb_ptr / nb_idx: N(f), the faces that share a vertex
 // with f, ascending.  The right-hand side of the global step is launch_pd_vertices' (S = the input positions, c_mass = fidelity) -------------

@@ -67,4 +67,12 @@ inline hipError_t copy_columns(double* dst, int ld_dst, const double* src, int l
 int upload_faces(const int* F, int nF, int nV, DevBuf<int>& d_F, DevBuf<int>& d_ptr, DevBuf<int>& d_idx, std::vector<int>* mp = nullptr,
                  std::vector<int>* mi = nullptr);
 
+// ---- smg_stylize.cpp: what smg_stylize_local_host and smg_debug_stylize check alike, in this order (operands, parameters, faces, the CSR, then
+// lambda, frame and targets where given), and the parameters as the kernels take them
+struct StyParams;
+StyParams sty_params(const smg_stylize_params& p);
+int stylize_check_operands(const char* who, int op, int nV, int nF, const int* F, const int* rowptr, const int* col, const double* w, const double* V0,
+                           const double* P, const double* lam, const double* Q, const double* targets, const double* R_in,
+                           const smg_stylize_params* p, const double* out, const int* iters);
+
 }  // namespace smg
