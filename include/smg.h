@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 513
+#define SMG_VERSION 514
 
 enum {
     SMG_OK = 0,
@@ -781,6 +781,71 @@ int smg_stylize_local_host(int op, int nV, int nF, const int *F, const int *rowp
                            const double *P, const double *lambda, const double *Q, const double *targets, const double *state_in,
                            const double *R_in, const smg_stylize_params *p, double *out, int *iters);
 
+/* ---- gradient-domain morphing on the scalar V-cycle (csrc/smg_morph.cpp): Poisson reconstruction from per-face gradients
+ * (Yu et al. 2004), pose interpolation through the faces' polar factors (Xu et al. 2005; Alexa et al. 2000), and deformation transfer in the
+ * Poisson form of Botsch et al. 2006.  An addition: the reference has none of them.  k sets -- in-between poses, frames -- are 3k right-hand sides
+ * of ONE constant matrix with the same pinned rows: a query is one or two face kernels, one vertex kernel and one 3k-column solve.
+ *   Rest mesh (V, F): n_f = the rest unit normal of face f, 2A_f its double area, W_fi = (n_f x e_i) / (2A_f) with e_i the edge opposite corner i,
+ *     counter-clockwise (e_0 = x_2 - x_1, e_1 = x_0 - x_2, e_2 = x_1 - x_0): the gradient of corner i's hat function, as smg_geodesics forms it.
+ *     L = smg_assemble's cotangent matrix of the rest mesh.
+ *   Face gradient of a pose X on a rest mesh: T_f = sum_i x_i W_fi^T (i = 0, 1, 2 in order), N_f = the unit normal of the pose face (0 where its
+ *     area is 0), J_f = T_f + N_f n_f^T: 3 x 3, row-major.
+ *   Polar factors: J_f = R_f S_f, R_f the rotation (det = +1) that maximises tr(R_f^T J_f) = U D V^T for J_f = U Sigma V^T, D = diag(1, 1,
+ *     det(U V^T)), the flip on the smallest singular value: smg_arap's one-sided Jacobi and its determinant rule.  S_f = (M + M^T) / 2, M = R_f^T J_f.
+ *   Rotation vector: R_f as a unit quaternion (w, v) by Shepperd's branch on the largest of the trace and the three diagonal entries, its sign
+ *     chosen so that w >= 0; theta = 2 atan2(|v|, w); omega_f = theta v / |v|, or 0 when |v| = 0.  Stored: 3 + 6 doubles per face (omega_f and
+ *     S_f as 00, 01, 02, 11, 12, 22).
+ *   Interpolation at time t, any finite t (extrapolation allowed): R_f(t) = Rodrigues' formula for t omega_f, S_f(t) = I + t (S_f - I),
+ *     J_f(t) = R_f(t) S_f(t).
+ *   Reconstruction: U minimises sum_f A_f |grad u - J_f|_F^2: row i of (-L) U = b with b_i = sum over the corners (f, j) of vertex i, faces
+ *     ascending, of A_f J_f W_fj; the pinned rows are known.
+ *   Blocks: U, U0 are nV x 3k column-major, pin_pos is n_pins x 3k column-major: column 3c + d is coordinate d of set c.
+ *
+ * smg_morph_create: h gives the prolongations (any scalar hierarchy on this mesh); they are copied into one internal handle, precomputed here,
+ *   once, with -L and known = pins; h is not modified.  V: nV x 3 row-major (the rest pose), F: nF x 3, pins: n_pins distinct vertices, their
+ *   order is the row order of pin_pos.  SMG_ERR_INVALID, before any device work, in this order: a null argument; a union or block hierarchy,
+ *   nV != the rows of level 0; a face index out of range, a face of zero area, a non-finite coordinate, more than one connected component;
+ *   n_pins < 1, a pin out of range or repeated, every vertex pinned.  SMG_ERR_NO_DEVICE comes after all of them.
+ * smg_morph_set_solver: as smg_arap_set_solver (PCG by default).  smg_morph_device_bytes: the internal handle and the object's own buffers; the
+ *   blocks of a query grow with the largest k seen and are kept.
+ * The three queries share their last arguments.  pin_pos, U0, U and the query's poses or gradients live in memspace (SMG_HOST / SMG_DEVICE); t,
+ *   Fs and cycles are host.  pin_pos NULL and U0 NULL select the defaults named below; the pinned rows of U0 are ignored.  ld_u >= nV (rows past
+ *   nV are left alone).  opts: the options of the solve (tol is absolute, as for smg_solve); NULL selects smg_solve_opts_default with max_iter =
+ *   100 and tol = 1e-10 |b|_F, |b|_F over all 3k columns (a fixed-order sum, one double read by the host per call).  A sum that is not finite
+ *   returns SMG_ERR_NONFINITE before the solve, with nothing written to U.  A solve that ends unconverged is not an error (*cycles ==
+ *   opts->max_iter tells; cycles may be NULL); a failing solve's code is returned unchanged.  SMG_ERR_INVALID, before any device work, in this
+ *   order: a null argument; k < 1; a bad memspace; a leading dimension that is too small; then what a query adds (a non-finite t).  Every call
+ *   with the same inputs returns the same bits (graphs on or off, SMG_HOST or SMG_DEVICE); nothing is kept between calls.
+ * smg_morph_reconstruct: J = k sets of nF x 9 row-major gradients (set c at c * 9 nF).  pin_pos NULL: the pins' rest positions in every set;
+ *   U0 NULL: the rest pose in every set.
+ * smg_morph_interpolate: X = one pose, nV x 3 row-major; t = k times.  pin_pos NULL: (1 - t_c) V[pin] + t_c X[pin]; U0 NULL: the linear blend
+ *   (1 - t_c) V + t_c X, the natural warm start.  The polar kernel runs once per call; the right-hand side kernel runs one lane per
+ *   (vertex, set) and recomputes J_f(t_c) at every corner: it is never stored.
+ * smg_morph_transfer: S0 = the source's rest pose (nVs x 3 row-major), S1 = its k poses (k x nVs x 3), Fs = the source's faces (nF x 3, host):
+ *   face f of the source corresponds to face f of the target.  Fs NULL = the object's F, and then nVs must equal nV.  J_f of set c = the face
+ *   gradient of pose c on the source's rest mesh (its basis is formed inside the kernel); the solve is on the target's -L with the target's W.
+ *   pin_pos and U0 as for reconstruct.  Refused too: Fs NULL with nVs != nV, a source face index out of range.  A source rest face of zero
+ *   area makes the sum non-finite.
+ * smg_morph_faces_host: the host twin of the kernels on caller arrays (no GPU, the text the kernels compile), with the operands and the layouts
+ *   of smg_debug_morph below.  sin, cos and atan2 are the host's there; everything else is the same correctly rounded arithmetic in one order.
+ * Not covered: rotations of more than half a turn (omega_f is the shortest one), a consistent choice of rotation across
+ *   neighbouring faces, blends of more than two poses, the search for a source-to-target correspondence, a new pin SET without a new object,
+ *   union / block / sharded forms, and degenerate pose faces: where N_f = 0 the result is finite and its accuracy is not stated. */
+typedef struct smg_morph smg_morph;
+enum { SMG_MORPH_FACE_GRADIENT = 0, SMG_MORPH_FACE_POLAR = 1, SMG_MORPH_RHS_GRADIENT = 2, SMG_MORPH_RHS_INTERP = 3, SMG_MORPH_PINS = 4 };
+int smg_morph_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const int *pins, int n_pins, smg_morph **out);
+void smg_morph_destroy(smg_morph *m);
+int smg_morph_set_solver(smg_morph *m, int pcg);
+long long smg_morph_device_bytes(const smg_morph *m);
+int smg_morph_reconstruct(smg_morph *m, const double *J, int k, const double *pin_pos, int ld_pp, const double *U0, int ld_u0, int memspace,
+                          const smg_solve_opts *opts, double *U, int ld_u, int *cycles);
+int smg_morph_interpolate(smg_morph *m, const double *X, const double *t, int k, const double *pin_pos, int ld_pp, const double *U0, int ld_u0,
+                          int memspace, const smg_solve_opts *opts, double *U, int ld_u, int *cycles);
+int smg_morph_transfer(smg_morph *m, const double *S0, int nVs, const int *Fs, const double *S1, int k, const double *pin_pos, int ld_pp,
+                       const double *U0, int ld_u0, int memspace, const smg_solve_opts *opts, double *U, int ld_u, int *cycles);
+int smg_morph_faces_host(int op, int nV, int nF, int k, const int *F, const double *V0, const double *X, const double *t, const double *in,
+                         const int *pins, int n_pins, double *out);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -1091,6 +1156,21 @@ int smg_debug_denoise(int op, int nV, int nF, const int *F, const double *V0, co
 int smg_debug_stylize(int op, int nV, int nF, const int *F, const int *rowptr, const int *col, const double *w, const double *V0, const double *P,
                       const double *lambda, const double *Q, const double *targets, const double *state_in, const double *R_in,
                       const smg_stylize_params *p, double *out, int *iters, int *guard_hits);
+
+/* One launcher of the morpher (csrc/smg_morph_device.hip), handle-free and guarded like the hooks above.  (V0, F): a rest mesh, nV x 3 xyz rows
+ * and nF x 3; k sets; every array is host.  The rest basis, normals and areas are computed from F and V0 by k_morph_basis first where an op reads
+ * them.
+ *   SMG_MORPH_FACE_GRADIENT  X = k poses (k x nV x 3)         -> out = J, k sets of nF x 9 (the rest basis formed inside the kernel)
+ *   SMG_MORPH_FACE_POLAR     X = one pose                     -> out = R (9 nF), omega (3 nF), S (6 nF)
+ *   SMG_MORPH_RHS_GRADIENT   in = J (k sets of nF x 9)        -> out = B (nV x 3k column-major), |b_v|^2 (k planes of nV)
+ *   SMG_MORPH_RHS_INTERP     in = omega (3 nF), S (6 nF); t[k] -> out = B, |b_v|^2 as above
+ *   SMG_MORPH_PINS           pins[n_pins]; X = one pose with t[k], or NULL = the rest pose
+ *                                                             -> out = the pins' default positions (n_pins x 3k column-major), then the default
+ *                                                                start (nV x 3k column-major) with its pinned rows set from them
+ * SMG_ERR_INVALID for an unknown op, a missing operand, k < 1, a non-finite t, a face index or a pin out of range; SMG_ERR_NO_DEVICE without
+ * a GPU. */
+int smg_debug_morph(int op, int nV, int nF, int k, const int *F, const double *V0, const double *X, const double *t, const double *in,
+                    const int *pins, int n_pins, double *out, int *guard_hits);
 
 /* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
  * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.

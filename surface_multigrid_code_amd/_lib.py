@@ -170,6 +170,15 @@ def load():
         "smg_stylize_admm_stats": (i, [vp, ip, dp, ip, ip, ip]),
         "smg_stylize_local_host": (i, [i, i, i, ip, ip, ip, dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(StylizeParamsC), dp, ip]),
         "smg_debug_stylize": (i, [i, i, i, ip, ip, ip, dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(StylizeParamsC), dp, ip, ip]),
+        "smg_morph_create": (i, [vp, dp, i, ip, i, ip, i, C.POINTER(vp)]),
+        "smg_morph_destroy": (None, [vp]),
+        "smg_morph_set_solver": (i, [vp, i]),
+        "smg_morph_device_bytes": (C.c_longlong, [vp]),
+        "smg_morph_reconstruct": (i, [vp, vp, i, vp, i, vp, i, i, C.POINTER(SolveOptsC), vp, i, ip]),
+        "smg_morph_interpolate": (i, [vp, vp, dp, i, vp, i, vp, i, i, C.POINTER(SolveOptsC), vp, i, ip]),
+        "smg_morph_transfer": (i, [vp, vp, i, ip, vp, i, vp, i, vp, i, i, C.POINTER(SolveOptsC), vp, i, ip]),
+        "smg_morph_faces_host": (i, [i, i, i, i, ip, dp, dp, dp, dp, ip, i, dp]),
+        "smg_debug_morph": (i, [i, i, i, i, ip, dp, dp, dp, dp, ip, i, dp, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

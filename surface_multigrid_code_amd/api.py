@@ -1030,6 +1030,92 @@ class Stylizer(_MeshObject):
                          ld_u or self.n)
 
 
+class Morpher(_MeshObject):
+    """Gradient-domain morphing on the scalar V-cycle (include/smg.h: smg_morph_*): Poisson reconstruction from per-face gradients, pose
+    interpolation through the faces' polar factors and deformation transfer.  k sets are 3k right-hand sides of one constant matrix, -L of the
+    rest pose with the pinned rows known, precomputed here, once: every query is one 3k-column solve.
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  V: the rest pose.
+    pins: the vertices whose positions a query is given, or takes from its default (None: vertex 0)."""
+
+    _prefix = "smg_morph_"
+    m = property(lambda self: self.o)
+
+    def __init__(self, hierarchy, V, F, pins=None):
+        self.pins = np.ascontiguousarray([0] if pins is None else pins, dtype=np.int32).reshape(-1)
+        self._create(hierarchy, V, F, _ip(self.pins), self.pins.shape[0])
+
+    def _tail(self, k, pin_pos, U0, opts):
+        """the arguments the three queries share, for host blocks: pin_pos k x n_pins x 3 and U0 k x n x 3, or None = the query's defaults"""
+        nh = self.pins.shape[0]
+        pp = None if pin_pos is None else np.asfortranarray(np.asarray(pin_pos, dtype=np.float64).reshape(k, nh, 3).transpose(1, 0, 2).reshape(nh, 3 * k))
+        u0 = None if U0 is None else np.asfortranarray(np.asarray(U0, dtype=np.float64).reshape(k, self.n, 3).transpose(1, 0, 2).reshape(self.n, 3 * k))
+        U = np.zeros((self.n, 3 * k), order="F")
+        cyc = C.c_int(0)
+        keep = (pp, u0)
+        return keep, U, cyc, (None if pp is None else pp.ctypes.data, nh, None if u0 is None else u0.ctypes.data, self.n, SMG_HOST, self._opts(opts),
+                              U.ctypes.data, self.n, C.byref(cyc))
+
+    def _sets(self, U, k):
+        return np.ascontiguousarray(U.reshape(self.n, k, 3).transpose(1, 0, 2))
+
+    def reconstruct(self, J, pin_pos=None, U0=None, opts=None):
+        """J: k x nF x 3 x 3 (or nF x 3 x 3) per-face gradients.  pin_pos: k x n_pins x 3 (None: the pins' rest positions); U0: k x n x 3 (None: the
+        rest pose).  Returns (U as k x n x 3, the loop entries of the solve)."""
+        J = np.ascontiguousarray(J, dtype=np.float64).reshape(-1, self.nF, 9)
+        k = J.shape[0]
+        keep, U, cyc, tail = self._tail(k, pin_pos, U0, opts)
+        self._call("reconstruct", J.ctypes.data, k, *tail)
+        return self._sets(U, k), cyc.value
+
+    def interpolate(self, X, ts, pin_pos=None, U0=None, opts=None):
+        """X: the n x 3 pose; ts: the k times (0: the rest pose, 1: X; any finite value).  pin_pos None: the pins blended linearly; U0 None: the
+        linear blend of the rest pose and X.  Returns (U as k x n x 3, the loop entries of the solve)."""
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(self.n, 3)
+        t = np.ascontiguousarray(np.atleast_1d(ts), dtype=np.float64).reshape(-1)
+        k = t.shape[0]
+        keep, U, cyc, tail = self._tail(k, pin_pos, U0, opts)
+        self._call("interpolate", X.ctypes.data, _dp(t), k, *tail)
+        return self._sets(U, k), cyc.value
+
+    def transfer(self, S0, S1s, Fs=None, pin_pos=None, U0=None, opts=None):
+        """S0: the source's rest pose (nVs x 3), S1s: its k poses (k x nVs x 3 or nVs x 3), Fs: its faces (nF x 3, face f corresponds to face f of
+        this mesh; None: this mesh's faces).  Returns (U as k x n x 3, the loop entries of the solve)."""
+        S0 = np.ascontiguousarray(S0, dtype=np.float64).reshape(-1, 3)
+        S1 = np.ascontiguousarray(S1s, dtype=np.float64).reshape(-1, S0.shape[0], 3)
+        Fs = None if Fs is None else np.ascontiguousarray(Fs, dtype=np.int32).reshape(self.nF, 3)
+        k = S1.shape[0]
+        keep, U, cyc, tail = self._tail(k, pin_pos, U0, opts)
+        self._call("transfer", S0.ctypes.data, S0.shape[0], None if Fs is None else _ip(Fs), S1.ctypes.data, k, *tail)
+        return self._sets(U, k), cyc.value
+
+    def _device_tail(self, U_ptr, ld_u, pp_ptr, ld_pp, U0_ptr, ld_u0, opts, cyc):
+        return (pp_ptr or None, ld_pp or self.pins.shape[0], U0_ptr or None, ld_u0 or self.n, SMG_DEVICE, self._opts(opts), U_ptr, ld_u or self.n,
+                C.byref(cyc))
+
+    def reconstruct_device(self, J_ptr, k, U_ptr, ld_u=None, pp_ptr=None, ld_pp=None, U0_ptr=None, ld_u0=None, opts=None):
+        """reconstruct() between blocks resident in HBM (device pointers; J: k sets of nF x 9; U, U0: n x 3k and pin_pos: n_pins x 3k column-major,
+        leading dimensions default to n and n_pins).  Returns the loop entries of the solve."""
+        cyc = C.c_int(0)
+        self._call("reconstruct", J_ptr, int(k), *self._device_tail(U_ptr, ld_u, pp_ptr, ld_pp, U0_ptr, ld_u0, opts, cyc))
+        return cyc.value
+
+    def interpolate_device(self, X_ptr, ts, U_ptr, ld_u=None, pp_ptr=None, ld_pp=None, U0_ptr=None, ld_u0=None, opts=None):
+        """interpolate() with the pose (n x 3 xyz rows) and the blocks resident in HBM; ts stays on the host."""
+        t = np.ascontiguousarray(np.atleast_1d(ts), dtype=np.float64).reshape(-1)
+        cyc = C.c_int(0)
+        self._call("interpolate", X_ptr, _dp(t), t.shape[0], *self._device_tail(U_ptr, ld_u, pp_ptr, ld_pp, U0_ptr, ld_u0, opts, cyc))
+        return cyc.value
+
+    def transfer_device(self, S0_ptr, nVs, S1_ptr, k, U_ptr, Fs=None, ld_u=None, pp_ptr=None, ld_pp=None, U0_ptr=None, ld_u0=None, opts=None):
+        """transfer() with the source's rest pose (nVs x 3) and poses (k x nVs x 3) and the blocks resident in HBM; Fs stays on the host."""
+        Fs = None if Fs is None else np.ascontiguousarray(Fs, dtype=np.int32).reshape(self.nF, 3)
+        cyc = C.c_int(0)
+        self._call("transfer", S0_ptr, int(nVs), None if Fs is None else _ip(Fs), S1_ptr, int(k),
+                   *self._device_tail(U_ptr, ld_u, pp_ptr, ld_pp, U0_ptr, ld_u0, opts, cyc))
+        return cyc.value
+
+
 def stylize_params(**params):
     """smg_stylize_params with the library's defaults and the given fields (lambda is spelled lambda_)"""
     p = _lib.StylizeParamsC()

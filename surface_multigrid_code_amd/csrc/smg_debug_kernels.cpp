@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -755,6 +755,64 @@ extern "C" int smg_debug_stylize(int op, int nV, int nF, const int* F, const int
         }
         int bad = 0;
         HIPCHK(X.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_morph(int op, int nV, int nF, int k, const int* F, const double* V0, const double* X, const double* t, const double* in,
+                               const int* pins, int n_pins, double* out, int* guard_hits)
+{
+    return guarded("smg_debug_morph", [&]() -> int {
+        const char* who = "smg_debug_morph";
+        if (int rc = morph_check_operands(who, op, nV, nF, k, F, V0, X, t, in, pins, n_pins, out)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, D = sizeof(double);
+        const bool rhs = op == SMG_MORPH_RHS_GRADIENT || op == SMG_MORPH_RHS_INTERP;
+        std::vector<int> mp, mi;
+        if (rhs) vertex_corner_lists(std::vector<int>(F, F + 3 * f), nV, mp, mi);
+        Scratch S;
+        HIPCHK(S.init());
+        const size_t out_count = op == SMG_MORPH_FACE_GRADIENT ? 9 * f * k : op == SMG_MORPH_FACE_POLAR ? 18 * f : rhs ? 4 * n * k : 3 * (n + (size_t)n_pins) * k;
+        const size_t x_count = op == SMG_MORPH_FACE_GRADIENT ? 3 * n * k : 3 * n;
+        const size_t in_count = op == SMG_MORPH_RHS_GRADIENT ? 9 * f * k : 9 * f;
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr, *dpins = nullptr;
+        double *dV0 = nullptr, *dX = nullptr, *dt = nullptr, *din = nullptr, *dout = nullptr, *dW = nullptr, *dn = nullptr, *dA = nullptr;
+        HIPCHK(S.add(F, nullptr, 3 * f * sizeof(int), &dF));
+        HIPCHK(S.add(V0, nullptr, 3 * n * D, &dV0));
+        if (X && !rhs) HIPCHK(S.add(X, nullptr, x_count * D, &dX));
+        if (t && (op == SMG_MORPH_RHS_INTERP || (op == SMG_MORPH_PINS && X))) HIPCHK(S.add(t, nullptr, (size_t)k * D, &dt));
+        if (rhs) {
+            HIPCHK(S.add(in, nullptr, in_count * D, &din));
+            HIPCHK(S.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+            HIPCHK(S.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+        }
+        if (rhs || op == SMG_MORPH_FACE_POLAR) {
+            HIPCHK(S.add(nullptr, nullptr, 9 * f * D, &dW));
+            HIPCHK(S.add(nullptr, nullptr, 3 * f * D, &dn));
+            HIPCHK(S.add(nullptr, nullptr, f * D, &dA));
+        }
+        if (op == SMG_MORPH_PINS) HIPCHK(S.add(pins, nullptr, (size_t)n_pins * sizeof(int), &dpins));
+        HIPCHK(S.add(out, out, out_count * D, &dout));
+        hipStream_t st = S.stream();
+        if (dW) HIPCHK(launch_morph_basis(dV0, dF, nF, dW, dn, dA, st));
+        switch (op) {
+            case SMG_MORPH_FACE_GRADIENT: HIPCHK(launch_morph_face_gradient(nF, k, dF, dV0, dX, 3 * n, dout, st)); break;
+            case SMG_MORPH_FACE_POLAR: HIPCHK(launch_morph_face_polar(nF, dF, dW, dn, dX, dout, dout + 9 * f, dout + 12 * f, st)); break;
+            case SMG_MORPH_RHS_GRADIENT: HIPCHK(launch_morph_rhs_gradient(nV, k, nF, dmp, dmi, dW, dA, din, dout, nV, dout + 3 * n * k, st)); break;
+            case SMG_MORPH_RHS_INTERP:
+                HIPCHK(launch_morph_rhs_interp(nV, k, nF, dmp, dmi, dW, dA, din, din + 3 * f, dt, dout, nV, dout + 3 * n * k, st));
+                break;
+            default: {
+                double *hp = dout, *U = dout + 3 * (size_t)n_pins * k;
+                HIPCHK(launch_morph_pins(n_pins, k, dpins, dV0, dX, dt, hp, n_pins, st));
+                HIPCHK(launch_morph_start(nV, k, dV0, dX, dt, U, nV, st));
+                HIPCHK(launch_morph_set_pins(n_pins, 3 * k, dpins, hp, n_pins, U, nV, st));
+                break;
+            }
+        }
+        int bad = 0;
+        HIPCHK(S.finish(&bad));
         if (guard_hits) *guard_hits = bad;
         return SMG_OK;
     });

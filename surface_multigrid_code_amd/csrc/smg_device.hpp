@@ -551,4 +551,24 @@ hipError_t launch_denoise_filter(int nF, const int* nb_ptr, const int* nb_idx, c
 hipError_t launch_denoise_project(int nF, const int* F, const double* rest, const double* m, const double* X, size_t sv, size_t sl, double* eterm,
                                   double* share, hipStream_t st);
 
+// gradient-domain morphing (smg_morph_device.hip; the maths in smg_morph_inl.hpp).  Poses are xyz rows; per-face arrays are face rows: W (9), nrm
+// (3), omega (3), S (6: 00, 01, 02, 11, 12, 22), J and R (9); set c of J at c * 9 nF; B, U, hp: column-major, column 3c + d = coordinate d of set
+// c; m_ptr / m_idx: the corner lists t = 3 f + i of every vertex, faces ascending ---------------------------------------------------------------
+// W as launch_geo_basis, nrm = the unit normal, Af = A
+hipError_t launch_morph_basis(const double* V, const int* F, int nF, double* W, double* nrm, double* Af, hipStream_t st);
+// J[c][f] = T + N n^T of pose c (X + c * set_stride) on the rest face f of (S0, Fs); the rest basis is formed inside
+hipError_t launch_morph_face_gradient(int nF, int k, const int* Fs, const double* S0, const double* X, size_t set_stride, double* J, hipStream_t st);
+// the polar factors J = R S of the pose's gradients on the stored basis and omega = log R; R may be nullptr
+hipError_t launch_morph_face_polar(int nF, const int* F, const double* W, const double* nrm, const double* X, double* R, double* omega, double* S,
+                                   hipStream_t st);
+// b_v = sum over v's corners (f, j), in list order, of A_f J_f W_fj; bsq[c * n + v] = |b_v|^2.  J_f is read, or recomputed from omega_f, S_f and t[c]
+hipError_t launch_morph_rhs_gradient(int n, int k, int nF, const int* m_ptr, const int* m_idx, const double* W, const double* Af, const double* J,
+                                     double* B, int ldb, double* bsq, hipStream_t st);
+hipError_t launch_morph_rhs_interp(int n, int k, int nF, const int* m_ptr, const int* m_idx, const double* W, const double* Af, const double* omega,
+                                   const double* S, const double* t, double* B, int ldb, double* bsq, hipStream_t st);
+// U = the rest pose V in every set, or with X the blend (1 - t_c) V + t_c X; hp = the same at the pins; the pinned rows of U from hp
+hipError_t launch_morph_start(int n, int k, const double* V, const double* X, const double* t, double* U, int ldu, hipStream_t st);
+hipError_t launch_morph_pins(int nh, int k, const int* pins, const double* V, const double* X, const double* t, double* hp, int ldh, hipStream_t st);
+hipError_t launch_morph_set_pins(int nh, int ncols, const int* pins, const double* hp, int ldh, double* U, int ldu, hipStream_t st);
+
 }  // namespace smg

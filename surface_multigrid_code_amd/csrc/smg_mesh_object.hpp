@@ -75,4 +75,9 @@ int stylize_check_operands(const char* who, int op, int nV, int nF, const int* F
                            const double* P, const double* lam, const double* Q, const double* targets, const double* R_in,
                            const smg_stylize_params* p, const double* out, const int* iters);
 
+// ---- smg_morph.cpp: what smg_morph_faces_host and smg_debug_morph check alike, in this order: the op and its operands, k, the times, the faces,
+// the pins
+int morph_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V0, const double* X, const double* t,
+                         const double* in, const int* pins, int n_pins, const double* out);
+
 }  // namespace smg
