@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 514
+#define SMG_VERSION 515
 
 enum {
     SMG_OK = 0,
@@ -846,6 +846,58 @@ int smg_morph_transfer(smg_morph *m, const double *S0, int nVs, const int *Fs, c
 int smg_morph_faces_host(int op, int nV, int nF, int k, const int *F, const double *V0, const double *X, const double *t, const double *in,
                          const int *pins, int n_pins, double *out);
 
+/* ---- conformalized mean-curvature flow on the scalar V-cycle (csrc/smg_flow.cpp): Kazhdan, Solomon, Ben-Chen 2012, the
+ * reference's 05_example_mean_curvature_flow, and the conformal map to the sphere it converges to on a closed genus-0 mesh.  L_0 is the cotangent
+ * matrix of the rest mesh, assembled once; step t rebuilds the barycentric mass M_t of the current positions U, solves
+ * (M_t - delta L_0) U' = M_t U (three columns, warm-started at U) and, with normalize, applies normalize_unit_area (unit area, x and y means 0,
+ * min z 0).  The matrix keeps its pattern: one full smg_precompute at create, smg_precompute_values_device on every step.
+ *   sphericity of U: a = the barycentric masses of U, c = sum a_i U_i / sum a_i, r_i = |U_i - c|, rbar = sum a_i r_i / sum a_i,
+ *   sqrt(sum a_i (r_i - rbar)^2 / sum a_i) / rbar; 0 on a sphere.  Every sum is a fixed-order reduction.
+ * smg_flow_params: delta = the time step (on the unit-area mesh), normalize = 1 normalises the rest mesh at create and the state after every
+ *   step, stop_sphericity > 0 ends smg_flow_step once the measured sphericity is at or below it.
+ * smg_flow_create: h gives the prolongations (any scalar hierarchy on this mesh); they are copied into one internal handle, h is not modified.
+ *   SMG_ERR_INVALID, before any device work, for: a union or block hierarchy, nV that is not the hierarchy's level-0 rows, a hierarchy of one
+ *   level (smg_precompute_values_device needs two), a face index out of range, a face of zero area, a non-finite coordinate, more than one
+ *   connected component; then delta not finite or <= 0, normalize outside
+ *   {0, 1}, stop_sphericity not finite or < 0.  SMG_ERR_NO_DEVICE comes after all of them.  V: nV x 3 row-major, as every create takes it.
+ * smg_flow_set_params: delta and stop_sphericity of the following steps (the next step's values are formed with the new delta: still value-only);
+ *   normalize is fixed at create and a change is refused.  smg_flow_set_solver: as smg_arap_set_solver (PCG by default).
+ * smg_flow_step: for t = 0 .. n_steps - 1: the sphericity of the current state into sphericity_his[t]; non-finite: SMG_ERR_NONFINITE; at or below
+ *   stop_sphericity (when > 0): SMG_OK; else the step.  After the last step the sphericity once more, into sphericity_his[n_steps].  opts: the
+ *   options of the solves (tol is absolute); NULL selects smg_solve_opts_default with tol = 5e-7, what the reference's caller passes.  A solve
+ *   that used all of max_iter is not an error (cycles[t] = its loop entries); a failing precompute or solve returns its code unchanged.  Every
+ *   end leaves *n_done = t with the state that of t completed steps; nothing is written past sphericity_his[*n_done].  sphericity_his
+ *   (n_steps + 1 doubles), cycles (n_steps ints) and n_done may be NULL; n_steps = 0 only measures.  Beside what the solve reads itself the host
+ *   reads one double per step.  The same calls give the same bits.
+ * smg_flow_positions / smg_flow_set_positions: the state as an nV x 3 column-major block with leading dimension ld_u >= nV in memspace, the
+ *   layout of smg_arap_solve's U.  smg_flow_reset: back to the (normalised) rest mesh.
+ * smg_flow_sphere: S_i = (U_i - c) / r_i of the current state (nV x 3 column-major, NULL ok); sigma (NULL ok; in memspace) holds 2 nF doubles in
+ *   planes, sigma1 then sigma2: the singular values of the 3 x 2 Jacobian that takes the rest face to the sphere face.  stats is a host array of 4
+ *   doubles: the rest-area-weighted mean of sigma1 / sigma2 (1 = conformal), its maximum, the number of flipped faces (n_f . centroid_f <= 0 on
+ *   the sphere), the sphericity of the state.  SMG_ERR_INVALID for a mesh with a boundary edge, a non-manifold edge or nV - nE + nF != 2
+ *   (checked on F at create).
+ * smg_flow_host: the host twin of the kernels on caller arrays (no GPU, the text the kernels compile, the sums in the device's order), with
+ *   the operands and the layouts of smg_debug_flow below.
+ * Not covered: the classical flow with L re-assembled from the current positions (its faces degenerate within a few steps and the assembly is
+ * refused), Voronoi masses, Moebius centring of the sphere map, pinned vertices, union / block / sharded forms, meshes whose rest faces are
+ * already degenerate. */
+typedef struct smg_flow smg_flow;
+typedef struct { double delta; int normalize; double stop_sphericity; } smg_flow_params;
+enum { SMG_FLOW_SYSTEM = 0, SMG_FLOW_NORMALIZE = 1, SMG_FLOW_SPHERICITY = 2, SMG_FLOW_SPHERE = 3 };
+smg_flow_params smg_flow_params_default(void);             /* 0.01, 1, 0.0 */
+int smg_flow_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const smg_flow_params *p, smg_flow **out);
+void smg_flow_destroy(smg_flow *f);
+int smg_flow_set_params(smg_flow *f, const smg_flow_params *p);
+int smg_flow_set_solver(smg_flow *f, int pcg);
+long long smg_flow_device_bytes(const smg_flow *f);
+int smg_flow_step(smg_flow *f, int n_steps, const smg_solve_opts *opts, double *sphericity_his, int *cycles, int *n_done);
+int smg_flow_positions(smg_flow *f, int memspace, double *U, int ld_u);
+int smg_flow_set_positions(smg_flow *f, const double *U, int ld_u, int memspace);
+int smg_flow_reset(smg_flow *f);
+int smg_flow_sphere(smg_flow *f, int memspace, double *S, int ld_s, double *sigma, double *stats);
+int smg_flow_host(int op, int nV, int nF, const int *F, const double *U, const double *V0, const int *rowptr, const int *col, const double *L0,
+                  double delta, double *out);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -1171,6 +1223,19 @@ int smg_debug_stylize(int op, int nV, int nF, const int *F, const int *rowptr, c
  * a GPU. */
 int smg_debug_morph(int op, int nV, int nF, int k, const int *F, const double *V0, const double *X, const double *t, const double *in,
                     const int *pins, int n_pins, double *out, int *guard_hits);
+
+/* One launcher of the flow (csrc/smg_flow_device.hip), handle-free and guarded like the hooks above.  F: nF x 3; U and V0: nV x 3 column-major
+ * blocks with leading dimension nV; every array is host.
+ *   SMG_FLOW_SYSTEM      U; (rowptr, col, L0): a CSR with one stored diagonal entry per row; delta
+ *                        -> out = the barycentric masses of U (nV), mass U (nV x 3 column-major), (-delta) L0 with the mass added on the diagonal
+ *   SMG_FLOW_NORMALIZE   U -> out = normalize_unit_area of U (nV x 3 column-major)
+ *   SMG_FLOW_SPHERICITY  U -> out = 7 doubles: the sphericity, sum a, sum a U (3), sum a r, sum a (r - rbar)^2
+ *   SMG_FLOW_SPHERE      U, V0 = the rest mesh -> out = S (nV x 3 column-major), sigma (2 planes of nF), the terms (4 planes of nF:
+ *                        A sigma1 / sigma2, A, sigma1 / sigma2, flipped), the 4 stats of smg_flow_sphere
+ * SMG_ERR_INVALID for an unknown op, a missing operand, a face index out of range, and for the system a delta that is not finite or <= 0 or a
+ * malformed CSR; SMG_ERR_NO_DEVICE without a GPU. */
+int smg_debug_flow(int op, int nV, int nF, const int *F, const double *U, const double *V0, const int *rowptr, const int *col, const double *L0,
+                   double delta, double *out, int *guard_hits);
 
 /* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
  * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.

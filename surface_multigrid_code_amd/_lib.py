@@ -34,6 +34,10 @@ class StylizeParamsC(C.Structure):
                 ("tau", C.c_double), ("admm_iters", C.c_int)]
 
 
+class FlowParamsC(C.Structure):
+    _fields_ = [("delta", C.c_double), ("normalize", C.c_int), ("stop_sphericity", C.c_double)]
+
+
 _lib = None
 
 
@@ -179,6 +183,19 @@ def load():
         "smg_morph_transfer": (i, [vp, vp, i, ip, vp, i, vp, i, vp, i, i, C.POINTER(SolveOptsC), vp, i, ip]),
         "smg_morph_faces_host": (i, [i, i, i, i, ip, dp, dp, dp, dp, ip, i, dp]),
         "smg_debug_morph": (i, [i, i, i, i, ip, dp, dp, dp, dp, ip, i, dp, ip]),
+        "smg_flow_params_default": (FlowParamsC, []),
+        "smg_flow_create": (i, [vp, dp, i, ip, i, C.POINTER(FlowParamsC), C.POINTER(vp)]),
+        "smg_flow_destroy": (None, [vp]),
+        "smg_flow_set_params": (i, [vp, C.POINTER(FlowParamsC)]),
+        "smg_flow_set_solver": (i, [vp, i]),
+        "smg_flow_device_bytes": (C.c_longlong, [vp]),
+        "smg_flow_step": (i, [vp, i, C.POINTER(SolveOptsC), dp, ip, ip]),
+        "smg_flow_positions": (i, [vp, i, vp, i]),
+        "smg_flow_set_positions": (i, [vp, vp, i, i]),
+        "smg_flow_reset": (i, [vp]),
+        "smg_flow_sphere": (i, [vp, i, vp, i, vp, dp]),
+        "smg_flow_host": (i, [i, i, i, ip, dp, dp, ip, ip, dp, d, dp]),
+        "smg_debug_flow": (i, [i, i, i, ip, dp, dp, ip, ip, dp, d, dp, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

@@ -1116,6 +1116,85 @@ class Morpher(_MeshObject):
         return cyc.value
 
 
+class MeanCurvatureFlow(_MeshObject):
+    """Conformalized mean-curvature flow on the scalar V-cycle (include/smg.h: smg_flow_*; Kazhdan, Solomon, Ben-Chen 2012; the reference's
+    05_example_mean_curvature_flow) and, on a closed genus-0 mesh, the conformal map to the sphere it converges to.  L of the rest mesh is
+    assembled once; a step rebuilds the barycentric mass of the current positions, re-precomputes M - delta L by values and runs one warm-started
+    3-column solve.
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  delta: the time step on
+    the unit-area mesh.  normalize: normalize_unit_area on the rest mesh and after every step.  stop_sphericity > 0 ends step() early."""
+
+    STATS = ("mean_ratio", "max_ratio", "flipped", "sphericity")
+    _prefix = "smg_flow_"
+    f = property(lambda self: self.o)
+
+    def __init__(self, hierarchy, V, F, delta=0.01, normalize=True, stop_sphericity=0.0):
+        self.params = flow_params(delta=delta, normalize=int(normalize), stop_sphericity=stop_sphericity)
+        self._create(hierarchy, V, F, C.byref(self.params))
+
+    def set_params(self, **params):
+        """delta, stop_sphericity: the following steps use them (normalize is fixed at create)"""
+        p = _lib.FlowParamsC(self.params.delta, self.params.normalize, self.params.stop_sphericity)
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise TypeError("unknown flow parameter %r" % k)
+            setattr(p, k, int(v) if k == "normalize" else v)
+        self._call("set_params", C.byref(p))
+        self.params = p
+
+    def step(self, n=1, opts=None):
+        """n steps.  Returns (sphericity_his, cycles) trimmed to the steps done: the sphericity before every step and after the last one, and the
+        loop entries of each solve."""
+        his = np.zeros(n + 1)
+        cyc = np.zeros(max(n, 1), dtype=np.int32)
+        done = C.c_int(0)
+        self._call("step", int(n), self._opts(opts), _dp(his), _ip(cyc), C.byref(done))
+        return his[:done.value + 1].copy(), cyc[:done.value].copy()
+
+    def positions(self):
+        """the state, n x 3"""
+        U = np.zeros((self.n, 3), order="F")
+        self._call("positions", SMG_HOST, U.ctypes.data, self.n)
+        return np.ascontiguousarray(U)
+
+    def positions_device(self, U_ptr, ld_u=None):
+        """the state into an n x 3 column-major block resident in HBM (device pointer)"""
+        self._call("positions", SMG_DEVICE, U_ptr, ld_u or self.n)
+
+    def set_positions(self, U):
+        U = np.asfortranarray(np.asarray(U, dtype=np.float64).reshape(self.n, 3))
+        self._call("set_positions", U.ctypes.data, self.n, SMG_HOST)
+
+    def set_positions_device(self, U_ptr, ld_u=None):
+        self._call("set_positions", U_ptr, ld_u or self.n, SMG_DEVICE)
+
+    def reset(self):
+        """back to the (normalised) rest mesh"""
+        self._call("reset")
+
+    def sphere(self):
+        """(S, sigma, stats) of the current state: S n x 3 on the unit sphere, sigma nF x 2 (the singular values of the Jacobian rest face ->
+        sphere face, larger first) and the dict of STATS.  Needs a closed genus-0 mesh."""
+        S = np.zeros((self.n, 3), order="F")
+        sigma = np.zeros((self.nF, 2), order="F")
+        st = np.zeros(4)
+        self._call("sphere", SMG_HOST, S.ctypes.data, self.n, sigma.ctypes.data, _dp(st))
+        stats = dict(zip(self.STATS, st.tolist()))
+        stats["flipped"] = int(stats["flipped"])
+        return np.ascontiguousarray(S), sigma, stats
+
+
+def flow_params(**params):
+    """smg_flow_params with the library's defaults and the given fields"""
+    p = _lib.load().smg_flow_params_default()
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError("unknown flow parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 def stylize_params(**params):
     """smg_stylize_params with the library's defaults and the given fields (lambda is spelled lambda_)"""
     p = _lib.StylizeParamsC()

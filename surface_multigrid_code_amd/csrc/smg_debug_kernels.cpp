@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -813,6 +813,69 @@ extern "C" int smg_debug_morph(int op, int nV, int nF, int k, const int* F, cons
         }
         int bad = 0;
         HIPCHK(S.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_flow(int op, int nV, int nF, const int* F, const double* U, const double* V0, const int* rowptr, const int* col,
+                              const double* L0, double delta, double* out, int* guard_hits)
+{
+    return guarded("smg_debug_flow", [&]() -> int {
+        const char* who = "smg_debug_flow";
+        if (int rc = flow_check_operands(who, op, nV, nF, F, U, V0, rowptr, col, L0, delta, out)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, D = sizeof(double);
+        std::vector<int> mp, mi, diag;
+        if (op == SMG_FLOW_SYSTEM || op == SMG_FLOW_SPHERICITY || op == SMG_FLOW_SPHERE) vertex_corner_lists(std::vector<int>(F, F + 3 * f), nV, mp, mi);
+        const size_t nnz = op == SMG_FLOW_SYSTEM ? (size_t)rowptr[nV] : 0;
+        if (op == SMG_FLOW_SYSTEM) flow_diagonal(nV, rowptr, col, diag);
+        Scratch S;
+        HIPCHK(S.init());
+        const size_t out_count = op == SMG_FLOW_SYSTEM ? 4 * n + nnz : op == SMG_FLOW_NORMALIZE ? 3 * n : op == SMG_FLOW_SPHERICITY ? 7 : 3 * n + 6 * f + 4;
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr, *drp = nullptr, *ddiag = nullptr;
+        double *dU = nullptr, *dV0 = nullptr, *dL0 = nullptr, *dout = nullptr, *da = nullptr, *dr = nullptr, *dterm = nullptr, *dpart = nullptr, *ds = nullptr;
+        double hs[FLOW_SUMS];
+        for (double& v : hs) v = 0.0;
+        HIPCHK(S.add(F, nullptr, 3 * f * sizeof(int), &dF));
+        HIPCHK(S.add(U, nullptr, 3 * n * D, &dU));
+        if (!mp.empty()) {
+            HIPCHK(S.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+            HIPCHK(S.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+        }
+        if (op == SMG_FLOW_SYSTEM) {
+            HIPCHK(S.add(rowptr, nullptr, (n + 1) * sizeof(int), &drp));
+            HIPCHK(S.add(diag.data(), nullptr, n * sizeof(int), &ddiag));
+            HIPCHK(S.add(L0, nullptr, nnz * D, &dL0));
+        } else {
+            HIPCHK(S.add(nullptr, nullptr, n * D, &da));
+            HIPCHK(S.add(nullptr, nullptr, n * D, &dr));
+            HIPCHK(S.add(nullptr, nullptr, std::max(3 * n, f) * D, &dterm));
+            HIPCHK(S.add(nullptr, nullptr, (size_t)fixed_sum_groups(std::max(nV, nF)) * D, &dpart));
+            HIPCHK(S.add(hs, hs, sizeof hs, &ds));
+        }
+        if (op == SMG_FLOW_SPHERE) HIPCHK(S.add(V0, nullptr, 3 * n * D, &dV0));
+        HIPCHK(S.add(out, out, out_count * D, &dout));
+        hipStream_t st = S.stream();
+        switch (op) {
+            case SMG_FLOW_SYSTEM:
+                HIPCHK(launch_flow_system(nV, dU, nV, dF, dmp, dmi, drp, ddiag, dL0, delta, nullptr, dout, dout + n, nV, dout + 4 * n, st));
+                break;
+            case SMG_FLOW_NORMALIZE: HIPCHK(launch_flow_normalize(nV, nF, dF, dU, nV, dterm, dpart, ds, dout, nV, st)); break;
+            case SMG_FLOW_SPHERICITY: HIPCHK(launch_flow_sphericity(nV, dU, nV, dF, dmp, dmi, da, dr, dterm, dpart, ds, st)); break;
+            default:
+                HIPCHK(launch_flow_sphericity(nV, dU, nV, dF, dmp, dmi, da, dr, dterm, dpart, ds, st));
+                HIPCHK(launch_flow_sphere(nV, nF, dF, dU, nV, dV0, nV, ds, dout, nV, dout + 3 * n, dout + 3 * n + 2 * f, dpart, ds + 12, st));
+                break;
+        }
+        int bad = 0;
+        HIPCHK(S.finish(&bad));
+        if (op == SMG_FLOW_SPHERICITY)
+            for (int e = 0; e < 7; e++) out[e] = hs[e];
+        if (op == SMG_FLOW_SPHERE) {
+            double* stats = out + 3 * n + 6 * f;
+            stats[0] = hs[12] / hs[13]; stats[1] = hs[14]; stats[2] = hs[15]; stats[3] = hs[0];
+        }
         if (guard_hits) *guard_hits = bad;
         return SMG_OK;
     });

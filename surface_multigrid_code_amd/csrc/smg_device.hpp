@@ -571,4 +571,23 @@ hipError_t launch_morph_start(int n, int k, const double* V, const double* X, co
 hipError_t launch_morph_pins(int nh, int k, const int* pins, const double* V, const double* X, const double* t, double* hp, int ldh, hipStream_t st);
 hipError_t launch_morph_set_pins(int nh, int ncols, const int* pins, const double* hp, int ldh, double* U, int ldu, hipStream_t st);
 
+// conformalized mean-curvature flow (smg_flow_device.hip; the maths in smg_flow_inl.hpp).  Positions are column-major nV x 3 blocks; m_ptr / m_idx:
+// the corner lists t = 3 f + i of every vertex, faces ascending; part: fixed_sum_groups(max(nF, nV)) doubles; s: the block of FLOW_SUMS sums
+// ([0] sphericity, [1] sum a, [2..4] sum a U, [5] sum a r, [6] sum a (r - rbar)^2, [8..11] the normalisation's, [12..15] the sphere map's) ---------
+constexpr int FLOW_SUMS = 16;
+// mass = the barycentric masses of U, B = mass U, val[j] = (-delta) L0[j] with the mass added at diag[row]: the values of M_t - delta L_0.
+// mass_in (nullptr ok): the masses of this U where launch_flow_sphericity has just formed them (its `a`); they are then read, not gathered again
+hipError_t launch_flow_system(int n, const double* U, int ldu, const int* F, const int* m_ptr, const int* m_idx, const int* rowptr, const int* diag,
+                              const double* L0, double delta, const double* mass_in, double* mass, double* B, int ldb, double* val, hipStream_t st);
+// out = U / sqrt(sum of double areas / 2), then x, y minus their means and z minus its minimum (normalize_unit_area); term: max(nF, n) doubles
+hipError_t launch_flow_normalize(int n, int nF, const int* F, const double* U, int ldu, double* term, double* part, double* s, double* out, int ldo,
+                                 hipStream_t st);
+// s[0..6] of U; a, r: n doubles each, term: 3 n
+hipError_t launch_flow_sphericity(int n, const double* U, int ldu, const int* F, const int* m_ptr, const int* m_idx, double* a, double* r, double* term,
+                                  double* part, double* s, hipStream_t st);
+// S = (U - c) / r with c from s_in[1..4]; sigma (2 planes of nF) rest face -> sphere face; terms (4 planes of nF) and their reductions
+// s_out[0..3] = sum A sigma1 / sigma2, sum A, max sigma1 / sigma2, the flipped count
+hipError_t launch_flow_sphere(int n, int nF, const int* F, const double* U, int ldu, const double* V0, int ld0, const double* s_in, double* S, int lds,
+                              double* sigma, double* terms, double* part, double* s_out, hipStream_t st);
+
 }  // namespace smg

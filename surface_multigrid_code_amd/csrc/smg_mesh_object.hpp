@@ -80,4 +80,10 @@ int stylize_check_operands(const char* who, int op, int nV, int nF, const int* F
 int morph_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V0, const double* X, const double* t,
                          const double* in, const int* pins, int n_pins, const double* out);
 
+// ---- smg_flow.cpp: what smg_flow_host and smg_debug_flow check alike, in this order: the op and its operands, the faces, then for the system
+// delta and the CSR (monotone row pointers, columns in range, one stored diagonal entry per row); the position of every row's diagonal entry
+int flow_check_operands(const char* who, int op, int nV, int nF, const int* F, const double* U, const double* V0, const int* rowptr, const int* col,
+                        const double* L0, double delta, const double* out);
+void flow_diagonal(int nV, const int* rowptr, const int* col, std::vector<int>& diag);
+
 }  // namespace smg
