@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 515
+#define SMG_VERSION 516
 
 enum {
     SMG_OK = 0,
@@ -898,6 +898,51 @@ int smg_flow_sphere(smg_flow *f, int memspace, double *S, int ld_s, double *sigm
 int smg_flow_host(int op, int nV, int nF, const int *F, const double *U, const double *V0, const int *rowptr, const int *col, const double *L0,
                   double delta, double *out);
 
+/* ---- Helmholtz-Hodge decomposition of per-face tangent vector fields (csrc/smg_hodge.cpp): Tong, Lombeyda, Hirani,
+ * Desbrun 2003, with vertex potentials.  Per face f with vertices p0, p1, p2, unit normal n_f, area A_f, e_fi the edge opposite corner i and
+ * W_fi = (n_f x e_fi) / (2 A_f) the gradient of vertex i's hat function (the basis of smg_geodesics, bit for bit), a field X_f (any 3-vector; only
+ * its tangent part Xt_f = X_f - (X_f . n_f) n_f matters) is split as
+ *     Xt = G + R + H,   G_f = sum_i u_i W_fi (grad u),   R_f = n_f x sum_i v_i W_fi (J grad v),   H = Xt - G - R
+ * where u minimises sum_f A_f |Xt_f - grad u_f|^2, that is (-L) u = b with b_i = (1/2) sum (n_f x e_fi) . X_f, and v minimises
+ * sum_f A_f |Xt_f - J grad v_f|^2, that is (-L) v = c with c_i = -(1/2) sum e_fi . X_f; both sums run over the corners (f, i) of the vertex, faces
+ * ascending.  u: vertex 0 is known and 0.  v: on a closed mesh the same pin; on a mesh with boundary every boundary vertex is known and 0 and
+ * nothing else.  With these constraints G, R and H are mutually orthogonal in the area inner product: |Xt|^2 = |G|^2 + |R|^2 + |H|^2.
+ * smg_hodge_create: h gives the prolongations (any scalar hierarchy on this mesh, one level included); they are copied, h is not modified.
+ *   A closed mesh gets ONE internal handle (-L, vertex 0 known), a mesh with boundary two (vertex 0 known; the boundary vertices known).
+ *   SMG_ERR_INVALID, before any device work, for: a union or block hierarchy, nV that is not the hierarchy's level-0 rows, a face index out of
+ *   range, a face of zero area, a non-finite coordinate, more than one connected component; then, for a mesh with boundary, no interior vertex.
+ *   SMG_ERR_NO_DEVICE comes after all of them.  V: nV x 3 row-major, as every create takes it.
+ * smg_hodge_set_solver: as smg_arap_set_solver (PCG by default).  smg_hodge_is_closed: 1 when no edge belongs to one face alone.
+ * smg_hodge_decompose: X is k fields of nF x 3 row-major, field c at c * 3 nF (how smg_morph_reconstruct takes J); u and v are nV x k
+ *   column-major with ld >= nV, rows past nV are left alone; parts (NULL ok) is k sets of nF x 9 row-major: G, R, H of the face; X, u, v and parts
+ *   live in memspace.  energy (NULL ok, host) holds 4k doubles: sum A_f |Xt|^2, sum A_f |G|^2, sum A_f |R|^2, sum A_f |H|^2 per field, each a
+ *   fixed-order sum.  cycles (NULL ok, host) holds 2 ints: the loop entries of the u solve and of the v solve.  On a closed mesh a call is ONE
+ *   solve of 2k columns (b in columns 0 .. k - 1, c in k .. 2k - 1) and both entries carry its count; with boundary it is two k-column solves.
+ *   The start is zero.  opts: the options of the solves (tol is absolute); NULL selects smg_solve_opts_default with max_iter = 100 and
+ *   tol = 1e-10 |rhs|_F over the solve's columns (all rows, a fixed-order sum that the host reads once).  A non-finite norm returns
+ *   SMG_ERR_NONFINITE before any solve, with nothing written to u, v, parts or energy.  A solve that used all of max_iter is not an error; a
+ *   failing solve returns its code unchanged.  SMG_ERR_INVALID, before any device work, for: a null g, X, u or v; k < 1 (or k fields past the
+ *   index range); a memspace that is neither SMG_HOST nor SMG_DEVICE; a leading dimension below nV.
+ * smg_hodge_field: the inverse direction, X_f = grad u_f + J grad v_f for k pairs of potentials: one launch, no solve.  Refusals as above.
+ * Nothing is allocated after create except the query blocks, which grow with the largest k seen and are kept (smg_hodge_device_bytes counts
+ * them).  The same calls give the same bits, with graphs on or off and for SMG_HOST or SMG_DEVICE blocks.
+ * smg_hodge_host: the host twin of the kernels on caller arrays (no GPU, the text the kernels compile, the sums in the device's order), with
+ *   the operands and the layouts of smg_debug_hodge below.
+ * Not covered: more than one boundary loop (v = 0 on all loops; the exact decomposition has one free constant per extra loop and the difference
+ * lands in H), the non-conforming part of H (2 nF - 2 nV + 2 dimensions on a closed mesh, not only the 2g harmonic fields), per-vertex input
+ * fields, union / block / sharded forms, moving meshes, an area-weighted zero mean for u. */
+typedef struct smg_hodge smg_hodge;
+enum { SMG_HODGE_RHS = 0, SMG_HODGE_PARTS = 1, SMG_HODGE_FIELD = 2 };
+int smg_hodge_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, smg_hodge **out);
+void smg_hodge_destroy(smg_hodge *g);
+int smg_hodge_set_solver(smg_hodge *g, int pcg);
+int smg_hodge_is_closed(const smg_hodge *g);
+long long smg_hodge_device_bytes(const smg_hodge *g);
+int smg_hodge_decompose(smg_hodge *g, const double *X, int k, int memspace, const smg_solve_opts *opts, double *u, int ld_u, double *v, int ld_v,
+                        double *parts, double *energy, int *cycles);
+int smg_hodge_field(smg_hodge *g, const double *u, int ld_u, const double *v, int ld_v, int k, int memspace, double *X);
+int smg_hodge_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *X, const double *u, const double *v, double *out);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -1236,6 +1281,17 @@ int smg_debug_morph(int op, int nV, int nF, int k, const int *F, const double *V
  * malformed CSR; SMG_ERR_NO_DEVICE without a GPU. */
 int smg_debug_flow(int op, int nV, int nF, const int *F, const double *U, const double *V0, const int *rowptr, const int *col, const double *L0,
                    double delta, double *out, int *guard_hits);
+
+/* One launcher of the Hodge decomposition (csrc/smg_hodge_device.hip), handle-free and guarded like the hooks above.  F: nF x 3; V: nV x 3
+ * row-major; X: k fields of nF x 3 row-major; u, v: nV x k column-major with leading dimension nV; every array is host.  k_hodge_geometry runs
+ * first on buffers of its own.
+ *   SMG_HODGE_RHS    V, X -> out = b (nV x k column-major), c (nV x k column-major), their squares (2 planes of k nV: b^2 then c^2)
+ *   SMG_HODGE_PARTS  V, X, u, v -> out = the parts (k sets of nF x 9: G, R, H), the terms (4 k planes of nF: plane 4 c + e = A_f |.|^2 of Xt, G, R,
+ *                    H of field c), the 4 k energies
+ *   SMG_HODGE_FIELD  V, u, v -> out = X (k fields of nF x 3)
+ * SMG_ERR_INVALID for an unknown op, a missing operand, k < 1, a face index out of range; SMG_ERR_NO_DEVICE without a GPU. */
+int smg_debug_hodge(int op, int nV, int nF, int k, const int *F, const double *V, const double *X, const double *u, const double *v, double *out,
+                    int *guard_hits);
 
 /* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
  * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.

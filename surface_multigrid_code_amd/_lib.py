@@ -196,6 +196,15 @@ def load():
         "smg_flow_sphere": (i, [vp, i, vp, i, vp, dp]),
         "smg_flow_host": (i, [i, i, i, ip, dp, dp, ip, ip, dp, d, dp]),
         "smg_debug_flow": (i, [i, i, i, ip, dp, dp, ip, ip, dp, d, dp, ip]),
+        "smg_hodge_create": (i, [vp, dp, i, ip, i, C.POINTER(vp)]),
+        "smg_hodge_destroy": (None, [vp]),
+        "smg_hodge_set_solver": (i, [vp, i]),
+        "smg_hodge_is_closed": (i, [vp]),
+        "smg_hodge_device_bytes": (C.c_longlong, [vp]),
+        "smg_hodge_decompose": (i, [vp, vp, i, i, C.POINTER(SolveOptsC), vp, i, vp, i, vp, dp, ip]),
+        "smg_hodge_field": (i, [vp, vp, i, vp, i, i, i, vp]),
+        "smg_hodge_host": (i, [i, i, i, i, ip, dp, dp, dp, dp, dp]),
+        "smg_debug_hodge": (i, [i, i, i, i, ip, dp, dp, dp, dp, dp, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

@@ -1185,6 +1185,49 @@ class MeanCurvatureFlow(_MeshObject):
         return np.ascontiguousarray(S), sigma, stats
 
 
+class HodgeDecomposition(_MeshObject):
+    """Helmholtz-Hodge decomposition of per-face tangent vector fields with vertex potentials (include/smg.h: smg_hodge_*; Tong, Lombeyda,
+    Hirani, Desbrun 2003): Xt = grad u + J grad v + H.  k fields are 2k right-hand sides of -L: ONE 2k-column solve on a closed mesh, two
+    k-column solves on a mesh with boundary.
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified."""
+
+    ENERGY = ("field", "gradient", "rotation", "remainder")
+    _prefix = "smg_hodge_"
+    g = property(lambda self: self.o)
+
+    def __init__(self, hierarchy, V, F):
+        self._create(hierarchy, V, F)
+
+    @property
+    def is_closed(self):
+        """whether the mesh has no boundary edge"""
+        return bool(self._fn("is_closed")(self.o))
+
+    def decompose(self, X, parts=False, opts=None):
+        """X: nF x 3 or k x nF x 3.  Returns (u, v, energy, cycles), or with parts (u, v, parts, energy, cycles): u, v n x k; parts k x nF x 3 x 3
+        (G, R, H of every face); energy k x 4 (sum A |Xt|^2, |G|^2, |R|^2, |H|^2); cycles: the loop entries of the u solve and of the v solve."""
+        X = np.ascontiguousarray(np.asarray(X, dtype=np.float64).reshape(-1, self.nF, 3))
+        k = X.shape[0]
+        u, v = np.zeros((self.n, k), order="F"), np.zeros((self.n, k), order="F")
+        P = np.zeros((k, self.nF, 3, 3)) if parts else None
+        E = np.zeros((k, 4))
+        cyc = np.zeros(2, dtype=np.int32)
+        self._call("decompose", X.ctypes.data, k, SMG_HOST, self._opts(opts), u.ctypes.data, self.n, v.ctypes.data, self.n,
+                   P.ctypes.data if parts else None, _dp(E), _ip(cyc))
+        return (u, v, P, E, cyc) if parts else (u, v, E, cyc)
+
+    def field(self, u, v):
+        """X = grad u + J grad v: k x nF x 3 for n x k potentials (nF x 3 for vectors)"""
+        u, v = np.asarray(u, dtype=np.float64), np.asarray(v, dtype=np.float64)
+        single = u.ndim == 1
+        u, v = np.asfortranarray(u.reshape(self.n, -1)), np.asfortranarray(v.reshape(self.n, -1))
+        k = u.shape[1]
+        X = np.zeros((k, self.nF, 3))
+        self._call("field", u.ctypes.data, self.n, v.ctypes.data, self.n, k, SMG_HOST, X.ctypes.data)
+        return X[0] if single else X
+
+
 def flow_params(**params):
     """smg_flow_params with the library's defaults and the given fields"""
     p = _lib.load().smg_flow_params_default()

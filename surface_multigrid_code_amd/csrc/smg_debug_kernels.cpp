@@ -1,8 +1,9 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow), of the Hodge kernels (smg_debug_hodge) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
+#include <climits>
 
 #include <algorithm>
 #include <cstring>
@@ -876,6 +877,56 @@ extern "C" int smg_debug_flow(int op, int nV, int nF, const int* F, const double
             double* stats = out + 3 * n + 6 * f;
             stats[0] = hs[12] / hs[13]; stats[1] = hs[14]; stats[2] = hs[15]; stats[3] = hs[0];
         }
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_hodge(int op, int nV, int nF, int k, const int* F, const double* V, const double* X, const double* u, const double* v,
+                               double* out, int* guard_hits)
+{
+    return guarded("smg_debug_hodge", [&]() -> int {
+        const char* who = "smg_debug_hodge";
+        if (int rc = hodge_check_operands(who, op, nV, nF, k, F, V, X, u, v, out)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, nk = n * (size_t)k, D = sizeof(double);
+        if (2 * nk > (size_t)INT_MAX || 4 * f * (size_t)k > (size_t)INT_MAX) return fail(SMG_ERR_INVALID, "%s: k = %d exceeds the index range", who, k);
+        std::vector<int> mp, mi;
+        if (op == SMG_HODGE_RHS) vertex_corner_lists(std::vector<int>(F, F + 3 * f), nV, mp, mi);
+        Scratch S;
+        HIPCHK(S.init());
+        const size_t out_count = op == SMG_HODGE_RHS ? 4 * nk : op == SMG_HODGE_PARTS ? 13 * f * k + 4 * (size_t)k : 3 * f * k;
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr;
+        double *dV = nullptr, *dX = nullptr, *du = nullptr, *dv = nullptr, *dout = nullptr, *dW = nullptr, *dn = nullptr, *dA = nullptr, *dpart = nullptr;
+        HIPCHK(S.add(F, nullptr, 3 * f * sizeof(int), &dF));
+        HIPCHK(S.add(V, nullptr, 3 * n * D, &dV));
+        if (op != SMG_HODGE_FIELD) HIPCHK(S.add(X, nullptr, 3 * f * k * D, &dX));
+        if (op == SMG_HODGE_RHS) {
+            HIPCHK(S.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+            HIPCHK(S.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+        } else {
+            HIPCHK(S.add(u, nullptr, nk * D, &du));
+            HIPCHK(S.add(v, nullptr, nk * D, &dv));
+        }
+        HIPCHK(S.add(nullptr, nullptr, 9 * f * D, &dW));
+        HIPCHK(S.add(nullptr, nullptr, 3 * f * D, &dn));
+        HIPCHK(S.add(nullptr, nullptr, f * D, &dA));
+        if (op == SMG_HODGE_PARTS) HIPCHK(S.add(nullptr, nullptr, (size_t)fixed_sum_groups(nF) * D, &dpart));
+        HIPCHK(S.add(out, out, out_count * D, &dout));
+        hipStream_t st = S.stream();
+        HIPCHK(launch_hodge_geometry(dV, dF, nF, dW, dn, dA, st));
+        switch (op) {
+            case SMG_HODGE_RHS: HIPCHK(launch_hodge_rhs(nV, k, nF, dmp, dmi, dF, dV, dn, dX, dout, dout + nk, nV, dout + 2 * nk, st)); break;
+            case SMG_HODGE_PARTS: {
+                double *terms = dout + 9 * f * k, *energy = dout + 13 * f * k;
+                HIPCHK(launch_hodge_parts(nF, k, dF, dW, dn, dA, dX, du, nV, dv, nV, dout, terms, st));
+                for (int e = 0; e < 4 * k; e++) HIPCHK(launch_fixed_sum(terms + (size_t)e * f, nF, dpart, energy + e, st));
+                break;
+            }
+            default: HIPCHK(launch_hodge_field(nF, k, dF, dW, dn, du, nV, dv, nV, dout, st)); break;
+        }
+        int bad = 0;
+        HIPCHK(S.finish(&bad));
         if (guard_hits) *guard_hits = bad;
         return SMG_OK;
     });

@@ -590,4 +590,17 @@ hipError_t launch_flow_sphericity(int n, const double* U, int ldu, const int* F,
 hipError_t launch_flow_sphere(int n, int nF, const int* F, const double* U, int ldu, const double* V0, int ld0, const double* s_in, double* S, int lds,
                               double* sigma, double* terms, double* part, double* s_out, hipStream_t st);
 
+// Helmholtz-Hodge decomposition (smg_hodge_device.hip; the maths in smg_hodge_inl.hpp).  V: xyz rows; W, nrm, Af: 9, 3, 1 doubles per face; a field
+// is nF x 3 row-major, set c at c * 3 nF; m_ptr / m_idx: the corner lists t = 3 f + i of every vertex, faces ascending ---------------------------
+hipError_t launch_hodge_geometry(const double* V, const int* F, int nF, double* W, double* nrm, double* Af, hipStream_t st);
+// Bb[c * ldb + v] = (1/2) sum (n_f x e_fi) . X_f, Bc[c * ldb + v] = -(1/2) sum e_fi . X_f over v's corners; bsq: 2 planes of k n, their squares
+hipError_t launch_hodge_rhs(int n, int k, int nF, const int* m_ptr, const int* m_idx, const int* F, const double* V, const double* nrm, const double* X,
+                            double* Bb, double* Bc, int ldb, double* bsq, hipStream_t st);
+// parts (nullptr ok): G, R, H per face, set c at c * 9 nF; terms: plane 4 c + e of nF doubles = A_f |.|^2 of Xt, G, R, H
+hipError_t launch_hodge_parts(int nF, int k, const int* F, const double* W, const double* nrm, const double* Af, const double* X, const double* u, int ldu,
+                              const double* v, int ldv, double* parts, double* terms, hipStream_t st);
+// X = grad u + n x grad v
+hipError_t launch_hodge_field(int nF, int k, const int* F, const double* W, const double* nrm, const double* u, int ldu, const double* v, int ldv,
+                              double* X, hipStream_t st);
+
 }  // namespace smg

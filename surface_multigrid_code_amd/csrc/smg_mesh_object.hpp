@@ -27,7 +27,7 @@ int check_mesh(const char* who, const double* V, int nV, const int* F, int nF, b
 struct MeshObject {
     hipStream_t stream = nullptr;
     int device = -1;
-    smg_hierarchy* handle[2] = {nullptr, nullptr};
+    smg_hierarchy* handle[2] = {nullptr, nullptr};                    // smg_geodesics and smg_hodge (a mesh with boundary) hold two
     MeshObject() = default;
     MeshObject(const MeshObject&) = delete;
     MeshObject& operator=(const MeshObject&) = delete;
@@ -85,5 +85,9 @@ int morph_check_operands(const char* who, int op, int nV, int nF, int k, const i
 int flow_check_operands(const char* who, int op, int nV, int nF, const int* F, const double* U, const double* V0, const int* rowptr, const int* col,
                         const double* L0, double delta, const double* out);
 void flow_diagonal(int nV, const int* rowptr, const int* col, std::vector<int>& diag);
+
+// ---- smg_hodge.cpp: what smg_hodge_host and smg_debug_hodge check alike, in this order: the op and its operands, k, the faces
+int hodge_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* X, const double* u, const double* v,
+                         const double* out);
 
 }  // namespace smg
