@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 516
+#define SMG_VERSION 517
 
 enum {
     SMG_OK = 0,
@@ -943,6 +943,70 @@ int smg_hodge_decompose(smg_hodge *g, const double *X, int k, int memspace, cons
 int smg_hodge_field(smg_hodge *g, const double *u, int ld_u, const double *v, int ld_v, int k, int memspace, double *X);
 int smg_hodge_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *X, const double *u, const double *v, double *out);
 
+/* ---- discrete conformal metrics with prescribed angle sums (csrc/smg_conformal.cpp): Springborn, Schroeder, Pinkall 2008,
+ * "Conformal equivalence of triangle meshes".  One log scale factor u_i per vertex; the metric l~_ij = l_ij exp((u_i + u_j) / 2) is to have the
+ * angle sum Theta_i at every free vertex.  The energy is convex, its gradient is g_i = (angle sum at i) - Theta_i and its Hessian half the
+ * cotangent matrix of the current metric, so a Newton step is (-L~)_uu d = g_u, u += t d with -L~ assembled from the half cotangents of l~.
+ * Every value of the matrix changes at every step and its pattern never: one full smg_precompute at create (-L of the rest mesh with the fixed
+ * vertices known), then per Newton step one face kernel, one row kernel, smg_precompute_values_device and a 1-column solve from zero.
+ *   The arithmetic: l0 = the rest length of the edge opposite every corner (nF x 3, index 3 f + c; the expressions of smg_mesh_cotmatrix);
+ *   s_i = exp(-u_i / 2), the only exp; a face works with a_c = l0[3 f + c] s_{F[f][c]}, its lengths divided by the face's common factor, so no
+ *   exp of a sum occurs.  With a, b, c the scaled lengths, S = a + b + c, s0 = b + c - a, s1 = a + c - b, s2 = a + b - c: the angle at corner 0 is
+ *   2 atan2(sqrt(s1 s2), sqrt(S s0)) and its half cotangent (b b + c c - a a) / sqrt(S s0 s1 s2) / 2, cyclically; the quotient is formed as
+ *   (b b + c c - a a) / (dA0 r) / 4 with dA0 twice the rest area (the cross product, as smg_mesh_cotmatrix has it) and r the ratio of
+ *   sqrt(S s0 s1 s2) to the same root of the rest lengths, which is exactly 1 at u = 0: there -L~ is -smg_mesh_cotmatrix bit for bit.  A face with some s_c <= 0 is
+ *   broken (Springborn's extension): the angle opposite the too-long edge is pi, the others 0, the half cotangents 0.  The angle sum of a vertex
+ *   runs over its corner list, faces ascending; -L~ is summed in smg_mesh_cotmatrix's CSR order and term order.  No atomics, no FMA contraction.
+ *   The line search is on the gradient norm: t = 1, 1/2, 1/4, ... is accepted when |g(u + t d)|_2 <= (1 - 1e-4 t) |g(u)|_2; below t = 2^-20 the
+ *   call ends with SMG_OK, *converged = 0 and u the last accepted iterate.  The call stops when max |g_i| <= grad_tol or after max_newton steps.
+ * smg_conformal_params: grad_tol (1e-10), max_newton (50), inner_rel_tol (1e-6: the inner solve's tol is inner_rel_tol |g|_2).
+ * smg_conformal_create: h gives the prolongations (any scalar hierarchy on this mesh); they are copied into one internal handle, h is not
+ *   modified.  fixed: the n_fixed vertices whose u is given, not solved for; they absorb whatever curvature remains (no Gauss-Bonnet test is
+ *   made).  SMG_ERR_INVALID, before any device work, for: a union or block hierarchy, nV that is not the hierarchy's level-0 rows, a hierarchy
+ *   of one level (smg_precompute_values_device needs two), a face index out of range, a face of zero area, a non-finite coordinate, more than
+ *   one connected component; then an empty list, a fixed vertex out of range or listed twice, no free vertex; then grad_tol or inner_rel_tol
+ *   not finite or <= 0, max_newton < 0.  SMG_ERR_NO_DEVICE comes after all of them.  V: nV x 3 row-major, as every create takes it.
+ * smg_conformal_set_params: the parameters of the following calls.  smg_conformal_set_solver: as smg_arap_set_solver (PCG by default).
+ * smg_conformal_solve: Theta (nV doubles; read at the free vertices) and u_fixed (n_fixed doubles in the order of create's list; NULL: zeros)
+ *   live in memspace.  The call starts from the object's current u with the fixed entries set, so a second call is warm.  grad_his[t] = max |g|
+ *   of iterate t (one entry more than *n_newton), step_his[t] = the accepted t, cycles[t] = the loop entries of the solve; all three, n_newton
+ *   and converged may be NULL; the arrays hold max_newton (+ 1) entries.  opts: the options of the inner solves (tol is absolute and replaces
+ *   inner_rel_tol |g|_2); NULL selects smg_solve_opts_default with that tol and max_iter = 100.  A solve that used all of max_iter is not an error; a failing
+ *   precompute or solve returns its code unchanged.  A non-finite gradient norm returns SMG_ERR_NONFINITE with *n_newton = t, nothing written
+ *   past grad_his[t] and u the last finite iterate (a trial with a non-finite norm is only a rejected trial).  SMG_ERR_INVALID, before any
+ *   device work, for a null object or Theta, a bad memspace, and for SMG_HOST blocks a non-finite Theta or u_fixed (device blocks are not read
+ *   by the host: there a non-finite entry ends as SMG_ERR_NONFINITE at step 0).  Per evaluation the host reads three doubles in one copy:
+ *   sum g^2, max |g| and the number of broken faces.  Nothing is allocated after create.  The same calls give the same bits.
+ * smg_conformal_reset: u = 0.  smg_conformal_set_u / smg_conformal_u: the state, nV doubles in memspace.
+ * smg_conformal_angle_sums: the achieved angle sums of the current u at ALL nV vertices, the fixed ones included.
+ * smg_conformal_lengths: l~ of the current u per corner (nF x 3, the edge opposite the corner) as l0 / (s_j s_k); what smg_mesh_unfold takes.
+ * smg_conformal_stats: 2 host doubles: the broken faces of the last accepted iterate, and their maximum over every evaluation of the last solve.
+ * smg_conformal_host: the host twin of the kernels on caller arrays (no GPU, the text the kernels compile, the sums in the device's order), with
+ *   the operands and the layouts of smg_debug_conformal below.
+ * Not covered: edge flips (Gu et al.: the metric stays on the given triangulation, so a broken face stays broken), a Gauss-Bonnet check of
+ * Theta, hyperbolic or spherical background metrics, the energy itself (the line search needs only its gradient), union / block / sharded
+ * forms, cutting a closed mesh into a disk for the layout. */
+typedef struct smg_conformal smg_conformal;
+typedef struct { double grad_tol; int max_newton; double inner_rel_tol; } smg_conformal_params;
+enum { SMG_CONFORMAL_SCALE = 0, SMG_CONFORMAL_FACES = 1, SMG_CONFORMAL_ROWS = 2 };
+smg_conformal_params smg_conformal_params_default(void);   /* 1e-10, 50, 1e-6 */
+int smg_conformal_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const int *fixed, int n_fixed,
+                         const smg_conformal_params *p, smg_conformal **out);
+void smg_conformal_destroy(smg_conformal *c);
+int smg_conformal_set_params(smg_conformal *c, const smg_conformal_params *p);
+int smg_conformal_set_solver(smg_conformal *c, int pcg);
+long long smg_conformal_device_bytes(const smg_conformal *c);
+int smg_conformal_reset(smg_conformal *c);
+int smg_conformal_set_u(smg_conformal *c, const double *u, int memspace);
+int smg_conformal_u(smg_conformal *c, int memspace, double *u);
+int smg_conformal_solve(smg_conformal *c, const double *Theta, const double *u_fixed, int memspace, const smg_solve_opts *opts, double *grad_his,
+                        double *step_his, int *cycles, int *n_newton, int *converged);
+int smg_conformal_angle_sums(smg_conformal *c, int memspace, double *sums);
+int smg_conformal_lengths(smg_conformal *c, int memspace, double *len);
+int smg_conformal_stats(const smg_conformal *c, double *stats);
+int smg_conformal_host(int op, int nV, int nF, const int *F, const double *l0, const double *area2, const double *u, const double *d, double t,
+                       const double *s, const double *Theta, const int *fixed, int n_fixed, double *out);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -1293,6 +1357,17 @@ int smg_debug_flow(int op, int nV, int nF, const int *F, const double *U, const 
 int smg_debug_hodge(int op, int nV, int nF, int k, const int *F, const double *V, const double *X, const double *u, const double *v, double *out,
                     int *guard_hits);
 
+/* One launcher of the conformal metric (csrc/smg_conformal_device.hip), handle-free and guarded like the hooks above.  F: nF x 3; l0: nF x 3, the
+ * rest length of the edge opposite every corner; area2: nF, twice the rest area of every face (the cross product's norm); u, d, s, Theta: nV; fixed: n_fixed vertex indices (may be empty); every array is host.
+ *   SMG_CONFORMAL_SCALE  u; d (NULL ok) and t: the trial u + t d -> out = s = exp(-(u + t d) / 2) (nV), then u + t d (nV)
+ *   SMG_CONFORMAL_FACES  l0, area2, s -> out = the angles (nF x 3), the half cotangents (nF x 3), the broken flags (nF, 1.0 / 0.0), l~ (nF x 3)
+ *   SMG_CONFORMAL_ROWS   l0, area2, s, Theta, fixed -> out = the angle sums (nV), g (nV), g^2 (nV), |g| (nV), then sum g^2, max |g| and the broken count,
+ *                        then the values of -L~ in smg_mesh_cotmatrix's CSR order (its nnz doubles); k_conformal_faces runs first on buffers of its own
+ * SMG_ERR_INVALID for an unknown op, a missing operand, a face index out of range, a non-finite t, a fixed vertex out of range or listed twice;
+ * SMG_ERR_NO_DEVICE without a GPU. */
+int smg_debug_conformal(int op, int nV, int nF, const int *F, const double *l0, const double *area2, const double *u, const double *d, double t,
+                        const double *s, const double *Theta, const int *fixed, int n_fixed, double *out, int *guard_hits);
+
 /* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
  * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.
  *   SMG_UNION_SUMSQ_DECIDE  rptr[m + 1], rows (member i's rows of the block: rows[rptr[i] .. rptr[i + 1]), each row at most once), r, u, zsave,
@@ -1329,6 +1404,17 @@ int smg_mesh_boundary_loop(const int *F, int nF, int nV, int *loop, int *n_loop)
 /* N(f): per face the faces that share at least one vertex with it, without f, as CSR with ascending, duplicate-free rows (ptr: nF + 1 ints).
  * Returns the number of entries (>= 0; with ptr and idx NULL only that: the size query) or a negative error code. */
 int smg_mesh_face_neighbours(const int *F, int nF, int nV, int *ptr, int *idx);
+/* Lays a flat disk metric out in the plane, host only.  len: nF x 3, the length of the edge opposite every corner (what smg_conformal_lengths
+ * returns); X: nV x 2.  Faces are unfolded one after the other in breadth-first order from face 0 (the neighbours across the edges opposite
+ * corners 0, 1, 2 in turn): vertex F[0][0] goes to the origin, F[0][1] onto the +x axis, and a vertex is placed once, by the first face that
+ * reaches it, to the left of the directed shared edge; a vertex in no face stays at the origin.  stats (2 doubles): the largest relative
+ * mismatch between len and the laid-out edge lengths over all faces, and the number of faces of non-positive signed area.  The mismatch is the
+ * check: it is the metric's angle defect times the conditioning of the unfolding (errors add up along the breadth-first paths), so a metric
+ * that is not flat, or flat but extremely distorted, shows there and not as an error code.  Cutting a closed mesh into a disk is the caller's
+ * business.  SMG_ERR_INVALID for a missing array, a face index out of range, a non-finite length, lengths that break the triangle inequality,
+ * a face that repeats a vertex, a directed edge that occurs twice (a non-manifold edge or inconsistent orientation), and faces that are not
+ * reached across edges from face 0 (more than one component). */
+int smg_mesh_unfold(const int *F, int nF, int nV, const double *len, double *X, double *stats);
 /* one mid-point upsampling step: S is (nV+nE) x nV in CSR (nV + 2 nE entries), NF is 4 nF x 3 */
 int smg_mesh_midpoint_upsample(int nV, const int *F, int nF, int *nE, int *S_rowptr, int *S_col, double *S_val,
                                int *NF);

@@ -38,6 +38,10 @@ class FlowParamsC(C.Structure):
     _fields_ = [("delta", C.c_double), ("normalize", C.c_int), ("stop_sphericity", C.c_double)]
 
 
+class ConformalParamsC(C.Structure):
+    _fields_ = [("grad_tol", C.c_double), ("max_newton", C.c_int), ("inner_rel_tol", C.c_double)]
+
+
 _lib = None
 
 
@@ -205,6 +209,21 @@ def load():
         "smg_hodge_field": (i, [vp, vp, i, vp, i, i, i, vp]),
         "smg_hodge_host": (i, [i, i, i, i, ip, dp, dp, dp, dp, dp]),
         "smg_debug_hodge": (i, [i, i, i, i, ip, dp, dp, dp, dp, dp, ip]),
+        "smg_conformal_params_default": (ConformalParamsC, []),
+        "smg_conformal_create": (i, [vp, dp, i, ip, i, ip, i, C.POINTER(ConformalParamsC), C.POINTER(vp)]),
+        "smg_conformal_destroy": (None, [vp]),
+        "smg_conformal_set_params": (i, [vp, C.POINTER(ConformalParamsC)]),
+        "smg_conformal_set_solver": (i, [vp, i]),
+        "smg_conformal_device_bytes": (C.c_longlong, [vp]),
+        "smg_conformal_reset": (i, [vp]),
+        "smg_conformal_set_u": (i, [vp, vp, i]),
+        "smg_conformal_u": (i, [vp, i, vp]),
+        "smg_conformal_solve": (i, [vp, vp, vp, i, C.POINTER(SolveOptsC), dp, dp, ip, ip, ip]),
+        "smg_conformal_angle_sums": (i, [vp, i, vp]),
+        "smg_conformal_lengths": (i, [vp, i, vp]),
+        "smg_conformal_stats": (i, [vp, dp]),
+        "smg_conformal_host": (i, [i, i, i, ip, dp, dp, dp, dp, d, dp, dp, ip, i, dp]),
+        "smg_debug_conformal": (i, [i, i, i, ip, dp, dp, dp, dp, d, dp, dp, ip, i, dp, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),
@@ -273,6 +292,7 @@ def load():
         "smg_mesh_massmatrix": (i, [dp, i, ip, i, i, dp]),
         "smg_mesh_boundary_loop": (i, [ip, i, i, ip, ip]),
         "smg_mesh_face_neighbours": (i, [ip, i, i, ip, ip]),
+        "smg_mesh_unfold": (i, [ip, i, i, dp, dp, dp]),
         "smg_mesh_midpoint_upsample": (i, [i, ip, i, ip, ip, ip, dp, ip]),
         "smg_mesh_torus": (i, [i, i, d, d, dp, ip]),
     }

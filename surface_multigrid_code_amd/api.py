@@ -1228,6 +1228,106 @@ class HodgeDecomposition(_MeshObject):
         return X[0] if single else X
 
 
+class ConformalMetric(_MeshObject):
+    """Discrete conformal metrics with prescribed angle sums (include/smg.h: smg_conformal_*; Springborn, Schroeder, Pinkall 2008): one log scale
+    factor u per vertex so that the metric l exp((u_i + u_j) / 2) has the angle sum Theta at every free vertex.  Newton's method on the convex
+    energy; every step re-precomputes the cotangent matrix of the current metric by values and runs one 1-column solve.
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  fixed: the vertices whose
+    u is given (at least one), in the order solve() takes their values."""
+
+    _prefix = "smg_conformal_"
+    c = property(lambda self: self.o)
+
+    def __init__(self, hierarchy, V, F, fixed, **params):
+        self.fixed = np.ascontiguousarray(fixed, dtype=np.int32).reshape(-1)
+        self.F = np.ascontiguousarray(F, dtype=np.int32)
+        self.params = conformal_params(**params)
+        self._create(hierarchy, V, F, _ip(self.fixed), self.fixed.shape[0], C.byref(self.params))
+
+    def set_params(self, **params):
+        """grad_tol, max_newton, inner_rel_tol of the following calls"""
+        p = _lib.ConformalParamsC(self.params.grad_tol, self.params.max_newton, self.params.inner_rel_tol)
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise TypeError("unknown conformal parameter %r" % k)
+            setattr(p, k, v)
+        self._call("set_params", C.byref(p))
+        self.params = p
+
+    def solve(self, Theta, u_fixed=None, opts=None):
+        """Newton from the current u.  Theta: n target angle sums; u_fixed: the fixed vertices' u (None: zeros).  Returns (grad_his, step_his,
+        cycles, converged): max |g| of every iterate, the accepted step lengths and the loop entries of the solves, trimmed to the steps done."""
+        Theta = np.ascontiguousarray(Theta, dtype=np.float64).reshape(self.n)
+        uf = None if u_fixed is None else np.ascontiguousarray(u_fixed, dtype=np.float64).reshape(self.fixed.shape[0])
+        cap = self.params.max_newton
+        g, st, cyc = np.zeros(cap + 1), np.zeros(max(cap, 1)), np.zeros(max(cap, 1), dtype=np.int32)
+        nn, conv = C.c_int(0), C.c_int(0)
+        self._call("solve", Theta.ctypes.data, None if uf is None else uf.ctypes.data, SMG_HOST, self._opts(opts), _dp(g), _dp(st), _ip(cyc),
+                   C.byref(nn), C.byref(conv))
+        return g[:nn.value + 1].copy(), st[:nn.value].copy(), cyc[:nn.value].copy(), bool(conv.value)
+
+    def solve_device(self, Theta_ptr, u_fixed_ptr=None, opts=None):
+        """solve() with Theta (and u_fixed) resident in HBM (device pointers)"""
+        cap = self.params.max_newton
+        g, st, cyc = np.zeros(cap + 1), np.zeros(max(cap, 1)), np.zeros(max(cap, 1), dtype=np.int32)
+        nn, conv = C.c_int(0), C.c_int(0)
+        self._call("solve", Theta_ptr, u_fixed_ptr or None, SMG_DEVICE, self._opts(opts), _dp(g), _dp(st), _ip(cyc), C.byref(nn), C.byref(conv))
+        return g[:nn.value + 1].copy(), st[:nn.value].copy(), cyc[:nn.value].copy(), bool(conv.value)
+
+    def reset(self):
+        """u = 0"""
+        self._call("reset")
+
+    def u(self):
+        u = np.zeros(self.n)
+        self._call("u", SMG_HOST, u.ctypes.data)
+        return u
+
+    def u_device(self, u_ptr):
+        self._call("u", SMG_DEVICE, u_ptr)
+
+    def set_u(self, u):
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(self.n)
+        self._call("set_u", u.ctypes.data, SMG_HOST)
+
+    def set_u_device(self, u_ptr):
+        self._call("set_u", u_ptr, SMG_DEVICE)
+
+    def angle_sums(self):
+        """the achieved angle sums of the current u at all n vertices"""
+        a = np.zeros(self.n)
+        self._call("angle_sums", SMG_HOST, a.ctypes.data)
+        return a
+
+    def lengths(self):
+        """nF x 3: the current length of the edge opposite every corner"""
+        lt = np.zeros((self.nF, 3))
+        self._call("lengths", SMG_HOST, lt.ctypes.data)
+        return lt
+
+    def stats(self):
+        """the broken faces of the last accepted iterate and their maximum over the last solve"""
+        s = np.zeros(2)
+        self._call("stats", _dp(s))
+        return dict(broken=int(s[0]), broken_max=int(s[1]))
+
+    def layout(self):
+        """(X n x 2, stats) of mesh.unfold on the current lengths: meaningful for a flat metric on a disk"""
+        from . import mesh
+        return mesh.unfold(self.F, self.lengths(), self.n)
+
+
+def conformal_params(**params):
+    """smg_conformal_params with the library's defaults and the given fields"""
+    p = _lib.load().smg_conformal_params_default()
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError("unknown conformal parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 def flow_params(**params):
     """smg_flow_params with the library's defaults and the given fields"""
     p = _lib.load().smg_flow_params_default()

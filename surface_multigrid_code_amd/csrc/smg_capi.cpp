@@ -820,6 +820,25 @@ extern "C" int smg_mesh_boundary_loop(const int* F, int nF, int nV, int* loop, i
     return SMG_OK;
 }
 
+extern "C" int smg_mesh_unfold(const int* F, int nF, int nV, const double* len, double* X, double* stats)
+{
+    return guarded("smg_mesh_unfold", [&]() -> int {
+        const char* who = "smg_mesh_unfold";
+        if (!F || !len || !X || !stats || nF <= 0 || nV <= 0) return fail(SMG_ERR_INVALID, "%s: bad arguments", who);
+        for (size_t i = 0; i < 3 * (size_t)nF; i++)
+            if (F[i] < 0 || F[i] >= nV) return fail(SMG_ERR_INVALID, "%s: face index out of range", who);
+        int where = 0;
+        switch (unfold(F, nF, nV, len, X, stats, &where)) {
+            case UNFOLD_OK: return SMG_OK;
+            case UNFOLD_NONFINITE: return fail(SMG_ERR_INVALID, "%s: face %d has a non-finite length", who, where);
+            case UNFOLD_TRIANGLE: return fail(SMG_ERR_INVALID, "%s: the lengths of face %d break the triangle inequality", who, where);
+            case UNFOLD_NONMANIFOLD:
+                return fail(SMG_ERR_INVALID, "%s: face %d repeats a vertex or a directed edge: a manifold, consistently oriented mesh is needed", who, where);
+            default: return fail(SMG_ERR_INVALID, "%s: %d of %d faces are reached across edges from face 0: one component is needed", who, where, nF);
+        }
+    });
+}
+
 extern "C" int smg_mesh_face_neighbours(const int* F, int nF, int nV, int* ptr, int* idx)
 {
     return guarded("smg_mesh_face_neighbours", [&]() -> int {

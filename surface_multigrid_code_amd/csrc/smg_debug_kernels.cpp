@@ -932,6 +932,73 @@ extern "C" int smg_debug_hodge(int op, int nV, int nF, int k, const int* F, cons
     });
 }
 
+extern "C" int smg_debug_conformal(int op, int nV, int nF, const int* F, const double* l0, const double* area2, const double* u, const double* d, double t,
+                                   const double* s, const double* Theta, const int* fixed, int n_fixed, double* out, int* guard_hits)
+{
+    return guarded("smg_debug_conformal", [&]() -> int {
+        const char* who = "smg_debug_conformal";
+        if (int rc = conformal_check_operands(who, op, nV, nF, F, l0, area2, u, d, t, s, Theta, fixed, n_fixed, out)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, D = sizeof(double), I = sizeof(int);
+        AssemblyPlan plan;
+        std::vector<int> mask;
+        if (op == SMG_CONFORMAL_ROWS) {
+            plan = make_assembly_plan(std::vector<int>(F, F + 3 * f), nV);
+            mask.assign(n, 0);
+            for (int i = 0; i < n_fixed; i++) mask[(size_t)fixed[i]] = 1;
+        }
+        const size_t nnz = plan.pattern.col.size();
+        Scratch S;
+        HIPCHK(S.init());
+        const size_t out_count = op == SMG_CONFORMAL_SCALE ? 2 * n : op == SMG_CONFORMAL_FACES ? 10 * f : 4 * n + 3 + nnz;
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr, *drp = nullptr, *dlp = nullptr, *dli = nullptr, *dmask = nullptr;
+        signed char* dls = nullptr;
+        double *dl0 = nullptr, *da2 = nullptr, *du = nullptr, *dd = nullptr, *ds = nullptr, *dTh = nullptr, *dout = nullptr, *dang = nullptr, *dhc = nullptr, *dbr = nullptr,
+               *dpart = nullptr;
+        HIPCHK(S.add(F, nullptr, 3 * f * I, &dF));
+        if (op == SMG_CONFORMAL_SCALE) {
+            HIPCHK(S.add(u, nullptr, n * D, &du));
+            if (d) HIPCHK(S.add(d, nullptr, n * D, &dd));
+        } else {
+            HIPCHK(S.add(l0, nullptr, 3 * f * D, &dl0));
+            HIPCHK(S.add(area2, nullptr, f * D, &da2));
+            HIPCHK(S.add(s, nullptr, n * D, &ds));
+        }
+        if (op == SMG_CONFORMAL_ROWS) {
+            HIPCHK(S.add(Theta, nullptr, n * D, &dTh));
+            HIPCHK(S.add(mask.data(), nullptr, n * I, &dmask));
+            HIPCHK(S.add(plan.m_ptr.data(), nullptr, plan.m_ptr.size() * I, &dmp));
+            HIPCHK(S.add(plan.m_idx.data(), nullptr, plan.m_idx.size() * I, &dmi));
+            HIPCHK(S.add(plan.pattern.ptr.data(), nullptr, plan.pattern.ptr.size() * I, &drp));
+            HIPCHK(S.add(plan.l_ptr.data(), nullptr, plan.l_ptr.size() * I, &dlp));
+            HIPCHK(S.add(plan.l_idx.data(), nullptr, plan.l_idx.size() * I, &dli));
+            HIPCHK(S.add(plan.l_sgn.data(), nullptr, plan.l_sgn.size(), &dls));
+            HIPCHK(S.add(nullptr, nullptr, 3 * f * D, &dang));
+            HIPCHK(S.add(nullptr, nullptr, 3 * f * D, &dhc));
+            HIPCHK(S.add(nullptr, nullptr, f * D, &dbr));
+            HIPCHK(S.add(nullptr, nullptr, (size_t)fixed_sum_groups(std::max(nV, nF)) * D, &dpart));
+        }
+        HIPCHK(S.add(out, out, out_count * D, &dout));
+        hipStream_t st = S.stream();
+        switch (op) {
+            case SMG_CONFORMAL_SCALE: HIPCHK(launch_conformal_scale(nV, du, dd, t, dout + n, dout, st)); break;
+            case SMG_CONFORMAL_FACES:
+                HIPCHK(launch_conformal_faces(nF, dF, dl0, da2, ds, dout, dout + 3 * f, dout + 6 * f, st));
+                HIPCHK(launch_conformal_lengths(nF, dF, dl0, ds, dout + 7 * f, st));
+                break;
+            default:
+                HIPCHK(launch_conformal_faces(nF, dF, dl0, da2, ds, dang, dhc, dbr, st));
+                HIPCHK(launch_conformal_rows(nV, nF, dang, dhc, dbr, dmp, dmi, dTh, dmask, drp, dlp, dli, dls, dout, dout + n, dout + 2 * n, dout + 3 * n,
+                                             dout + 4 * n + 3, dpart, dout + 4 * n, st));
+                break;
+        }
+        int bad = 0;
+        HIPCHK(S.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
 namespace {
 
 // what the union launchers index with: the level-0 row lists (SUMSQ_DECIDE, RESTORE) or the coarsest level's member blocks (COARSE)

@@ -603,4 +603,20 @@ hipError_t launch_hodge_parts(int nF, int k, const int* F, const double* W, cons
 hipError_t launch_hodge_field(int nF, int k, const int* F, const double* W, const double* nrm, const double* u, int ldu, const double* v, int ldv,
                               double* X, hipStream_t st);
 
+// discrete conformal metrics (smg_conformal_device.hip; the maths in smg_conformal_inl.hpp).  u, s, sum, g: nV; ang, hc, l0, lt: nF x 3 in corner
+// order (3 f + c); area2: nF, twice the rest area; broken: nF doubles, 1.0 / 0.0; m_ptr / m_idx: the corner lists; (rowptr; l_ptr, l_idx, l_sgn): the CSR's rows and the assembly
+// recipe of its entries (AssemblyPlan) ---------------------------------------------------------------------------------------------------------------
+// ut = u + t d (d == nullptr: u), s = exp(-ut / 2)
+hipError_t launch_conformal_scale(int n, const double* u, const double* d, double t, double* ut, double* s, hipStream_t st);
+hipError_t launch_conformal_faces(int nF, const int* F, const double* l0, const double* area2, const double* s, double* ang, double* hc, double* broken,
+                                  hipStream_t st);
+hipError_t launch_conformal_lengths(int nF, const int* F, const double* l0, const double* s, double* lt, hipStream_t st);
+// sum = the angle sums, g = sum - Theta (0 where fixed[v] != 0), gsq = g^2, gabs = |g|; val (nullptr ok) = the values of -L~; red (nullptr ok) =
+// sum g^2, max |g|, the broken count (part: fixed_sum_groups(max(n, nF)) doubles)
+hipError_t launch_conformal_rows(int n, int nF, const double* ang, const double* hc, const double* broken, const int* m_ptr, const int* m_idx,
+                                 const double* Theta, const int* fixed, const int* rowptr, const int* l_ptr, const int* l_idx, const signed char* l_sgn,
+                                 double* sum, double* g, double* gsq, double* gabs, double* val, double* part, double* red, hipStream_t st);
+// u[list[i]] = values[i] (values == nullptr: 0)
+hipError_t launch_conformal_fix(int nf, const int* list, const double* values, double* u, hipStream_t st);
+
 }  // namespace smg

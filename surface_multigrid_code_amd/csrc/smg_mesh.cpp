@@ -361,6 +361,71 @@ bool face_neighbours(const std::vector<int>& F, const std::vector<int>& m_ptr, c
     return true;
 }
 
+int unfold(const int* F, int nF, int nV, const double* len, double* X, double* stats, int* where)
+{
+    const size_t nf = (size_t)nF;
+    for (size_t f = 0; f < nf; f++) {
+        const double a = len[3 * f], b = len[3 * f + 1], c = len[3 * f + 2];
+        *where = (int)f;
+        if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(c)) return UNFOLD_NONFINITE;
+        if (!(b + c - a > 0.0) || !(a + c - b > 0.0) || !(a + b - c > 0.0)) return UNFOLD_TRIANGLE;
+    }
+    // the face on the other side of every directed edge: edge c of face f runs from corner c + 1 to corner c + 2, opposite corner c
+    std::unordered_map<uint64_t, int> half;
+    half.reserve(3 * nf);
+    auto key = [](int a, int b) { return ((uint64_t)(uint32_t)a << 32) | (uint32_t)b; };
+    for (size_t f = 0; f < nf; f++)
+        for (int c = 0; c < 3; c++) {
+            *where = (int)f;
+            if (F[3 * f + c] == F[3 * f + (c + 1) % 3]) return UNFOLD_NONMANIFOLD;
+            if (!half.emplace(key(F[3 * f + (c + 1) % 3], F[3 * f + (c + 2) % 3]), (int)(3 * f + c)).second) return UNFOLD_NONMANIFOLD;
+        }
+    std::vector<char> placed((size_t)nV, 0), seen(nf, 0);
+    auto put = [&](int v, double x, double y) { X[2 * (size_t)v] = x; X[2 * (size_t)v + 1] = y; placed[(size_t)v] = 1; };
+    // corner c of face f to the left of the directed edge A -> B (corners c + 1, c + 2), both laid out already
+    auto place = [&](size_t f, int c) {
+        const int A = F[3 * f + (c + 1) % 3], B = F[3 * f + (c + 2) % 3];
+        const double L = len[3 * f + c], dA = len[3 * f + (c + 2) % 3], dB = len[3 * f + (c + 1) % 3];
+        const double ex = X[2 * (size_t)B] - X[2 * (size_t)A], ey = X[2 * (size_t)B + 1] - X[2 * (size_t)A + 1];
+        const double el = std::sqrt(ex * ex + ey * ey);
+        const double x = (dA * dA - dB * dB + L * L) / (2.0 * L);
+        const double y = std::sqrt(std::max(dA * dA - x * x, 0.0));
+        put(F[3 * f + c], X[2 * (size_t)A] + x * (ex / el) - y * (ey / el), X[2 * (size_t)A + 1] + x * (ey / el) + y * (ex / el));
+    };
+    for (size_t i = 0; i < 2 * (size_t)nV; i++) X[i] = 0.0;
+    put(F[0], 0.0, 0.0);
+    put(F[1], len[2], 0.0);
+    place(0, 2);
+    std::vector<int> queue(1, 0);
+    seen[0] = 1;
+    for (size_t head = 0; head < queue.size(); head++) {
+        const size_t f = (size_t)queue[head];
+        for (int c = 0; c < 3; c++) {
+            const auto it = half.find(key(F[3 * f + (c + 2) % 3], F[3 * f + (c + 1) % 3]));
+            if (it == half.end() || seen[(size_t)(it->second / 3)]) continue;
+            const size_t g = (size_t)(it->second / 3);
+            seen[g] = 1;
+            if (!placed[(size_t)F[3 * g + it->second % 3]]) place(g, it->second % 3);
+            queue.push_back((int)g);
+        }
+    }
+    *where = (int)queue.size();
+    if (queue.size() != nf) return UNFOLD_COMPONENTS;
+    double worst = 0.0, flipped = 0.0;
+    for (size_t f = 0; f < nf; f++) {
+        const double* p[3] = {X + 2 * (size_t)F[3 * f], X + 2 * (size_t)F[3 * f + 1], X + 2 * (size_t)F[3 * f + 2]};
+        for (int c = 0; c < 3; c++) {
+            const double dx = p[(c + 2) % 3][0] - p[(c + 1) % 3][0], dy = p[(c + 2) % 3][1] - p[(c + 1) % 3][1];
+            worst = std::max(worst, std::fabs(std::sqrt(dx * dx + dy * dy) - len[3 * f + c]) / len[3 * f + c]);
+        }
+        const double area2 = (p[1][0] - p[0][0]) * (p[2][1] - p[0][1]) - (p[1][1] - p[0][1]) * (p[2][0] - p[0][0]);
+        if (!(area2 > 0.0)) flipped += 1.0;
+    }
+    stats[0] = worst;
+    stats[1] = flipped;
+    return UNFOLD_OK;
+}
+
 Mesh make_torus(int nu, int nv, double R, double r)
 {
     Mesh m;

@@ -39,6 +39,14 @@ void subdivide(Mesh& m, int n_sub, std::vector<Csr>& Ps);
 
 Mesh make_torus(int nu, int nv, double R, double r);           // BASELINE config C5 base mesh
 
+// Lays a flat disk metric out in the plane (smg_mesh_unfold, include/smg.h): len is nF x 3, the length of the edge opposite every corner; X is
+// nV x 2.  Faces are unfolded in breadth-first order from face 0 (a face's neighbours across the edges opposite corners 0, 1, 2 in turn); vertex
+// F[0][0] goes to the origin, F[0][1] onto the +x axis; a vertex is placed once, by the first face that reaches it, to the left of the directed
+// shared edge.  stats[0] = the largest relative mismatch between len and the laid-out edge lengths, stats[1] = the faces of non-positive
+// signed area.  *where: the face (or, for UNFOLD_COMPONENTS, the number of faces reached) a refusal speaks of.  F must be in range.
+enum { UNFOLD_OK = 0, UNFOLD_NONFINITE = 1, UNFOLD_TRIANGLE = 2, UNFOLD_NONMANIFOLD = 3, UNFOLD_COMPONENTS = 4 };
+int unfold(const int* F, int nF, int nV, const double* len, double* X, double* stats, int* where);
+
 // Assembly plan for a FIXED connectivity: the sparsity of cotmatrix(V, F) and, per stored
 // entry, the ordered list of per-face cotangent terms (+/- C(f,e)) that cotmatrix() sums into it; per vertex the ordered
 // list of per-corner mass terms.  Replaying the plan on new vertex positions reproduces cotmatrix()/massmatrix_diag()

@@ -27,7 +27,7 @@ int check_mesh(const char* who, const double* V, int nV, const int* F, int nF, b
 struct MeshObject {
     hipStream_t stream = nullptr;
     int device = -1;
-    smg_hierarchy* handle[2] = {nullptr, nullptr};                    // smg_geodesics and smg_hodge (a mesh with boundary) hold two
+    smg_hierarchy* handle[2] = {nullptr, nullptr};                    // smg_geodesics and smg_hodge (a mesh with boundary) hold two; smg_conformal one
     MeshObject() = default;
     MeshObject(const MeshObject&) = delete;
     MeshObject& operator=(const MeshObject&) = delete;
@@ -89,5 +89,10 @@ void flow_diagonal(int nV, const int* rowptr, const int* col, std::vector<int>& 
 // ---- smg_hodge.cpp: what smg_hodge_host and smg_debug_hodge check alike, in this order: the op and its operands, k, the faces
 int hodge_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* X, const double* u, const double* v,
                          const double* out);
+
+// ---- smg_conformal.cpp: what smg_conformal_host and smg_debug_conformal check alike, in this order: the op and its operands, the faces, a finite
+// trial step, the fixed list (in range, no vertex twice; empty is allowed here)
+int conformal_check_operands(const char* who, int op, int nV, int nF, const int* F, const double* l0, const double* area2, const double* u, const double* d, double t,
+                             const double* s, const double* Theta, const int* fixed, int n_fixed, const double* out);
 
 }  // namespace smg

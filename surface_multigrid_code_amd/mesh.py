@@ -67,6 +67,17 @@ def boundary_loop(F, nV=None):
     return loop[: n.value].copy()
 
 
+def unfold(F, lengths, nV=None):
+    """smg_mesh_unfold: a flat disk metric (lengths: nF x 3, the edge opposite every corner) laid out in the plane.  Returns (X nV x 2, stats)
+    with stats = dict(mismatch: the largest relative difference between the given and the laid-out lengths, flipped: faces of non-positive area)"""
+    F = np.ascontiguousarray(F, dtype=np.int32)
+    lengths = np.ascontiguousarray(lengths, dtype=np.float64).reshape(F.shape[0], 3)
+    nV = int(F.max()) + 1 if nV is None else int(nV)
+    X, st = np.zeros((nV, 2)), np.zeros(2)
+    _chk(_lib.load().smg_mesh_unfold(_ip(F), F.shape[0], nV, _dp(lengths), _dp(X), _dp(st)), "smg_mesh_unfold")
+    return X, dict(mismatch=float(st[0]), flipped=int(st[1]))
+
+
 def midpoint_upsample(nV, F):
     L = _lib.load()
     F = np.ascontiguousarray(F, dtype=np.int32)
