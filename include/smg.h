@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 517
+#define SMG_VERSION 518
 
 enum {
     SMG_OK = 0,
@@ -1007,6 +1007,51 @@ int smg_conformal_stats(const smg_conformal *c, double *stats);
 int smg_conformal_host(int op, int nV, int nF, const int *F, const double *l0, const double *area2, const double *u, const double *d, double t,
                        const double *s, const double *Theta, const int *fixed, int n_fixed, double *out);
 
+/* ---- Earth mover's (1-Wasserstein) distance between distributions on a mesh, with geodesic ground cost (csrc/smg_emd.cpp):
+ * Solomon, Rustamov, Guibas, Butscher 2014 in Beckmann form.  With b = mu1 - mu0 (integrated masses per vertex, sum_i b_i = 0), A_f the face
+ * areas and W2_fi the gradient of vertex i's hat function in the face's frame (t1 = (p1 - p0) / |p1 - p0|, t2 = n x t1):
+ *     minimise  sum_f A_f |J_f|   subject to  sum_f A_f W2_fi . J_f = b_i for every vertex i;     dual: maximise b . psi, |grad psi_f| <= 1
+ * by ADMM with one penalty rho_c = rho_scale sqrt(total area) / m_c per column (m_c = (1/2) sum_i |b_i|; 1 for a zero column), over-relaxation
+ * alpha and the state Z, U (2 doubles each per face and column, zero at the start).  Iteration t: Y = Z - U; r_i = sum A_f W2_fi . Y_f - b_i;
+ * (-L) phi = r with vertex 0 known and 0, ONE k-column solve warm-started from the previous phi with the absolute tolerance
+ * inner_rel_tol |b|_F; J = Y - grad phi; T = alpha J + (1 - alpha) Z + U; Z = max(0, 1 - (1 / rho) / |T|) T; U = T - Z.  The bounds:
+ * upper = sum_f A_f |J_f|; potential = (-rho / max(1, gmax)) phi with gmax = max_f rho |grad phi_f|, which is dual feasible whatever the
+ * solve's accuracy; lower = b . potential.  A column is done when upper - lower <= gap_tol upper; the loop ends at an iteration that is a
+ * multiple of check_every (or the last) at which every column is done, or at max_iter, which is not an error.  Between checks the host reads
+ * nothing beside what the inner solve itself returns on every iteration (its history and its convergence flag); at a check it reads the 3 k
+ * doubles of the bounds in one copy.  A query's fixed cost: the masses are brought to the host for the refusals, m_c and rho_c (SMG_DEVICE
+ * blocks too: two copies of nV x k doubles down and b up again), DESIGN.md section 30 gives the figures.
+ * smg_emd_create: h gives the prolongations (any scalar hierarchy on this mesh, one level included); they are copied, h is not modified.
+ *   The checks of DESIGN.md section 21 in their order, with a connected mesh, then the parameters: gap_tol, rho_scale and inner_rel_tol finite
+ *   and > 0, alpha inside (0, 2), max_iter >= 0, check_every >= 1; all SMG_ERR_INVALID before the device is touched.  Builds one cloned handle,
+ *   precomputed once with -L and vertex 0 known.
+ * smg_emd_solve: mu0, mu1 are nV x k column-major blocks (leading dimensions ld0, ld1 >= nV) in `memspace`; upper, lower and residual (k doubles
+ *   each, host; residual may be NULL) and n_iter (host, may be NULL) are written; residual[c] = |weak divergence of J - b|_2 over the unknown
+ *   rows of the last iteration, relative to |b_c|_2: the last solve's residual.  potential (NULL ok): nV x k in `memspace`, leading dimension
+ *   ld_p >= nV.  flow (NULL ok): J of the last iteration as k x nF x 3 row-major in `memspace`, one extra launch.  warm != 0 continues from the
+ *   kept Z, U, phi when k is the k of the previous call, otherwise the state is zeroed.  A column with b = 0 returns upper = lower = 0.
+ *   max_iter = 0 writes upper = +infinity and lower = 0 for the non-zero columns.  opts (NULL: the defaults with the tolerance above and
+ *   max_iter 100) are the inner solve's.  Refusals, SMG_ERR_INVALID before any launch: a null object or required block, k < 1, a bad memspace,
+ *   a leading dimension below nV, a non-finite mass, a column with |sum_i b_i| > 1e-12 sum_i |b_i| ("masses differ").  A failing inner solve
+ *   returns its code.
+ * smg_emd_set_solver: as smg_arap_set_solver (PCG by default).  Nothing is allocated after create except the query blocks, which grow with
+ *   the largest k seen and are kept (smg_emd_device_bytes counts them).
+ * smg_emd_host: the host twin of the kernels on caller arrays (no GPU, the text the kernels compile, the sums in the device's order), with the
+ *   operands and the layouts of smg_debug_emd below. */
+typedef struct { double gap_tol; int max_iter; int check_every; double alpha, rho_scale, inner_rel_tol; } smg_emd_params;
+enum { SMG_EMD_GEOMETRY = 0, SMG_EMD_RHS = 1, SMG_EMD_UPDATE = 2, SMG_EMD_DUAL = 3, SMG_EMD_FLOW = 4, SMG_EMD_RESIDUAL = 5 };
+typedef struct smg_emd smg_emd;
+smg_emd_params smg_emd_params_default(void);               /* 1e-2, 2000, 10, 1.7, 0.1, 1e-8 */
+int smg_emd_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const smg_emd_params *p, smg_emd **out);
+void smg_emd_destroy(smg_emd *g);
+int smg_emd_set_params(smg_emd *g, const smg_emd_params *p);
+int smg_emd_set_solver(smg_emd *g, int pcg);
+long long smg_emd_device_bytes(const smg_emd *g);
+int smg_emd_solve(smg_emd *g, const double *mu0, int ld0, const double *mu1, int ld1, int k, int memspace, const smg_solve_opts *opts, int warm,
+                  double *upper, double *lower, int *n_iter, double *residual, double *potential, int ld_p, double *flow);
+int smg_emd_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *b, const double *phi, const double *state,
+                 const double *rho, double alpha, double *out);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -1367,6 +1412,20 @@ int smg_debug_hodge(int op, int nV, int nF, int k, const int *F, const double *V
  * SMG_ERR_NO_DEVICE without a GPU. */
 int smg_debug_conformal(int op, int nV, int nF, const int *F, const double *l0, const double *area2, const double *u, const double *d, double t,
                         const double *s, const double *Theta, const int *fixed, int n_fixed, double *out, int *guard_hits);
+
+/* One launcher of the earth mover's distance (csrc/smg_emd_device.hip), handle-free and guarded like the hooks above.  F: nF x 3; V: nV x 3
+ * row-major; b, phi: nV x k column-major with leading dimension nV; rho: k; every array is host.  k_emd_geometry runs first where an op reads W2.
+ *   SMG_EMD_GEOMETRY  V -> out = W2 (nF x 6), A (nF), their fixed-order sum (1)
+ *   SMG_EMD_RHS       V, b, state = ZU (k sets of nF x 4) -> out = r (nV x k column-major)
+ *   SMG_EMD_UPDATE    V, phi, state = ZU, rho, alpha -> out = ZU (k sets of nF x 4), J (k sets of nF x 2), the planes A |J| and rho^2 |grad phi|^2
+ *                     (k planes of nF each), their fixed-order sums (k) and maxima (k)
+ *   SMG_EMD_DUAL      b, phi, rho, state = gmax^2 (k) -> out = the potential (nV x k column-major), the terms b potential (k planes of nV), their sums (k)
+ *   SMG_EMD_FLOW      V, state = J (k sets of nF x 2) -> out = J in 3-D (k sets of nF x 3)
+ *   SMG_EMD_RESIDUAL  V, b, state = J -> out = d = the weak divergence of J minus b (nV x k column-major), its squares with vertex 0's zero (k planes
+ *                     of nV), their sums (k)
+ * SMG_ERR_INVALID for an unknown op, nV < 1, nF < 1, a missing operand, k < 1, a face index out of range; SMG_ERR_NO_DEVICE without a GPU. */
+int smg_debug_emd(int op, int nV, int nF, int k, const int *F, const double *V, const double *b, const double *phi, const double *state,
+                  const double *rho, double alpha, double *out, int *guard_hits);
 
 /* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
  * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.

@@ -42,6 +42,11 @@ class ConformalParamsC(C.Structure):
     _fields_ = [("grad_tol", C.c_double), ("max_newton", C.c_int), ("inner_rel_tol", C.c_double)]
 
 
+class EmdParamsC(C.Structure):
+    _fields_ = [("gap_tol", C.c_double), ("max_iter", C.c_int), ("check_every", C.c_int), ("alpha", C.c_double), ("rho_scale", C.c_double),
+                ("inner_rel_tol", C.c_double)]
+
+
 _lib = None
 
 
@@ -224,6 +229,15 @@ def load():
         "smg_conformal_stats": (i, [vp, dp]),
         "smg_conformal_host": (i, [i, i, i, ip, dp, dp, dp, dp, d, dp, dp, ip, i, dp]),
         "smg_debug_conformal": (i, [i, i, i, ip, dp, dp, dp, dp, d, dp, dp, ip, i, dp, ip]),
+        "smg_emd_params_default": (EmdParamsC, []),
+        "smg_emd_create": (i, [vp, dp, i, ip, i, C.POINTER(EmdParamsC), C.POINTER(vp)]),
+        "smg_emd_destroy": (None, [vp]),
+        "smg_emd_set_params": (i, [vp, C.POINTER(EmdParamsC)]),
+        "smg_emd_set_solver": (i, [vp, i]),
+        "smg_emd_device_bytes": (C.c_longlong, [vp]),
+        "smg_emd_solve": (i, [vp, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), i, dp, dp, ip, dp, vp, i, vp]),
+        "smg_emd_host": (i, [i, i, i, i, ip, dp, dp, dp, dp, dp, d, dp]),
+        "smg_debug_emd": (i, [i, i, i, i, ip, dp, dp, dp, dp, dp, d, dp, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

@@ -1328,6 +1328,85 @@ def conformal_params(**params):
     return p
 
 
+class EmdResult:
+    """upper, lower, gap = (upper - lower) / upper (0 where upper is 0) and residual per column; iterations; potential (n x k) and flow
+    (k x nF x 3) where asked for, else None"""
+
+    def __init__(self, upper, lower, iterations, residual, potential, flow):
+        self.upper, self.lower, self.iterations, self.residual, self.potential, self.flow = upper, lower, iterations, residual, potential, flow
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.gap = np.where(upper > 0.0, (upper - lower) / np.where(upper > 0.0, upper, 1.0), 0.0)
+
+    def __repr__(self):
+        return "EmdResult(upper=%r, lower=%r, iterations=%d)" % (self.upper, self.lower, self.iterations)
+
+
+class EarthMover(_MeshObject):
+    """Earth mover's (1-Wasserstein) distances between distributions on a mesh with geodesic ground cost, with the transport flow and the
+    Kantorovich potential (include/smg.h: smg_emd_*; Solomon, Rustamov, Guibas, Butscher 2014).  ADMM on the Beckmann form: every iteration is ONE
+    warm-started k-column solve of -L for k pairs of distributions, one vertex kernel and one face kernel; the stopping rule is a certificate,
+    lower <= the discrete optimum <= upper (up to the solve's residual).
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  params: gap_tol,
+    max_iter, check_every, alpha, rho_scale, inner_rel_tol."""
+
+    _prefix = "smg_emd_"
+    e = property(lambda self: self.o)
+
+    def __init__(self, hierarchy, V, F, **params):
+        self.params = emd_params(**params)
+        self.V, self.F = np.ascontiguousarray(V, dtype=np.float64), np.ascontiguousarray(F, dtype=np.int32)
+        self._create(hierarchy, V, F, C.byref(self.params))
+
+    def set_params(self, **params):
+        """gap_tol, max_iter, check_every, alpha, rho_scale, inner_rel_tol of the following calls"""
+        p = _lib.EmdParamsC(*[getattr(self.params, f) for f, _ in _lib.EmdParamsC._fields_])
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise TypeError("unknown earth mover parameter %r" % k)
+            setattr(p, k, v)
+        self._call("set_params", C.byref(p))
+        self.params = p
+
+    def masses(self, density):
+        """integrated masses per vertex of a per-vertex density (n or n x k): the barycentric mass matrix times the density"""
+        from . import mesh
+        return mesh.massmatrix(self.V, self.F, "barycentric") @ np.asarray(density, dtype=np.float64)
+
+    def distance(self, mu0, mu1, warm=False, potential=False, flow=False, opts=None):
+        """mu0, mu1: integrated masses per vertex, n or n x k, with equal sums per column.  Returns an EmdResult."""
+        mu0 = np.asfortranarray(np.asarray(mu0, dtype=np.float64).reshape(self.n, -1))
+        mu1 = np.asfortranarray(np.asarray(mu1, dtype=np.float64).reshape(self.n, -1))
+        k = mu0.shape[1]
+        if mu1.shape[1] != k:
+            raise ValueError("mu0 and mu1 differ in their columns")
+        up, lo, res = np.zeros(k), np.zeros(k), np.zeros(k)
+        P = np.zeros((self.n, k), order="F") if potential else None
+        J = np.zeros((k, self.nF, 3)) if flow else None
+        nit = C.c_int(0)
+        self._call("solve", mu0.ctypes.data, self.n, mu1.ctypes.data, self.n, k, SMG_HOST, self._opts(opts), int(bool(warm)), _dp(up), _dp(lo),
+                   C.byref(nit), _dp(res), P.ctypes.data if potential else None, self.n, J.ctypes.data if flow else None)
+        return EmdResult(up, lo, nit.value, res, P, J)
+
+    def distance_device(self, mu0_ptr, ld0, mu1_ptr, ld1, k, warm=False, potential_ptr=None, ld_p=0, flow_ptr=None, opts=None):
+        """distance() with the masses (and the optional outputs) resident in HBM (device pointers, column-major with leading dimensions)"""
+        up, lo, res = np.zeros(k), np.zeros(k), np.zeros(k)
+        nit = C.c_int(0)
+        self._call("solve", mu0_ptr, ld0, mu1_ptr, ld1, k, SMG_DEVICE, self._opts(opts), int(bool(warm)), _dp(up), _dp(lo), C.byref(nit), _dp(res),
+                   potential_ptr or None, ld_p or self.n, flow_ptr or None)
+        return EmdResult(up, lo, nit.value, res, None, None)
+
+
+def emd_params(**params):
+    """smg_emd_params with the library's defaults and the given fields"""
+    p = _lib.load().smg_emd_params_default()
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError("unknown earth mover parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 def flow_params(**params):
     """smg_flow_params with the library's defaults and the given fields"""
     p = _lib.load().smg_flow_params_default()

@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow), of the Hodge kernels (smg_debug_hodge) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow), of the Hodge kernels (smg_debug_hodge), of the earth mover's kernels (smg_debug_emd) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -924,6 +924,75 @@ extern "C" int smg_debug_hodge(int op, int nV, int nF, int k, const int* F, cons
                 break;
             }
             default: HIPCHK(launch_hodge_field(nF, k, dF, dW, dn, du, nV, dv, nV, dout, st)); break;
+        }
+        int bad = 0;
+        HIPCHK(S.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_emd(int op, int nV, int nF, int k, const int* F, const double* V, const double* b, const double* phi, const double* state,
+                             const double* rho, double alpha, double* out, int* guard_hits)
+{
+    return guarded("smg_debug_emd", [&]() -> int {
+        const char* who = "smg_debug_emd";
+        if (int rc = emd_check_operands(who, op, nV, nF, k, F, V, b, phi, state, rho, out)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, kk = (size_t)k, nk = n * kk, fk = f * kk, D = sizeof(double);
+        if (nk > (size_t)INT_MAX || 4 * fk > (size_t)INT_MAX) return fail(SMG_ERR_INVALID, "%s: k = %d exceeds the index range", who, k);
+        const bool corners = op == SMG_EMD_RHS || op == SMG_EMD_RESIDUAL;
+        std::vector<int> mp, mi;
+        if (corners) vertex_corner_lists(std::vector<int>(F, F + 3 * f), nV, mp, mi);
+        Scratch S;
+        HIPCHK(S.init());
+        const size_t out_count = op == SMG_EMD_GEOMETRY ? 7 * f + 1 : op == SMG_EMD_RHS ? nk : op == SMG_EMD_UPDATE ? 8 * fk + 2 * kk
+                                 : op == SMG_EMD_FLOW ? 3 * fk : 2 * nk + kk;
+        const size_t state_count = op == SMG_EMD_RHS || op == SMG_EMD_UPDATE ? 4 * fk : op == SMG_EMD_DUAL ? kk : 2 * fk;
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr;
+        double *dV = nullptr, *db = nullptr, *dphi = nullptr, *dstate = nullptr, *drho = nullptr, *dout = nullptr, *dW2 = nullptr, *dA = nullptr, *dpart = nullptr;
+        HIPCHK(S.add(F, nullptr, 3 * f * sizeof(int), &dF));
+        HIPCHK(S.add(V, nullptr, 3 * n * D, &dV));
+        if (b) HIPCHK(S.add(b, nullptr, nk * D, &db));
+        if (phi) HIPCHK(S.add(phi, nullptr, nk * D, &dphi));
+        if (rho) HIPCHK(S.add(rho, nullptr, kk * D, &drho));
+        if (op != SMG_EMD_GEOMETRY) HIPCHK(S.add(state, nullptr, state_count * D, &dstate));
+        if (corners) {
+            HIPCHK(S.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+            HIPCHK(S.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+        }
+        HIPCHK(S.add(nullptr, nullptr, 6 * f * D, &dW2));
+        HIPCHK(S.add(nullptr, nullptr, f * D, &dA));
+        HIPCHK(S.add(nullptr, nullptr, (size_t)fixed_sum_groups(std::max(nV, nF)) * D, &dpart));
+        HIPCHK(S.add(out, out, out_count * D, &dout));
+        hipStream_t st = S.stream();
+        HIPCHK(launch_emd_geometry(dV, dF, nF, dW2, dA, st));
+        switch (op) {
+            case SMG_EMD_GEOMETRY:
+                HIPCHK(hipMemcpyAsync(dout, dW2, 6 * f * D, hipMemcpyDeviceToDevice, st));
+                HIPCHK(hipMemcpyAsync(dout + 6 * f, dA, f * D, hipMemcpyDeviceToDevice, st));
+                HIPCHK(launch_fixed_sum(dA, nF, dpart, dout + 7 * f, st));
+                break;
+            case SMG_EMD_RHS: HIPCHK(launch_emd_rhs(nV, k, nF, dmp, dmi, dW2, dA, dstate, true, db, nV, dout, nV, nullptr, st)); break;
+            case SMG_EMD_UPDATE: {
+                double *up = dout + 6 * fk, *gq = dout + 7 * fk;
+                HIPCHK(hipMemcpyAsync(dout, dstate, 4 * fk * D, hipMemcpyDeviceToDevice, st));
+                HIPCHK(launch_emd_update(nF, k, dF, dW2, dA, dphi, nV, dout, drho, alpha, dout + 4 * fk, up, gq, st));
+                for (int c = 0; c < k; c++) {
+                    HIPCHK(launch_fixed_sum(up + (size_t)c * f, nF, dpart, dout + 8 * fk + c, st));
+                    HIPCHK(launch_fixed_max(gq + (size_t)c * f, nF, dpart, dout + 8 * fk + kk + c, st));
+                }
+                break;
+            }
+            case SMG_EMD_DUAL:
+                HIPCHK(launch_emd_dual(nV, k, db, nV, dphi, nV, drho, dstate, dout, nV, dout + nk, st));
+                for (int c = 0; c < k; c++) HIPCHK(launch_fixed_sum(dout + nk + (size_t)c * n, nV, dpart, dout + 2 * nk + c, st));
+                break;
+            case SMG_EMD_FLOW: HIPCHK(launch_emd_flow(nF, k, dV, dF, dstate, dout, st)); break;
+            default:
+                HIPCHK(launch_emd_rhs(nV, k, nF, dmp, dmi, dW2, dA, dstate, false, db, nV, dout, nV, dout + nk, st));
+                for (int c = 0; c < k; c++) HIPCHK(launch_fixed_sum(dout + nk + (size_t)c * n, nV, dpart, dout + 2 * nk + c, st));
+                break;
         }
         int bad = 0;
         HIPCHK(S.finish(&bad));

@@ -619,4 +619,21 @@ hipError_t launch_conformal_rows(int n, int nF, const double* ang, const double*
 // u[list[i]] = values[i] (values == nullptr: 0)
 hipError_t launch_conformal_fix(int nf, const int* list, const double* values, double* u, hipStream_t st);
 
+// earth mover's distance (smg_emd_device.hip; the maths in smg_emd_inl.hpp).  V: xyz rows; W2, Af: 6, 1 doubles per face; the state ZU: 4 doubles per
+// (face, column), Z then U, column c at c * 4 nF; a field in the faces' frames: 2 doubles per (face, column); rho, gmax2: k doubles on the device;
+// m_ptr / m_idx: the corner lists t = 3 f + i of every vertex, faces ascending --------------------------------------------------------------------
+hipError_t launch_emd_geometry(const double* V, const int* F, int nF, double* W2, double* Af, hipStream_t st);
+// R[c * ldr + v] = sum A_f (W2_fi . X_f) over v's corners - b[c * ldb + v]; state: X is ZU and X_f = Z_f - U_f, else a field in the frames;
+// dsq (nullptr ok): k planes of n, the squares with vertex 0's zero
+hipError_t launch_emd_rhs(int n, int k, int nF, const int* m_ptr, const int* m_idx, const double* W2, const double* Af, const double* X, bool state,
+                          const double* b, int ldb, double* R, int ldr, double* dsq, hipStream_t st);
+// one ADMM update of ZU in place from phi; J2 (nullptr ok): J in the frames; up, gq: k planes of nF, A_f |J_f| and rho^2 |grad phi_f|^2
+hipError_t launch_emd_update(int nF, int k, const int* F, const double* W2, const double* Af, const double* phi, int ldp, double* ZU, const double* rho,
+                             double alpha, double* J2, double* up, double* gq, hipStream_t st);
+// pot = (-rho / max(1, sqrt(gmax2))) phi; terms: k planes of n, b pot
+hipError_t launch_emd_dual(int n, int k, const double* b, int ldb, const double* phi, int ldp, const double* rho, const double* gmax2, double* pot, int ldq,
+                           double* terms, hipStream_t st);
+// out (3 doubles per (face, column)) = J2[0] t1 + J2[1] t2
+hipError_t launch_emd_flow(int nF, int k, const double* V, const int* F, const double* J2, double* out, hipStream_t st);
+
 }  // namespace smg

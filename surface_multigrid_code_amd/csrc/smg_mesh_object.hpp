@@ -95,4 +95,8 @@ int hodge_check_operands(const char* who, int op, int nV, int nF, int k, const i
 int conformal_check_operands(const char* who, int op, int nV, int nF, const int* F, const double* l0, const double* area2, const double* u, const double* d, double t,
                              const double* s, const double* Theta, const int* fixed, int n_fixed, const double* out);
 
+// ---- smg_emd.cpp: what smg_emd_host and smg_debug_emd check alike, in this order: the op and its operands, k, the faces
+int emd_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* b, const double* phi, const double* state,
+                       const double* rho, const double* out);
+
 }  // namespace smg
