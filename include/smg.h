@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 518
+#define SMG_VERSION 519
 
 enum {
     SMG_OK = 0,
@@ -1256,6 +1256,11 @@ int smg_debug_cycle_f32(smg_hierarchy *h, int op, int lv, int k, int pre, int po
 enum { SMG_F32_RESIDUAL_TO_F32 = 0, SMG_F32_ADD_CORRECTION = 1 };
 int smg_debug_convert_f32(smg_hierarchy *h, int op, int k, int done, const double *in64, const float *in32, double *out64, float *out_b32,
                           float *out_u32, int *inputs_changed);
+/* Test hook, read-only: the side of the size gate of the multi-column SELL launches (csrc/smg_device.hip: launch_wide_one) a launch of n_slices
+ * slices takes for a block of kw in {8, 16, 32} columns in THIS process: 1 = one row per lane with the whole row in flight (k_sell_wide<.., R = 1,
+ * U = 8 / 16 / 32>), 0 = the streaming kernel with two rows per lane (R = 2, U = 8).  n_slices * kw <= SMG_WIDE_LAT_MAX (default 16384, read once
+ * per process) selects the former.  Blocks of 64 columns have one variant and do not consult the gate.  Needs no GPU. */
+int smg_debug_wide_latency_variant(int n_slices, int kw);
 /* One launcher of the heat-method geodesics (csrc/smg_geodesics_device.hip), handle-free and guarded like the hooks above.  Blocks are
  * column-major n x k; `in` has leading dimension n, `out` has ld_out >= n and is in/out.  Source lists: src_ptr[0] = 0, k non-empty sets.
  *   SMG_GEO_BASIS       in = V (n x 3 row-major), F (nF x 3) -> W[9f + 3i + d] = ((N x e_i) / (2A))_d, Af[f] = A   (out unused)

@@ -274,6 +274,7 @@ def load():
         "smg_hierarchy_set_coarse_schur": (i, [vp, i, i]),
         "smg_debug_schur_solve_host": (i, [i, ip, ip, dp, dp, dp, ip, ip]),
         "smg_debug_schur_partition": (i, [vp, ip, ip, ip]),
+        "smg_debug_wide_latency_variant": (i, [i, i]),
         "smg_hierarchy_set_block_gs": (i, [vp, i]),
         "smg_hierarchy_set_wave_gs": (i, [vp, i]),
         "smg_hierarchy_set_memory_lean": (i, [vp, i]),

@@ -107,6 +107,9 @@ bool bad_block_shape(int n, int m, int nb) { return n < 1 || m < 1 || m > 64 || 
 
 }  // namespace
 
+// which side of launch_wide_one's size gate a launch sits on (read-only: the launcher's own predicate)
+extern "C" int smg_debug_wide_latency_variant(int n_slices, int kw) { return wide_latency_variant(n_slices, kw) ? 1 : 0; }
+
 extern "C" int smg_debug_eig_gram(int n, int m, int nb_a, const double* Sa, int nb_b, const double* Sb, const double* w, int sym, int done,
                                   double* G, int* groups, int* guard_bad)
 {

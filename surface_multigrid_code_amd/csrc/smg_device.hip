@@ -614,7 +614,7 @@ static long wide_latency_max()
     static const long v = getenv("SMG_WIDE_LAT_MAX") ? atol(getenv("SMG_WIDE_LAT_MAX")) : 16384;
     return v;
 }
-static bool wide_latency_variant(int n_slices, int kw) { return (long)n_slices * kw <= wide_latency_max(); }
+bool wide_latency_variant(int n_slices, int kw) { return (long)n_slices * kw <= wide_latency_max(); }
 
 template <int MODE, int KW, typename T>
 static void launch_wide_one(const SellDev& A, int s_begin, int s_end, int use_order, const T* x, const T* b, T* y,

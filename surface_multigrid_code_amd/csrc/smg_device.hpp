@@ -280,6 +280,7 @@ hipError_t launch_schur_solve(const SchurDev& F, const float* b, float* u, int k
 
 int sell_blocks(int n_slices);  // 4 slices (waves) per 256-thread block
 int sell_wide_blocks(int n_slices, int k);  // partial-sum slots the wide (k >= 8) path needs
+bool wide_latency_variant(int n_slices, int kw);  // a wide launch of n_slices slices, kw < 64 columns: one row per lane (true) or the streaming kernel
 
 // ctrl->sumsq = sum(partials[0..n)) in a fixed order (deterministic).  The buffer must have ss_partials_room() doubles of room behind the n partials
 // (large n: a first launch leaves per-share sums there).
