@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 519
+#define SMG_VERSION 520
 
 enum {
     SMG_OK = 0,
@@ -1052,6 +1052,64 @@ int smg_emd_solve(smg_emd *g, const double *mu0, int ld0, const double *mu1, int
 int smg_emd_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *b, const double *phi, const double *state,
                  const double *rho, double alpha, double *out);
 
+/* ---- Incompressible flow on a surface in vorticity - stream-function form (csrc/smg_fluid.cpp): the state is the
+ * vorticity w, one double per (vertex, column), resident on the device; k columns are k independent simulations and k columns of every solve.
+ * With -L the positive semi-definite cotangent matrix and m_i the barycentric mass (a third of the areas around i):
+ *     (-L) psi = -m (w - wbar),    u_f = n_f x grad psi_f,    dw/dt + u . grad w = viscosity Laplace w
+ * Closed mesh: wbar_c = sum(m w_c) / sum(m) (fixed-order sums) and vertex 0 is known and 0.  Mesh with boundary: wbar = 0 and every boundary
+ * vertex is known and 0, so the boundary is a streamline.  Transport is a finite-volume scheme on the barycentric dual cells: in face (i, j, k),
+ * counter-clockwise, with c = (psi_i + psi_j + psi_k) / 3 the flux out of i's cell into j's is Phi_ij = (psi_i + psi_j) / 2 - c and into k's
+ * Phi_ik = c - (psi_i + psi_k) / 2 -- no geometry is read;
+ *     adv_i = -(1 / m_i) sum_segments (1/2) (Phi - theta |Phi|) (w_nbr - w_i),      rate_i = (1 / m_i) sum_segments max(Phi, 0)
+ * summed in corner-list order (faces ascending, ij before ik); theta = 1 is first-order upwind, 0 the central flux.  Time stepping is SSP
+ * Runge-Kutta in Shu-Osher form: every stage is out = a w_n + b (w_s + dt adv(w_s)) with its own psi_s, (a, b) = (0, 1) | (0, 1), (1/2, 1/2) |
+ * (0, 1), (3/4, 1/4), (1/3, 2/3) for stages = 1 | 2 | 3; every solve is warm-started from the previous stage's psi.  dt > 0 is the fixed step;
+ * dt == 0 takes dt_c = cfl / max_i rate_i of the step's first stage per column, formed on the device (no host read).  A step's reported cfl is
+ * dt_c times the maximum over its stages of max_i rate_i.  viscosity > 0 (needs dt > 0): after the stages (M + viscosity dt (-L)) w_new = m w*
+ * on a second handle without known rows -- the natural boundary condition for w, NOT a no-slip wall -- precomputed at create and by values
+ * again when set_params changes viscosity dt.  Between two stages the host reads one double, |rhs|_F^2: it sets the default tolerance
+ * (opts NULL: 1e-10 |rhs|_F, max_iter 100, per solve) and refuses non-finite input.
+ * smg_fluid_create: h gives the prolongations (any scalar hierarchy on this mesh; one level is accepted when viscosity == 0); they are copied,
+ *   h is not modified.  The checks of DESIGN.md section 21 in their order with a connected mesh, then "no interior vertex", then the parameters:
+ *   theta finite and inside [0, 1], stages in 1..3, viscosity >= 0 (not NaN), dt >= 0, viscosity > 0 needs dt > 0, dt == 0 needs cfl > 0; all
+ *   SMG_ERR_INVALID before the device is touched.
+ * smg_fluid_set_params: the same parameter checks; changing between zero and non-zero viscosity is refused.
+ * smg_fluid_set_vorticity: w is nV x k column-major (leading dimension ld >= nV) in `memspace`; sets k, zeroes psi and the times.
+ * smg_fluid_vorticity: the state into w (nV x k, leading dimension ld, in `memspace`).
+ * smg_fluid_step: n_steps steps.  cfl_his and time (n_steps x k row-major, host, NULL ok): every step's cfl and the time after it; cycles
+ *   (n_steps, host, NULL ok): the loop entries of the step's solves, summed; n_done (host, NULL ok): the completed steps.  A non-finite
+ *   right-hand side ends the call with SMG_ERR_NONFINITE: the state and the times of the last completed step are kept and the histories hold
+ *   n_done rows.  A solve that does not reach its tolerance is not an error.
+ * smg_fluid_stream: solves for the current state (warm-started; the result is kept as the next warm start) and writes psi (nV x k, leading
+ *   dimension ld) in `memspace`.  smg_fluid_velocity: the same solve, then U = n x grad psi as k x nF x 3 row-major in `memspace`.
+ * smg_fluid_diagnostics: the same solve, then out (host, 4 k: four rows of k) = circulation sum m w, enstrophy (1/2) sum m w^2, energy
+ *   (1/2) sum A_f |grad psi_f|^2, and wbar as the solve uses it.
+ * Call refusals, SMG_ERR_INVALID before any launch: a null object or block, k < 1, a bad memspace, a leading dimension below nV, a call before
+ *   smg_fluid_set_vorticity, n_steps < 1.
+ * smg_fluid_set_solver: as smg_arap_set_solver (PCG by default).  smg_fluid_is_closed: 1 when no edge belongs to one face alone.  Nothing is
+ *   allocated after create except the state's blocks, which grow with the largest k seen and are kept, and the histories of the longest call
+ *   (smg_fluid_device_bytes counts them).
+ * smg_fluid_host: the host twin of the kernels on caller arrays (no GPU, the text the kernels compile, the sums in the device's order), with the
+ *   operands and the layouts of smg_debug_fluid below. */
+typedef struct { double theta; int stages; double viscosity, dt, cfl; } smg_fluid_params;
+enum { SMG_FLUID_RHS = 0, SMG_FLUID_ADVECT = 1, SMG_FLUID_VELOCITY = 2, SMG_FLUID_DIAG = 3, SMG_FLUID_DT = 4 };
+typedef struct smg_fluid smg_fluid;
+smg_fluid_params smg_fluid_params_default(void);           /* 0.0, 3, 0.0, 0.0, 0.5 */
+int smg_fluid_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const smg_fluid_params *p, smg_fluid **out);
+void smg_fluid_destroy(smg_fluid *g);
+int smg_fluid_set_params(smg_fluid *g, const smg_fluid_params *p);
+int smg_fluid_set_solver(smg_fluid *g, int pcg);
+int smg_fluid_is_closed(const smg_fluid *g);
+long long smg_fluid_device_bytes(const smg_fluid *g);
+int smg_fluid_set_vorticity(smg_fluid *g, const double *w, int ld, int k, int memspace);
+int smg_fluid_vorticity(smg_fluid *g, double *w, int ld, int memspace);
+int smg_fluid_step(smg_fluid *g, int n_steps, const smg_solve_opts *opts, double *cfl_his, double *time, int *cycles, int *n_done);
+int smg_fluid_stream(smg_fluid *g, const smg_solve_opts *opts, double *psi, int ld, int memspace);
+int smg_fluid_velocity(smg_fluid *g, const smg_solve_opts *opts, double *U, int memspace);
+int smg_fluid_diagnostics(smg_fluid *g, const smg_solve_opts *opts, double *out);
+int smg_fluid_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *w, const double *psi, const double *wn, double a,
+                   double b, const double *dt, double theta, int rates_only, double *out);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -1431,6 +1489,27 @@ int smg_debug_conformal(int op, int nV, int nF, const int *F, const double *l0, 
  * SMG_ERR_INVALID for an unknown op, nV < 1, nF < 1, a missing operand, k < 1, a face index out of range; SMG_ERR_NO_DEVICE without a GPU. */
 int smg_debug_emd(int op, int nV, int nF, int k, const int *F, const double *V, const double *b, const double *phi, const double *state,
                   const double *rho, double alpha, double *out, int *guard_hits);
+
+/* One launcher of the surface fluid (csrc/smg_fluid_device.hip), handle-free and guarded like the hooks above.  F: nF x 3; V: nV x 3 row-major;
+ * w, psi, wn: nV x k column-major with leading dimension nV; dt: k; every array is host.  k_hodge_geometry and k_fluid_mass run first; the known
+ * rows are the boundary vertices, or vertex 0 on a closed mesh, and wbar is 0 on a mesh with boundary.
+ *   SMG_FLUID_RHS       V, w -> out = m (nV), its sum (1), the terms m w (k planes of nV), their sums (k), r (nV x k column-major), its squares
+ *                       with the known rows' zero (k planes of nV), their one sum (1)
+ *   SMG_FLUID_ADVECT    V, psi, w, wn, a, b, dt, theta -> out = the stage's output (nV x k column-major), the rates (k planes of nV), the terms
+ *                       m out (k planes of nV), the rates' maxima (k), the terms' sums (k); rates_only != 0: V, psi -> the rates, their maxima
+ *   SMG_FLUID_VELOCITY  V, psi -> out = U (k sets of nF x 3), the terms (1/2) A |grad psi|^2 (k planes of nF), their sums (k)
+ *   SMG_FLUID_DIAG      V, w -> out = the terms m w and (1/2) m w^2 (k planes of nV each), their sums (k each)
+ *   SMG_FLUID_DT        w = the maxima of three stages (3 x k row-major), psi = the times (k), a = cfl -> out = dt (k) of the first row, the
+ *                       three-stage step's cfl (k), the times after it (k)
+ * SMG_ERR_INVALID for an unknown op, nV < 1, nF < 1, a missing operand, k < 1, theta outside [0, 1], a face index out of range;
+ * SMG_ERR_NO_DEVICE without a GPU. */
+int smg_debug_fluid(int op, int nV, int nF, int k, const int *F, const double *V, const double *w, const double *psi, const double *wn, double a,
+                    double b, const double *dt, double theta, int rates_only, double *out, int *guard_hits);
+/* The time of one launcher of the surface fluid alone, for tools/fluid_time.py: SMG_FLUID_RHS, _ADVECT (rates_only as above), _VELOCITY or _DIAG on
+ * device blocks of zeros of k columns over the mesh (F, V: host), launched `reps` times back to back on one stream between two events after one
+ * launch that is not timed; *ms = the mean time of a launch in milliseconds.  SMG_ERR_INVALID for another op, nV < 1, nF < 1, a missing array,
+ * k < 1, reps < 1, a face index out of range; SMG_ERR_NO_DEVICE without a GPU. */
+int smg_debug_fluid_time(int op, int nV, int nF, int k, const int *F, const double *V, int rates_only, int reps, double *ms);
 
 /* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
  * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.

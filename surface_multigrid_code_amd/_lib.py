@@ -47,6 +47,10 @@ class EmdParamsC(C.Structure):
                 ("inner_rel_tol", C.c_double)]
 
 
+class FluidParamsC(C.Structure):
+    _fields_ = [("theta", C.c_double), ("stages", C.c_int), ("viscosity", C.c_double), ("dt", C.c_double), ("cfl", C.c_double)]
+
+
 _lib = None
 
 
@@ -238,6 +242,22 @@ def load():
         "smg_emd_solve": (i, [vp, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), i, dp, dp, ip, dp, vp, i, vp]),
         "smg_emd_host": (i, [i, i, i, i, ip, dp, dp, dp, dp, dp, d, dp]),
         "smg_debug_emd": (i, [i, i, i, i, ip, dp, dp, dp, dp, dp, d, dp, ip]),
+        "smg_fluid_params_default": (FluidParamsC, []),
+        "smg_fluid_create": (i, [vp, dp, i, ip, i, C.POINTER(FluidParamsC), C.POINTER(vp)]),
+        "smg_fluid_destroy": (None, [vp]),
+        "smg_fluid_set_params": (i, [vp, C.POINTER(FluidParamsC)]),
+        "smg_fluid_set_solver": (i, [vp, i]),
+        "smg_fluid_is_closed": (i, [vp]),
+        "smg_fluid_device_bytes": (C.c_longlong, [vp]),
+        "smg_fluid_set_vorticity": (i, [vp, vp, i, i, i]),
+        "smg_fluid_vorticity": (i, [vp, vp, i, i]),
+        "smg_fluid_step": (i, [vp, i, C.POINTER(SolveOptsC), dp, dp, ip, ip]),
+        "smg_fluid_stream": (i, [vp, C.POINTER(SolveOptsC), vp, i, i]),
+        "smg_fluid_velocity": (i, [vp, C.POINTER(SolveOptsC), vp, i]),
+        "smg_fluid_diagnostics": (i, [vp, C.POINTER(SolveOptsC), dp]),
+        "smg_fluid_host": (i, [i, i, i, i, ip, dp, dp, dp, dp, d, d, dp, d, i, dp]),
+        "smg_debug_fluid": (i, [i, i, i, i, ip, dp, dp, dp, dp, d, d, dp, d, i, dp, ip]),
+        "smg_debug_fluid_time": (i, [i, i, i, i, ip, dp, i, i, dp]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

@@ -1407,6 +1407,96 @@ def emd_params(**params):
     return p
 
 
+class SurfaceFluid(_MeshObject):
+    """Incompressible flow on a surface in vorticity - stream-function form (include/smg.h: smg_fluid_*): (-L) psi = -m (w - wbar),
+    u = n x grad psi, a finite-volume transport of w on the barycentric dual cells, SSP Runge-Kutta stages, optional implicit viscosity.  The
+    state w (n x k: k independent simulations) lives on the device; every stage is ONE warm-started k-column solve of -L and one vertex kernel.
+    On a mesh with boundary psi = 0 there (the boundary is a streamline); the viscous solve has the natural boundary condition for w, not a
+    no-slip wall.
+
+    hierarchy: a scalar Hierarchy whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.  params: theta, stages,
+    viscosity, dt, cfl."""
+
+    _prefix = "smg_fluid_"
+    f = property(lambda self: self.o)
+
+    def __init__(self, hierarchy, V, F, **params):
+        self.params = fluid_params(**params)
+        self.k = 0
+        self._create(hierarchy, V, F, C.byref(self.params))
+
+    @property
+    def closed(self):
+        return bool(self.L.smg_fluid_is_closed(self.o))
+
+    def set_params(self, **params):
+        """theta, stages, viscosity, dt, cfl of the following steps; zero and non-zero viscosity cannot change"""
+        p = _lib.FluidParamsC(*[getattr(self.params, f) for f, _ in _lib.FluidParamsC._fields_])
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise TypeError("unknown fluid parameter %r" % k)
+            setattr(p, k, v)
+        self._call("set_params", C.byref(p))
+        self.params = p
+
+    def set_vorticity(self, w):
+        """w: n or n x k; sets k, zeroes psi and the times"""
+        w = np.asfortranarray(np.asarray(w, dtype=np.float64).reshape(self.n, -1))
+        self._call("set_vorticity", w.ctypes.data, self.n, w.shape[1], SMG_HOST)
+        self.k = w.shape[1]
+
+    def set_vorticity_device(self, w_ptr, ld, k):
+        self._call("set_vorticity", w_ptr, ld, k, SMG_DEVICE)
+        self.k = k
+
+    def step(self, n_steps=1, opts=None):
+        """n_steps steps -> (cfl n_done x k, time n_done x k, cycles n_done): every step's cfl, the time after it, the loop entries of its solves"""
+        k = max(self.k, 1)
+        cfl, time, cyc = np.zeros((max(n_steps, 1), k)), np.zeros((max(n_steps, 1), k)), np.zeros(max(n_steps, 1), dtype=np.int32)
+        nd = C.c_int(0)
+        try:
+            self._call("step", int(n_steps), self._opts(opts), _dp(cfl), _dp(time), _ip(cyc), C.byref(nd))
+        finally:
+            self.n_done = nd.value
+        return cfl[:nd.value].copy(), time[:nd.value].copy(), cyc[:nd.value].copy()
+
+    def vorticity(self):
+        w = np.zeros((self.n, max(self.k, 1)), order="F")
+        self._call("vorticity", w.ctypes.data, self.n, SMG_HOST)
+        return w
+
+    def vorticity_device(self, w_ptr, ld):
+        self._call("vorticity", w_ptr, ld, SMG_DEVICE)
+
+    def stream(self, opts=None):
+        """psi (n x k) of the current state"""
+        psi = np.zeros((self.n, max(self.k, 1)), order="F")
+        self._call("stream", self._opts(opts), psi.ctypes.data, self.n, SMG_HOST)
+        return psi
+
+    def velocity(self, opts=None):
+        """U (k x nF x 3) = n x grad psi of the current state"""
+        U = np.zeros((max(self.k, 1), self.nF, 3))
+        self._call("velocity", self._opts(opts), U.ctypes.data, SMG_HOST)
+        return U
+
+    def diagnostics(self, opts=None):
+        """dict(circulation, enstrophy, energy, wbar), k each"""
+        d = np.zeros((4, max(self.k, 1)))
+        self._call("diagnostics", self._opts(opts), _dp(d))
+        return dict(circulation=d[0].copy(), enstrophy=d[1].copy(), energy=d[2].copy(), wbar=d[3].copy())
+
+
+def fluid_params(**params):
+    """smg_fluid_params with the library's defaults and the given fields"""
+    p = _lib.load().smg_fluid_params_default()
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError("unknown fluid parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 def flow_params(**params):
     """smg_flow_params with the library's defaults and the given fields"""
     p = _lib.load().smg_flow_params_default()

@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow), of the Hodge kernels (smg_debug_hodge), of the earth mover's kernels (smg_debug_emd) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow), of the Hodge kernels (smg_debug_hodge), of the earth mover's kernels (smg_debug_emd), of the surface-fluid kernels (smg_debug_fluid) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "smg_device.hpp"
+#include "smg_fluid_inl.hpp"
 #include "smg_internal.hpp"
 #include "smg_membrane_inl.hpp"
 #include "smg_mesh.hpp"
@@ -1000,6 +1001,167 @@ extern "C" int smg_debug_emd(int op, int nV, int nF, int k, const int* F, const 
         int bad = 0;
         HIPCHK(S.finish(&bad));
         if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_fluid(int op, int nV, int nF, int k, const int* F, const double* V, const double* w, const double* psi, const double* wn, double a,
+                               double b, const double* dt, double theta, int rates_only, double* out, int* guard_hits)
+{
+    return guarded("smg_debug_fluid", [&]() -> int {
+        const char* who = "smg_debug_fluid";
+        if (int rc = fluid_check_operands(who, op, nV, nF, k, F, V, w, psi, wn, dt, theta, rates_only, out)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, kk = (size_t)k, nk = n * kk, fk = f * kk, D = sizeof(double);
+        if (nk > (size_t)INT_MAX || 3 * fk > (size_t)INT_MAX) return fail(SMG_ERR_INVALID, "%s: k = %d exceeds the index range", who, k);
+        const bool full = op == SMG_FLUID_ADVECT && !rates_only;
+        Scratch S;
+        HIPCHK(S.init());
+        hipStream_t st = S.stream();
+        if (op == SMG_FLUID_DT) {
+            double *drm = nullptr, *dtime = nullptr, *dout = nullptr;
+            HIPCHK(S.add(w, nullptr, 3 * kk * D, &drm));
+            HIPCHK(S.add(psi, nullptr, kk * D, &dtime));
+            HIPCHK(S.add(out, out, 3 * kk * D, &dout));
+            HIPCHK(launch_fluid_dt(0, k, 3, a, drm, dout, nullptr, nullptr, nullptr, st));
+            HIPCHK(launch_fluid_dt(1, k, 3, a, drm, dout, dtime, dout + kk, dout + 2 * kk, st));
+            int bad = 0;
+            HIPCHK(S.finish(&bad));
+            if (guard_hits) *guard_hits = bad;
+            return SMG_OK;
+        }
+        std::vector<int> mp, mi, known;
+        vertex_corner_lists(std::vector<int>(F, F + 3 * f), nV, mp, mi);
+        const int nb = fluid_known_rows(nV, nF, F, known);
+        const size_t out_count = op == SMG_FLUID_RHS ? n + 1 + 3 * nk + kk + 1 : op == SMG_FLUID_ADVECT ? (full ? 3 * nk + 2 * kk : nk + kk)
+                                 : op == SMG_FLUID_VELOCITY ? 4 * fk + kk : 2 * nk + 2 * kk;
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr, *dknown = nullptr;
+        double *dV = nullptr, *dw = nullptr, *dpsi = nullptr, *dwn = nullptr, *ddt = nullptr, *dout = nullptr, *dW = nullptr, *dn = nullptr, *dA = nullptr,
+               *dm = nullptr, *dpart = nullptr, *dew = nullptr;
+        HIPCHK(S.add(F, nullptr, 3 * f * sizeof(int), &dF));
+        HIPCHK(S.add(V, nullptr, 3 * n * D, &dV));
+        HIPCHK(S.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+        HIPCHK(S.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+        HIPCHK(S.add(known.data(), nullptr, n * sizeof(int), &dknown));
+        if (w && op != SMG_FLUID_VELOCITY && (op != SMG_FLUID_ADVECT || full)) HIPCHK(S.add(w, nullptr, nk * D, &dw));
+        if (psi && (op == SMG_FLUID_ADVECT || op == SMG_FLUID_VELOCITY)) HIPCHK(S.add(psi, nullptr, nk * D, &dpsi));
+        if (full) {
+            HIPCHK(S.add(wn, nullptr, nk * D, &dwn));
+            HIPCHK(S.add(dt, nullptr, kk * D, &ddt));
+        }
+        HIPCHK(S.add(nullptr, nullptr, 9 * f * D, &dW));
+        HIPCHK(S.add(nullptr, nullptr, 3 * f * D, &dn));
+        HIPCHK(S.add(nullptr, nullptr, f * D, &dA));
+        HIPCHK(S.add(nullptr, nullptr, n * D, &dm));
+        HIPCHK(S.add(nullptr, nullptr, (size_t)fixed_sum_groups((int)std::max(nk, f)) * D, &dpart));
+        if (op == SMG_FLUID_RHS) HIPCHK(S.add(nullptr, nullptr, nk * D, &dew));
+        HIPCHK(S.add(out, out, out_count * D, &dout));
+        HIPCHK(launch_hodge_geometry(dV, dF, nF, dW, dn, dA, st));
+        HIPCHK(launch_fluid_mass(nV, dmp, dmi, dA, dm, st));
+        switch (op) {
+            case SMG_FLUID_RHS: {
+                double *msum = dout + n, *mw = dout + n + 1, *mwsum = mw + nk, *R = mwsum + kk, *rsq = R + nk;
+                HIPCHK(hipMemcpyAsync(dout, dm, n * D, hipMemcpyDeviceToDevice, st));
+                HIPCHK(launch_fixed_sum(dm, nV, dpart, msum, st));
+                HIPCHK(launch_fluid_diag(nV, k, dm, dw, nV, mw, dew, st));
+                for (int c = 0; c < k; c++) HIPCHK(launch_fixed_sum(mw + (size_t)c * n, nV, dpart, mwsum + c, st));
+                HIPCHK(launch_fluid_rhs(nV, k, dm, dknown, dw, nV, nb > 0 ? nullptr : mwsum, msum, R, nV, rsq, st));
+                HIPCHK(launch_fixed_sum(rsq, (int)nk, dpart, rsq + nk, st));
+                break;
+            }
+            case SMG_FLUID_ADVECT:
+                if (!full) {
+                    HIPCHK(launch_fluid_advect(nV, k, dF, dmp, dmi, dm, dpsi, nV, nullptr, nV, nullptr, nV, a, b, nullptr, theta, nullptr, nV, dout, nullptr,
+                                               true, st));
+                    for (int c = 0; c < k; c++) HIPCHK(launch_fixed_max(dout + (size_t)c * n, nV, dpart, dout + nk + c, st));
+                } else {
+                    double *rate = dout + nk, *mw = dout + 2 * nk;
+                    HIPCHK(launch_fluid_advect(nV, k, dF, dmp, dmi, dm, dpsi, nV, dw, nV, dwn, nV, a, b, ddt, theta, dout, nV, rate, mw, false, st));
+                    for (int c = 0; c < k; c++) {
+                        HIPCHK(launch_fixed_max(rate + (size_t)c * n, nV, dpart, dout + 3 * nk + c, st));
+                        HIPCHK(launch_fixed_sum(mw + (size_t)c * n, nV, dpart, dout + 3 * nk + kk + c, st));
+                    }
+                }
+                break;
+            case SMG_FLUID_VELOCITY:
+                HIPCHK(launch_fluid_velocity(nF, k, dF, dW, dn, dA, dpsi, nV, dout, dout + 3 * fk, st));
+                for (int c = 0; c < k; c++) HIPCHK(launch_fixed_sum(dout + 3 * fk + (size_t)c * f, nF, dpart, dout + 4 * fk + c, st));
+                break;
+            default:
+                HIPCHK(launch_fluid_diag(nV, k, dm, dw, nV, dout, dout + nk, st));
+                for (int c = 0; c < k; c++) {
+                    HIPCHK(launch_fixed_sum(dout + (size_t)c * n, nV, dpart, dout + 2 * nk + c, st));
+                    HIPCHK(launch_fixed_sum(dout + nk + (size_t)c * n, nV, dpart, dout + 2 * nk + kk + c, st));
+                }
+                break;
+        }
+        int bad = 0;
+        HIPCHK(S.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_fluid_time(int op, int nV, int nF, int k, const int* F, const double* V, int rates_only, int reps, double* ms)
+{
+    return guarded("smg_debug_fluid_time", [&]() -> int {
+        const char* who = "smg_debug_fluid_time";
+        if (op < SMG_FLUID_RHS || op > SMG_FLUID_DIAG || nV < 1 || nF < 1 || !F || !V || !ms) return fail(SMG_ERR_INVALID, "%s: bad arguments", who);
+        if (k < 1 || reps < 1) return fail(SMG_ERR_INVALID, "%s: k = %d, reps = %d, at least 1 each is needed", who, k, reps);
+        if (int rc = check_faces(who, F, nF, nV)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, kk = (size_t)k, nk = n * kk, fk = f * kk, D = sizeof(double);
+        if (nk > (size_t)INT_MAX || 3 * fk > (size_t)INT_MAX) return fail(SMG_ERR_INVALID, "%s: k = %d exceeds the index range", who, k);
+        std::vector<int> mp, mi, known;
+        vertex_corner_lists(std::vector<int>(F, F + 3 * f), nV, mp, mi);
+        fluid_known_rows(nV, nF, F, known);
+        struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void)hipEventDestroy(e); } } t0, t1;
+        Scratch S;                                                           // for its stream alone
+        HIPCHK(S.init());
+        hipStream_t st = S.stream();
+        DevBuf<int> dF, dmp, dmi, dknown;
+        DevBuf<double> dV, dW, dn, dA, dm, dsum, dk, dpart, w, psi, wn, out, rate, mw, U;
+        HIPCHK(dF.upload(std::vector<int>(F, F + 3 * f)));
+        HIPCHK(dmp.upload(mp));
+        HIPCHK(dmi.upload(mi));
+        HIPCHK(dknown.upload(known));
+        HIPCHK(dV.upload(std::vector<double>(V, V + 3 * n)));
+        HIPCHK(dW.alloc(9 * f));
+        HIPCHK(dn.alloc(3 * f));
+        HIPCHK(dA.alloc(f));
+        HIPCHK(dm.alloc(n));
+        HIPCHK(dsum.alloc(1));
+        HIPCHK(dk.alloc(kk));
+        HIPCHK(dpart.alloc((size_t)fixed_sum_groups(nV)));
+        for (DevBuf<double>* b : {&w, &psi, &wn, &out, &rate, &mw}) {        // zeros: the operands' values do not change what a launch moves
+            HIPCHK(b->alloc(std::max(nk, fk)));
+            HIPCHK(hipMemsetAsync(b->p, 0, std::max(nk, fk) * D, st));
+        }
+        if (op == SMG_FLUID_VELOCITY) HIPCHK(U.alloc(3 * fk));
+        HIPCHK(hipMemsetAsync(dk.p, 0, kk * D, st));
+        HIPCHK(launch_hodge_geometry(dV.p, dF.p, nF, dW.p, dn.p, dA.p, st));
+        HIPCHK(launch_fluid_mass(nV, dmp.p, dmi.p, dA.p, dm.p, st));
+        HIPCHK(launch_fixed_sum(dm.p, nV, dpart.p, dsum.p, st));
+        auto launch = [&]() -> hipError_t {
+            switch (op) {
+                case SMG_FLUID_RHS: return launch_fluid_rhs(nV, k, dm.p, dknown.p, w.p, nV, dk.p, dsum.p, out.p, nV, rate.p, st);
+                case SMG_FLUID_ADVECT:
+                    return launch_fluid_advect(nV, k, dF.p, dmp.p, dmi.p, dm.p, psi.p, nV, w.p, nV, wn.p, nV, 0.75, 0.25, dk.p, 0.0, out.p, nV, rate.p, mw.p,
+                                               rates_only != 0, st);
+                case SMG_FLUID_VELOCITY: return launch_fluid_velocity(nF, k, dF.p, dW.p, dn.p, dA.p, psi.p, nV, U.p, rate.p, st);
+                default: return launch_fluid_diag(nV, k, dm.p, w.p, nV, out.p, mw.p, st);
+            }
+        };
+        HIPCHK(hipEventCreate(&t0.e));
+        HIPCHK(hipEventCreate(&t1.e));
+        HIPCHK(launch());                                                    // one launch that is not timed
+        HIPCHK(hipEventRecord(t0.e, st));
+        for (int r = 0; r < reps; r++) HIPCHK(launch());
+        HIPCHK(hipEventRecord(t1.e, st));
+        HIPCHK(hipStreamSynchronize(st));
+        float total = 0.0f;
+        HIPCHK(hipEventElapsedTime(&total, t0.e, t1.e));
+        *ms = (double)total / reps;
         return SMG_OK;
     });
 }

@@ -637,4 +637,25 @@ hipError_t launch_emd_dual(int n, int k, const double* b, int ldb, const double*
 // out (3 doubles per (face, column)) = J2[0] t1 + J2[1] t2
 hipError_t launch_emd_flow(int nF, int k, const double* V, const int* F, const double* J2, double* out, hipStream_t st);
 
+// incompressible flow on a surface, vorticity form (smg_fluid_device.hip; the maths in smg_fluid_inl.hpp).  W, nrm, Af: launch_hodge_geometry's; m:
+// the barycentric masses; known: 1 on the rows whose psi is given; dt, mwsum, rmax: k doubles per row on the device; per-vertex term planes are k
+// planes of n; m_ptr / m_idx: the corner lists t = 3 f + i of every vertex, faces ascending -----------------------------------------------------
+hipError_t launch_fluid_mass(int n, const int* m_ptr, const int* m_idx, const double* Af, double* m, hipStream_t st);
+// R[c * ldr + v] = 0.0 - m_v (w - wbar_c), wbar_c = mwsum[c] / *msum (mwsum nullptr: 0.0); rsq: the squares, 0.0 on the known rows
+hipError_t launch_fluid_rhs(int n, int k, const double* m, const int* known, const double* w, int ldw, const double* mwsum, const double* msum, double* R,
+                            int ldr, double* rsq, hipStream_t st);
+// one stage: out = a wn + b (w + dt_c adv(psi, w)), rate = the outflow over m, mw = m out; rates_only: rate alone (w, wn, dt, out, mw unread).
+// out must not be w (refused)
+hipError_t launch_fluid_advect(int n, int k, const int* F, const int* m_ptr, const int* m_idx, const double* m, const double* psi, int ldp,
+                               const double* w, int ldw, const double* wn, int ldn, double a, double b, const double* dt, double theta, double* out,
+                               int ldo, double* rate, double* mw, bool rates_only, hipStream_t st);
+// op 0: dt[c] = cfl / rmax[c] (0.0 where rmax is not > 0); op 1: his_cfl[c] = dt[c] max_s rmax[s * k + c], time[c] += dt[c], his_time[c] = time[c]
+hipError_t launch_fluid_dt(int op, int k, int stages, double cfl, const double* rmax, double* dt, double* time, double* his_cfl, double* his_time,
+                           hipStream_t st);
+// U (nullptr ok; 3 doubles per (face, column)) = n x grad psi; terms: k planes of nF, 0.5 (A_f |grad psi_f|^2)
+hipError_t launch_fluid_velocity(int nF, int k, const int* F, const double* W, const double* nrm, const double* Af, const double* psi, int ldp, double* U,
+                                 double* terms, hipStream_t st);
+// mw = m w, ew (nullptr ok) = 0.5 ((m w) w): k planes of n each
+hipError_t launch_fluid_diag(int n, int k, const double* m, const double* w, int ldw, double* mw, double* ew, hipStream_t st);
+
 }  // namespace smg

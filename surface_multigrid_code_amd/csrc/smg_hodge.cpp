@@ -12,7 +12,6 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <map>
 #include <memory>
 #include <utility>
 #include <vector>
@@ -51,24 +50,6 @@ int hodge_check_operands(const char* who, int op, int nV, int nF, int k, const i
 }  // namespace smg
 
 namespace {
-
-// the vertices of the edges that one face alone holds, ascending
-std::vector<int> boundary_vertices(const int* F, int nF, int nV)
-{
-    std::map<std::pair<int, int>, int> count;
-    for (size_t f = 0; f < (size_t)nF; f++)
-        for (int j = 0; j < 3; j++) {
-            const int a = F[3 * f + j], b = F[3 * f + (j + 1) % 3];
-            count[{std::min(a, b), std::max(a, b)}]++;
-        }
-    std::vector<char> on((size_t)nV, 0);
-    for (const auto& e : count)
-        if (e.second == 1) on[(size_t)e.first.first] = on[(size_t)e.first.second] = 1;
-    std::vector<int> out;
-    for (int v = 0; v < nV; v++)
-        if (on[(size_t)v]) out.push_back(v);
-    return out;
-}
 
 int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, int nF, smg_hodge** out)
 {

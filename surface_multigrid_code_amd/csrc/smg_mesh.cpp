@@ -327,6 +327,29 @@ AssemblyPlan make_assembly_plan(const std::vector<int>& F, int nV)
     return P;
 }
 
+std::vector<int> boundary_vertices(const int* F, int nF, int nV)
+{
+    std::vector<std::pair<int, int>> edges;                      // every face's edges, smaller vertex first; sorted, an edge of one face stands alone
+    edges.reserve(3 * (size_t)nF);
+    for (size_t f = 0; f < (size_t)nF; f++)
+        for (int j = 0; j < 3; j++) {
+            const int a = F[3 * f + j], b = F[3 * f + (j + 1) % 3];
+            edges.emplace_back(std::min(a, b), std::max(a, b));
+        }
+    std::sort(edges.begin(), edges.end());
+    std::vector<char> on((size_t)nV, 0);
+    for (size_t i = 0; i < edges.size();) {
+        size_t j = i + 1;
+        while (j < edges.size() && edges[j] == edges[i]) j++;
+        if (j - i == 1) on[(size_t)edges[i].first] = on[(size_t)edges[i].second] = 1;
+        i = j;
+    }
+    std::vector<int> out;
+    for (int v = 0; v < nV; v++)
+        if (on[(size_t)v]) out.push_back(v);
+    return out;
+}
+
 void vertex_corner_lists(const std::vector<int>& F, int nV, std::vector<int>& m_ptr, std::vector<int>& m_idx)
 {
     const int nF = (int)(F.size() / 3);

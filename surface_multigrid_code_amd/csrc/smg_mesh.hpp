@@ -64,6 +64,8 @@ struct AssemblyPlan {
 AssemblyPlan make_assembly_plan(const std::vector<int>& F, int nV);
 // per vertex the corners t = 3f + c that touch it, faces ascending (AssemblyPlan::m_ptr / m_idx; the heat-method divergence gathers in this order)
 void vertex_corner_lists(const std::vector<int>& F, int nV, std::vector<int>& m_ptr, std::vector<int>& m_idx);
+// the vertices of the edges that one face alone holds, ascending (empty: a closed mesh); F: nF x 3 with every index in [0, nV)
+std::vector<int> boundary_vertices(const int* F, int nF, int nV);
 // per face f the faces that share at least one vertex with it, without f, ascending and duplicate-free (CSR: nb_ptr has nF + 1 entries), from
 // the corner lists; false when the entries do not fit an int
 bool face_neighbours(const std::vector<int>& F, const std::vector<int>& m_ptr, const std::vector<int>& m_idx, std::vector<int>& nb_ptr,

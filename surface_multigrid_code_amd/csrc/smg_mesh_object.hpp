@@ -99,4 +99,8 @@ int conformal_check_operands(const char* who, int op, int nV, int nF, const int*
 int emd_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* b, const double* phi, const double* state,
                        const double* rho, const double* out);
 
+// ---- smg_fluid.cpp: what smg_fluid_host and smg_debug_fluid check alike, in this order: the op and its operands, k, theta (a full stage), the faces
+int fluid_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* w, const double* psi, const double* wn,
+                         const double* dt, double theta, int rates_only, const double* out);
+
 }  // namespace smg
