@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 520
+#define SMG_VERSION 521
 
 enum {
     SMG_OK = 0,
@@ -1319,6 +1319,31 @@ int smg_debug_convert_f32(smg_hierarchy *h, int op, int k, int done, const doubl
  * U = 8 / 16 / 32>), 0 = the streaming kernel with two rows per lane (R = 2, U = 8).  n_slices * kw <= SMG_WIDE_LAT_MAX (default 16384, read once
  * per process) selects the former.  Blocks of 64 columns have one variant and do not consult the gate.  Needs no GPU. */
 int smg_debug_wide_latency_variant(int n_slices, int kw);
+/* Test hooks, read-only, no device work: which instantiations of the wave Gauss-Seidel kernel k_wgs<NBMAX, KB, RIMI> (csrc/smg_wgs_device.hip) run in
+ * THIS process.  They answer through the functions launch_wgs itself calls, whose knobs (SMG_WGS_KB2_MAX_PIECES, default 1600; SMG_WGS_KB_SMALL,
+ * default 1; SMG_WGS_KB_BIG, default 4) are read once per process.
+ * smg_debug_wgs_launches: the launches one piece colour of a sweep takes for k columns on a plan of n_pieces pieces whose widest row needs nb_max
+ *   batches of 8 entry slots and whose rim pitch is rim_pitch: *nbmax = 3 / 5 / 8 (nb_max <= 3, <= 5, <= 8), *rimi = 2 / 4 / 7 (rim_pitch 128 / 256 /
+ *   448), launches[2 i], launches[2 i + 1] = (KB columns per lane, groups in the grid's second dimension) of launch i for i < min(*n_launches, cap).
+ *   The launches cover columns 0 .. k - 1 in order.  SMG_ERR_INVALID for a plan the kernel has no variant for.  Needs no GPU.
+ * smg_debug_wgs_level_plan: n_pieces, nb_max and rim_pitch of the plan of level lv.  from_host 0: the plan relax() sweeps with for k columns in the
+ *   handle's present state; nothing is built -- *n_pieces = 0 where the level sweeps another way (colour launches, the one-launch relax) or no sweep
+ *   has asked for the plan yet.  from_host 1: the plan as the first sweep would build it, built on the host and dropped (no GPU needed after the
+ *   host half of smg_precompute); *n_pieces = 0: the level does not qualify (a row of more than 64 off-diagonal entries, a rim above 448 rows). */
+int smg_debug_wgs_launches(int n_pieces, int nb_max, int rim_pitch, int k, int *nbmax, int *rimi, int *launches, int cap, int *n_launches);
+int smg_debug_wgs_level_plan(smg_hierarchy *h, int lv, int k, int from_host, int *n_pieces, int *nb_max, int *rim_pitch);
+/* Test hook, read-only, no device work: the launches that y = A x (mode 0) or y = b - A x (mode 1) with 1 <= k <= 4 fp64 columns -- one narrow group of
+ * launch_sell_mode (csrc/smg_device.hip) -- take on the device image `which` (0 A, 1 P, 2 PT) of level lv in THIS process, through the function the
+ * launcher itself calls (SMG_DEEP, SMG_DEEP_MIN_W: read once per process).  *w_max: panel columns of the image's widest slice;
+ * launches[2 i] = columns per lane, launches[2 i + 1] = 3 / 5 / 8, the row-width class of k_sell_deep (w_max <= 24: at most 3 columns per lane,
+ * <= 40: 2, <= 64: 1 -- four columns go 3 + 1, 2 + 2 or 1 + 1 + 1 + 1), or 0: k_sell.  Needs the device half of smg_precompute. */
+int smg_debug_deep_launches(const smg_hierarchy *h, int lv, int which, int mode, int k, int *w_max, int *launches, int cap, int *n_launches);
+/* Test hook, read-only, no device work: *wpb = the waves per workgroup (2, 4 or 8) of a one-column Gauss-Seidel colour launch of n_slices slices on
+ * the image level lv sweeps on, in THIS process, through the function launch_narrow itself branches on: SMG_GS_WPB (default 4) = 2 / 8 selects
+ * k_sell<SELL_GS, 1, T, 7, 2 / 8> where the image has fixed-pitch panels of lower width 7, the launch is not confined to one XCD (SMG_ONE_XCD_MAX) and
+ * does not request the whole pitch ahead (SMG_PITCH_SPEC_MAX); 4 otherwise.  *stride, *w_lo (optional): the image's panel pitch (0: compact panels)
+ * and lower width.  Needs the device half of smg_precompute. */
+int smg_debug_gs_colour_wpb(const smg_hierarchy *h, int lv, int n_slices, int *wpb, int *stride, int *w_lo);
 /* One launcher of the heat-method geodesics (csrc/smg_geodesics_device.hip), handle-free and guarded like the hooks above.  Blocks are
  * column-major n x k; `in` has leading dimension n, `out` has ld_out >= n and is in/out.  Source lists: src_ptr[0] = 0, k non-empty sets.
  *   SMG_GEO_BASIS       in = V (n x 3 row-major), F (nF x 3) -> W[9f + 3i + d] = ((N x e_i) / (2A))_d, Af[f] = A   (out unused)

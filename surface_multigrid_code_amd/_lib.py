@@ -295,6 +295,10 @@ def load():
         "smg_debug_schur_solve_host": (i, [i, ip, ip, dp, dp, dp, ip, ip]),
         "smg_debug_schur_partition": (i, [vp, ip, ip, ip]),
         "smg_debug_wide_latency_variant": (i, [i, i]),
+        "smg_debug_wgs_launches": (i, [i, i, i, i, ip, ip, ip, i, ip]),
+        "smg_debug_wgs_level_plan": (i, [vp, i, i, i, ip, ip, ip]),
+        "smg_debug_deep_launches": (i, [vp, i, i, i, i, ip, ip, i, ip]),
+        "smg_debug_gs_colour_wpb": (i, [vp, i, i, ip, ip, ip]),
         "smg_hierarchy_set_block_gs": (i, [vp, i]),
         "smg_hierarchy_set_wave_gs": (i, [vp, i]),
         "smg_hierarchy_set_memory_lean": (i, [vp, i]),

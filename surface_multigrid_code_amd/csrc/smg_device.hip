@@ -351,6 +351,25 @@ static bool deep_wanted(int mode, int w_max, int kb)
     return nbm == 3 ? kb <= 3 : nbm == 5 ? kb <= 2 : kb == 1;
 }
 
+// Row-width classes of the deep variant and their column limits: widest row <= 24 entries NBMAX = 3, KB <= 3; <= 40: 5, KB <= 2; <= 64: 8, KB = 1.
+// A group of 4 columns goes 3 + 1, 2 + 2 or 1 + 1 + 1 + 1.  launch_sell_mode launches what this returns; smg_debug_deep_launches reports it.
+int deep_split(int mode, int w_max, int kb, int* cols, int* nbmax)
+{
+    if (kb < 1 || kb > 4) return 0;
+    int kd = kb;
+    if (kd == 4 && !deep_wanted(mode, w_max, 4) && deep_wanted(mode, w_max, 2)) kd = 2;
+    if (!(deep_wanted(mode, w_max, kd) || (kd > 1 && deep_wanted(mode, w_max, 1)))) return 0;
+    *nbmax = w_max <= 24 ? 3 : w_max <= 40 ? 5 : 8;
+    int n = 0;
+    for (int cc = 0; cc < kb;) {
+        int kk = kb - cc;
+        while (kk > 1 && !deep_wanted(mode, w_max, kk)) kk--;
+        cols[n++] = kk;
+        cc += kk;
+    }
+    return n;
+}
+
 // ---- wide multi-RHS variant --------------------------------------------------------------------------------------
 // For k >= 8 right-hand sides the lanes run ACROSS COLUMNS: lane = (g, c) with c = lane % KW the column inside a block of
 // KW in {8,16,32,64} columns and g = lane / KW one of G = 64/KW rows handled concurrently.  A neighbour gather is then
@@ -653,6 +672,30 @@ int sell_wide_blocks(int n_slices, int k)
 static constexpr int sell_wpb() { return 4; }
 static int gs_wpb() { static const int v = getenv("SMG_GS_WPB") ? atoi(getenv("SMG_GS_WPB")) : 4; return v; }   // A/B knob: waves per workgroup of the big colour launches
 int sell_blocks(int n_slices) { return (n_slices + sell_wpb() - 1) / sell_wpb(); }
+// small colour sweeps run on one XCD (see k_sell): grid 8 nb, n_blocks passed negated
+static bool one_xcd_launch(bool gs, int nb)
+{
+    static const int one_xcd_max = getenv("SMG_ONE_XCD_MAX") ? atoi(getenv("SMG_ONE_XCD_MAX")) : 32;
+    return gs && nb <= one_xcd_max;
+}
+// whole-pitch look-ahead: colour sweeps of <= 32 workgroups, and the whole-matrix launches (Jacobi / Chebyshev sweeps,
+// residual, transfer) of a level that small, <= 64 workgroups (C3 level 3: 37.3 -> 34.1 us per visit; colour sweeps of 62
+// workgroups lose with it)
+static bool whole_pitch_ahead(const SellDev& A, bool gs, int nb)
+{
+    static const int pitch_env = getenv("SMG_PITCH_SPEC_MAX") ? atoi(getenv("SMG_PITCH_SPEC_MAX")) : -1;
+    const int pitch_max = pitch_env >= 0 ? pitch_env : (gs ? 32 : 64);
+    return nb <= pitch_max && A.stride == 12 && A.w_lo >= 7;
+}
+// Waves per workgroup of a one-column Gauss-Seidel colour launch (SELL_GS, values not coded) of n_slices slices of A: SMG_GS_WPB = 2 / 8 where the
+// launch is not confined to one XCD, does not request the whole pitch ahead, and A has fixed-pitch panels of lower width 7; 4 otherwise.
+// launch_narrow branches on this; smg_debug_gs_colour_wpb reports it.
+int gs_colour_wpb(const SellDev& A, int n_slices)
+{
+    const int nb = sell_blocks(n_slices);
+    if (A.codes || !(A.stride > 0 && A.w_lo == 7) || one_xcd_launch(true, nb) || whole_pitch_ahead(A, true, nb)) return 4;
+    return gs_wpb() == 8 ? 8 : gs_wpb() == 2 ? 2 : 4;
+}
 
 // the narrow launches (kb <= 4 columns per lane) of one group of columns; CODED: the matrix holds weight codes (SELL_AX / SELL_ADD only)
 template <typename T>
@@ -682,14 +725,10 @@ static void launch_narrow(const SellDev& A, int kb, int nb, int ns, int grid, in
         case 1: {
             // the usual widths get kernels with the look-ahead count fixed at compile time (no branch per panel column)
             const int w0 = A.stride > 0 ? (A.w_lo < 8 ? A.w_lo : 8) : -1;
-            // whole-pitch look-ahead: colour sweeps of <= 32 workgroups, and the whole-matrix launches (Jacobi / Chebyshev sweeps,
-            // residual, transfer) of a level that small, <= 64 workgroups (C3 level 3: 37.3 -> 34.1 us per visit; colour sweeps of 62
-            // workgroups lose with it)
-            static const int pitch_env = getenv("SMG_PITCH_SPEC_MAX") ? atoi(getenv("SMG_PITCH_SPEC_MAX")) : -1;
-            const int pitch_max = pitch_env >= 0 ? pitch_env : (sell_is_gs(MODE) ? 32 : 64);
-            if (nb <= pitch_max && A.stride == 12 && w0 >= 7) narrow_one<MODE, 1, T, 12, 4, CODED>(A, grid, nbarg, R);
-            else if (!CODED && w0 == 7 && MODE == SELL_GS && !one_xcd && gs_wpb() == 8) narrow_one<SELL_GS, 1, T, 7, 8, false>(A, (ns + 7) / 8, (ns + 7) / 8, R);
-            else if (!CODED && w0 == 7 && MODE == SELL_GS && !one_xcd && gs_wpb() == 2) narrow_one<SELL_GS, 1, T, 7, 2, false>(A, (ns + 1) / 2, (ns + 1) / 2, R);
+            const int wpb = (!CODED && MODE == SELL_GS) ? gs_colour_wpb(A, ns) : 4;      // (4 whenever one_xcd or the whole pitch goes ahead)
+            if (whole_pitch_ahead(A, sell_is_gs(MODE), nb)) narrow_one<MODE, 1, T, 12, 4, CODED>(A, grid, nbarg, R);
+            else if (wpb == 8) narrow_one<SELL_GS, 1, T, 7, 8, false>(A, (ns + 7) / 8, (ns + 7) / 8, R);
+            else if (wpb == 2) narrow_one<SELL_GS, 1, T, 7, 2, false>(A, (ns + 1) / 2, (ns + 1) / 2, R);
             else if (w0 == 7) narrow_one<MODE, 1, T, 7, 4, CODED>(A, grid, nbarg, R);
             else if (w0 == 8) narrow_one<MODE, 1, T, 8, 4, CODED>(A, grid, nbarg, R);
             else if (w0 == 2) narrow_one<MODE, 1, T, 2, 4, CODED>(A, grid, nbarg, R);
@@ -752,9 +791,7 @@ static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, 
             c0 += kw;
         }
     }
-    // small colour sweeps run on one XCD (see k_sell): grid 8 nb, n_blocks passed negated
-    static const int one_xcd_max = getenv("SMG_ONE_XCD_MAX") ? atoi(getenv("SMG_ONE_XCD_MAX")) : 32;
-    const bool one_xcd = sell_is_gs(MODE) && nb <= one_xcd_max;
+    const bool one_xcd = one_xcd_launch(sell_is_gs(MODE), nb);
     const int grid = one_xcd ? nb * 8 : nb, nbarg = one_xcd ? -nb : nb;
     for (; c0 < k; c0 += 4) {
         const int kb = (k - c0) < 4 ? (k - c0) : 4;
@@ -766,13 +803,11 @@ static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, 
         poff += (size_t)nb;
         if constexpr (std::is_same<T, double>::value && (MODE == SELL_AX || MODE == SELL_RESID)) {
             // (k = 4 on a matrix the deep variant serves with 3 columns per lane: 3 + 1)
-            int kd = kb;
-            if (kd == 4 && !deep_wanted(MODE, A.w_max, 4) && deep_wanted(MODE, A.w_max, 2)) kd = 2;
-            if (deep_wanted(MODE, A.w_max, kd) || (kd > 1 && deep_wanted(MODE, A.w_max, 1))) {
-                for (int cc = 0; cc < kb;) {
-                    int kk = kb - cc;
-                    while (kk > 1 && !deep_wanted(MODE, A.w_max, kk)) kk--;
-                    const int nbm = A.w_max <= 24 ? 3 : A.w_max <= 40 ? 5 : 8;
+            int cols[4], nbm = 0;
+            const int n_deep = deep_split(MODE, A.w_max, kb, cols, &nbm);
+            if (n_deep > 0) {
+                for (int i = 0, cc = 0; i < n_deep; cc += cols[i++]) {
+                    const int kk = cols[i];
                     const CoarseInit<T> zc = coarse_codes<T>(A, zero_rows, c0 + cc, first, omega);
 #define SMG_DEEP_LAUNCH(KB, NB) hipLaunchKernelGGL((k_sell_deep<MODE, KB, NB>), dim3(nb), dim3(256), 0, st, A.col, A.val, A.order, A.slice_off, A.stride, s_begin, s_end, nb, use_order, \
                                                    xx ? xx + cc : nullptr, A.slice_row, A.slice_w, bb ? bb + cc : nullptr, yy + cc, k, done, zc)
@@ -780,7 +815,6 @@ static hipError_t launch_sell_mode(const SellDev& A, int s_begin, int s_end_in, 
                     else if (nbm == 5) { if (kk == 1) SMG_DEEP_LAUNCH(1, 5); else SMG_DEEP_LAUNCH(2, 5); }
                     else SMG_DEEP_LAUNCH(1, 8);
 #undef SMG_DEEP_LAUNCH
-                    cc += kk;
                 }
                 continue;
             }

@@ -198,6 +198,10 @@ struct WgsDev {
 };
 // the pieces [q_begin, q_end) -- one piece colour -- of one sweep, in place on u (row-major n x k, any k >= 1: column groups ride in the grid's second dimension)
 hipError_t launch_wgs(const WgsDev& P, int q_begin, int q_end, const double* b, double* u, int k, const Ctrl* ctrl, hipStream_t st);
+// what launch_wgs decides, and nothing else decides it: the kernel's row-width class NBMAX (3 / 5 / 8) and rim slots per lane RIMI (2 / 4 / 7) of a
+// plan (false: no variant), and the launch -- `groups` groups of kb columns per lane -- that serves columns c0 ... of k on a level of n_pieces pieces
+bool wgs_kernel_class(int nb_max, int rim_pitch, int* nbmax, int* rimi);
+void wgs_column_split(int n_pieces, int k, int c0, int* kb, int* groups);
 
 // ---- independent meshes in one handle (smg_hierarchy_create_union; kernels: smg_union_device.hip) ----
 struct UnionDev {
@@ -280,6 +284,10 @@ hipError_t launch_schur_solve(const SchurDev& F, const float* b, float* u, int k
 
 int sell_blocks(int n_slices);  // 4 slices (waves) per 256-thread block
 int sell_wide_blocks(int n_slices, int k);  // partial-sum slots the wide (k >= 8) path needs
+// The k_sell_deep launches (smg_device.hip) that serve a narrow group of kb <= 4 fp64 columns of mode (SELL_AX / SELL_RESID) on a matrix whose widest
+// row has w_max entries: columns per launch in cols[0 .. return value), *nbmax the kernel's row-width class (3 / 5 / 8); 0: k_sell serves the group
+int deep_split(int mode, int w_max, int kb, int* cols, int* nbmax);
+int gs_colour_wpb(const SellDev& A, int n_slices);  // waves per workgroup (2 / 4 / 8) of a one-column Gauss-Seidel colour launch of n_slices slices of A
 bool wide_latency_variant(int n_slices, int kw);  // a wide launch of n_slices slices, kw < 64 columns: one row per lane (true) or the streaming kernel
 
 // ctrl->sumsq = sum(partials[0..n)) in a fixed order (deterministic).  The buffer must have ss_partials_room() doubles of room behind the n partials

@@ -375,6 +375,91 @@ extern "C" int smg_level_get_wave_gs_order(smg_hierarchy* h, int lv, int k, int*
     return 1;
 }
 
+// ------------------------------------------------------------------------------------------------ read-only hooks: which kernel variants run
+// the internal matrix of a smoothed level of a scalar handle whose host half of smg_precompute has run, or an error
+static int check_level_matrix(smg_hierarchy* h, int lv, const char* who, const Csr** G)
+{
+    int rc = ensure_A_int(h, lv);
+    if (rc) return rc;
+    const Level& Lv = h->lv[lv];
+    if (Lv.A_int.nr != Lv.n || Lv.n == 0 || h->bs != 1) return fail(SMG_ERR_INVALID, "%s: the host half of smg_precompute has not run (scalar hierarchies only)", who);
+    *G = &Lv.A_int;
+    return SMG_OK;
+}
+// The k_wgs launches of one piece colour: launch_wgs's own functions (wgs_kernel_class, wgs_column_split -- same statics, same knobs) walked the way it walks them.
+extern "C" int smg_debug_wgs_launches(int n_pieces, int nb_max, int rim_pitch, int k, int* nbmax, int* rimi, int* launches, int cap, int* n_launches)
+{
+    if (n_pieces < 1 || k < 1 || k > 4 * 65535 || cap < 0 || (cap > 0 && !launches) || !n_launches)
+        return fail(SMG_ERR_INVALID, "smg_debug_wgs_launches: bad arguments");
+    int nbm = 0, ri = 0;
+    if (!wgs_kernel_class(nb_max, rim_pitch, &nbm, &ri))
+        return fail(SMG_ERR_INVALID, "smg_debug_wgs_launches: k_wgs has no variant for rows of %d batches and a rim pitch of %d", nb_max, rim_pitch);
+    if (nbmax) *nbmax = nbm;
+    if (rimi) *rimi = ri;
+    int n = 0;
+    for (int c0 = 0; c0 < k; n++) {
+        int kb = 0, groups = 0;
+        wgs_column_split(n_pieces, k, c0, &kb, &groups);
+        if (n < cap) { launches[2 * n] = kb; launches[2 * n + 1] = groups; }
+        c0 += kb * groups;
+    }
+    *n_launches = n;
+    return SMG_OK;
+}
+// The plan those launches run on.  from_host 0: the plan relax() of level lv sweeps with for k columns in the handle's present state -- nothing is
+// built: a level whose plan no sweep has asked for yet, or that sweeps another way, reports none; 1: the plan as ensure_wgs would build it, on the host.
+extern "C" int smg_debug_wgs_level_plan(smg_hierarchy* h, int lv, int k, int from_host, int* n_pieces, int* nb_max, int* rim_pitch)
+{
+    return guarded("smg_debug_wgs_level_plan", [&]() -> int {
+        if (!h || lv < 0 || lv >= h->n_levels - 1 || k < 1 || !n_pieces || !nb_max || !rim_pitch)
+            return fail(SMG_ERR_INVALID, "smg_debug_wgs_level_plan: bad arguments");
+        *n_pieces = *nb_max = *rim_pitch = 0;
+        if (from_host) {
+            const Csr* G = nullptr;
+            int rc = check_level_matrix(h, lv, "smg_debug_wgs_level_plan", &G);
+            if (rc) return rc;
+            SweepMatrix M;
+            if ((rc = sweep_matrix(h, lv, &M, !h->lv[lv].dA.view.val))) return rc;
+            const WgsPlan P = host_wgs_plan(M);
+            *n_pieces = P.n_pieces; *nb_max = P.nb_max; *rim_pitch = P.rim_pitch;
+            return SMG_OK;
+        }
+        const WgsBuf* Q = wgs_plan(h, lv, k);
+        if (!Q || tiled_either(h, lv, k, h->pre, h->post)) return SMG_OK;
+        *n_pieces = Q->view.n_pieces; *nb_max = Q->view.nb_max; *rim_pitch = Q->view.rim_pitch;
+        return SMG_OK;
+    });
+}
+// The launches of A x (mode 0) or b - A x (mode 1) with k <= 4 fp64 columns -- one narrow group of launch_sell_mode -- on a level matrix: its own
+// deep_split.  Per launch (columns, NBMAX class of k_sell_deep or 0 for k_sell).
+extern "C" int smg_debug_deep_launches(const smg_hierarchy* h, int lv, int which, int mode, int k, int* w_max, int* launches, int cap, int* n_launches)
+{
+    if (!h || lv < 0 || lv >= h->n_levels || which < 0 || which > 2 || mode < 0 || mode > 1 || k < 1 || k > 4 || cap < 0 || (cap > 0 && !launches) || !n_launches)
+        return fail(SMG_ERR_INVALID, "smg_debug_deep_launches: bad arguments (one narrow group: 1 <= k <= 4)");
+    const SellBuf& S = which == 0 ? h->lv[lv].dA : which == 1 ? h->lv[lv].dP : h->lv[lv].dPT;
+    if (h->bs != 1 || S.view.n_slices <= 0) return fail(SMG_ERR_INVALID, "smg_debug_deep_launches: the level has no such scalar device image (smg_precompute first)");
+    if (w_max) *w_max = S.view.w_max;
+    int cols[4] = {k, 0, 0, 0}, nbm = 0;
+    const int nd = deep_split(mode == 0 ? SELL_AX : SELL_RESID, S.view.w_max, k, cols, &nbm), n = std::max(nd, 1);
+    for (int i = 0; i < std::min(n, cap); i++) { launches[2 * i] = cols[i]; launches[2 * i + 1] = nd > 0 ? nbm : 0; }
+    *n_launches = n;
+    return SMG_OK;
+}
+// Waves per workgroup of a one-column Gauss-Seidel colour launch of n_slices slices on the image level lv sweeps on (A, or A^T where A is not
+// bit-symmetric): launch_narrow's own gs_colour_wpb; the image's panel pitch and lower width beside it.
+extern "C" int smg_debug_gs_colour_wpb(const smg_hierarchy* h, int lv, int n_slices, int* wpb, int* stride, int* w_lo)
+{
+    if (!h || lv < 0 || lv >= h->n_levels - 1 || n_slices < 1 || !wpb) return fail(SMG_ERR_INVALID, "smg_debug_gs_colour_wpb: bad arguments");
+    const Level& Lv = h->lv[lv];
+    const SellBuf& G = Lv.gs_on_transpose ? Lv.dAT : Lv.dA;
+    if (h->bs != 1 || G.view.n_slices <= 0 || n_slices > G.view.n_slices)
+        return fail(SMG_ERR_INVALID, "smg_debug_gs_colour_wpb: the level has no scalar device image of that many slices (smg_precompute first)");
+    *wpb = gs_colour_wpb(G.view, n_slices);
+    if (stride) *stride = G.view.stride;
+    if (w_lo) *w_lo = G.view.w_lo;
+    return SMG_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ host-side self-checks
 // Each check builds a plan of level lv from A_int on the host and EXECUTES it there the way its kernel does (tiled_sweep_host, bgs_sweep_host,
 // wgs_sweep_host), one sweep on fixed test vectors, against a plain sweep: *max_abs_diff must be 0.  Need no GPU once the host half of smg_precompute
@@ -384,12 +469,7 @@ extern "C" int smg_level_get_wave_gs_order(smg_hierarchy* h, int lv, int k, int*
 static int check_level(smg_hierarchy* h, int lv, bool args_ok, const char* who, const Csr** G)
 {
     if (!h || lv < 0 || lv >= h->n_levels - 1 || !args_ok) return fail(SMG_ERR_INVALID, "%s: bad arguments", who);
-    int rc = ensure_A_int(h, lv);
-    if (rc) return rc;
-    const Level& Lv = h->lv[lv];
-    if (Lv.A_int.nr != Lv.n || Lv.n == 0 || h->bs != 1) return fail(SMG_ERR_INVALID, "%s: the host half of smg_precompute has not run (scalar hierarchies only)", who);
-    *G = &Lv.A_int;
-    return SMG_OK;
+    return check_level_matrix(h, lv, who, G);
 }
 // the checks' test vectors: the iterate x, the right-hand side b
 static std::vector<double> check_vector(int n, bool rhs)

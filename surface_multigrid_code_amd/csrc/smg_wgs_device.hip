@@ -124,29 +124,51 @@ __global__ __launch_bounds__(64) void k_wgs(const int* __restrict__ hdr, const i
     }
 }
 
+// Which k_wgs<NBMAX, KB, RIMI> a launch takes.  The three choices below are all there is: launch_wgs makes them through these functions and
+// smg_debug_wgs_launches (smg_sweep_plans.cpp) reports them through the same ones, so the two cannot disagree.
+// The row-width class NBMAX (3 / 5 / 8 batches of 8 entry slots) of a level whose widest row needs nb_max batches and the rim slots per lane RIMI
+// (2 / 4 / 7) of its rim pitch, wgs_rim_pitch(); false: the kernel has no variant for the plan.
+bool wgs_kernel_class(int nb_max, int rim_pitch, int* nbmax, int* rimi)
+{
+    if (nb_max < 1 || nb_max > WGS_MAX_BATCHES) return false;
+    if (rim_pitch != 2 * WGS_ROWS && rim_pitch != 4 * WGS_ROWS && rim_pitch != 7 * WGS_ROWS) return false;
+    *nbmax = nb_max <= 3 ? 3 : nb_max <= 5 ? 5 : 8;
+    *rimi = rim_pitch / WGS_ROWS;
+    return true;
+}
+// Columns per lane: on a latency-bound level (few pieces per launch) a phase costs its instruction count, and four columns per lane are four times the
+// multiply-adds of one -- groups of 2 side by side in the grid's second dimension (ogre.obj, 5 038 rows: k = 4 in 367 us per cycle as one group of 4,
+// as two groups of 2 like k = 2); a big level re-reads its rows per group, so it takes groups of 4.
+// The launch that serves columns c0, c0 + 1, ... of k on a level of n_pieces pieces: `groups` groups of kb columns each (a value outside 1 .. 4 of an
+// A/B knob is brought into that range: the kernel has 1 .. 4 columns per lane).
+void wgs_column_split(int n_pieces, int k, int c0, int* kb_out, int* groups_out)
+{
+    static const int small_pieces = getenv("SMG_WGS_KB2_MAX_PIECES") ? atoi(getenv("SMG_WGS_KB2_MAX_PIECES")) : 1600;
+    static const int kb_small = getenv("SMG_WGS_KB_SMALL") ? atoi(getenv("SMG_WGS_KB_SMALL")) : 1, kb_big = getenv("SMG_WGS_KB_BIG") ? atoi(getenv("SMG_WGS_KB_BIG")) : 4;
+    const int kbw = n_pieces <= small_pieces ? kb_small : kb_big, kbp = kbw < 1 ? 1 : kbw > 4 ? 4 : kbw;
+    int kb = k - c0, groups = 1;
+    if (kb >= kbp) { groups = kb / kbp; kb = kbp; }
+    *kb_out = kb;
+    *groups_out = groups;
+}
+
 // the pieces [q_begin, q_end) -- one piece colour -- of one sweep, in place on u (row-major n x k).  Up to 7 columns: one or two launches (groups of <= 4
 // columns per lane); 8 and more: groups of 4 in the grid's second dimension, one launch (+ one for k % 4 columns).  The order of the sweep does not depend
 // on k: a column-sharded solve (smg_solve_sharded) iterates bit for bit like the fused one.
 hipError_t launch_wgs(const WgsDev& P, int q_begin, int q_end, const double* b, double* u, int k, const Ctrl* ctrl, hipStream_t st)
 {
     if (q_end <= q_begin) return hipSuccess;
-    if (k < 1 || k > 4 * 65535 || P.nb_max < 1 || P.nb_max > WGS_MAX_BATCHES) return hipErrorInvalidValue;
-    if (P.rim_pitch != 2 * WGS_ROWS && P.rim_pitch != 4 * WGS_ROWS && P.rim_pitch != 7 * WGS_ROWS) return hipErrorInvalidValue;     // wgs_rim_pitch()
+    int nbmax = 0, rimi = 0;
+    if (k < 1 || k > 4 * 65535 || !wgs_kernel_class(P.nb_max, P.rim_pitch, &nbmax, &rimi)) return hipErrorInvalidValue;
     const int* done = ctrl ? &ctrl->done : never_done();
     const int n_wg = q_end - q_begin;
     static const int dbg = getenv("SMG_DEBUG_WGS_PHASES") ? atoi(getenv("SMG_DEBUG_WGS_PHASES")) : 1 << 20;   // timing probe (wrong results)
-    // Columns per lane: on a latency-bound level (few pieces per launch) a phase costs its instruction count, and four columns per lane are four times the
-    // multiply-adds of one -- groups of 2 side by side in the grid's second dimension (ogre.obj, 5 038 rows: k = 4 in 367 us per cycle as one group of 4,
-    // as two groups of 2 like k = 2); a big level re-reads its rows per group, so it takes groups of 4.
-    static const int small_pieces = getenv("SMG_WGS_KB2_MAX_PIECES") ? atoi(getenv("SMG_WGS_KB2_MAX_PIECES")) : 1600;
-    static const int kb_small = getenv("SMG_WGS_KB_SMALL") ? atoi(getenv("SMG_WGS_KB_SMALL")) : 1, kb_big = getenv("SMG_WGS_KB_BIG") ? atoi(getenv("SMG_WGS_KB_BIG")) : 4;
-    const int kbp = P.n_pieces <= small_pieces ? kb_small : kb_big;
     for (int c0 = 0; c0 < k;) {
-        int kb = k - c0, groups = 1;
-        if (kb >= kbp) { groups = kb / kbp; kb = kbp; }
+        int kb = 0, groups = 0;
+        wgs_column_split(P.n_pieces, k, c0, &kb, &groups);
 #define SMG_WGS_LAUNCH(NB, KB, RI) hipLaunchKernelGGL((k_wgs<NB, KB, RI>), dim3((unsigned)n_wg, (unsigned)groups), dim3(64), 0, st, P.hdr, P.grow, P.meta, P.diag, P.rim, P.eoff, P.eval, q_begin, n_wg, P.rim_pitch, b + c0, u + c0, k, done, dbg)
-#define SMG_WGS_RI(NB, KB) do { if (P.rim_pitch == 2 * WGS_ROWS) SMG_WGS_LAUNCH(NB, KB, 2); else if (P.rim_pitch == 4 * WGS_ROWS) SMG_WGS_LAUNCH(NB, KB, 4); else SMG_WGS_LAUNCH(NB, KB, 7); } while (0)
-#define SMG_WGS_NB(KB) do { if (P.nb_max <= 3) SMG_WGS_RI(3, KB); else if (P.nb_max <= 5) SMG_WGS_RI(5, KB); else SMG_WGS_RI(8, KB); } while (0)
+#define SMG_WGS_RI(NB, KB) do { if (rimi == 2) SMG_WGS_LAUNCH(NB, KB, 2); else if (rimi == 4) SMG_WGS_LAUNCH(NB, KB, 4); else SMG_WGS_LAUNCH(NB, KB, 7); } while (0)
+#define SMG_WGS_NB(KB) do { if (nbmax == 3) SMG_WGS_RI(3, KB); else if (nbmax == 5) SMG_WGS_RI(5, KB); else SMG_WGS_RI(8, KB); } while (0)
         if (kb == 1) SMG_WGS_NB(1);
         else if (kb == 2) SMG_WGS_NB(2);
         else if (kb == 3) SMG_WGS_NB(3);

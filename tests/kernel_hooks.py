@@ -1,5 +1,6 @@
 """numpy wrappers of the kernel test hooks (include/smg.h: the handle-free smg_debug_eig_gram, smg_debug_eig_combine, smg_debug_eig_residual,
-smg_debug_krylov, smg_debug_union; on a handle smg_debug_cycle_f32, smg_debug_convert_f32) and the rounding-error bounds the tests hold them to.
+smg_debug_krylov, smg_debug_union; on a handle smg_debug_cycle_f32, smg_debug_convert_f32; read-only, which kernel variants run: smg_debug_wgs_launches,
+smg_debug_wgs_level_plan, smg_debug_deep_launches, smg_debug_gs_colour_wpb) and the rounding-error bounds the tests hold them to.
 
 Every wrapper asserts that the hook succeeded and that no guard region around a device buffer changed (no write out of place)."""
 import ctypes as C
@@ -251,6 +252,46 @@ def schur_partition(mg):
     assert rc == 0, mg.L.smg_last_error()
     assert out.min() >= -1 and (out == -1).sum() == ns.value and out.max() == nb.value - 1, "not a partition"
     return out
+
+
+def wgs_level_plan(mg, lv, k, from_host=False):
+    """(n_pieces, nb_max, rim_pitch) of the wave Gauss-Seidel plan of level lv -- the one relax() sweeps with for k columns in the handle's present
+    state (nothing is built), or from_host: the plan as the first sweep would build it, built on the host -- or None"""
+    a, b, c = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    rc = mg.L.smg_debug_wgs_level_plan(mg.h, lv, k, int(from_host), C.byref(a), C.byref(b), C.byref(c))
+    assert rc == 0, mg.L.smg_last_error()
+    return (a.value, b.value, c.value) if a.value > 0 else None
+
+
+def wgs_launches(L, n_pieces, nb_max, rim_pitch, k):
+    """(NBMAX, RIMI, [(KB, groups), ...]): the k_wgs launches of one piece colour in this process (smg_debug_wgs_launches)"""
+    nbm, ri, n = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    out = np.full(2 * (k + 1), -1, np.int32)
+    rc = L.smg_debug_wgs_launches(n_pieces, nb_max, rim_pitch, k, C.byref(nbm), C.byref(ri), _p(out, C.c_int), k + 1, C.byref(n))
+    assert rc == 0, L.smg_last_error()
+    assert 1 <= n.value <= k
+    la = [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n.value)]
+    assert sum(kb * g for kb, g in la) == k and all(1 <= kb <= 4 and g >= 1 for kb, g in la), la
+    return nbm.value, ri.value, la
+
+
+def deep_launches(mg, lv, which, mode, k):
+    """(w_max, [(columns, NBMAX class of k_sell_deep or 0 = k_sell), ...]): the launches of A x (mode "A") or b - A x ("RESID") with k <= 4 fp64
+    columns on the device image which ("A", "P", "PT") of level lv in this process (smg_debug_deep_launches)"""
+    w, n = C.c_int(-1), C.c_int(-1)
+    out = np.full(2 * (k + 1), -1, np.int32)
+    rc = mg.L.smg_debug_deep_launches(mg.h, lv, {"A": 0, "P": 1, "PT": 2}[which], {"A": 0, "RESID": 1}[mode], k, C.byref(w), _p(out, C.c_int), k + 1, C.byref(n))
+    assert rc == 0, mg.L.smg_last_error()
+    return w.value, [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n.value)]
+
+
+def gs_colour_wpb(mg, lv, n_slices):
+    """(waves per workgroup, panel pitch, lower width): a one-column Gauss-Seidel colour launch of n_slices slices on the image level lv sweeps on, in
+    this process (smg_debug_gs_colour_wpb)"""
+    wpb, stride, w_lo = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    rc = mg.L.smg_debug_gs_colour_wpb(mg.h, lv, n_slices, C.byref(wpb), C.byref(stride), C.byref(w_lo))
+    assert rc == 0, mg.L.smg_last_error()
+    return wpb.value, stride.value, w_lo.value
 
 
 def exact_dot(a, b):

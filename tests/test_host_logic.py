@@ -681,6 +681,50 @@ def test_wave_gauss_seidel_plan_is_the_lexicographic_sweep_in_its_order(smg_mod)
                 assert diff.value == 0.0, "level %d, pieces of %d rows (mode %d): the piece sweep differs by %g" % (lv, piece_rows, mode, diff.value)
 
 
+def test_wave_kernel_variant_hooks_state_the_launchers_choice(smg_mod):
+    """smg_debug_wgs_launches and smg_debug_wgs_level_plan (read-only; the launcher's own functions; smg_debug_deep_launches and smg_debug_gs_colour_wpb refuse what they cannot answer): with the default knobs a level of at most 1 600
+    pieces runs every column as KB = 1, one group per column; a larger one groups of 4 and one launch of k % 4 columns at the column offset; the
+    row-width classes change at 3 / 5 batches, the rim slots per lane follow the pitch; a plan the kernel has no variant for is refused.  On the host
+    the plan of a Galerkin level of the decimated bunny is the one the first sweep would build (tests/test_gpu_wgs_variants.py asserts the same
+    numbers on the device), and a level no sweep has run on reports no plan in use."""
+    import ctypes as C
+    import kernel_hooks as H
+    smg = smg_mod
+    L = smg._lib.load()
+    for k in (1, 2, 3, 4, 5, 7, 8, 11, 18, 64):
+        for n_pieces in (1, 37, 1600):
+            assert H.wgs_launches(L, n_pieces, 4, 256, k) == (5, 4, [(1, k)])
+        tail = [(k % 4, 1)] if k % 4 else []
+        assert H.wgs_launches(L, 1601, 4, 256, k) == (5, 4, ([(4, k // 4)] if k >= 4 else []) + tail)
+    assert [H.wgs_launches(L, 10, nb, 128, 1)[0] for nb in range(1, 9)] == [3, 3, 3, 5, 5, 8, 8, 8]
+    assert [H.wgs_launches(L, 10, 1, pitch, 1)[1] for pitch in (128, 256, 448)] == [2, 4, 7]
+    n = C.c_int(-1)
+    out = np.zeros(8, np.int32)
+    ip = out.ctypes.data_as(C.POINTER(C.c_int))
+    for bad in ((0, 4, 256, 1), (10, 0, 256, 1), (10, 9, 256, 1), (10, 4, 192, 1), (10, 4, 512, 1), (10, 4, 256, 0)):
+        assert L.smg_debug_wgs_launches(*bad, None, None, ip, 4, C.byref(n)) == -1 and b"smg_debug_wgs_launches" in L.smg_last_error(), bad
+    assert L.smg_debug_wgs_launches(10, 4, 256, 1, None, None, None, 4, C.byref(n)) == -1 and L.smg_debug_wgs_launches(10, 4, 256, 1, None, None, ip, 4, None) == -1
+    assert L.smg_debug_wgs_launches(2000, 4, 256, 7, None, None, ip, 1, C.byref(n)) == 0 and n.value == 2 and out[:4].tolist() == [4, 1, 0, 0]      # cap: no write behind it
+    V, F = M.read_smgm("bunny.smgm")
+    V = M.normalize_unit_area(V, F)
+    mg = smg.mg_precompute(V, F, 0.25, 60, 1)
+    A = (M.massmatrix(V, F, "barycentric") - 0.01 * M.cotmatrix(V, F)).tocsr()
+    A.sort_indices()
+    _host_precompute(smg, mg, A)
+    assert [H.wgs_level_plan(mg, lv, 1, from_host=True) for lv in (1, 2)] == [(62, 4, 256), (18, 6, 128)]
+    if L.smg_device_count() == 0:
+        assert H.wgs_level_plan(mg, 1, 1) is None
+    a = C.c_int(-1)
+    assert L.smg_debug_wgs_level_plan(None, 1, 1, 1, C.byref(a), C.byref(a), C.byref(a)) == -1
+    assert L.smg_debug_wgs_level_plan(mg.h, mg.n_levels - 1, 1, 1, C.byref(a), C.byref(a), C.byref(a)) == -1
+    assert L.smg_debug_wgs_level_plan(mg.h, 1, 0, 1, C.byref(a), C.byref(a), C.byref(a)) == -1
+    assert L.smg_debug_deep_launches(None, 0, 0, 0, 1, None, None, 0, C.byref(a)) == -1
+    assert L.smg_debug_deep_launches(mg.h, 0, 3, 0, 1, None, None, 0, C.byref(a)) == -1 and L.smg_debug_deep_launches(mg.h, 0, 0, 2, 1, None, None, 0, C.byref(a)) == -1
+    assert L.smg_debug_deep_launches(mg.h, 0, 0, 0, 5, None, None, 0, C.byref(a)) == -1 and L.smg_debug_deep_launches(mg.h, 0, 0, 0, 0, None, None, 0, C.byref(a)) == -1      # one narrow group
+    assert L.smg_debug_gs_colour_wpb(None, 0, 1, C.byref(a), None, None) == -1 and L.smg_debug_gs_colour_wpb(mg.h, 0, 0, C.byref(a), None, None) == -1
+    assert L.smg_debug_gs_colour_wpb(mg.h, 0, 1, None, None, None) == -1 and L.smg_debug_gs_colour_wpb(mg.h, mg.n_levels - 1, 1, C.byref(a), None, None) == -1
+
+
 def test_sweep_plans_copy_the_level_values_their_maps_name_and_pad_with_zero_and_one(smg_mod):
     """The three plan-based sweeps keep copies of the level's values and diagonals; a value-only re-precompute gathers them anew through the plans'
     maps and leaves every slot without a map untouched (csrc/smg_sweep_plans.cpp: refresh_plan_values).  So, for every plan as the solves build it:
