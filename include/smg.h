@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 521
+#define SMG_VERSION 530
 
 enum {
     SMG_OK = 0,
@@ -1110,6 +1110,57 @@ int smg_fluid_diagnostics(smg_fluid *g, const smg_solve_opts *opts, double *out)
 int smg_fluid_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *w, const double *psi, const double *wn, double a,
                    double b, const double *dt, double theta, int rates_only, double *out);
 
+/* ---- Two-species reaction-diffusion on a surface (csrc/smg_rd.cpp): the state is the pair (u, v), two doubles per
+ * (vertex, column), resident on the device; k columns are k independent simulations with their own reactions and k (or 2k) columns of every
+ * solve.  With -L the positive semi-definite cotangent matrix and m_i the barycentric mass (a third of the areas around i), per column c
+ *     u_t = Du Laplace u + R_u(u, v; c),    v_t = Dv Laplace v + R_v(u, v; c)
+ * with the natural (no-flux) boundary condition: no row is known, on closed and on open meshes.  R_u and R_v are bivariate cubics over the
+ * monomials 1, u, v, u^2, uv, v^2, u^3, u^2 v, u v^2, v^3 in this order: 20 doubles per column, R_u's ten first (the table `coeff`, k x 20
+ * row-major).  A step is IMEX: the reaction explicit, the diffusion implicit.
+ *   1. k_rd_react: (u, v) through react_substeps Euler steps of length dt / react_substeps of the reaction alone (both rates from the same
+ *      (u, v)), giving (u*, v*); the right-hand sides m u*, m v* and their squares.
+ *   2. (M + dt Du (-L)) u' = m u*, (M + dt Dv (-L)) v' = m v*, warm-started from (u, v).  Du != Dv, Dv > 0: a k-column solve on each of two
+ *      handles.  Du == Dv: ONE 2k-column solve on one handle.  Dv == 0: v' = v* from the kernel, bit for bit, and one k-column solve.
+ *   3. k_rd_close: the terms m u', m v' and max(|u' - u|, |v' - v|); fixed-order sums and maxima per column.
+ * The matrices are precomputed at create and by values again when set_params changes dt Du or dt Dv.  The host reads per step |m u*|_F^2 and
+ * |m v*|_F^2 before the solves -- they set the default tolerance (opts NULL: 1e-10 |rhs|_F of the solve's own columns, max_iter 100) and
+ * refuse non-finite input -- and the 3k sums and maxima after them.  A step writes into the block beside the state and commits by an index
+ * swap, so a refused step leaves the state of the last completed one.
+ * smg_rd_create: h gives the prolongations (any scalar hierarchy on this mesh, at least two levels); they are copied, h is not modified.  The
+ *   checks, all SMG_ERR_INVALID before the device is touched, in this order: a null argument; a union or block hierarchy; nV not the level-0
+ *   rows; fewer than two levels; the mesh (indices, areas, finite coordinates, one component); then the parameters in their order: Du finite
+ *   and > 0, Dv finite and >= 0, dt finite and > 0, react_substeps >= 1, stop_change >= 0 (not NaN).  SMG_ERR_NO_DEVICE after all of them.
+ * smg_rd_set_params: the same parameter checks; a change between the three cases of handle use (Du != Dv with Dv > 0 | Du == Dv | Dv == 0)
+ *   is refused.
+ * smg_rd_set_state: u, v are nV x k column-major (leading dimension ld >= nV) in `memspace`; coeff is k x 20 row-major on the HOST, every
+ *   entry finite; sets k.
+ * smg_rd_state: the state into u, v (nV x k each, leading dimension ld, in `memspace`).
+ * smg_rd_step: at most n_steps steps.  mass_his (n_steps x 2k row-major: sum m u per column, then sum m v), change_his (n_steps x k: max_i
+ *   max(|u' - u|, |v' - v|)), cycles (n_steps x 2: the loop entries of the first and of the second solve, 0 where there is none), n_done: host,
+ *   NULL ok.  The loop ends after a step whose change is <= stop_change in every column (stop_change == 0: never early).  A non-finite
+ *   right-hand side ends the call with SMG_ERR_NONFINITE: the state of the last completed step is kept and the histories hold n_done rows.  A
+ *   solve that does not reach its tolerance is not an error.
+ * Call refusals, SMG_ERR_INVALID before any launch: a null object or block, k < 1, a bad memspace, a leading dimension below nV, a non-finite
+ *   coefficient, a call before smg_rd_set_state, n_steps < 1.
+ * smg_rd_set_solver: as smg_arap_set_solver (PCG by default).  Nothing is allocated after create except the state's blocks, which grow with
+ *   the largest k seen and are kept (smg_rd_device_bytes counts them).
+ * smg_rd_host: the host twin of the kernels on caller arrays (no GPU, the text the kernels compile, the sums in the device's order), with the
+ *   operands and the layouts of smg_debug_rd below. */
+typedef struct { double Du, Dv, dt; int react_substeps; double stop_change; } smg_rd_params;
+enum { SMG_RD_REACT = 0, SMG_RD_CLOSE = 1 };
+typedef struct smg_rd smg_rd;
+smg_rd_params smg_rd_params_default(void);                 /* 1.0, 1.0, 1.0, 1, 0.0 */
+int smg_rd_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const smg_rd_params *p, smg_rd **out);
+void smg_rd_destroy(smg_rd *g);
+int smg_rd_set_params(smg_rd *g, const smg_rd_params *p);
+int smg_rd_set_solver(smg_rd *g, int pcg);
+long long smg_rd_device_bytes(const smg_rd *g);
+int smg_rd_set_state(smg_rd *g, const double *u, const double *v, int ld, int k, const double *coeff, int memspace);
+int smg_rd_state(smg_rd *g, double *u, double *v, int ld, int memspace);
+int smg_rd_step(smg_rd *g, int n_steps, const smg_solve_opts *opts, double *mass_his, double *change_his, int *cycles, int *n_done);
+int smg_rd_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *u, const double *v, const double *coeff, double dt,
+                int substeps, const double *un, const double *vn, double *out);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -1535,6 +1586,23 @@ int smg_debug_fluid(int op, int nV, int nF, int k, const int *F, const double *V
  * launch that is not timed; *ms = the mean time of a launch in milliseconds.  SMG_ERR_INVALID for another op, nV < 1, nF < 1, a missing array,
  * k < 1, reps < 1, a face index out of range; SMG_ERR_NO_DEVICE without a GPU. */
 int smg_debug_fluid_time(int op, int nV, int nF, int k, const int *F, const double *V, int rates_only, int reps, double *ms);
+
+/* One launcher of the reaction-diffusion object (csrc/smg_rd_device.hip), handle-free and guarded like the hooks above.  F: nF x 3; V: nV x 3
+ * row-major; u, v, un, vn: nV x k column-major with leading dimension nV; coeff: k x 20 row-major; every array is host.  k_hodge_geometry and
+ * k_fluid_mass run first.
+ *   SMG_RD_REACT  V, u, v, coeff, dt, substeps -> out = the right-hand sides m u* then m v* (nV x 2k column-major), their squares (2k planes of
+ *                 nV), v* (nV x k column-major), the sums of the squares of m u* and of m v* (2)
+ *   SMG_RD_CLOSE  V, u, v (the step's start), un, vn (its end) -> out = the terms m un then m vn (2k planes of nV), the changes (k planes of nV),
+ *                 the terms' sums (2k), the changes' maxima (k)
+ * SMG_ERR_INVALID for an unknown op, nV < 1, nF < 1, a missing operand, k < 1, substeps < 1, dt not finite and > 0, a non-finite coefficient, a
+ * face index out of range; SMG_ERR_NO_DEVICE without a GPU. */
+int smg_debug_rd(int op, int nV, int nF, int k, const int *F, const double *V, const double *u, const double *v, const double *coeff, double dt,
+                 int substeps, const double *un, const double *vn, double *out, int *guard_hits);
+/* The time of one launcher of the reaction-diffusion object alone, for tools/rd_time.py: SMG_RD_REACT (with `substeps` sub-steps) or SMG_RD_CLOSE
+ * on device blocks of zeros of k columns over the mesh (F, V: host), launched `reps` times back to back on one stream between two events after
+ * one launch that is not timed; *ms = the mean time of a launch in milliseconds.  SMG_ERR_INVALID for another op, nV < 1, nF < 1, a missing
+ * array, k < 1, substeps < 1, reps < 1, a face index out of range; SMG_ERR_NO_DEVICE without a GPU. */
+int smg_debug_rd_time(int op, int nV, int nF, int k, const int *F, const double *V, int substeps, int reps, double *ms);
 
 /* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
  * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.

@@ -51,6 +51,10 @@ class FluidParamsC(C.Structure):
     _fields_ = [("theta", C.c_double), ("stages", C.c_int), ("viscosity", C.c_double), ("dt", C.c_double), ("cfl", C.c_double)]
 
 
+class RdParamsC(C.Structure):
+    _fields_ = [("Du", C.c_double), ("Dv", C.c_double), ("dt", C.c_double), ("react_substeps", C.c_int), ("stop_change", C.c_double)]
+
+
 _lib = None
 
 
@@ -258,6 +262,18 @@ def load():
         "smg_fluid_host": (i, [i, i, i, i, ip, dp, dp, dp, dp, d, d, dp, d, i, dp]),
         "smg_debug_fluid": (i, [i, i, i, i, ip, dp, dp, dp, dp, d, d, dp, d, i, dp, ip]),
         "smg_debug_fluid_time": (i, [i, i, i, i, ip, dp, i, i, dp]),
+        "smg_rd_params_default": (RdParamsC, []),
+        "smg_rd_create": (i, [vp, dp, i, ip, i, C.POINTER(RdParamsC), C.POINTER(vp)]),
+        "smg_rd_destroy": (None, [vp]),
+        "smg_rd_set_params": (i, [vp, C.POINTER(RdParamsC)]),
+        "smg_rd_set_solver": (i, [vp, i]),
+        "smg_rd_device_bytes": (C.c_longlong, [vp]),
+        "smg_rd_set_state": (i, [vp, vp, vp, i, i, dp, i]),
+        "smg_rd_state": (i, [vp, vp, vp, i, i]),
+        "smg_rd_step": (i, [vp, i, C.POINTER(SolveOptsC), dp, dp, ip, ip]),
+        "smg_rd_host": (i, [i, i, i, i, ip, dp, dp, dp, dp, d, i, dp, dp, dp]),
+        "smg_debug_rd": (i, [i, i, i, i, ip, dp, dp, dp, dp, d, i, dp, dp, dp, ip]),
+        "smg_debug_rd_time": (i, [i, i, i, i, ip, dp, i, i, dp]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

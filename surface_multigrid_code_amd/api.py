@@ -1497,6 +1497,83 @@ def fluid_params(**params):
     return p
 
 
+class ReactionDiffusion(_MeshObject):
+    """Two-species reaction-diffusion on a surface (include/smg.h: smg_rd_*): per column u_t = Du Laplace u + R_u(u, v), v_t = Dv Laplace v +
+    R_v(u, v) with the no-flux boundary condition, R_u and R_v bivariate cubics given per column as 20 coefficients (reactions.py has the named
+    models).  The reaction is explicit (react_substeps Euler sub-steps in one vertex kernel), the diffusion implicit on the constant matrices
+    M + dt D (-L): two k-column solves, ONE 2k-column solve when Du == Dv, one k-column solve when Dv == 0.  The state (n x k each: k independent
+    simulations) lives on the device.
+
+    hierarchy: a scalar Hierarchy of at least two levels whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified."""
+
+    _prefix = "smg_rd_"
+    g = property(lambda self: self.o)
+
+    def __init__(self, hierarchy, V, F, Du, Dv, dt, react_substeps=1, stop_change=0.0):
+        self.params = rd_params(Du=Du, Dv=Dv, dt=dt, react_substeps=react_substeps, stop_change=stop_change)
+        self.k = 0
+        self._create(hierarchy, V, F, C.byref(self.params))
+
+    def set_params(self, **params):
+        """Du, Dv, dt, react_substeps, stop_change of the following steps; a changed dt Du or dt Dv re-precomputes by values; the case of
+        handle use (Du != Dv with Dv > 0 | Du == Dv | Dv == 0) cannot change"""
+        p = _lib.RdParamsC(*[getattr(self.params, f) for f, _ in _lib.RdParamsC._fields_])
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise TypeError("unknown reaction-diffusion parameter %r" % k)
+            setattr(p, k, v)
+        self._call("set_params", C.byref(p))
+        self.params = p
+
+    def set_state(self, u, v, coeff):
+        """u, v: n or n x k; coeff: 20 (every column's reaction) or k x 20; sets k"""
+        u = np.asfortranarray(np.asarray(u, dtype=np.float64).reshape(self.n, -1))
+        v = np.asfortranarray(np.asarray(v, dtype=np.float64).reshape(self.n, -1))
+        k = u.shape[1]
+        if v.shape[1] != k:
+            raise ValueError("u has %d columns, v has %d" % (k, v.shape[1]))
+        coeff = np.asarray(coeff, dtype=np.float64)
+        coeff = np.ascontiguousarray(np.broadcast_to(coeff, (k, 20)) if coeff.ndim == 1 else coeff.reshape(k, 20))
+        self._call("set_state", u.ctypes.data, v.ctypes.data, self.n, k, _dp(coeff), SMG_HOST)
+        self.k = k
+
+    def set_state_device(self, u_ptr, v_ptr, ld, k, coeff):
+        coeff = np.ascontiguousarray(np.asarray(coeff, dtype=np.float64).reshape(k, 20))
+        self._call("set_state", u_ptr, v_ptr, ld, k, _dp(coeff), SMG_DEVICE)
+        self.k = k
+
+    def step(self, n_steps=1, opts=None):
+        """at most n_steps steps -> (mass n_done x 2k: sum m u then sum m v per column, change n_done x k, cycles n_done x 2: the loop entries of
+        the step's solves); self.n_done: the steps done"""
+        k, rows = max(self.k, 1), max(n_steps, 1)
+        mass, change, cyc = np.zeros((rows, 2 * k)), np.zeros((rows, k)), np.zeros((rows, 2), dtype=np.int32)
+        nd = C.c_int(0)
+        try:
+            self._call("step", int(n_steps), self._opts(opts), _dp(mass), _dp(change), _ip(cyc), C.byref(nd))
+        finally:
+            self.n_done = nd.value
+        return mass[:nd.value].copy(), change[:nd.value].copy(), cyc[:nd.value].copy()
+
+    def state(self):
+        """(u, v), n x k each"""
+        u, v = np.zeros((self.n, max(self.k, 1)), order="F"), np.zeros((self.n, max(self.k, 1)), order="F")
+        self._call("state", u.ctypes.data, v.ctypes.data, self.n, SMG_HOST)
+        return u, v
+
+    def state_device(self, u_ptr, v_ptr, ld):
+        self._call("state", u_ptr, v_ptr, ld, SMG_DEVICE)
+
+
+def rd_params(**params):
+    """smg_rd_params with the library's defaults and the given fields"""
+    p = _lib.load().smg_rd_params_default()
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError("unknown reaction-diffusion parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 def flow_params(**params):
     """smg_flow_params with the library's defaults and the given fields"""
     p = _lib.load().smg_flow_params_default()

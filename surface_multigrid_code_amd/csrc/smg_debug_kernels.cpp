@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow), of the Hodge kernels (smg_debug_hodge), of the earth mover's kernels (smg_debug_emd), of the surface-fluid kernels (smg_debug_fluid) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow), of the Hodge kernels (smg_debug_hodge), of the earth mover's kernels (smg_debug_emd), of the surface-fluid kernels (smg_debug_fluid), of the reaction-diffusion kernels (smg_debug_rd) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -15,6 +15,7 @@
 #include "smg_membrane_inl.hpp"
 #include "smg_mesh.hpp"
 #include "smg_mesh_object.hpp"
+#include "smg_rd_inl.hpp"
 #include "smg_stylize_inl.hpp"
 
 using namespace smg;
@@ -1151,6 +1152,116 @@ extern "C" int smg_debug_fluid_time(int op, int nV, int nF, int k, const int* F,
                 case SMG_FLUID_VELOCITY: return launch_fluid_velocity(nF, k, dF.p, dW.p, dn.p, dA.p, psi.p, nV, U.p, rate.p, st);
                 default: return launch_fluid_diag(nV, k, dm.p, w.p, nV, out.p, mw.p, st);
             }
+        };
+        HIPCHK(hipEventCreate(&t0.e));
+        HIPCHK(hipEventCreate(&t1.e));
+        HIPCHK(launch());                                                    // one launch that is not timed
+        HIPCHK(hipEventRecord(t0.e, st));
+        for (int r = 0; r < reps; r++) HIPCHK(launch());
+        HIPCHK(hipEventRecord(t1.e, st));
+        HIPCHK(hipStreamSynchronize(st));
+        float total = 0.0f;
+        HIPCHK(hipEventElapsedTime(&total, t0.e, t1.e));
+        *ms = (double)total / reps;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_rd(int op, int nV, int nF, int k, const int* F, const double* V, const double* u, const double* v, const double* coeff, double dt,
+                            int substeps, const double* un, const double* vn, double* out, int* guard_hits)
+{
+    return guarded("smg_debug_rd", [&]() -> int {
+        const char* who = "smg_debug_rd";
+        if (int rc = rd_check_operands(who, op, nV, nF, k, F, V, u, v, coeff, dt, substeps, un, vn, out)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, kk = (size_t)k, nk = n * kk, D = sizeof(double);
+        if (2 * nk > (size_t)INT_MAX) return fail(SMG_ERR_INVALID, "%s: k = %d exceeds the index range", who, k);
+        Scratch S;
+        HIPCHK(S.init());
+        hipStream_t st = S.stream();
+        std::vector<int> mp, mi;
+        vertex_corner_lists(std::vector<int>(F, F + 3 * f), nV, mp, mi);
+        const size_t out_count = op == SMG_RD_REACT ? 5 * nk + 2 : 3 * nk + 3 * kk;
+        int *dF = nullptr, *dmp = nullptr, *dmi = nullptr;
+        double *dV = nullptr, *du = nullptr, *dv = nullptr, *dun = nullptr, *dvn = nullptr, *dcoef = nullptr, *dout = nullptr, *dW = nullptr, *dn = nullptr,
+               *dA = nullptr, *dm = nullptr, *dpart = nullptr;
+        HIPCHK(S.add(F, nullptr, 3 * f * sizeof(int), &dF));
+        HIPCHK(S.add(V, nullptr, 3 * n * D, &dV));
+        HIPCHK(S.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+        HIPCHK(S.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+        HIPCHK(S.add(u, nullptr, nk * D, &du));
+        HIPCHK(S.add(v, nullptr, nk * D, &dv));
+        if (op == SMG_RD_REACT) {
+            HIPCHK(S.add(coeff, nullptr, kk * RD_COEFFS * D, &dcoef));
+        } else {
+            HIPCHK(S.add(un, nullptr, nk * D, &dun));
+            HIPCHK(S.add(vn, nullptr, nk * D, &dvn));
+        }
+        HIPCHK(S.add(nullptr, nullptr, 9 * f * D, &dW));
+        HIPCHK(S.add(nullptr, nullptr, 3 * f * D, &dn));
+        HIPCHK(S.add(nullptr, nullptr, f * D, &dA));
+        HIPCHK(S.add(nullptr, nullptr, n * D, &dm));
+        HIPCHK(S.add(nullptr, nullptr, (size_t)fixed_sum_groups((int)nk) * D, &dpart));
+        HIPCHK(S.add(out, out, out_count * D, &dout));
+        HIPCHK(launch_hodge_geometry(dV, dF, nF, dW, dn, dA, st));
+        HIPCHK(launch_fluid_mass(nV, dmp, dmi, dA, dm, st));
+        if (op == SMG_RD_REACT) {
+            double* rsq = dout + 2 * nk;
+            HIPCHK(launch_rd_react(nV, k, dm, du, dv, nV, dcoef, dt / substeps, substeps, dout, dout + nk, nV, rsq, dout + 4 * nk, nV, st));
+            HIPCHK(launch_fixed_sum(rsq, (int)nk, dpart, dout + 5 * nk, st));
+            HIPCHK(launch_fixed_sum(rsq + nk, (int)nk, dpart, dout + 5 * nk + 1, st));
+        } else {
+            double* chg = dout + 2 * nk;
+            HIPCHK(launch_rd_close(nV, k, dm, du, dv, dun, dvn, nV, dout, chg, st));
+            for (size_t c = 0; c < 2 * kk; c++) HIPCHK(launch_fixed_sum(dout + c * n, nV, dpart, dout + 3 * nk + c, st));
+            for (size_t c = 0; c < kk; c++) HIPCHK(launch_fixed_max(chg + c * n, nV, dpart, dout + 3 * nk + 2 * kk + c, st));
+        }
+        int bad = 0;
+        HIPCHK(S.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_rd_time(int op, int nV, int nF, int k, const int* F, const double* V, int substeps, int reps, double* ms)
+{
+    return guarded("smg_debug_rd_time", [&]() -> int {
+        const char* who = "smg_debug_rd_time";
+        if (op < SMG_RD_REACT || op > SMG_RD_CLOSE || nV < 1 || nF < 1 || !F || !V || !ms) return fail(SMG_ERR_INVALID, "%s: bad arguments", who);
+        if (k < 1 || substeps < 1 || reps < 1) return fail(SMG_ERR_INVALID, "%s: k = %d, substeps = %d, reps = %d, at least 1 each is needed", who, k, substeps, reps);
+        if (int rc = check_faces(who, F, nF, nV)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, kk = (size_t)k, nk = n * kk, D = sizeof(double);
+        if (2 * nk > (size_t)INT_MAX) return fail(SMG_ERR_INVALID, "%s: k = %d exceeds the index range", who, k);
+        std::vector<int> mp, mi;
+        vertex_corner_lists(std::vector<int>(F, F + 3 * f), nV, mp, mi);
+        struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void)hipEventDestroy(e); } } t0, t1;
+        Scratch S;                                                           // for its stream alone
+        HIPCHK(S.init());
+        hipStream_t st = S.stream();
+        DevBuf<int> dF, dmp, dmi;
+        DevBuf<double> dV, dW, dn, dA, dm, coef, s0, s1, R, rsq, chg;
+        HIPCHK(dF.upload(std::vector<int>(F, F + 3 * f)));
+        HIPCHK(dmp.upload(mp));
+        HIPCHK(dmi.upload(mi));
+        HIPCHK(dV.upload(std::vector<double>(V, V + 3 * n)));
+        HIPCHK(dW.alloc(9 * f));
+        HIPCHK(dn.alloc(3 * f));
+        HIPCHK(dA.alloc(f));
+        HIPCHK(dm.alloc(n));
+        HIPCHK(coef.alloc(kk * RD_COEFFS));
+        HIPCHK(chg.alloc(nk));
+        HIPCHK(hipMemsetAsync(coef.p, 0, kk * RD_COEFFS * D, st));
+        for (DevBuf<double>* b : {&s0, &s1, &R, &rsq}) {                     // zeros: the operands' values do not change what a launch moves
+            HIPCHK(b->alloc(2 * nk));
+            HIPCHK(hipMemsetAsync(b->p, 0, 2 * nk * D, st));
+        }
+        HIPCHK(launch_hodge_geometry(dV.p, dF.p, nF, dW.p, dn.p, dA.p, st));
+        HIPCHK(launch_fluid_mass(nV, dmp.p, dmi.p, dA.p, dm.p, st));
+        auto launch = [&]() -> hipError_t {
+            if (op == SMG_RD_REACT)
+                return launch_rd_react(nV, k, dm.p, s0.p, s0.p + nk, nV, coef.p, 0.5, substeps, R.p, R.p + nk, nV, rsq.p, nullptr, nV, st);
+            return launch_rd_close(nV, k, dm.p, s0.p, s0.p + nk, s1.p, s1.p + nk, nV, rsq.p, chg.p, st);
         };
         HIPCHK(hipEventCreate(&t0.e));
         HIPCHK(hipEventCreate(&t1.e));

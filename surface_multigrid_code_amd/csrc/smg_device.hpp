@@ -666,4 +666,15 @@ hipError_t launch_fluid_velocity(int nF, int k, const int* F, const double* W, c
 // mw = m w, ew (nullptr ok) = 0.5 ((m w) w): k planes of n each
 hipError_t launch_fluid_diag(int n, int k, const double* m, const double* w, int ldw, double* mw, double* ew, hipStream_t st);
 
+// two-species reaction-diffusion on a surface (smg_rd_device.hip; the maths in smg_rd_inl.hpp).  m: the barycentric masses of launch_fluid_mass;
+// u, v and the outputs: column-major blocks of k columns with a leading dimension; coef: k x 20 on the device; per-vertex term planes are planes
+// of n.  One wavefront per (64 vertices, column) ----------------------------------------------------------------------------------------------
+// (u, v) through `substeps` Euler steps of length h of the column's cubic reaction; Ru = m u*, Rv = m v*; rsq: 2k planes, the squares of Ru then
+// of Rv; vout (nullptr ok) = v*
+hipError_t launch_rd_react(int n, int k, const double* m, const double* u, const double* v, int ld, const double* coef, double h, int substeps,
+                           double* Ru, double* Rv, int ldr, double* rsq, double* vout, int ldv, hipStream_t st);
+// mt: 2k planes, m u1 then m v1; chg: k planes, max(|u1 - u0|, |v1 - v0|)
+hipError_t launch_rd_close(int n, int k, const double* m, const double* u0, const double* v0, const double* u1, const double* v1, int ld, double* mt,
+                           double* chg, hipStream_t st);
+
 }  // namespace smg

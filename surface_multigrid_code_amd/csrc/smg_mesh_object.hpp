@@ -103,4 +103,9 @@ int emd_check_operands(const char* who, int op, int nV, int nF, int k, const int
 int fluid_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* w, const double* psi, const double* wn,
                          const double* dt, double theta, int rates_only, const double* out);
 
+// ---- smg_rd.cpp: what smg_rd_host and smg_debug_rd check alike, in this order: the op and its operands, k, then for the reaction the sub-steps,
+// dt and the coefficients (finite), the faces
+int rd_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* u, const double* v, const double* coeff,
+                      double dt, int substeps, const double* un, const double* vn, const double* out);
+
 }  // namespace smg
