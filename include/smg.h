@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 530
+#define SMG_VERSION 540
 
 enum {
     SMG_OK = 0,
@@ -1161,6 +1161,73 @@ int smg_rd_step(smg_rd *g, int n_steps, const smg_solve_opts *opts, double *mass
 int smg_rd_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *u, const double *v, const double *coeff, double dt,
                 int substeps, const double *un, const double *vn, double *out);
 
+/* ---- The wave equation on a surface, with shots and receivers (csrc/smg_wave.cpp): the state is the pair (u, v = u_t), two
+ * doubles per (vertex, column), resident on the device; k columns are k independent experiments ("shots") and k columns of every solve.  With
+ * C = -L the positive semi-definite cotangent matrix, m_i the barycentric mass (a third of the areas around i), mt_i = m_i / speed_i^2,
+ * sigma_i >= 0 a damping rate per vertex and f(t) integrated nodal forces, per column
+ *     Mt u_tt + Sigma Mt u_t + C u = f(t),      Mt = diag(mt_i), Sigma = diag(sigma_i)
+ * stepped by the trapezoidal rule in (u, v) (Newmark with beta = 1/4, gamma = 1/2).  With s2_i = 2.0 + sigma_i * dt, a = 0.25 * dt * dt,
+ * q2 = 2.0 / dt (host doubles, formed once) and w = u + u':
+ *   1. k_wave_rhs: b_i = mt_i * (s2_i * u_i + dt * v_i), its squares (0.0 on a known row) and the warm start 2.0 * u + dt * v.  Within a call
+ *      and across calls the previous step's k_wave_advance has already left all three: only the first step after set_state or set_params runs
+ *      this kernel.
+ *   2. k_wave_sources (a signal is given): b_i += a * (f_i(t_n) + f_i(t_n+1)) at the source vertices, the squares rewritten there.
+ *   3. A w = b,  A = diag(0.5 * s2_i * mt_i) + a C, warm-started from 2u + dt v, which the kernels write into the block the solve returns w in
+ *      (smg_solve and smg_solve_pcg gather z0 into the handle before they scatter z).
+ *   4. k_wave_advance: u' = w - u, v' = q2 * (u' - u) - v, the kinetic terms 0.5 * ((mt_i * v') * v'), and the next step's b, squares and warm
+ *      start from (u', v') with k_wave_rhs's expressions; the potential energy 0.5 u' C u' is the sum of k_fluid_velocity's face terms of u'.
+ *   5. k_wave_record: u' at the receivers into row t of the trace buffer.
+ * No product with C is needed.  A is precomputed at create and by values again when set_params changes dt or damping.  The host reads per step
+ * |b|_F^2 before the solve -- it sets the default tolerance (opts NULL: 1e-10 |b|_F, max_iter 100) and refuses non-finite input -- and, where
+ * energy_his is given, the 2k energy sums after it.  A step writes into the block beside the state and commits by an index swap, so a refused
+ * step leaves the state of the last completed one.
+ * Boundary: clamped = 0 is the natural (free) boundary, no row is known, on closed and on open meshes; clamped = 1 makes the boundary vertices
+ *   known rows of the handle with value 0: u, v and forces on those rows must be 0, and the kernels then return exact zeros there.
+ * smg_wave_create: h gives the prolongations (any scalar hierarchy on this mesh, at least two levels); they are copied, h is not modified.
+ *   speed: nV doubles, finite and > 0, NULL: 1 everywhere; sigma: nV doubles, finite and >= 0, NULL: p->damping everywhere.  The checks, all
+ *   SMG_ERR_INVALID before the device is touched, in this order: a null argument; a union or block hierarchy; nV not the level-0 rows; fewer
+ *   than two levels; the mesh (indices, areas, finite coordinates, one component); the parameters in their order: dt finite and > 0, damping
+ *   finite and >= 0, clamped 0 or 1; speed; sigma; then for clamped = 1 a mesh without boundary and a mesh without interior vertex.
+ *   SMG_ERR_NO_DEVICE after all of them.
+ * smg_wave_set_params: the same parameter checks; a new dt or damping (damping counts only where sigma was NULL) rebuilds s2, a, q2 and
+ *   re-precomputes by values; a change of clamped is refused.  The kept right-hand side is dropped.
+ * smg_wave_set_state: u, v are nV x k column-major (leading dimension ld >= nV) in `memspace`; sets k.  When clamped, a u or v that is not 0
+ *   on a boundary row is refused (one small kernel and one host read) and the object is left without a state.
+ * smg_wave_state: the state into u, v (nV x k each, leading dimension ld, in `memspace`).
+ * smg_wave_set_sources: any time after create; n_src >= 0 vertices in range, none twice (so the source kernel writes without atomics), none on
+ *   a clamped boundary vertex.  smg_wave_set_receivers: n_rec >= 0 vertices in range; duplicates are allowed.
+ * smg_wave_step: at most n_steps steps.  signal (host, NULL: no force): (n_steps + 1) x n_src x k row-major, entry [t][j][c] the nodal force at
+ *   source j in column c at the call's start time plus t dt; with n_src == 0 or a non-finite entry it is refused; uploaded once per call.
+ *   energy_his (n_steps x 2k row-major: kinetic then potential energy per column, after each step; NULL: the potential-energy launches and
+ *   the read are skipped), traces (n_steps x n_rec x k: u' at the receivers after each step, gathered on the device and copied once at the
+ *   end of the call; NULL or n_rec == 0: skipped), cycles (n_steps: the loop entries of each solve), n_done: host, NULL ok.  A non-finite
+ *   right-hand side ends the call with SMG_ERR_NONFINITE: the state of the last completed step is kept and the histories hold n_done rows.
+ *   A solve that does not reach its tolerance is not an error.
+ * Call refusals, SMG_ERR_INVALID before any launch: a null object or block, k < 1, k columns beyond the index range, a bad memspace, a leading
+ *   dimension below nV, a bad list, a call before smg_wave_set_state, n_steps < 1, a bad signal.
+ * smg_wave_set_solver: as smg_arap_set_solver (PCG by default).  Nothing is allocated after create except the blocks that grow with the largest
+ *   k, n_steps, n_src and n_rec seen and are kept (smg_wave_device_bytes counts them).
+ * smg_wave_host: the host twin of the kernels on caller arrays (no GPU, the text the kernels compile, the sums in the device's order), with the
+ *   operands and the layouts of smg_debug_wave below. */
+typedef struct { double dt, damping; int clamped; } smg_wave_params;
+enum { SMG_WAVE_RHS = 0, SMG_WAVE_SOURCES = 1, SMG_WAVE_ADVANCE = 2, SMG_WAVE_RECORD = 3 };
+typedef struct smg_wave smg_wave;
+smg_wave_params smg_wave_params_default(void);             /* 1.0, 0.0, 0 */
+int smg_wave_create(const smg_hierarchy *h, const double *V, int nV, const int *F, int nF, const double *speed, const double *sigma,
+                    const smg_wave_params *p, smg_wave **out);
+void smg_wave_destroy(smg_wave *g);
+int smg_wave_set_params(smg_wave *g, const smg_wave_params *p);
+int smg_wave_set_solver(smg_wave *g, int pcg);
+long long smg_wave_device_bytes(const smg_wave *g);
+int smg_wave_set_state(smg_wave *g, const double *u, const double *v, int ld, int k, int memspace);
+int smg_wave_state(smg_wave *g, double *u, double *v, int ld, int memspace);
+int smg_wave_set_sources(smg_wave *g, const int *idx, int n_src);
+int smg_wave_set_receivers(smg_wave *g, const int *idx, int n_rec);
+int smg_wave_step(smg_wave *g, int n_steps, const double *signal, const smg_solve_opts *opts, double *energy_his, double *traces, int *cycles,
+                  int *n_done);
+int smg_wave_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *speed, const double *sigma, int clamped, double dt,
+                  const double *u, const double *v, const double *w, const int *idx, int n_idx, const double *sig0, const double *sig1, double *out);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -1603,6 +1670,28 @@ int smg_debug_rd(int op, int nV, int nF, int k, const int *F, const double *V, c
  * one launch that is not timed; *ms = the mean time of a launch in milliseconds.  SMG_ERR_INVALID for another op, nV < 1, nF < 1, a missing
  * array, k < 1, substeps < 1, reps < 1, a face index out of range; SMG_ERR_NO_DEVICE without a GPU. */
 int smg_debug_rd_time(int op, int nV, int nF, int k, const int *F, const double *V, int substeps, int reps, double *ms);
+
+/* One launcher of the wave object (csrc/smg_wave_device.hip), handle-free and guarded like the hooks above.  F: nF x 3; V: nV x 3 row-major;
+ * speed, sigma: nV or NULL (1 and 0 everywhere); u, v, w: nV x k column-major with leading dimension nV; idx: n_idx vertices; sig0, sig1: n_idx x k
+ * row-major; every array is host.  k_hodge_geometry and k_fluid_mass run first; mt = m / speed^2 and s2 = 2.0 + sigma dt are formed on the host
+ * from the device's masses; clamped = 1: the boundary vertices are the known rows.  a = 0.25 dt dt, q2 = 2.0 / dt.
+ *   SMG_WAVE_RHS      u, v -> out = b (nV x k column-major), its squares (k planes of nV), the warm start (nV x k), the squares' sum (1)
+ *   SMG_WAVE_SOURCES  u, v, idx, sig0, sig1 -> k_wave_rhs, then k_wave_sources: out as for SMG_WAVE_RHS
+ *   SMG_WAVE_ADVANCE  u, v, w -> out = u', v' (nV x k each) and the kinetic terms (k planes of nV) of a launch without the next right-hand side;
+ *                     the same three of a launch with it, then its b, squares and warm start (nV x k each); the kinetic sums (k), the potential
+ *                     sums (k: k_fluid_velocity's terms of u'), the squares' sum (1)
+ *   SMG_WAVE_RECORD   u, idx -> out = u at the vertices idx (n_idx x k row-major); F and V are only checked
+ * SMG_ERR_INVALID for an unknown op, nV < 1, nF < 1, a missing operand, k < 1, dt not finite and > 0, clamped not 0 or 1, a speed not finite and
+ * > 0, a sigma not finite and >= 0, a face index out of range, n_idx < 1, a list index out of range, a source listed twice; SMG_ERR_NO_DEVICE
+ * without a GPU. */
+int smg_debug_wave(int op, int nV, int nF, int k, const int *F, const double *V, const double *speed, const double *sigma, int clamped, double dt,
+                   const double *u, const double *v, const double *w, const int *idx, int n_idx, const double *sig0, const double *sig1, double *out,
+                   int *guard_hits);
+/* The time of one launcher of the wave object alone, for tools/wave_time.py: SMG_WAVE_RHS or SMG_WAVE_ADVANCE (with the next right-hand side) on
+ * device blocks of zeros of k columns over the mesh (F, V: host), launched `reps` times back to back on one stream between two events after one
+ * launch that is not timed; *ms = the mean time of a launch in milliseconds.  SMG_ERR_INVALID for another op, nV < 1, nF < 1, a missing array,
+ * k < 1, reps < 1, a face index out of range; SMG_ERR_NO_DEVICE without a GPU. */
+int smg_debug_wave_time(int op, int nV, int nF, int k, const int *F, const double *V, int reps, double *ms);
 
 /* One launcher of the union handles (csrc/smg_union_device.hip: smg_hierarchy_create_union), handle-free and guarded like the hooks above.
  * Blocks are row-major n x k, as the solve keeps them; every non-const array is in/out (uploaded, then copied back).  m members.

@@ -55,6 +55,10 @@ class RdParamsC(C.Structure):
     _fields_ = [("Du", C.c_double), ("Dv", C.c_double), ("dt", C.c_double), ("react_substeps", C.c_int), ("stop_change", C.c_double)]
 
 
+class WaveParamsC(C.Structure):
+    _fields_ = [("dt", C.c_double), ("damping", C.c_double), ("clamped", C.c_int)]
+
+
 _lib = None
 
 
@@ -274,6 +278,20 @@ def load():
         "smg_rd_host": (i, [i, i, i, i, ip, dp, dp, dp, dp, d, i, dp, dp, dp]),
         "smg_debug_rd": (i, [i, i, i, i, ip, dp, dp, dp, dp, d, i, dp, dp, dp, ip]),
         "smg_debug_rd_time": (i, [i, i, i, i, ip, dp, i, i, dp]),
+        "smg_wave_params_default": (WaveParamsC, []),
+        "smg_wave_create": (i, [vp, dp, i, ip, i, dp, dp, C.POINTER(WaveParamsC), C.POINTER(vp)]),
+        "smg_wave_destroy": (None, [vp]),
+        "smg_wave_set_params": (i, [vp, C.POINTER(WaveParamsC)]),
+        "smg_wave_set_solver": (i, [vp, i]),
+        "smg_wave_device_bytes": (C.c_longlong, [vp]),
+        "smg_wave_set_state": (i, [vp, vp, vp, i, i, i]),
+        "smg_wave_state": (i, [vp, vp, vp, i, i]),
+        "smg_wave_set_sources": (i, [vp, ip, i]),
+        "smg_wave_set_receivers": (i, [vp, ip, i]),
+        "smg_wave_step": (i, [vp, i, dp, C.POINTER(SolveOptsC), dp, dp, ip, ip]),
+        "smg_wave_host": (i, [i, i, i, i, ip, dp, dp, dp, i, d, dp, dp, dp, ip, i, dp, dp, dp]),
+        "smg_debug_wave": (i, [i, i, i, i, ip, dp, dp, dp, i, d, dp, dp, dp, ip, i, dp, dp, dp, ip]),
+        "smg_debug_wave_time": (i, [i, i, i, i, ip, dp, i, dp]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

@@ -1574,6 +1574,102 @@ def rd_params(**params):
     return p
 
 
+class WaveEquation(_MeshObject):
+    """The wave equation on a surface with shots and receivers (include/smg.h: smg_wave_*): per column Mt u_tt + Sigma Mt u_t + C u = f(t) with
+    C = -L, Mt = diag(m / speed^2) and Sigma = diag(sigma), stepped by the trapezoidal rule in (u, v = u_t): ONE k-column solve of the constant
+    matrix diag((1 + sigma dt / 2) mt) + (dt^2 / 4) C per step, k experiments at once.  clamped=False is the free boundary; clamped=True holds
+    the boundary vertices at 0.  The state (n x k each) lives on the device.
+
+    hierarchy: a scalar Hierarchy of at least two levels whose level 0 is the mesh (V, F); its prolongations are copied, it is not modified.
+    speed, sigma: n values or None (1 everywhere; `damping` everywhere)."""
+
+    _prefix = "smg_wave_"
+    g = property(lambda self: self.o)
+
+    def __init__(self, hierarchy, V, F, dt, speed=None, sigma=None, damping=0.0, clamped=False):
+        self.params = wave_params(dt=dt, damping=damping, clamped=int(clamped))
+        self.k = self.n_src = self.n_rec = 0
+        n = np.asarray(V).shape[0]
+        speed = None if speed is None else np.ascontiguousarray(np.broadcast_to(np.asarray(speed, dtype=np.float64), (n,)))
+        sigma = None if sigma is None else np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (n,)))
+        self._create(hierarchy, V, F, None if speed is None else _dp(speed), None if sigma is None else _dp(sigma), C.byref(self.params))
+
+    def set_params(self, **params):
+        """dt, damping of the following steps: a changed value re-precomputes by values; clamped cannot change"""
+        p = _lib.WaveParamsC(*[getattr(self.params, f) for f, _ in _lib.WaveParamsC._fields_])
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise TypeError("unknown wave parameter %r" % k)
+            setattr(p, k, v)
+        self._call("set_params", C.byref(p))
+        self.params = p
+
+    def set_state(self, u, v):
+        """u, v: n or n x k; sets k"""
+        u = np.asfortranarray(np.asarray(u, dtype=np.float64).reshape(self.n, -1))
+        v = np.asfortranarray(np.asarray(v, dtype=np.float64).reshape(self.n, -1))
+        k = u.shape[1]
+        if v.shape[1] != k:
+            raise ValueError("u has %d columns, v has %d" % (k, v.shape[1]))
+        self.k = 0
+        self._call("set_state", u.ctypes.data, v.ctypes.data, self.n, k, SMG_HOST)
+        self.k = k
+
+    def set_state_device(self, u_ptr, v_ptr, ld, k):
+        self.k = 0
+        self._call("set_state", u_ptr, v_ptr, ld, k, SMG_DEVICE)
+        self.k = k
+
+    def set_sources(self, idx):
+        """the vertices that step()'s signal drives: no vertex twice, none on a clamped boundary"""
+        idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1))
+        self._call("set_sources", _ip(idx), idx.size)
+        self.n_src = idx.size
+
+    def set_receivers(self, idx):
+        """the vertices whose u every step records"""
+        idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1))
+        self._call("set_receivers", _ip(idx), idx.size)
+        self.n_rec = idx.size
+
+    def step(self, n_steps=1, signal=None, energy=True, opts=None):
+        """at most n_steps steps -> (energy n_done x 2k: kinetic then potential per column, or None; traces n_done x n_rec x k; cycles n_done);
+        signal: (n_steps + 1) x n_src x k nodal forces at the step times, or None; self.n_done: the steps done"""
+        k, rows = max(self.k, 1), max(n_steps, 1)
+        E = np.zeros((rows, 2 * k)) if energy else None
+        tr, cyc = np.zeros((rows, self.n_rec, k)), np.zeros(rows, dtype=np.int32)
+        if signal is not None:
+            signal = np.ascontiguousarray(np.asarray(signal, dtype=np.float64))
+            if signal.size != (rows + 1) * self.n_src * k:
+                raise ValueError("the signal has %d entries, (n_steps + 1) x n_src x k = %d are needed" % (signal.size, (rows + 1) * self.n_src * k))
+        nd = C.c_int(0)
+        try:
+            self._call("step", int(n_steps), None if signal is None else _dp(signal), self._opts(opts), None if E is None else _dp(E),
+                       _dp(tr) if self.n_rec else None, _ip(cyc), C.byref(nd))
+        finally:
+            self.n_done = nd.value
+        return None if E is None else E[:nd.value].copy(), tr[:nd.value].copy(), cyc[:nd.value].copy()
+
+    def state(self):
+        """(u, v), n x k each"""
+        u, v = np.zeros((self.n, max(self.k, 1)), order="F"), np.zeros((self.n, max(self.k, 1)), order="F")
+        self._call("state", u.ctypes.data, v.ctypes.data, self.n, SMG_HOST)
+        return u, v
+
+    def state_device(self, u_ptr, v_ptr, ld):
+        self._call("state", u_ptr, v_ptr, ld, SMG_DEVICE)
+
+
+def wave_params(**params):
+    """smg_wave_params with the library's defaults and the given fields"""
+    p = _lib.load().smg_wave_params_default()
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError("unknown wave parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 def flow_params(**params):
     """smg_flow_params with the library's defaults and the given fields"""
     p = _lib.load().smg_flow_params_default()

@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow), of the Hodge kernels (smg_debug_hodge), of the earth mover's kernels (smg_debug_emd), of the surface-fluid kernels (smg_debug_fluid), of the reaction-diffusion kernels (smg_debug_rd) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow), of the Hodge kernels (smg_debug_hodge), of the earth mover's kernels (smg_debug_emd), of the surface-fluid kernels (smg_debug_fluid), of the reaction-diffusion kernels (smg_debug_rd), of the wave-equation kernels (smg_debug_wave) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -17,6 +17,7 @@
 #include "smg_mesh_object.hpp"
 #include "smg_rd_inl.hpp"
 #include "smg_stylize_inl.hpp"
+#include "smg_wave_inl.hpp"
 
 using namespace smg;
 
@@ -1262,6 +1263,163 @@ extern "C" int smg_debug_rd_time(int op, int nV, int nF, int k, const int* F, co
             if (op == SMG_RD_REACT)
                 return launch_rd_react(nV, k, dm.p, s0.p, s0.p + nk, nV, coef.p, 0.5, substeps, R.p, R.p + nk, nV, rsq.p, nullptr, nV, st);
             return launch_rd_close(nV, k, dm.p, s0.p, s0.p + nk, s1.p, s1.p + nk, nV, rsq.p, chg.p, st);
+        };
+        HIPCHK(hipEventCreate(&t0.e));
+        HIPCHK(hipEventCreate(&t1.e));
+        HIPCHK(launch());                                                    // one launch that is not timed
+        HIPCHK(hipEventRecord(t0.e, st));
+        for (int r = 0; r < reps; r++) HIPCHK(launch());
+        HIPCHK(hipEventRecord(t1.e, st));
+        HIPCHK(hipStreamSynchronize(st));
+        float total = 0.0f;
+        HIPCHK(hipEventElapsedTime(&total, t0.e, t1.e));
+        *ms = (double)total / reps;
+        return SMG_OK;
+    });
+}
+
+namespace {
+
+// the geometry, the masses (on the device, then read back) and the planes mt, s2 of a wave hook; dm: n doubles of scratch
+int wave_planes(hipStream_t st, int nV, int nF, const double* dV, const int* dF, const int* dmp, const int* dmi, double* dW, double* dn, double* dA, double* dm,
+                const double* speed, const double* sigma, double dt, std::vector<double>& mt, std::vector<double>& s2)
+{
+    std::vector<double> m((size_t)nV);
+    mt.resize((size_t)nV);
+    s2.resize((size_t)nV);
+    HIPCHK(launch_hodge_geometry(dV, dF, nF, dW, dn, dA, st));
+    HIPCHK(launch_fluid_mass(nV, dmp, dmi, dA, dm, st));
+    HIPCHK(hipMemcpyAsync(m.data(), dm, (size_t)nV * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    wave_host_planes(nV, m.data(), speed, sigma, dt, mt.data(), s2.data());
+    return SMG_OK;
+}
+
+}  // namespace
+
+extern "C" int smg_debug_wave(int op, int nV, int nF, int k, const int* F, const double* V, const double* speed, const double* sigma, int clamped, double dt,
+                              const double* u, const double* v, const double* w, const int* idx, int n_idx, const double* sig0, const double* sig1, double* out,
+                              int* guard_hits)
+{
+    return guarded("smg_debug_wave", [&]() -> int {
+        const char* who = "smg_debug_wave";
+        if (int rc = wave_check_operands(who, op, nV, nF, k, F, V, speed, sigma, clamped, dt, u, v, w, idx, n_idx, sig0, sig1, out)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, kk = (size_t)k, nk = n * kk, D = sizeof(double);
+        if (2 * nk > (size_t)INT_MAX || 3 * f * kk > (size_t)INT_MAX) return fail(SMG_ERR_INVALID, "%s: k = %d exceeds the index range", who, k);
+        Scratch S;
+        HIPCHK(S.init());
+        hipStream_t st = S.stream();
+        const size_t ni = (size_t)std::max(n_idx, 0);
+        const size_t out_count = op == SMG_WAVE_RECORD ? ni * kk : op == SMG_WAVE_ADVANCE ? 9 * nk + 2 * kk + 1 : 3 * nk + 1;
+        double *du = nullptr, *dv = nullptr, *dw = nullptr, *dout = nullptr, *ds0 = nullptr, *ds1 = nullptr;
+        int* didx = nullptr;
+        HIPCHK(S.add(u, nullptr, nk * D, &du));
+        if (v) HIPCHK(S.add(v, nullptr, nk * D, &dv));
+        if (op == SMG_WAVE_ADVANCE) HIPCHK(S.add(w, nullptr, nk * D, &dw));
+        if (op == SMG_WAVE_SOURCES || op == SMG_WAVE_RECORD) HIPCHK(S.add(idx, nullptr, ni * sizeof(int), &didx));
+        if (op == SMG_WAVE_SOURCES) {
+            HIPCHK(S.add(sig0, nullptr, ni * kk * D, &ds0));
+            HIPCHK(S.add(sig1, nullptr, ni * kk * D, &ds1));
+        }
+        HIPCHK(S.add(out, out, out_count * D, &dout));
+        if (op == SMG_WAVE_RECORD) {
+            HIPCHK(launch_wave_record(nV, k, n_idx, didx, du, nV, dout, st));
+        } else {
+            std::vector<int> mp, mi, known;
+            vertex_corner_lists(std::vector<int>(F, F + 3 * f), nV, mp, mi);
+            int *dF = nullptr, *dmp = nullptr, *dmi = nullptr, *dknown = nullptr;
+            double *dV = nullptr, *dW = nullptr, *dn = nullptr, *dA = nullptr, *dm = nullptr, *dmt = nullptr, *ds2 = nullptr, *dpart = nullptr, *dterms = nullptr;
+            HIPCHK(S.add(F, nullptr, 3 * f * sizeof(int), &dF));
+            HIPCHK(S.add(V, nullptr, 3 * n * D, &dV));
+            HIPCHK(S.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+            HIPCHK(S.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+            HIPCHK(S.add(nullptr, nullptr, 9 * f * D, &dW));
+            HIPCHK(S.add(nullptr, nullptr, 3 * f * D, &dn));
+            HIPCHK(S.add(nullptr, nullptr, f * D, &dA));
+            HIPCHK(S.add(nullptr, nullptr, n * D, &dm));
+            HIPCHK(S.add(nullptr, nullptr, (size_t)fixed_sum_groups((int)std::max(nk, f)) * D, &dpart));
+            if (clamped) {
+                known.assign(n, 0);
+                for (int b : boundary_vertices(F, nF, nV)) known[(size_t)b] = 1;
+                HIPCHK(S.add(known.data(), nullptr, n * sizeof(int), &dknown));
+            }
+            std::vector<double> mt, s2;
+            if (int rc = wave_planes(st, nV, nF, dV, dF, dmp, dmi, dW, dn, dA, dm, speed, sigma, dt, mt, s2)) return rc;
+            HIPCHK(S.add(mt.data(), nullptr, n * D, &dmt));
+            HIPCHK(S.add(s2.data(), nullptr, n * D, &ds2));
+            const double a = 0.25 * dt * dt, q2 = 2.0 / dt;
+            if (op == SMG_WAVE_ADVANCE) {
+                HIPCHK(S.add(nullptr, nullptr, f * kk * D, &dterms));
+                HIPCHK(launch_wave_advance(nV, k, dmt, ds2, dknown, dt, q2, dw, nV, du, dv, nV, dout, dout + nk, nV, dout + 2 * nk, nullptr, nullptr, nV, nullptr, st));
+                double* o = dout + 3 * nk;
+                HIPCHK(launch_wave_advance(nV, k, dmt, ds2, dknown, dt, q2, dw, nV, du, dv, nV, o, o + nk, nV, o + 2 * nk, o + 3 * nk, o + 5 * nk, nV, o + 4 * nk, st));
+                HIPCHK(launch_fluid_velocity(nF, k, dF, dW, dn, dA, o, nV, nullptr, dterms, st));
+                double* s = dout + 9 * nk;
+                for (size_t c = 0; c < kk; c++) {
+                    HIPCHK(launch_fixed_sum(o + 2 * nk + c * n, nV, dpart, s + c, st));
+                    HIPCHK(launch_fixed_sum(dterms + c * f, nF, dpart, s + kk + c, st));
+                }
+                HIPCHK(launch_fixed_sum(o + 4 * nk, (int)nk, dpart, s + 2 * kk, st));
+            } else {
+                double *b = dout, *rsq = dout + nk, *z = dout + 2 * nk;
+                HIPCHK(launch_wave_rhs(nV, k, dmt, ds2, dknown, dt, du, dv, nV, b, z, nV, rsq, st));
+                if (op == SMG_WAVE_SOURCES) HIPCHK(launch_wave_sources(nV, k, n_idx, didx, ds0, ds1, a, b, nV, rsq, st));
+                HIPCHK(launch_fixed_sum(rsq, (int)nk, dpart, dout + 3 * nk, st));
+            }
+            int bad = 0;
+            HIPCHK(S.finish(&bad));   // mt, s2 and the lists live until the stream has drained
+            if (guard_hits) *guard_hits = bad;
+            return SMG_OK;
+        }
+        int bad = 0;
+        HIPCHK(S.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_wave_time(int op, int nV, int nF, int k, const int* F, const double* V, int reps, double* ms)
+{
+    return guarded("smg_debug_wave_time", [&]() -> int {
+        const char* who = "smg_debug_wave_time";
+        if ((op != SMG_WAVE_RHS && op != SMG_WAVE_ADVANCE) || nV < 1 || nF < 1 || !F || !V || !ms) return fail(SMG_ERR_INVALID, "%s: bad arguments", who);
+        if (k < 1 || reps < 1) return fail(SMG_ERR_INVALID, "%s: k = %d, reps = %d, at least 1 each is needed", who, k, reps);
+        if (int rc = check_faces(who, F, nF, nV)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, kk = (size_t)k, nk = n * kk, D = sizeof(double);
+        if (2 * nk > (size_t)INT_MAX) return fail(SMG_ERR_INVALID, "%s: k = %d exceeds the index range", who, k);
+        std::vector<int> mp, mi;
+        vertex_corner_lists(std::vector<int>(F, F + 3 * f), nV, mp, mi);
+        struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void)hipEventDestroy(e); } } t0, t1;
+        Scratch S;                                                           // for its stream alone
+        HIPCHK(S.init());
+        hipStream_t st = S.stream();
+        DevBuf<int> dF, dmp, dmi;
+        DevBuf<double> dV, dW, dn, dA, dm, dmt, ds2, s0, s1, B, Wb, rsq, ke;
+        HIPCHK(dF.upload(std::vector<int>(F, F + 3 * f)));
+        HIPCHK(dmp.upload(mp));
+        HIPCHK(dmi.upload(mi));
+        HIPCHK(dV.upload(std::vector<double>(V, V + 3 * n)));
+        HIPCHK(dW.alloc(9 * f));
+        HIPCHK(dn.alloc(3 * f));
+        HIPCHK(dA.alloc(f));
+        HIPCHK(dm.alloc(n));
+        std::vector<double> mt, s2;
+        if (int rc = wave_planes(st, nV, nF, dV.p, dF.p, dmp.p, dmi.p, dW.p, dn.p, dA.p, dm.p, nullptr, nullptr, 0.5, mt, s2)) return rc;
+        HIPCHK(dmt.upload(mt));
+        HIPCHK(ds2.upload(s2));
+        for (DevBuf<double>* b : {&s0, &s1}) {                               // zeros: the operands' values do not change what a launch moves
+            HIPCHK(b->alloc(2 * nk));
+            HIPCHK(hipMemsetAsync(b->p, 0, 2 * nk * D, st));
+        }
+        for (DevBuf<double>* b : {&B, &Wb, &rsq, &ke}) {
+            HIPCHK(b->alloc(nk));
+            HIPCHK(hipMemsetAsync(b->p, 0, nk * D, st));
+        }
+        auto launch = [&]() -> hipError_t {
+            if (op == SMG_WAVE_RHS) return launch_wave_rhs(nV, k, dmt.p, ds2.p, nullptr, 0.5, s0.p, s0.p + nk, nV, B.p, Wb.p, nV, rsq.p, st);
+            return launch_wave_advance(nV, k, dmt.p, ds2.p, nullptr, 0.5, 4.0, Wb.p, nV, s0.p, s0.p + nk, nV, s1.p, s1.p + nk, nV, ke.p, B.p, Wb.p, nV, rsq.p, st);   // as the object: the warm start over w
         };
         HIPCHK(hipEventCreate(&t0.e));
         HIPCHK(hipEventCreate(&t1.e));

@@ -677,4 +677,23 @@ hipError_t launch_rd_react(int n, int k, const double* m, const double* u, const
 hipError_t launch_rd_close(int n, int k, const double* m, const double* u0, const double* v0, const double* u1, const double* v1, int ld, double* mt,
                            double* chg, hipStream_t st);
 
+// the wave equation on a surface (smg_wave_device.hip; the maths in smg_wave_inl.hpp).  mt = m / speed^2, s2 = 2.0 + sigma dt: planes of n; known
+// (nullptr ok): 1 on the clamped rows; u, v, b, z, w: column-major blocks of k columns with a leading dimension; per-vertex term planes are k planes
+// of n.  One wavefront per (64 vertices, column); the list kernels one lane per (entry, column) --------------------------------------------------
+// b = mt (s2 u + dt v), z = 2 u + dt v (both with leading dimension ldb), rsq = b^2 (0.0 on the known rows)
+hipError_t launch_wave_rhs(int n, int k, const double* mt, const double* s2, const int* known, double dt, const double* u, const double* v, int ld, double* b,
+                           double* z, int ldb, double* rsq, hipStream_t st);
+// b += a (sig0 + sig1) at the n_src vertices idx (no vertex twice), sig0 and sig1 n_src x k row-major; rsq rewritten there
+hipError_t launch_wave_sources(int n, int k, int n_src, const int* idx, const double* sig0, const double* sig1, double a, double* b, int ldb, double* rsq,
+                               hipStream_t st);
+// un = w - u, vn = q2 (un - u) - v, ke = 0.5 ((mt vn) vn); bnext != nullptr: launch_wave_rhs of (un, vn) into bnext, znext, rsqnext as well; znext may
+// be w (with ldb == ldw): the warm start then replaces the answer it was formed from
+hipError_t launch_wave_advance(int n, int k, const double* mt, const double* s2, const int* known, double dt, double q2, const double* w, int ldw,
+                               const double* u, const double* v, int ld, double* un, double* vn, int ldn, double* ke, double* bnext, double* znext, int ldb,
+                               double* rsqnext, hipStream_t st);
+// out (n_rec x k row-major) = u at the vertices idx
+hipError_t launch_wave_record(int n, int k, int n_rec, const int* idx, const double* u, int ld, double* out, hipStream_t st);
+// flag (n_rows x k) = 1.0 where u or v is not 0.0 on a listed row, else 0.0
+hipError_t launch_wave_rows_nonzero(int n, int k, int n_rows, const int* rows, const double* u, const double* v, int ld, double* flag, hipStream_t st);
+
 }  // namespace smg

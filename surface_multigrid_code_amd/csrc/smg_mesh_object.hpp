@@ -108,4 +108,10 @@ int fluid_check_operands(const char* who, int op, int nV, int nF, int k, const i
 int rd_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* u, const double* v, const double* coeff,
                       double dt, int substeps, const double* un, const double* vn, const double* out);
 
+// ---- smg_wave.cpp: what smg_wave_host and smg_debug_wave check alike, in this order: the op and its operands, k, dt, clamped, speed (finite and
+// > 0), sigma (finite and >= 0), the faces, then the list of a source or record op: at least one vertex, in range, as sources no vertex twice
+int wave_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* speed, const double* sigma, int clamped,
+                        double dt, const double* u, const double* v, const double* w, const int* idx, int n_idx, const double* sig0, const double* sig1,
+                        const double* out);
+
 }  // namespace smg
