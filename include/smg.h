@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 540
+#define SMG_VERSION 550
 
 enum {
     SMG_OK = 0,
@@ -1228,6 +1228,53 @@ int smg_wave_step(smg_wave *g, int n_steps, const double *signal, const smg_solv
 int smg_wave_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *speed, const double *sigma, int clamped, double dt,
                   const double *u, const double *v, const double *w, const int *idx, int n_idx, const double *sig0, const double *sig1, double *out);
 
+/* ---- Adjoint-state gradients of a trace misfit through the wave object's own time stepper (csrc/smg_wave_adjoint.cpp).
+ * With rho_n = R u_n - observed_n (R gathers u at the receivers; a duplicated receiver counts once per slot) the misfit of column c is
+ *     J_c = 0.5 * sum_{n = 1 .. N} sum_r rho_{n,r,c}^2
+ * and smg_wave_gradient differentiates it exactly -- the discrete adjoint of the scheme above, not of the differential equation -- with respect
+ * to the speed, the state (u_0, v_0) the call starts from and the signal.  A = diag(0.5 * s2 * mt) + a C is symmetric, so the transposed step
+ * is ONE solve of the same precomputed matrix on the same handle between pointwise kernels; k shots stay k columns:
+ *   forward, step n = 0 .. N - 1: smg_wave_step's launches, then k_wave_adj_keep: e_n = dt * v_n - (0.5 * s2) * (u_{n+1} - u_n), one nV x k block.
+ *   k_wave_adj_residual: rho = traces - observed and its squares in k planes; J_c = 0.5 * their fixed-order sum.
+ *   backward from p = R' rho_N, q = 0, Y = 0, G = 0; for n = N - 1 .. 0:
+ *     1. k_wave_adj_rhs: g = p + q2 * q and its squares, both 0.0 on a known row.
+ *     2. A y = g, warm-started from the y of step n + 1; the host reads |g|_F^2 as the forward step reads |b|_F^2 (opts NULL: 1e-10 |g|_F, max_iter
+ *        100).  |g|_F^2 == 0.0: the solve is skipped, y = 0 and the step's cycles entry is 0.
+ *     3. k_wave_adj_advance: G += y * e_n, t = mt * y, p = (s2 * t - p) - (2.0 * q2) * q, q = dt * t - q (both from the old p and q).
+ *     4. k_wave_adj_signal (grad_signal wanted): gs[n] += a * y[src], gs[n + 1] += a * y[src].
+ *     5. k_wave_adj_inject (n >= 1): p += R' rho_n.  The receivers are grouped by vertex at the first call after smg_wave_set_receivers: one lane
+ *        owns a vertex and adds its slots in ascending slot order, without atomics.  A receiver on a clamped row contributes nothing.
+ *   k_wave_adj_scale: grad_speed = ((-2.0 * mt) / speed) * G, the factor a host plane formed once, as mt is.
+ * On clamped rows y, p, q and G are exact zeros.
+ * smg_wave_gradient: runs n_steps steps from the current state.  signal, opts, traces, n_done: as smg_wave_step; the forward half leaves the state
+ *   and the traces that smg_wave_step with the same arguments would leave, bit for bit: the state afterwards is (u_N, v_N).  observed (host, NULL:
+ *   zeros): n_steps x n_rec x k, the layout of traces.  Outputs, host, each NULL ok: misfit (k); grad_speed (nV x k column-major, leading dimension
+ *   ld: one gradient per shot, the caller sums them); grad_u0, grad_v0 (nV x k, leading dimension ld0); grad_signal ((n_steps + 1) x n_src x k);
+ *   cycles (2 * n_steps: the forward solves' loop entries in step order, then the backward solves' in the order they ran, entry n_steps + j of
+ *   step n_steps - 1 - j).  With every gradient output NULL the backward pass is skipped and nothing is kept.
+ *   Refusals, SMG_ERR_INVALID before any launch, in this order: a null object; no state; n_steps < 1; no receivers; a signal without sources or with
+ *   a non-finite entry; n_steps x n_rec x k beyond the index range; a non-finite observed entry; a leading dimension below nV; grad_signal without a
+ *   signal.  A forward step that is refused ends the call as it ends smg_wave_step: the state of the last completed step, *n_done, and neither
+ *   misfit nor gradient written.  A non-finite |g|_F^2 ends the call with SMG_ERR_NONFINITE: the state is (u_N, v_N), no gradient is written.
+ *   The adjoint right-hand side uses the forward step's blocks, so the kept right-hand side is dropped: the next smg_wave_step forms it again,
+ *   to the same bits.
+ *   Memory: allocated at the first call, grown with the largest shape seen, kept, counted by smg_wave_device_bytes: the history, n_steps x nV x k
+ *   doubles (at 1 M vertices -- the 1 011 330 of the benchmark's mesh -- k = 8 and 100 steps it is 6.5 GB; there is no checkpointing, so a longer
+ *   run needs fewer columns per call); p, q, y, G (nV x k each); the residuals, their squares and the observed traces (3 x n_steps x n_rec x k); the grouped
+ *   receiver list; the signal's gradient; the factor plane.
+ * smg_wave_set_speed: a new speed for the following steps (nV doubles, finite and > 0 -- create's check and message; NULL: 1 everywhere): rebuilds
+ *   mt from the masses kept on the host and re-precomputes by values; the kept right-hand side is dropped.  The state is kept.
+ * smg_wave_adjoint_host: the host twin of the new kernels on caller arrays (no GPU), with the operands and layouts of smg_debug_wave_adjoint. */
+enum { SMG_WAVE_ADJ_KEEP = 0, SMG_WAVE_ADJ_RESIDUAL = 1, SMG_WAVE_ADJ_INJECT = 2, SMG_WAVE_ADJ_RHS = 3, SMG_WAVE_ADJ_ADVANCE = 4, SMG_WAVE_ADJ_SIGNAL = 5,
+       SMG_WAVE_ADJ_SCALE = 6 };
+int smg_wave_gradient(smg_wave *g, int n_steps, const double *signal, const double *observed, const smg_solve_opts *opts, double *misfit,
+                      double *grad_speed, int ld, double *grad_u0, double *grad_v0, int ld0, double *grad_signal, double *traces, int *cycles,
+                      int *n_done);
+int smg_wave_set_speed(smg_wave *g, const double *speed);
+int smg_wave_adjoint_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *speed, const double *sigma, int clamped, double dt,
+                          const double *x0, const double *x1, const double *x2, const double *x3, const double *x4, const int *idx, int n_idx, int n_rows,
+                          double *out);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -1687,6 +1734,23 @@ int smg_debug_rd_time(int op, int nV, int nF, int k, const int *F, const double 
 int smg_debug_wave(int op, int nV, int nF, int k, const int *F, const double *V, const double *speed, const double *sigma, int clamped, double dt,
                    const double *u, const double *v, const double *w, const int *idx, int n_idx, const double *sig0, const double *sig1, double *out,
                    int *guard_hits);
+/* One launcher of the wave object's adjoint pass (csrc/smg_wave_adjoint_device.hip), handle-free and guarded like the hooks above.  F, V, speed, sigma,
+ * clamped, dt: as smg_debug_wave (mt, s2 and the factor plane are formed on the host from the device's masses; q2 = 2.0 / dt, a = 0.25 dt dt).
+ * Vertex blocks are nV x k column-major with leading dimension nV; a trace row is n_idx slots x k row-major; every array is host.
+ *   SMG_WAVE_ADJ_KEEP      x0 = u, x1 = v, x2 = u' -> out = e (nV x k)
+ *   SMG_WAVE_ADJ_RESIDUAL  x0 = traces, x1 = observed or NULL (n_rows x n_idx x k each) -> out = rho (the same layout), its squares (k planes of
+ *                          n_rows x n_idx), the k fixed-order sums of the planes; F and V are only checked
+ *   SMG_WAVE_ADJ_INJECT    x0 = p, x1 = rho (one row: n_idx x k), idx = the receivers (a vertex may repeat) -> out = p + R' rho (nV x k)
+ *   SMG_WAVE_ADJ_RHS       x0 = p, x1 = q -> out = g (nV x k), its squares (k planes of nV), their sum (1)
+ *   SMG_WAVE_ADJ_ADVANCE   x0 = y, x1 = p, x2 = q, x3 = e, x4 = G -> out = p', q', G' (nV x k each)
+ *   SMG_WAVE_ADJ_SIGNAL    x0 = y, x1 = gs0, x2 = gs1 (n_idx x k each), idx = the sources -> out = gs0', gs1'
+ *   SMG_WAVE_ADJ_SCALE     x0 = G -> out = ((-2.0 mt) / speed) G (nV x k)
+ * SMG_ERR_INVALID for an unknown op, nV < 1, nF < 1, a missing operand, k < 1, dt not finite and > 0, clamped not 0 or 1, a speed not finite and
+ * > 0, a sigma not finite and >= 0, a face index out of range, n_rows < 1 or n_idx < 1 where they count, a list index out of range, a source
+ * listed twice; SMG_ERR_NO_DEVICE without a GPU. */
+int smg_debug_wave_adjoint(int op, int nV, int nF, int k, const int *F, const double *V, const double *speed, const double *sigma, int clamped, double dt,
+                           const double *x0, const double *x1, const double *x2, const double *x3, const double *x4, const int *idx, int n_idx, int n_rows,
+                           double *out, int *guard_hits);
 /* The time of one launcher of the wave object alone, for tools/wave_time.py: SMG_WAVE_RHS or SMG_WAVE_ADVANCE (with the next right-hand side) on
  * device blocks of zeros of k columns over the mesh (F, V: host), launched `reps` times back to back on one stream between two events after one
  * launch that is not timed; *ms = the mean time of a launch in milliseconds.  SMG_ERR_INVALID for another op, nV < 1, nF < 1, a missing array,

@@ -1659,6 +1659,48 @@ class WaveEquation(_MeshObject):
     def state_device(self, u_ptr, v_ptr, ld):
         self._call("state", u_ptr, v_ptr, ld, SMG_DEVICE)
 
+    def set_speed(self, speed):
+        """a new speed for the following steps (n values, a scalar, or None: 1 everywhere): a value-only re-precompute; the state is kept"""
+        speed = None if speed is None else np.ascontiguousarray(np.broadcast_to(np.asarray(speed, dtype=np.float64), (self.n,)))
+        self._call("set_speed", None if speed is None else _dp(speed))
+
+    def gradient(self, n_steps, signal=None, observed=None, speed=True, state=True, grad_signal=None, opts=None):
+        """n_steps steps from the current state, then the adjoint pass: the misfit J_c = 0.5 sum (traces - observed)^2 per column and its exact
+        discrete gradients -> WaveGradient.  signal: as step(); observed: n_steps x n_rec x k or None (zeros); speed, state: whether grad_speed and
+        (grad_u0, grad_v0) are wanted; grad_signal: whether the signal's gradient is (None: where a signal is given).  With none of them wanted
+        the backward pass is skipped.  The state afterwards is the one n_steps steps on; self.n_done: the forward steps done"""
+        k, rows = max(self.k, 1), max(n_steps, 1)
+        want_gs = (signal is not None) if grad_signal is None else bool(grad_signal)
+        if signal is not None:
+            signal = np.ascontiguousarray(np.asarray(signal, dtype=np.float64))
+            if signal.size != (rows + 1) * self.n_src * k:
+                raise ValueError("the signal has %d entries, (n_steps + 1) x n_src x k = %d are needed" % (signal.size, (rows + 1) * self.n_src * k))
+        if observed is not None:
+            observed = np.ascontiguousarray(np.asarray(observed, dtype=np.float64))
+            if observed.size != rows * self.n_rec * k:
+                raise ValueError("observed has %d entries, n_steps x n_rec x k = %d are needed" % (observed.size, rows * self.n_rec * k))
+        r = WaveGradient()
+        r.misfit = np.zeros(k)
+        r.grad_speed = np.zeros((self.n, k), order="F") if speed else None
+        r.grad_u0, r.grad_v0 = (np.zeros((self.n, k), order="F"), np.zeros((self.n, k), order="F")) if state else (None, None)
+        r.grad_signal = np.zeros((rows + 1, self.n_src, k)) if want_gs else None
+        r.traces, r.cycles = np.zeros((rows, self.n_rec, k)), np.zeros(2 * rows, dtype=np.int32)
+        ptr = lambda x: None if x is None else x.ctypes.data_as(C.POINTER(C.c_double))   # noqa: E731
+        nd = C.c_int(0)
+        try:
+            self._call("gradient", int(n_steps), ptr(signal), ptr(observed), self._opts(opts), _dp(r.misfit), ptr(r.grad_speed), self.n, ptr(r.grad_u0),
+                       ptr(r.grad_v0), self.n, ptr(r.grad_signal), _dp(r.traces) if self.n_rec else None, _ip(r.cycles), C.byref(nd))
+        finally:
+            self.n_done = nd.value
+        return r
+
+
+class WaveGradient:
+    """what WaveEquation.gradient returns: misfit (k), grad_speed, grad_u0, grad_v0 (n x k, one gradient per shot), grad_signal ((n_steps + 1) x
+    n_src x k), traces (n_steps x n_rec x k), cycles (2 n_steps: the forward solves, then the backward solves in the order they ran); a gradient
+    that was not asked for is None"""
+    misfit = grad_speed = grad_u0 = grad_v0 = grad_signal = traces = cycles = None
+
 
 def wave_params(**params):
     """smg_wave_params with the library's defaults and the given fields"""

@@ -17,7 +17,9 @@
 #include "smg_mesh_object.hpp"
 #include "smg_rd_inl.hpp"
 #include "smg_stylize_inl.hpp"
+#include "smg_wave_adjoint_inl.hpp"
 #include "smg_wave_inl.hpp"
+#include "smg_wave_object.hpp"
 
 using namespace smg;
 
@@ -1371,6 +1373,96 @@ extern "C" int smg_debug_wave(int op, int nV, int nF, int k, const int* F, const
             HIPCHK(S.finish(&bad));   // mt, s2 and the lists live until the stream has drained
             if (guard_hits) *guard_hits = bad;
             return SMG_OK;
+        }
+        int bad = 0;
+        HIPCHK(S.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_wave_adjoint(int op, int nV, int nF, int k, const int* F, const double* V, const double* speed, const double* sigma, int clamped,
+                                      double dt, const double* x0, const double* x1, const double* x2, const double* x3, const double* x4, const int* idx, int n_idx,
+                                      int n_rows, double* out, int* guard_hits)
+{
+    return guarded("smg_debug_wave_adjoint", [&]() -> int {
+        const char* who = "smg_debug_wave_adjoint";
+        if (int rc = wave_adjoint_check_operands(who, op, nV, nF, k, F, V, speed, sigma, clamped, dt, x0, x1, x2, x3, x4, idx, n_idx, n_rows, out)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, f = (size_t)nF, kk = (size_t)k, nk = n * kk, D = sizeof(double);
+        if (2 * nk > (size_t)INT_MAX) return fail(SMG_ERR_INVALID, "%s: k = %d exceeds the index range", who, k);
+        Scratch S;
+        HIPCHK(S.init());
+        hipStream_t st = S.stream();
+        const size_t ni = (size_t)std::max(n_idx, 0), ent = (size_t)std::max(n_rows, 0) * ni, sk = ni * kk;
+        const size_t xs[7][5] = {{nk, nk, nk, 0, 0}, {ent * kk, ent * kk, 0, 0, 0}, {nk, sk, 0, 0, 0}, {nk, nk, 0, 0, 0}, {nk, nk, nk, nk, nk}, {nk, sk, sk, 0, 0},
+                                 {nk, 0, 0, 0, 0}};   // the operands' extents per op
+        const size_t outs[7] = {nk, 2 * ent * kk + kk, nk, 2 * nk + 1, 3 * nk, 2 * sk, nk};
+        const double* x[5] = {x0, x1, x2, x3, x4};
+        double *dx[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *dout = nullptr, *dpart = nullptr;
+        for (int j = 0; j < 5; j++)
+            if (x[j] && xs[op][j] > 0) HIPCHK(S.add(x[j], nullptr, xs[op][j] * D, &dx[j]));
+        HIPCHK(S.add(out, out, outs[op] * D, &dout));
+        HIPCHK(S.add(nullptr, nullptr, (size_t)fixed_sum_groups((int)std::max(nk, ent)) * D, &dpart));
+        std::vector<int> known, gv, gp, gl, mp, mi;   // they live until the stream has drained
+        std::vector<double> mt, s2, fac;
+        int *dknown = nullptr, *didx = nullptr;
+        if (clamped) {
+            known.assign(n, 0);
+            for (int b : boundary_vertices(F, nF, nV)) known[(size_t)b] = 1;
+            HIPCHK(S.add(known.data(), nullptr, n * sizeof(int), &dknown));
+        }
+        const double a = 0.25 * dt * dt, q2 = 2.0 / dt;
+        if (op == SMG_WAVE_ADJ_RESIDUAL) {
+            double* sq = dout + ent * kk;
+            HIPCHK(launch_wave_adj_residual(k, (long long)ent, dx[0], dx[1], dout, sq, st));
+            for (size_t c = 0; c < kk; c++) HIPCHK(launch_fixed_sum(sq + c * ent, (int)ent, dpart, dout + 2 * ent * kk + c, st));
+        } else if (op == SMG_WAVE_ADJ_INJECT) {
+            wave_group_receivers(nV, n_idx, idx, clamped ? known.data() : nullptr, gv, gp, gl);
+            int *dgv = nullptr, *dgp = nullptr, *dgl = nullptr;
+            if (!gv.empty()) {
+                HIPCHK(S.add(gv.data(), nullptr, gv.size() * sizeof(int), &dgv));
+                HIPCHK(S.add(gl.data(), nullptr, gl.size() * sizeof(int), &dgl));
+            }
+            HIPCHK(S.add(gp.data(), nullptr, gp.size() * sizeof(int), &dgp));
+            HIPCHK(hipMemcpyAsync(dout, dx[0], nk * D, hipMemcpyDeviceToDevice, st));
+            HIPCHK(launch_wave_adj_inject(nV, k, (int)gv.size(), dgv, dgp, dgl, dx[1], dout, nV, st));
+        } else if (op == SMG_WAVE_ADJ_RHS) {
+            HIPCHK(launch_wave_adj_rhs(nV, k, dknown, q2, dx[0], dx[1], nV, dout, nV, dout + nk, st));
+            HIPCHK(launch_fixed_sum(dout + nk, (int)nk, dpart, dout + 2 * nk, st));
+        } else if (op == SMG_WAVE_ADJ_SIGNAL) {
+            HIPCHK(S.add(idx, nullptr, ni * sizeof(int), &didx));
+            HIPCHK(hipMemcpyAsync(dout, dx[1], sk * D, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemcpyAsync(dout + sk, dx[2], sk * D, hipMemcpyDeviceToDevice, st));
+            HIPCHK(launch_wave_adj_signal(nV, k, n_idx, didx, a, dx[0], nV, dout, dout + sk, st));
+        } else {
+            vertex_corner_lists(std::vector<int>(F, F + 3 * f), nV, mp, mi);
+            int *dF = nullptr, *dmp = nullptr, *dmi = nullptr;
+            double *dV = nullptr, *dW = nullptr, *dn = nullptr, *dA = nullptr, *dm = nullptr, *dmt = nullptr, *ds2 = nullptr, *dfac = nullptr;
+            HIPCHK(S.add(F, nullptr, 3 * f * sizeof(int), &dF));
+            HIPCHK(S.add(V, nullptr, 3 * n * D, &dV));
+            HIPCHK(S.add(mp.data(), nullptr, mp.size() * sizeof(int), &dmp));
+            HIPCHK(S.add(mi.data(), nullptr, mi.size() * sizeof(int), &dmi));
+            HIPCHK(S.add(nullptr, nullptr, 9 * f * D, &dW));
+            HIPCHK(S.add(nullptr, nullptr, 3 * f * D, &dn));
+            HIPCHK(S.add(nullptr, nullptr, f * D, &dA));
+            HIPCHK(S.add(nullptr, nullptr, n * D, &dm));
+            if (int rc = wave_planes(st, nV, nF, dV, dF, dmp, dmi, dW, dn, dA, dm, speed, sigma, dt, mt, s2)) return rc;
+            HIPCHK(S.add(mt.data(), nullptr, n * D, &dmt));
+            HIPCHK(S.add(s2.data(), nullptr, n * D, &ds2));
+            if (op == SMG_WAVE_ADJ_KEEP) {
+                HIPCHK(launch_wave_adj_keep(nV, k, ds2, dt, dx[0], dx[1], dx[2], nV, dout, st));
+            } else if (op == SMG_WAVE_ADJ_ADVANCE) {
+                HIPCHK(hipMemcpyAsync(dout, dx[1], nk * D, hipMemcpyDeviceToDevice, st));
+                HIPCHK(hipMemcpyAsync(dout + nk, dx[2], nk * D, hipMemcpyDeviceToDevice, st));
+                HIPCHK(hipMemcpyAsync(dout + 2 * nk, dx[4], nk * D, hipMemcpyDeviceToDevice, st));
+                HIPCHK(launch_wave_adj_advance(nV, k, dmt, ds2, dt, q2, dx[0], nV, dx[3], dout, dout + nk, dout + 2 * nk, nV, st));
+            } else {
+                fac.resize(n);
+                wave_adj_host_planes(nV, mt.data(), speed, fac.data());
+                HIPCHK(S.add(fac.data(), nullptr, n * D, &dfac));
+                HIPCHK(launch_wave_adj_scale(nV, k, dfac, dx[0], nV, dout, nV, st));
+            }
         }
         int bad = 0;
         HIPCHK(S.finish(&bad));

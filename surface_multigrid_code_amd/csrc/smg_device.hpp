@@ -696,4 +696,24 @@ hipError_t launch_wave_record(int n, int k, int n_rec, const int* idx, const dou
 // flag (n_rows x k) = 1.0 where u or v is not 0.0 on a listed row, else 0.0
 hipError_t launch_wave_rows_nonzero(int n, int k, int n_rows, const int* rows, const double* u, const double* v, int ld, double* flag, hipStream_t st);
 
+// the wave object's adjoint pass (smg_wave_adjoint_device.hip; the maths in smg_wave_adjoint_inl.hpp).  p, q, y, G: column-major blocks of k columns
+// with a leading dimension; a history block e and the squares are k planes of n; a trace row is (receiver slot) x column ------------------------------
+// e = dt v - (0.5 s2) (u1 - u): what the adjoint pass reads of a forward step from (u, v) to u1
+hipError_t launch_wave_adj_keep(int n, int k, const double* s2, double dt, const double* u, const double* v, const double* u1, int ld, double* e, hipStream_t st);
+// rho = trace - observed (nullptr: zeros) over `entries` (rows x slots) x k values, sq: their squares in k planes of `entries`
+hipError_t launch_wave_adj_residual(int k, long long entries, const double* trace, const double* observed, double* rho, double* sq, hipStream_t st);
+// p += R' rho for one trace row: group j is the vertex grp_v[j] with the slots grp_slot[grp_ptr[j] .. grp_ptr[j + 1]), added in that order
+hipError_t launch_wave_adj_inject(int n, int k, int n_grp, const int* grp_v, const int* grp_ptr, const int* grp_slot, const double* rho, double* p, int ld,
+                                  hipStream_t st);
+// g = p + q2 q (leading dimension ldg), gsq = g^2, both 0.0 on the known rows
+hipError_t launch_wave_adj_rhs(int n, int k, const int* known, double q2, const double* p, const double* q, int ld, double* g, int ldg, double* gsq,
+                               hipStream_t st);
+// G += y e, t = mt y, p = (s2 t - p) - (2.0 q2) q, q = dt t - q, in place
+hipError_t launch_wave_adj_advance(int n, int k, const double* mt, const double* s2, double dt, double q2, const double* y, int ldy, const double* e, double* p,
+                                   double* q, double* G, int ld, hipStream_t st);
+// gs0 += a y, gs1 += a y at the n_src vertices idx (no vertex twice); gs0, gs1 n_src x k row-major
+hipError_t launch_wave_adj_signal(int n, int k, int n_src, const int* idx, double a, const double* y, int ld, double* gs0, double* gs1, hipStream_t st);
+// out = fac G; out may be G
+hipError_t launch_wave_adj_scale(int n, int k, const double* fac, const double* G, int ld, double* out, int ldo, hipStream_t st);
+
 }  // namespace smg

@@ -9,7 +9,8 @@
 // on the object's stream, which the handle uses too.  The host reads one double before the solve, |b|_F^2 -- it sets the default tolerance and
 // refuses non-finite input -- and 2k after it, the energies.  A step writes into the block beside the state and commits by an index swap, so a
 // refused step leaves the state of the last completed one.  Checks, stream, handle, the cotangent system and the inner solve:
-// smg_mesh_object.hpp.
+// smg_mesh_object.hpp.  The object's struct and what this file shares with smg_wave_adjoint.cpp (smg_wave_gradient runs the step loop below
+// and keeps one block per step): smg_wave_object.hpp.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -23,32 +24,9 @@
 #include "smg_mesh.hpp"
 #include "smg_mesh_object.hpp"
 #include "smg_wave_inl.hpp"
+#include "smg_wave_object.hpp"
 
 using namespace smg;
-
-struct smg_wave : MeshObject {             // handle[0]: diag(0.5 s2 mt) + a (-L), the boundary known when clamped
-    int nV = 0, nF = 0, nb = 0;            // nb: the clamped rows (0: free boundary)
-    int pcg = 1;                           // the inner solver: 1 smg_solve_pcg, 0 smg_solve
-    bool fused = true;                     // the advance kernel leaves the next step's right-hand side (SMG_WAVE_FUSED=0 at create: it does not)
-    bool has_sigma = false, rhs_valid = false;
-    smg_wave_params p;
-    double a = 0.0, q2 = 0.0;              // 0.25 dt dt, 2.0 / dt
-    size_t kcap = 0;                       // the columns the state's blocks hold
-    int k = 0, cur = 0;                    // the state's columns (0: none); which of S[2] holds the state
-    int n_src = 0, n_rec = 0;
-    CotanSystem Sys;                       // the pattern and -L's values
-    std::vector<double> mt_host, sigma_host, red_host;
-    std::vector<int> bnd, on_bnd;          // the clamped rows; 1 on them (empty: free)
-    DevBuf<int> F, known, rows, src, rec;  // faces; 1 on the clamped rows; the clamped rows; the source and receiver vertices
-    DevBuf<double> W, nrm, Af;             // gradient basis (9 per face), normals (3), areas: the potential energy's geometry
-    DevBuf<double> mt, s2, val;            // planes of n; the system's values on their way to the handle
-    DevBuf<double> S[2], B, Wb;            // column-major n x 2k: the state and the step's output; n x k: right-hand side; the warm start, then the solve's answer
-    DevBuf<double> rsq, ke, terms;         // k planes of n: squares, kinetic terms; k planes of nF: the potential terms
-    DevBuf<double> part, red;              // the chunk sums; |b|^2 then k kinetic and k potential energies
-    DevBuf<double> zero, flag;             // nb x k: the known rows' values; set_state's check of them
-    DevBuf<double> sig, trace;             // a call's signal and its traces
-    ~smg_wave() { quiesce(); }
-};
 
 namespace smg {
 
@@ -80,18 +58,6 @@ int wave_check_operands(const char* who, int op, int nV, int nF, int k, const in
     return SMG_OK;
 }
 
-}  // namespace smg
-
-namespace {
-
-int check_params(const char* who, const smg_wave_params& p)
-{
-    if (!std::isfinite(p.dt) || !(p.dt > 0.0)) return fail(SMG_ERR_INVALID, "%s: dt = %g, a finite value > 0 is needed", who, p.dt);
-    if (!std::isfinite(p.damping) || p.damping < 0.0) return fail(SMG_ERR_INVALID, "%s: damping = %g, a finite value >= 0 is needed", who, p.damping);
-    if (p.clamped != 0 && p.clamped != 1) return fail(SMG_ERR_INVALID, "%s: clamped = %d, 0 or 1 is needed", who, p.clamped);
-    return SMG_OK;
-}
-
 // s2, a, q2 from p and the handle's values diag(0.5 s2 mt) + a (-L) from the kept pattern; first: the pattern-setting precompute with the
 // clamped rows known, else by values
 int wave_system(smg_wave* g, bool first)
@@ -118,6 +84,98 @@ int wave_system(smg_wave* g, bool first)
         if (int rc = smg_precompute_values_device(g->handle[0], g->val.p)) return rc;
     }
     g->rhs_valid = false;
+    return SMG_OK;
+}
+
+int wave_check_steps(const char* who, const smg_wave* g, int n_steps)
+{
+    if (!g) return fail(SMG_ERR_INVALID, "%s: null object", who);
+    if (g->k < 1) return fail(SMG_ERR_INVALID, "%s: no state: call smg_wave_set_state first", who);
+    if (n_steps < 1) return fail(SMG_ERR_INVALID, "%s: n_steps = %d, at least 1 is needed", who, n_steps);
+    return SMG_OK;
+}
+
+int wave_check_signal(const char* who, const smg_wave* g, int n_steps, const double* signal)
+{
+    if (signal && g->n_src == 0) return fail(SMG_ERR_INVALID, "%s: a signal without sources: call smg_wave_set_sources first", who);
+    const int k = g->k;
+    const size_t row_s = (size_t)g->n_src * k;
+    if (signal)
+        for (size_t j = 0; j < ((size_t)n_steps + 1) * row_s; j++)
+            if (!std::isfinite(signal[j]))
+                return fail(SMG_ERR_INVALID, "%s: the signal is not finite at time %d, source %d, column %d", who, (int)(j / row_s), (int)(j % row_s) / k,
+                            (int)(j % row_s) % k);
+    return SMG_OK;
+}
+
+int wave_forward(smg_wave* g, const char* who, int n_steps, const double* signal, const smg_solve_opts* opts, double* energy_his, double* traces, bool record,
+                 int* cycles, int* n_done, double* keep)
+{
+    const int n = g->nV, k = g->k, ns = g->n_src, nr = traces || record ? g->n_rec : 0;
+    const size_t nk = (size_t)n * k, D = sizeof(double), row_s = (size_t)ns * k, row_r = (size_t)nr * k;
+    DeviceScope dsc(g->device);
+    hipStream_t st = g->stream;
+    HIPCHK(hipStreamSynchronize(st));
+    if (signal) {   // uploaded once per call
+        HIPCHK(g->sig.ensure(((size_t)n_steps + 1) * row_s));
+        HIPCHK(hipMemcpy(g->sig.p, signal, ((size_t)n_steps + 1) * row_s * D, hipMemcpyHostToDevice));
+    }
+    if (nr > 0) HIPCHK(g->trace.ensure((size_t)n_steps * row_r));
+    g->red_host.assign(1 + 2 * (size_t)k, 0.0);
+    double* rh = g->red_host.data();
+    const double dt = g->p.dt;
+    const int* known = g->nb > 0 ? g->known.p : nullptr;
+    int done = 0, rc = SMG_OK;
+    for (int t = 0; t < n_steps; t++) {
+        const double* s0 = g->S[g->cur].p;
+        double* s1 = g->S[1 - g->cur].p;
+        if (!g->rhs_valid) HIPCHK(launch_wave_rhs(n, k, g->mt.p, g->s2.p, known, dt, s0, s0 + nk, n, g->B.p, g->Wb.p, n, g->rsq.p, st));
+        g->rhs_valid = false;   // the sources change it in place, and the advance kernel overwrites it
+        if (signal) HIPCHK(launch_wave_sources(n, k, ns, g->src.p, g->sig.p + (size_t)t * row_s, g->sig.p + ((size_t)t + 1) * row_s, g->a, g->B.p, n, g->rsq.p, st));
+        HIPCHK(launch_fixed_sum(g->rsq.p, (int)nk, g->part.p, g->red.p, st));
+        HIPCHK(hipMemcpyAsync(rh, g->red.p, D, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (!std::isfinite(rh[0])) {
+            rc = fail(SMG_ERR_NONFINITE, "%s: the right-hand side is not finite (step %d)", who, t);
+            break;
+        }
+        const smg_solve_opts so = opts_or_default(opts, 1e-10 * std::sqrt(rh[0]), 100);
+        int e = 0;
+        if ((rc = inner_solve(g->handle[0], g->pcg, g->B.p, n, g->nb > 0 ? g->zero.p : nullptr, g->nb, g->Wb.p, n, k, so, g->Wb.p, n, &e))) break;
+        double* bn = g->fused ? g->B.p : nullptr;
+        HIPCHK(launch_wave_advance(n, k, g->mt.p, g->s2.p, known, dt, g->q2, g->Wb.p, n, s0, s0 + nk, n, s1, s1 + nk, n, g->ke.p, bn, g->Wb.p, n, g->rsq.p, st));
+        if (energy_his) {
+            double* d = g->red.p + 1;
+            HIPCHK(launch_fluid_velocity(g->nF, k, g->F.p, g->W.p, g->nrm.p, g->Af.p, s1, n, nullptr, g->terms.p, st));
+            for (int c = 0; c < k; c++) {
+                HIPCHK(launch_fixed_sum(g->ke.p + (size_t)c * n, n, g->part.p, d + c, st));
+                HIPCHK(launch_fixed_sum(g->terms.p + (size_t)c * g->nF, g->nF, g->part.p, d + k + c, st));
+            }
+            HIPCHK(hipMemcpyAsync(rh + 1, d, 2 * (size_t)k * D, hipMemcpyDeviceToHost, st));
+        }
+        if (keep) HIPCHK(launch_wave_adj_keep(n, k, g->s2.p, dt, s0, s0 + nk, s1, n, keep + (size_t)t * nk, st));
+        if (nr > 0) HIPCHK(launch_wave_record(n, k, nr, g->rec.p, s1, n, g->trace.p + (size_t)t * row_r, st));
+        HIPCHK(hipStreamSynchronize(st));
+        g->cur = 1 - g->cur;
+        g->rhs_valid = g->fused;
+        if (energy_his) std::copy(rh + 1, rh + 1 + 2 * (size_t)k, energy_his + (size_t)t * 2 * k);
+        if (cycles) cycles[t] = e;
+        done = t + 1;
+    }
+    if (traces && nr > 0 && done > 0) HIPCHK(hipMemcpy(traces, g->trace.p, (size_t)done * row_r * D, hipMemcpyDeviceToHost));   // once, at the end of the call
+    if (n_done) *n_done = done;
+    return rc;
+}
+
+}  // namespace smg
+
+namespace {
+
+int check_params(const char* who, const smg_wave_params& p)
+{
+    if (!std::isfinite(p.dt) || !(p.dt > 0.0)) return fail(SMG_ERR_INVALID, "%s: dt = %g, a finite value > 0 is needed", who, p.dt);
+    if (!std::isfinite(p.damping) || p.damping < 0.0) return fail(SMG_ERR_INVALID, "%s: damping = %g, a finite value >= 0 is needed", who, p.damping);
+    if (p.clamped != 0 && p.clamped != 1) return fail(SMG_ERR_INVALID, "%s: clamped = %d, 0 or 1 is needed", who, p.clamped);
     return SMG_OK;
 }
 
@@ -166,6 +224,8 @@ int create_impl(const smg_hierarchy* h, const double* V, int nV, const int* F, i
     HIPCHK(hipMemcpyAsync(g->mt_host.data(), m.p, (size_t)nV * sizeof(double), hipMemcpyDeviceToHost, g->stream));
     if (int rc = cotan_system(F, nF, nV, dV.p, 0, 0.0, -1.0, g->stream, g->Sys, false)) return rc;   // synchronises: the masses have arrived
     for (double& x : g->Sys.L) x = -x;
+    g->m_host = g->mt_host;   // kept for smg_wave_set_speed
+    if (speed) g->speed_host.assign(speed, speed + nV);
     for (int i = 0; speed && i < nV; i++) g->mt_host[(size_t)i] = g->mt_host[(size_t)i] / (speed[i] * speed[i]);
     HIPCHK(g->mt.upload(g->mt_host));
     HIPCHK(g->s2.alloc((size_t)nV));
@@ -279,67 +339,9 @@ int step_impl(smg_wave* g, int n_steps, const double* signal, const smg_solve_op
 {
     const char* who = "smg_wave_step";
     if (n_done) *n_done = 0;
-    if (int rc = check_state(who, g)) return rc;
-    if (n_steps < 1) return fail(SMG_ERR_INVALID, "%s: n_steps = %d, at least 1 is needed", who, n_steps);
-    if (signal && g->n_src == 0) return fail(SMG_ERR_INVALID, "%s: a signal without sources: call smg_wave_set_sources first", who);
-    const int n = g->nV, k = g->k, ns = g->n_src, nr = traces ? g->n_rec : 0;
-    const size_t nk = (size_t)n * k, D = sizeof(double), row_s = (size_t)ns * k, row_r = (size_t)nr * k;
-    if (signal)
-        for (size_t j = 0; j < ((size_t)n_steps + 1) * row_s; j++)
-            if (!std::isfinite(signal[j]))
-                return fail(SMG_ERR_INVALID, "%s: the signal is not finite at time %d, source %d, column %d", who, (int)(j / row_s), (int)(j % row_s) / k,
-                            (int)(j % row_s) % k);
-    DeviceScope dsc(g->device);
-    hipStream_t st = g->stream;
-    HIPCHK(hipStreamSynchronize(st));
-    if (signal) {   // uploaded once per call
-        HIPCHK(g->sig.ensure(((size_t)n_steps + 1) * row_s));
-        HIPCHK(hipMemcpy(g->sig.p, signal, ((size_t)n_steps + 1) * row_s * D, hipMemcpyHostToDevice));
-    }
-    if (nr > 0) HIPCHK(g->trace.ensure((size_t)n_steps * row_r));
-    g->red_host.assign(1 + 2 * (size_t)k, 0.0);
-    double* rh = g->red_host.data();
-    const double dt = g->p.dt;
-    const int* known = g->nb > 0 ? g->known.p : nullptr;
-    int done = 0, rc = SMG_OK;
-    for (int t = 0; t < n_steps; t++) {
-        const double* s0 = g->S[g->cur].p;
-        double* s1 = g->S[1 - g->cur].p;
-        if (!g->rhs_valid) HIPCHK(launch_wave_rhs(n, k, g->mt.p, g->s2.p, known, dt, s0, s0 + nk, n, g->B.p, g->Wb.p, n, g->rsq.p, st));
-        g->rhs_valid = false;   // the sources change it in place, and the advance kernel overwrites it
-        if (signal) HIPCHK(launch_wave_sources(n, k, ns, g->src.p, g->sig.p + (size_t)t * row_s, g->sig.p + ((size_t)t + 1) * row_s, g->a, g->B.p, n, g->rsq.p, st));
-        HIPCHK(launch_fixed_sum(g->rsq.p, (int)nk, g->part.p, g->red.p, st));
-        HIPCHK(hipMemcpyAsync(rh, g->red.p, D, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (!std::isfinite(rh[0])) {
-            rc = fail(SMG_ERR_NONFINITE, "%s: the right-hand side is not finite (step %d)", who, t);
-            break;
-        }
-        const smg_solve_opts so = opts_or_default(opts, 1e-10 * std::sqrt(rh[0]), 100);
-        int e = 0;
-        if ((rc = inner_solve(g->handle[0], g->pcg, g->B.p, n, g->nb > 0 ? g->zero.p : nullptr, g->nb, g->Wb.p, n, k, so, g->Wb.p, n, &e))) break;
-        double* bn = g->fused ? g->B.p : nullptr;
-        HIPCHK(launch_wave_advance(n, k, g->mt.p, g->s2.p, known, dt, g->q2, g->Wb.p, n, s0, s0 + nk, n, s1, s1 + nk, n, g->ke.p, bn, g->Wb.p, n, g->rsq.p, st));
-        if (energy_his) {
-            double* d = g->red.p + 1;
-            HIPCHK(launch_fluid_velocity(g->nF, k, g->F.p, g->W.p, g->nrm.p, g->Af.p, s1, n, nullptr, g->terms.p, st));
-            for (int c = 0; c < k; c++) {
-                HIPCHK(launch_fixed_sum(g->ke.p + (size_t)c * n, n, g->part.p, d + c, st));
-                HIPCHK(launch_fixed_sum(g->terms.p + (size_t)c * g->nF, g->nF, g->part.p, d + k + c, st));
-            }
-            HIPCHK(hipMemcpyAsync(rh + 1, d, 2 * (size_t)k * D, hipMemcpyDeviceToHost, st));
-        }
-        if (nr > 0) HIPCHK(launch_wave_record(n, k, nr, g->rec.p, s1, n, g->trace.p + (size_t)t * row_r, st));
-        HIPCHK(hipStreamSynchronize(st));
-        g->cur = 1 - g->cur;
-        g->rhs_valid = g->fused;
-        if (energy_his) std::copy(rh + 1, rh + 1 + 2 * (size_t)k, energy_his + (size_t)t * 2 * k);
-        if (cycles) cycles[t] = e;
-        done = t + 1;
-    }
-    if (nr > 0 && done > 0) HIPCHK(hipMemcpy(traces, g->trace.p, (size_t)done * row_r * D, hipMemcpyDeviceToHost));   // once, at the end of the call
-    if (n_done) *n_done = done;
-    return rc;
+    if (int rc = wave_check_steps(who, g, n_steps)) return rc;
+    if (int rc = wave_check_signal(who, g, n_steps, signal)) return rc;
+    return wave_forward(g, who, n_steps, signal, opts, energy_his, traces, false, cycles, n_done, nullptr);
 }
 
 int set_params_impl(smg_wave* g, const smg_wave_params* p)
@@ -395,7 +397,8 @@ extern "C" long long smg_wave_device_bytes(const smg_wave* g)
 {
     if (!g) return 0;   // one list: every DevBuf of the struct
     return device_bytes(*g, g->F, g->known, g->rows, g->src, g->rec, g->W, g->nrm, g->Af, g->mt, g->s2, g->val, g->S[0], g->S[1], g->B, g->Wb, g->rsq,
-                        g->ke, g->terms, g->part, g->red, g->zero, g->flag, g->sig, g->trace);
+                        g->ke, g->terms, g->part, g->red, g->zero, g->flag, g->sig, g->trace, g->grp_v, g->grp_ptr, g->grp_slot, g->H, g->P, g->Q, g->Y, g->G, g->rho,
+                        g->apart, g->ared, g->gs, g->fac);
 }
 
 extern "C" int smg_wave_set_state(smg_wave* g, const double* u, const double* v, int ld, int k, int memspace)
@@ -420,7 +423,10 @@ extern "C" int smg_wave_set_receivers(smg_wave* g, const int* idx, int n_rec)
 {
     return guarded("smg_wave_set_receivers", [&]() -> int {
         if (!g) return fail(SMG_ERR_INVALID, "smg_wave_set_receivers: null object");
-        return set_list(g, "smg_wave_set_receivers", idx, n_rec, false, g->rec, &g->n_rec);
+        if (int rc = set_list(g, "smg_wave_set_receivers", idx, n_rec, false, g->rec, &g->n_rec)) return rc;
+        g->rec_host.assign(idx, idx + n_rec);   // smg_wave_gradient groups it by vertex at its next call
+        g->grouped = false;
+        return SMG_OK;
     });
 }
 

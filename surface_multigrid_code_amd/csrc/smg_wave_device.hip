@@ -18,38 +18,10 @@
 #include <hip/hip_runtime.h>
 
 #include "smg_device.hpp"
+#include "smg_wave_grid.hpp"
 #include "smg_wave_inl.hpp"
 
 namespace smg {
-
-namespace {
-
-constexpr int WAVE_THREADS = 256, WAVE_LANES = 64, WAVE_WAVES = WAVE_THREADS / WAVE_LANES;
-
-// the blocks of a (64 vertices, column) wave grid; false: it does not fit a grid dimension
-bool wave_grid(int rows, int k, unsigned* blocks)
-{
-    const long long waves = (((long long)rows + WAVE_LANES - 1) / WAVE_LANES) * k;
-    const long long b = (waves + WAVE_WAVES - 1) / WAVE_WAVES;
-    *blocks = (unsigned)b;
-    return b <= 0x7fffffffLL;
-}
-
-// the wave's column and the lane's vertex; false: the wave is past the grid's last one or the lane past the last vertex
-__device__ __forceinline__ bool wave_lane(int n, int k, int* c, int* v)
-{
-    const int W = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVE_WAVES + (threadIdx.x / WAVE_LANES)));
-    const int waves = ((n + WAVE_LANES - 1) / WAVE_LANES) * k;   // wave_grid has checked the range
-    if (W >= waves) return false;
-    *c = W % k;
-    *v = (W / k) * WAVE_LANES + (int)(threadIdx.x % WAVE_LANES);
-    return *v < n;
-}
-
-// the blocks of one lane per (list entry, column)
-unsigned list_grid(int count, int k) { return (unsigned)(((long long)count * k + WAVE_THREADS - 1) / WAVE_THREADS); }
-
-}  // namespace
 
 // One lane per (vertex i, column c): b = mt_i (s2_i u + dt v), rsq[c * n + i] = b^2 (0.0 where known[i]), z = 2 u + dt v
 __global__ __launch_bounds__(WAVE_THREADS) void k_wave_rhs(int n, int k, const double* __restrict__ mt, const double* __restrict__ s2,
