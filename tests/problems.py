@@ -88,6 +88,82 @@ def random_spd_hierarchy(rng, n, levels, hub):
     return A, Ps
 
 
+def random_block_system(W, rng, keep=1.0, diag_only_frac=0.0):
+    """A 3-DOF SPD system on the vertex graph of W (a scalar symmetric matrix: its off-diagonal pattern is the graph), DOF index 3 v + d,
+    with 3 x 3 blocks that are NOT all full -- what the mesh systems and kron(S, B) never give the block kernels:
+      off-diagonal blocks  B_ij = |W_ij| U(-1,1)^{3x3} for i < j and B_ji = B_ij^T; every entry is stored with probability `keep` (the mirror
+                           block gets the transposed mask: the scalar pattern stays symmetric), one entry per block always, so that every
+                           edge of the graph keeps its block;
+      diagonal blocks      a symmetric coupling U(-0.3, 0.3) on (0,1), (0,2), (1,2) -- stored on none of them on a fraction `diag_only_frac`
+                           of the vertices, whose diagonal block then holds its three diagonal entries and nothing else;
+      diagonal entries     the scalar row's absolute off-diagonal sum plus U(0.05, 0.5): strictly diagonally dominant and symmetric => SPD.
+    Entries that are masked out are not stored at all (no explicit zeros).  Returns the 3n x 3n CSR matrix, indices sorted."""
+    W = sp.coo_matrix(W)
+    n = W.shape[0]
+    up = W.row < W.col
+    ei, ej, ew = W.row[up], W.col[up], np.abs(W.data[up])
+    m = len(ei)
+    B = ew[:, None, None] * rng.uniform(-1, 1, (m, 3, 3))
+    mask = rng.uniform(size=(m, 3, 3)) < keep
+    forced = rng.integers(0, 9, m)
+    mask[np.arange(m), forced // 3, forced % 3] = True
+    q, d, e = np.nonzero(mask)
+    rows = [3 * ei[q] + d, 3 * ej[q] + e]
+    cols = [3 * ej[q] + e, 3 * ei[q] + d]
+    vals = [B[q, d, e], B[q, d, e]]
+    coupled = np.flatnonzero(rng.uniform(size=n) >= diag_only_frac)
+    for d, e in ((0, 1), (0, 2), (1, 2)):
+        c = rng.uniform(-0.3, 0.3, len(coupled))
+        rows += [3 * coupled + d, 3 * coupled + e]; cols += [3 * coupled + e, 3 * coupled + d]; vals += [c, c]
+    off = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(3 * n, 3 * n))
+    diag = np.asarray(abs(off).sum(axis=1)).ravel() + rng.uniform(0.05, 0.5, 3 * n)
+    A = (off + sp.diags(diag)).tocsr()
+    A.sort_indices()
+    assert A.nnz == off.nnz + 3 * n and (A != A.T).nnz == 0
+    return A
+
+
+def kron3_prolongs(Ps):
+    """P (x) I_3 of every prolongation of a vertex hierarchy (row 3 r + d holds P(r, c) at column 3 c + d), indices sorted"""
+    out = []
+    for P in Ps:
+        K = sp.kron(sp.csr_matrix(P), sp.identity(3), format="csr")
+        K.sort_indices()
+        out.append(K)
+    return out
+
+
+# The block systems off the mesh (tests/test_gpu_block_shapes.py, the block-* builders of tests/test_gpu_f32_cycle.py): name ->
+# (seed, vertices, levels, hub rows, keep, diag_only_frac) on random_spd_hierarchy graphs; "path-<n>" / "path-<n>-3lv": the path graph.
+BLOCK_SHAPES = {
+    "random": (1, 200, 2, False, 1.0, 0.0),
+    "random-sparse-blocks": (2, 777, 3, False, 0.6, 0.3),
+    "hub": (3, 1500, 3, True, 0.6, 0.3),
+    "under-half-fill": (5, 65, 2, False, 0.35, 0.5),
+    "hub-wide-k": (7, 300, 3, True, 1.0, 0.0),
+}
+_BLOCK_SYSTEMS = {}
+
+
+def block_shape_system(name):
+    """(A, [P (x) I_3 ...]) of a named block system; built once per process, to be left unchanged"""
+    if name not in _BLOCK_SYSTEMS:
+        if name.startswith("path-"):
+            part = name.split("-")
+            n, levels = int(part[1]), 3 if part[-1] == "3lv" else 2
+            Ps, m = [], n
+            for _ in range(levels - 1):
+                Ps.append(_path_interp(m)); m = (m + 1) // 2
+            A = random_block_system(_path_matrix(n), np.random.default_rng(100 + n), 0.7, 0.3)
+        else:
+            seed, n, levels, hub, keep, diag_only = BLOCK_SHAPES[name]
+            rng = np.random.default_rng(seed)
+            W, Ps = random_spd_hierarchy(rng, n, levels, hub)
+            A = random_block_system(W, rng, keep, diag_only)
+        _BLOCK_SYSTEMS[name] = (A, kron3_prolongs(Ps))
+    return _BLOCK_SYSTEMS[name]
+
+
 def _path_matrix(n):
     """the tiny and ragged systems: a path graph's diagonally dominant matrix"""
     return sp.diags([-1.0, 2.5, -1.0], [-1, 0, 1], shape=(n, n)).tocsr()

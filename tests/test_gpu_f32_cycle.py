@@ -22,7 +22,7 @@ import scipy.sparse as sp
 import f32_reference as R
 import kernel_hooks as H
 from oracle import mesh_np as M
-from problems import random_spd_hierarchy, subdiv_problem
+from problems import block_shape_system, random_spd_hierarchy, subdiv_problem
 from test_gpu_parity import _path_interp, _path_matrix, smg  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -119,6 +119,17 @@ def _block(smg, kron=False, pinned=False, schur=False, nVCoarsest=100, nonsym=Fa
     return (mg, A, known) if with_system else mg
 
 
+def _block_shape(smg, name):
+    """a block system off the mesh (problems.BLOCK_SHAPES; the fp64 checks and the proofs that these inputs reach the tail loop, ragged slices
+    and partly filled blocks: test_gpu_block_shapes.py)"""
+    A, Ps = block_shape_system(name)
+    mg = smg.Hierarchy.from_prolongs(Ps)
+    mg.set_block_mode("block")
+    mg.precompute(A)
+    assert mg.block_size() == 3
+    return mg
+
+
 BUILDERS = {
     "subdiv-mcf": lambda s: _subdiv(s, "mcf"),
     "subdiv-poisson": lambda s: _subdiv(s, "poisson"),
@@ -133,6 +144,8 @@ BUILDERS = {
     "nonsym": _nonsym,
     "block-nonsym": lambda s: _block(s, nonsym=True),
     "block": lambda s: _block(s), "block-kron": lambda s: _block(s, kron=True), "block-pinned": lambda s: _block(s, pinned=True),
+    "block-random-sparse": lambda s: _block_shape(s, "random-sparse-blocks"), "block-hub": lambda s: _block_shape(s, "hub"),
+    "block-path-3": lambda s: _block_shape(s, "path-3"), "block-path-65": lambda s: _block_shape(s, "path-65"), "block-path-22": lambda s: _block_shape(s, "path-22"),
 }
 _CACHE = {}
 
@@ -314,6 +327,14 @@ def test_sparse_pieces_on_block_hierarchies_are_the_restatement_bit_for_bit(smg,
     """launch_bsr3 on the fp32 image (3 x 3 blocks; the restatement runs on the scalar 3n x 3n matrix: a block's structural zeros add +-0 to a sum that is
     never -0) and the transfers on 3 k columns"""
     check_sparse_pieces(case(smg, name), k, ALL3 if name == "block" else ("gs",))
+
+
+@pytest.mark.parametrize("name,k", [("block-hub", 1)] + [(n, k) for n in ("block-random-sparse", "block-path-3", "block-path-65", "block-path-22") for k in (1, 2)]
+                         + [("block-random-sparse", k) for k in (5, 11, 22)])
+def test_sparse_pieces_on_block_systems_off_the_mesh_are_the_restatement_bit_for_bit(smg, name, k):
+    """k_bsr3<.., float> on block rows wider than its 8 register columns (the Gauss-Seidel tail loop), slices of one to 33 vertices, dozens of tiny
+    colours, partly stored blocks and diagonal blocks without a coupling; the transfers on 3 k = 15, 33 and 66 columns (a wide launch and its remainder)"""
+    check_sparse_pieces(case(smg, name), k, ALL3 if name == "block-hub" else ("gs",))
 
 
 def _more_diagonal(A):
