@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 550
+#define SMG_VERSION 551
 
 enum {
     SMG_OK = 0,
@@ -1160,6 +1160,29 @@ int smg_rd_state(smg_rd *g, double *u, double *v, int ld, int memspace);
 int smg_rd_step(smg_rd *g, int n_steps, const smg_solve_opts *opts, double *mass_his, double *change_his, int *cycles, int *n_done);
 int smg_rd_host(int op, int nV, int nF, int k, const int *F, const double *V, const double *u, const double *v, const double *coeff, double dt,
                 int substeps, const double *un, const double *vn, double *out);
+
+/* ---- Heat-kernel optimal transport on a mesh, the host side (csrc/smg_sinkhorn.cpp; Solomon et al. 2015, Convolutional
+ * Wasserstein Distances): the pointwise operations of Sinkhorn iterations whose only non-pointwise operation is the heat kernel, on caller
+ * arrays, with no GPU.  Mass form, as smg_emd: m_i the barycentric vertex mass (the expression of k_fluid_mass), A = sum m in the order of the
+ * fixed-order sums; distributions are integrated masses per vertex.  With y = K(r) the output of a kernel application to the block r and sr_c the
+ * fixed-order sum of r's column c,
+ *     y_eff = max(y, 0) + (floor sr_c) / A
+ * a uniform rank-one part that keeps the kernel symmetric and strictly positive where a solve's tail is below its accuracy.
+ * F: nF x 3; V: nV x 3 row-major; blocks are column-major with leading dimension nV; planes are planes of nV; every sum is a fixed-order sum.
+ *   SMG_SINKHORN_SCALE    y, r (nV x k), mu (nV x k_in: column c reads mu's column c % k_in), sr (k), floor -> out = r' = mu / y_eff (0 where
+ *                         mu == 0; nV x k), the planes |r y_eff - mu| and r'^2 (k planes each), sum r' (k), the errors' sums (k), the squares' sum (1)
+ *   SMG_SINKHORN_SUBSTEP  y (nV x k) -> out = m y (nV x k), its squares (k planes), their sum (1)
+ *   SMG_SINKHORN_VALUE    r = r_v, y = r_w, mu = mu0, mu1 (nV x k each) -> out = the terms mu0 ln(r_v / m) + mu1 ln(r_w / m), a product with a zero
+ *                         mass left out (k planes), ln v, ln w (nV x k each; -inf where the mass is 0), the terms' sums (k)
+ *   SMG_SINKHORN_GEOMEAN  k = G groups of k_in columns: y = z, r = r_v (nV x G k_in), mu = the previous masses (nV x G), sr (G k_in), alphas (G x k_in
+ *                         row-major), floor; per column d_c = (r_v,c / m) z_eff,c, mu = exp(sum_c alpha_c ln d_c) over the columns with alpha_c > 0
+ *                         (0 where such a d_c is not > 0) -> out = r_v' = m mu / z_eff (nV x G k_in), the masses m mu (nV x G), |m mu - previous| (G
+ *                         planes), r_v'^2 (G k_in planes), sum r_v' (G k_in), the changes' sums (G), the masses' sums (G), the squares' sum (1)
+ * SMG_ERR_INVALID, in this order, for an unknown op, nV < 1, nF < 1, F, V or out missing; a missing operand; k < 1; for the scale and the
+ * geomean k_in < 1, then a floor that is not finite and >= 0; a face index out of range. */
+enum { SMG_SINKHORN_SCALE = 0, SMG_SINKHORN_SUBSTEP = 1, SMG_SINKHORN_VALUE = 2, SMG_SINKHORN_GEOMEAN = 3 };
+int smg_sinkhorn_host(int op, int nV, int nF, int k, int k_in, const int *F, const double *V, const double *y, const double *r, const double *mu,
+                      const double *mu1, const double *sr, const double *alphas, double floor, double *out);
 
 /* ---- The wave equation on a surface, with shots and receivers (csrc/smg_wave.cpp): the state is the pair (u, v = u_t), two
  * doubles per (vertex, column), resident on the device; k columns are k independent experiments ("shots") and k columns of every solve.  With

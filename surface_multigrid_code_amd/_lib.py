@@ -278,6 +278,7 @@ def load():
         "smg_rd_host": (i, [i, i, i, i, ip, dp, dp, dp, dp, d, i, dp, dp, dp]),
         "smg_debug_rd": (i, [i, i, i, i, ip, dp, dp, dp, dp, d, i, dp, dp, dp, ip]),
         "smg_debug_rd_time": (i, [i, i, i, i, ip, dp, i, i, dp]),
+        "smg_sinkhorn_host": (i, [i, i, i, i, i, ip, dp, dp, dp, dp, dp, dp, dp, d, dp]),
         "smg_wave_params_default": (WaveParamsC, []),
         "smg_wave_create": (i, [vp, dp, i, ip, i, dp, dp, C.POINTER(WaveParamsC), C.POINTER(vp)]),
         "smg_wave_destroy": (None, [vp]),

@@ -108,6 +108,11 @@ int fluid_check_operands(const char* who, int op, int nV, int nF, int k, const i
 int rd_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* u, const double* v, const double* coeff,
                       double dt, int substeps, const double* un, const double* vn, const double* out);
 
+// ---- smg_sinkhorn.cpp: what smg_sinkhorn_host checks, in this order: the op and its operands, k, then for the scale
+// and the geomean k_in and the floor (finite and >= 0), the faces
+int sinkhorn_check_operands(const char* who, int op, int nV, int nF, int k, int k_in, const int* F, const double* V, const double* y, const double* r,
+                            const double* mu, const double* mu1, const double* sr, const double* alphas, double floor, const double* out);
+
 // ---- smg_wave.cpp: what smg_wave_host and smg_debug_wave check alike, in this order: the op and its operands, k, dt, clamped, speed (finite and
 // > 0), sigma (finite and >= 0), the faces, then the list of a source or record op: at least one vertex, in range, as sources no vertex twice
 int wave_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* speed, const double* sigma, int clamped,
