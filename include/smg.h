@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 551
+#define SMG_VERSION 552
 
 enum {
     SMG_OK = 0,
@@ -1298,6 +1298,43 @@ int smg_wave_adjoint_host(int op, int nV, int nF, int k, const int *F, const dou
                           const double *x0, const double *x1, const double *x2, const double *x3, const double *x4, const int *idx, int n_idx, int n_rows,
                           double *out);
 
+/* ---- Born traces and Gauss-Newton products of the trace misfit (csrc/smg_wave_born.cpp).  With J = d traces / d speed,
+ * smg_wave_gauss_newton returns the linearised (Born) traces J d and the Gauss-Newton product H d = J' J d that truncated-Newton inversion
+ * (Gauss-Newton with conjugate gradients) is built on.  A speed perturbation d changes mt by fd = fac * d, fac = (-2.0 * mt) / speed the plane
+ * k_wave_adj_scale reads, and the right-hand side of step n by fd * e_n, e_n the block smg_wave_gradient keeps: the tangent run is the forward
+ * step itself from the zero state, without nodal sources, with one distributed source per step; J d is its traces.  The adjoint pass is linear
+ * in its residual and its coefficients do not depend on it: run with rho = J d it leaves J' J d in the place of grad_speed.  Hence
+ * <d, H d> = |J d|^2 per column and <w, H d> = <J w, J d>.
+ * Linearisation point: the run of the last smg_wave_gradient call that completed with a backward pass (a gradient output was given): its
+ *   n_steps = N, its k columns, its kept history.  The object records it as valid at the end of such a call.  smg_wave_set_speed,
+ *   smg_wave_set_params, smg_wave_set_receivers, a smg_wave_set_state that changes k and a gradient call with a backward pass that fails after its
+ *   forward half has begun drop it; smg_wave_step, smg_wave_set_sources, a smg_wave_set_state with the same k and a gradient call without a backward
+ *   pass (it does not write the history) keep it.
+ * The call: fd formed on the host, one multiply per entry, uploaded once.  The tangent run, step n = 0 .. N - 1 on two state blocks of its own:
+ *     1. k_wave_rhs where the previous k_wave_advance has not left the right-hand side (the first step runs it on the zeroed state).
+ *     2. k_wave_born: off the known rows b = b + fd[i, c % d_cols] * e_n[i, c] and its square; a known row keeps its 0.0.
+ *     3. the fixed-order sum and the host's read of |b|_F^2: non-finite refuses; exactly 0.0 (d == 0) skips the solve with w = 0 and a cycles
+ *        entry of 0; otherwise opts NULL is 1e-10 |b|_F, max_iter 100.
+ *     4. the solve, warm-started from 2 * du + dt * dv.   5. k_wave_advance.   6. k_wave_record.
+ *   No energies, no sources, no k_wave_adj_keep.  Then k_wave_adj_residual of the Born traces without an observed block and k fixed-order
+ *   sums (curvature); then, where product is wanted, smg_wave_gradient's backward loop without the signal's gradient, k_wave_adj_scale and the copy.
+ * d: host, nV x d_cols column-major, leading dimension ldd, d_cols 1 or k; column c reads column c % d_cols, so one direction serves every shot.
+ * Outputs, host, each NULL ok but not all three: product (nV x k, leading dimension ld: one H d per shot, the caller sums them as with grad_speed;
+ *   exact zeros on clamped rows; NULL: the backward pass is skipped -- Born modelling alone, one forward run's cost); born_traces (N x n_rec x k, the
+ *   layout of traces); curvature (k: |J d|^2 per column, the fixed-order sum of the squares of the returned born_traces, bit for bit); cycles (2 N,
+ *   NULL ok: the tangent solves in step order, then the backward solves in the order they ran; N entries are written where product is NULL).
+ * The object's state (u, v) is not touched.  The kept right-hand side is dropped, as the gradient call drops it; the next smg_wave_step forms it
+ *   again, to the same bits.
+ * Refusals, SMG_ERR_INVALID before any launch, in this order: a null object; no linearisation point; d missing; d_cols not 1 or k; ldd < nV; a
+ *   non-finite entry of d; every output NULL; product with ld < nV.  A non-finite right-hand side in either half ends the call with
+ *   SMG_ERR_NONFINITE and nothing written; the linearisation point is kept.
+ * Memory: two tangent state blocks (nV x 2k each) and the plane fd (nV x d_cols), allocated at the first call, grown with the largest shape
+ *   seen, kept, counted by smg_wave_device_bytes; everything else is the gradient call's.
+ * smg_wave_born_host: the host twin of k_wave_born on caller arrays (no GPU), with the operands and layouts of smg_debug_wave_born. */
+int smg_wave_gauss_newton(smg_wave *g, const double *d, int ldd, int d_cols, const smg_solve_opts *opts, double *product, int ld,
+                          double *born_traces, double *curvature, int *cycles);
+int smg_wave_born_host(int nV, int nF, int k, int d_cols, const int *F, int clamped, const double *b, const double *e, const double *fd, double *out);
+
 /* Split-phase form of the same loop for column-sharded multi-GPU runs: the caller owns
  * the all-reduce of the residual sum of squares between the two halves of an iteration.
  *   begin:     gathers RHS/z0 (column-major) into the handle, resets the control block.  SMG_DEVICE: the gathers are ENQUEUED on the
@@ -1774,6 +1811,14 @@ int smg_debug_wave(int op, int nV, int nF, int k, const int *F, const double *V,
 int smg_debug_wave_adjoint(int op, int nV, int nF, int k, const int *F, const double *V, const double *speed, const double *sigma, int clamped, double dt,
                            const double *x0, const double *x1, const double *x2, const double *x3, const double *x4, const int *idx, int n_idx, int n_rows,
                            double *out, int *guard_hits);
+/* The launcher of the tangent (Born) run's distributed source (csrc/smg_wave_born_device.hip), handle-free and guarded like the hooks above.  F,
+ * clamped: the known mask, 1 on the boundary vertices where clamped, as smg_debug_wave derives it.  b, e: nV x k column-major; fd: nV x d_cols,
+ * d_cols 1 or k; every array is host.  out = b' (nV x k: b + fd[:, c % d_cols] e off the known rows, b on them), the squares (k planes of nV: 0.0
+ * on the known rows, where the kernel leaves what k_wave_rhs wrote), their fixed-order sum (1).
+ * SMG_ERR_INVALID, in this order, for nV < 1, nF < 1, F or out missing; a missing operand; k < 1; d_cols not 1 or k; clamped not 0 or 1; a face
+ * index out of range; SMG_ERR_NO_DEVICE without a GPU. */
+int smg_debug_wave_born(int nV, int nF, int k, int d_cols, const int *F, int clamped, const double *b, const double *e, const double *fd, double *out,
+                        int *guard_hits);
 /* The time of one launcher of the wave object alone, for tools/wave_time.py: SMG_WAVE_RHS or SMG_WAVE_ADVANCE (with the next right-hand side) on
  * device blocks of zeros of k columns over the mesh (F, V: host), launched `reps` times back to back on one stream between two events after one
  * launch that is not timed; *ms = the mean time of a launch in milliseconds.  SMG_ERR_INVALID for another op, nV < 1, nF < 1, a missing array,

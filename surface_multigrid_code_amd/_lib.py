@@ -297,6 +297,9 @@ def load():
         "smg_wave_set_speed": (i, [vp, dp]),
         "smg_wave_adjoint_host": (i, [i, i, i, i, ip, dp, dp, dp, i, d, dp, dp, dp, dp, dp, ip, i, i, dp]),
         "smg_debug_wave_adjoint": (i, [i, i, i, i, ip, dp, dp, dp, i, d, dp, dp, dp, dp, dp, ip, i, i, dp, ip]),
+        "smg_wave_gauss_newton": (i, [vp, dp, i, i, C.POINTER(SolveOptsC), dp, i, dp, dp, ip]),
+        "smg_wave_born_host": (i, [i, i, i, i, ip, i, dp, dp, dp, dp]),
+        "smg_debug_wave_born": (i, [i, i, i, i, ip, i, dp, dp, dp, dp, ip]),
         "smg_solve_sharded": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC), REDUCE_FN, vp, vp, i, dp, ip, ip]),
         "smg_solve_begin": (i, [vp, vp, i, vp, i, vp, i, i, i, C.POINTER(SolveOptsC)]),
         "smg_solve_iter_residual": (i, [vp, vp]),

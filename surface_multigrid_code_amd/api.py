@@ -1588,7 +1588,7 @@ class WaveEquation(_MeshObject):
 
     def __init__(self, hierarchy, V, F, dt, speed=None, sigma=None, damping=0.0, clamped=False):
         self.params = wave_params(dt=dt, damping=damping, clamped=int(clamped))
-        self.k = self.n_src = self.n_rec = 0
+        self.k = self.n_src = self.n_rec = self.lin_steps = 0
         n = np.asarray(V).shape[0]
         speed = None if speed is None else np.ascontiguousarray(np.broadcast_to(np.asarray(speed, dtype=np.float64), (n,)))
         sigma = None if sigma is None else np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (n,)))
@@ -1692,6 +1692,23 @@ class WaveEquation(_MeshObject):
                        ptr(r.grad_v0), self.n, ptr(r.grad_signal), _dp(r.traces) if self.n_rec else None, _ip(r.cycles), C.byref(nd))
         finally:
             self.n_done = nd.value
+        if speed or state or want_gs:
+            self.lin_steps = rows   # the shape of gauss_newton()'s traces; whether the point stands is the library's to say
+        return r
+
+    def gauss_newton(self, d, product=True, traces=False, opts=None):
+        """Born traces J d and the Gauss-Newton product H d = J' J d at the run of the last gradient() call that asked for a gradient (include/smg.h:
+        smg_wave_gauss_newton) -> WaveGaussNewton.  d: n values or n x k, a speed perturbation (one direction for every shot, or one per shot);
+        product: whether H d is wanted (False: Born modelling alone, the backward pass is skipped); traces: whether born_traces is.  The curvature
+        |J d|^2 per column always is.  The state is not touched"""
+        k, rows = max(self.k, 1), max(self.lin_steps, 1)
+        d = np.asfortranarray(np.asarray(d, dtype=np.float64).reshape(self.n, -1))
+        r = WaveGaussNewton()
+        r.product = np.zeros((self.n, k), order="F") if product else None
+        r.born_traces = np.zeros((rows, self.n_rec, k)) if traces else None
+        r.curvature, r.cycles = np.zeros(k), np.zeros(2 * rows if product else rows, dtype=np.int32)
+        ptr = lambda x: None if x is None else x.ctypes.data_as(C.POINTER(C.c_double))   # noqa: E731
+        self._call("gauss_newton", ptr(d), self.n, d.shape[1], self._opts(opts), ptr(r.product), self.n, ptr(r.born_traces), _dp(r.curvature), _ip(r.cycles))
         return r
 
 
@@ -1700,6 +1717,12 @@ class WaveGradient:
     n_src x k), traces (n_steps x n_rec x k), cycles (2 n_steps: the forward solves, then the backward solves in the order they ran); a gradient
     that was not asked for is None"""
     misfit = grad_speed = grad_u0 = grad_v0 = grad_signal = traces = cycles = None
+
+
+class WaveGaussNewton:
+    """what WaveEquation.gauss_newton returns: product (n x k, one H d per shot; None where it was not asked for), born_traces (n_steps x n_rec x
+    k, or None), curvature (k: |J d|^2 per column), cycles (the tangent solves, then the backward solves in the order they ran)"""
+    product = born_traces = curvature = cycles = None
 
 
 def wave_params(**params):

@@ -13,9 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsmg.so")
-SOURCES = ["smg_device.hip", "smg_bsr3_device.hip", "smg_tiled_device.hip", "smg_coarse_device.hip", "smg_bgs_device.hip", "smg_wgs_device.hip", "smg_union_device.hip", "smg_schur_device.hip", "smg_krylov_device.hip", "smg_eig_device.hip", "smg_geodesics_device.hip", "smg_arap_device.hip", "smg_membrane_device.hip", "smg_param_device.hip", "smg_pd_device.hip", "smg_denoise_device.hip", "smg_stylize_device.hip", "smg_morph_device.hip", "smg_flow_device.hip", "smg_hodge_device.hip", "smg_conformal_device.hip", "smg_emd_device.hip", "smg_fluid_device.hip", "smg_rd_device.hip", "smg_wave_device.hip", "smg_wave_adjoint_device.hip", "smg_fixed_sum_device.hip", "smg_bgs.cpp", "smg_wgs.cpp", "smg_union.cpp", "smg_schur.cpp", "smg_bsr3.cpp", "smg_tiled.cpp", "smg_coarse.cpp", "smg_capi.cpp", "smg_eig.cpp", "smg_geodesics.cpp", "smg_arap.cpp", "smg_membrane.cpp", "smg_param.cpp", "smg_pd.cpp", "smg_denoise.cpp", "smg_stylize.cpp", "smg_morph.cpp", "smg_flow.cpp", "smg_hodge.cpp", "smg_conformal.cpp", "smg_emd.cpp", "smg_fluid.cpp", "smg_rd.cpp", "smg_sinkhorn.cpp", "smg_wave.cpp", "smg_wave_adjoint.cpp", "smg_mesh_object.cpp", "smg_debug_kernels.cpp", "smg_precompute.cpp", "smg_cycle.cpp", "smg_solve.cpp", "smg_sweep_plans.cpp", "smg_hierarchy_io.cpp", "smg_sparse.cpp", "smg_mesh.cpp",
+SOURCES = ["smg_device.hip", "smg_bsr3_device.hip", "smg_tiled_device.hip", "smg_coarse_device.hip", "smg_bgs_device.hip", "smg_wgs_device.hip", "smg_union_device.hip", "smg_schur_device.hip", "smg_krylov_device.hip", "smg_eig_device.hip", "smg_geodesics_device.hip", "smg_arap_device.hip", "smg_membrane_device.hip", "smg_param_device.hip", "smg_pd_device.hip", "smg_denoise_device.hip", "smg_stylize_device.hip", "smg_morph_device.hip", "smg_flow_device.hip", "smg_hodge_device.hip", "smg_conformal_device.hip", "smg_emd_device.hip", "smg_fluid_device.hip", "smg_rd_device.hip", "smg_wave_device.hip", "smg_wave_adjoint_device.hip", "smg_wave_born_device.hip", "smg_fixed_sum_device.hip", "smg_bgs.cpp", "smg_wgs.cpp", "smg_union.cpp", "smg_schur.cpp", "smg_bsr3.cpp", "smg_tiled.cpp", "smg_coarse.cpp", "smg_capi.cpp", "smg_eig.cpp", "smg_geodesics.cpp", "smg_arap.cpp", "smg_membrane.cpp", "smg_param.cpp", "smg_pd.cpp", "smg_denoise.cpp", "smg_stylize.cpp", "smg_morph.cpp", "smg_flow.cpp", "smg_hodge.cpp", "smg_conformal.cpp", "smg_emd.cpp", "smg_fluid.cpp", "smg_rd.cpp", "smg_sinkhorn.cpp", "smg_wave.cpp", "smg_wave_adjoint.cpp", "smg_wave_born.cpp", "smg_mesh_object.cpp", "smg_debug_kernels.cpp", "smg_precompute.cpp", "smg_cycle.cpp", "smg_solve.cpp", "smg_sweep_plans.cpp", "smg_hierarchy_io.cpp", "smg_sparse.cpp", "smg_mesh.cpp",
            "smg_order.cpp", "smg_decimate.cpp"]
-HEADERS = ["smg_device.hpp", "smg_hier.hpp", "smg_internal.hpp", "smg_device_inl.hpp", "smg_gj_inl.hpp", "smg_arap_inl.hpp", "smg_membrane_inl.hpp", "smg_param_inl.hpp", "smg_pd_inl.hpp", "smg_denoise_inl.hpp", "smg_stylize_inl.hpp", "smg_morph_inl.hpp", "smg_flow_inl.hpp", "smg_hodge_inl.hpp", "smg_conformal_inl.hpp", "smg_emd_inl.hpp", "smg_fluid_inl.hpp", "smg_rd_inl.hpp", "smg_sinkhorn_inl.hpp", "smg_wave_inl.hpp", "smg_wave_adjoint_inl.hpp", "smg_wave_grid.hpp", "smg_wave_object.hpp", "smg_mesh_object.hpp", "smg_local_global.hpp", "smg_schur.hpp", "smg_bsr3.hpp", "smg_tiled.hpp", "smg_coarse.hpp", "smg_bgs.hpp", "smg_wgs.hpp", "smg_sparse.hpp", "smg_mesh.hpp", "smg_order.hpp",
+HEADERS = ["smg_device.hpp", "smg_hier.hpp", "smg_internal.hpp", "smg_device_inl.hpp", "smg_gj_inl.hpp", "smg_arap_inl.hpp", "smg_membrane_inl.hpp", "smg_param_inl.hpp", "smg_pd_inl.hpp", "smg_denoise_inl.hpp", "smg_stylize_inl.hpp", "smg_morph_inl.hpp", "smg_flow_inl.hpp", "smg_hodge_inl.hpp", "smg_conformal_inl.hpp", "smg_emd_inl.hpp", "smg_fluid_inl.hpp", "smg_rd_inl.hpp", "smg_sinkhorn_inl.hpp", "smg_wave_inl.hpp", "smg_wave_adjoint_inl.hpp", "smg_wave_born_inl.hpp", "smg_wave_grid.hpp", "smg_wave_object.hpp", "smg_mesh_object.hpp", "smg_local_global.hpp", "smg_schur.hpp", "smg_bsr3.hpp", "smg_tiled.hpp", "smg_coarse.hpp", "smg_bgs.hpp", "smg_wgs.hpp", "smg_sparse.hpp", "smg_mesh.hpp", "smg_order.hpp",
            os.path.join("..", "..", "include", "smg.h")]
 # -amdgpu-kernarg-preload-count: the leading scalar / pointer kernel arguments arrive in SGPRs with the wave (k_sell orders its
 # arguments for this: its first panel loads need no kernarg read at all).  SMG_KERNARG_PRELOAD=0 builds without it (A/B).

@@ -18,6 +18,7 @@
 #include "smg_rd_inl.hpp"
 #include "smg_stylize_inl.hpp"
 #include "smg_wave_adjoint_inl.hpp"
+#include "smg_wave_born_inl.hpp"
 #include "smg_wave_inl.hpp"
 #include "smg_wave_object.hpp"
 
@@ -1464,6 +1465,42 @@ extern "C" int smg_debug_wave_adjoint(int op, int nV, int nF, int k, const int* 
                 HIPCHK(launch_wave_adj_scale(nV, k, dfac, dx[0], nV, dout, nV, st));
             }
         }
+        int bad = 0;
+        HIPCHK(S.finish(&bad));
+        if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_wave_born(int nV, int nF, int k, int d_cols, const int* F, int clamped, const double* b, const double* e, const double* fd,
+                                   double* out, int* guard_hits)
+{
+    return guarded("smg_debug_wave_born", [&]() -> int {
+        const char* who = "smg_debug_wave_born";
+        if (int rc = wave_born_check_operands(who, nV, nF, k, d_cols, F, clamped, b, e, fd, out)) return rc;
+        if (int rc = need_device(who)) return rc;
+        const size_t n = (size_t)nV, kk = (size_t)k, nk = n * kk, D = sizeof(double);
+        if (2 * nk > (size_t)INT_MAX) return fail(SMG_ERR_INVALID, "%s: k = %d exceeds the index range", who, k);
+        Scratch S;
+        HIPCHK(S.init());
+        hipStream_t st = S.stream();
+        double *db = nullptr, *de = nullptr, *dfd = nullptr, *dout = nullptr, *dpart = nullptr;
+        int* dknown = nullptr;
+        HIPCHK(S.add(b, nullptr, nk * D, &db));
+        HIPCHK(S.add(e, nullptr, nk * D, &de));
+        HIPCHK(S.add(fd, nullptr, n * (size_t)d_cols * D, &dfd));
+        HIPCHK(S.add(nullptr, out, (2 * nk + 1) * D, &dout));
+        HIPCHK(S.add(nullptr, nullptr, (size_t)fixed_sum_groups((int)nk) * D, &dpart));
+        std::vector<int> known;   // lives until the stream has drained
+        if (clamped) {
+            known.assign(n, 0);
+            for (int v : boundary_vertices(F, nF, nV)) known[(size_t)v] = 1;
+            HIPCHK(S.add(known.data(), nullptr, n * sizeof(int), &dknown));
+        }
+        HIPCHK(hipMemcpyAsync(dout, db, nk * D, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemsetAsync(dout + nk, 0, nk * D, st));   // the squares start as k_wave_rhs leaves the known rows
+        HIPCHK(launch_wave_born(nV, k, d_cols, dknown, dfd, de, dout, nV, dout + nk, st));
+        HIPCHK(launch_fixed_sum(dout + nk, (int)nk, dpart, dout + 2 * nk, st));
         int bad = 0;
         HIPCHK(S.finish(&bad));
         if (guard_hits) *guard_hits = bad;

@@ -716,4 +716,8 @@ hipError_t launch_wave_adj_signal(int n, int k, int n_src, const int* idx, doubl
 // out = fac G; out may be G
 hipError_t launch_wave_adj_scale(int n, int k, const double* fac, const double* G, int ld, double* out, int ldo, hipStream_t st);
 
+// the distributed source of a tangent (Born) step (smg_wave_born_device.hip; the maths in smg_wave_born_inl.hpp): off the known rows
+// b = b + fd[i, c % d_cols] e[i, c] and rsq = b^2; fd: d_cols planes of n, e: k planes of n, b: column-major with leading dimension ldb
+hipError_t launch_wave_born(int n, int k, int d_cols, const int* known, const double* fd, const double* e, double* b, int ldb, double* rsq, hipStream_t st);
+
 }  // namespace smg

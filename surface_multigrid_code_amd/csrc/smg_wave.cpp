@@ -8,7 +8,8 @@
 // smg_solve_pcg gather z0 into the handle before they scatter z, on one stream -- and the advance kernel with the sums of its energies, all enqueued
 // on the object's stream, which the handle uses too.  The host reads one double before the solve, |b|_F^2 -- it sets the default tolerance and
 // refuses non-finite input -- and 2k after it, the energies.  A step writes into the block beside the state and commits by an index swap, so a
-// refused step leaves the state of the last completed one.  Checks, stream, handle, the cotangent system and the inner solve:
+// refused step leaves the state of the last completed one.  The loop takes its state blocks as parameters: smg_wave_gauss_newton
+// (smg_wave_born.cpp) runs it on the tangent state with one more launch per step, k_wave_born.  Checks, stream, handle, the cotangent system and the inner solve:
 // smg_mesh_object.hpp.  The object's struct and what this file shares with smg_wave_adjoint.cpp (smg_wave_gradient runs the step loop below
 // and keeps one block per step): smg_wave_object.hpp.
 #include <hip/hip_runtime_api.h>
@@ -108,8 +109,8 @@ int wave_check_signal(const char* who, const smg_wave* g, int n_steps, const dou
     return SMG_OK;
 }
 
-int wave_forward(smg_wave* g, const char* who, int n_steps, const double* signal, const smg_solve_opts* opts, double* energy_his, double* traces, bool record,
-                 int* cycles, int* n_done, double* keep)
+int wave_forward(smg_wave* g, const char* who, DevBuf<double>* S, int* cur, const WaveBorn* born, int n_steps, const double* signal,
+                 const smg_solve_opts* opts, double* energy_his, double* traces, bool record, int* cycles, int* n_done, double* keep)
 {
     const int n = g->nV, k = g->k, ns = g->n_src, nr = traces || record ? g->n_rec : 0;
     const size_t nk = (size_t)n * k, D = sizeof(double), row_s = (size_t)ns * k, row_r = (size_t)nr * k;
@@ -127,11 +128,12 @@ int wave_forward(smg_wave* g, const char* who, int n_steps, const double* signal
     const int* known = g->nb > 0 ? g->known.p : nullptr;
     int done = 0, rc = SMG_OK;
     for (int t = 0; t < n_steps; t++) {
-        const double* s0 = g->S[g->cur].p;
-        double* s1 = g->S[1 - g->cur].p;
+        const double* s0 = S[*cur].p;
+        double* s1 = S[1 - *cur].p;
         if (!g->rhs_valid) HIPCHK(launch_wave_rhs(n, k, g->mt.p, g->s2.p, known, dt, s0, s0 + nk, n, g->B.p, g->Wb.p, n, g->rsq.p, st));
         g->rhs_valid = false;   // the sources change it in place, and the advance kernel overwrites it
         if (signal) HIPCHK(launch_wave_sources(n, k, ns, g->src.p, g->sig.p + (size_t)t * row_s, g->sig.p + ((size_t)t + 1) * row_s, g->a, g->B.p, n, g->rsq.p, st));
+        if (born) HIPCHK(launch_wave_born(n, k, born->d_cols, known, born->fd, born->e + (size_t)t * nk, g->B.p, n, g->rsq.p, st));
         HIPCHK(launch_fixed_sum(g->rsq.p, (int)nk, g->part.p, g->red.p, st));
         HIPCHK(hipMemcpyAsync(rh, g->red.p, D, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -139,9 +141,13 @@ int wave_forward(smg_wave* g, const char* who, int n_steps, const double* signal
             rc = fail(SMG_ERR_NONFINITE, "%s: the right-hand side is not finite (step %d)", who, t);
             break;
         }
-        const smg_solve_opts so = opts_or_default(opts, 1e-10 * std::sqrt(rh[0]), 100);
         int e = 0;
-        if ((rc = inner_solve(g->handle[0], g->pcg, g->B.p, n, g->nb > 0 ? g->zero.p : nullptr, g->nb, g->Wb.p, n, k, so, g->Wb.p, n, &e))) break;
+        if (born && rh[0] == 0.0) {   // as the adjoint loop: w = 0 without a solve
+            HIPCHK(hipMemsetAsync(g->Wb.p, 0, nk * D, st));
+        } else {
+            const smg_solve_opts so = opts_or_default(opts, 1e-10 * std::sqrt(rh[0]), 100);
+            if ((rc = inner_solve(g->handle[0], g->pcg, g->B.p, n, g->nb > 0 ? g->zero.p : nullptr, g->nb, g->Wb.p, n, k, so, g->Wb.p, n, &e))) break;
+        }
         double* bn = g->fused ? g->B.p : nullptr;
         HIPCHK(launch_wave_advance(n, k, g->mt.p, g->s2.p, known, dt, g->q2, g->Wb.p, n, s0, s0 + nk, n, s1, s1 + nk, n, g->ke.p, bn, g->Wb.p, n, g->rsq.p, st));
         if (energy_his) {
@@ -156,7 +162,7 @@ int wave_forward(smg_wave* g, const char* who, int n_steps, const double* signal
         if (keep) HIPCHK(launch_wave_adj_keep(n, k, g->s2.p, dt, s0, s0 + nk, s1, n, keep + (size_t)t * nk, st));
         if (nr > 0) HIPCHK(launch_wave_record(n, k, nr, g->rec.p, s1, n, g->trace.p + (size_t)t * row_r, st));
         HIPCHK(hipStreamSynchronize(st));
-        g->cur = 1 - g->cur;
+        *cur = 1 - *cur;
         g->rhs_valid = g->fused;
         if (energy_his) std::copy(rh + 1, rh + 1 + 2 * (size_t)k, energy_his + (size_t)t * 2 * k);
         if (cycles) cycles[t] = e;
@@ -278,6 +284,7 @@ int set_state_impl(smg_wave* g, const double* u, const double* v, int ld, int k,
     if (bad_memspace(memspace)) return fail(SMG_ERR_INVALID, "%s: memspace must be SMG_HOST or SMG_DEVICE", who);
     if (ld < g->nV) return fail(SMG_ERR_INVALID, "%s: a leading dimension is too small", who);
     DeviceScope dsc(g->device);
+    if (k != g->k) g->lin_valid = false;   // smg_wave_gauss_newton's linearisation point has the columns of the state
     g->k = 0;
     g->rhs_valid = false;
     if (int rc = ensure_columns(g, k)) return rc;
@@ -341,7 +348,7 @@ int step_impl(smg_wave* g, int n_steps, const double* signal, const smg_solve_op
     if (n_done) *n_done = 0;
     if (int rc = wave_check_steps(who, g, n_steps)) return rc;
     if (int rc = wave_check_signal(who, g, n_steps, signal)) return rc;
-    return wave_forward(g, who, n_steps, signal, opts, energy_his, traces, false, cycles, n_done, nullptr);
+    return wave_forward(g, who, g->S, &g->cur, nullptr, n_steps, signal, opts, energy_his, traces, false, cycles, n_done, nullptr);
 }
 
 int set_params_impl(smg_wave* g, const smg_wave_params* p)
@@ -353,6 +360,7 @@ int set_params_impl(smg_wave* g, const smg_wave_params* p)
         return fail(SMG_ERR_INVALID, "%s: clamped = %d, but the object was created with clamped = %d: the known rows cannot change", who, p->clamped,
                     g->p.clamped);
     DeviceScope dsc(g->device);
+    g->lin_valid = false;
     const bool changed = p->dt != g->p.dt || (!g->has_sigma && p->damping != g->p.damping);
     const smg_wave_params old = g->p;
     g->p = *p;
@@ -398,7 +406,7 @@ extern "C" long long smg_wave_device_bytes(const smg_wave* g)
     if (!g) return 0;   // one list: every DevBuf of the struct
     return device_bytes(*g, g->F, g->known, g->rows, g->src, g->rec, g->W, g->nrm, g->Af, g->mt, g->s2, g->val, g->S[0], g->S[1], g->B, g->Wb, g->rsq,
                         g->ke, g->terms, g->part, g->red, g->zero, g->flag, g->sig, g->trace, g->grp_v, g->grp_ptr, g->grp_slot, g->H, g->P, g->Q, g->Y, g->G, g->rho,
-                        g->apart, g->ared, g->gs, g->fac);
+                        g->apart, g->ared, g->gs, g->fac, g->T[0], g->T[1], g->fd);
 }
 
 extern "C" int smg_wave_set_state(smg_wave* g, const double* u, const double* v, int ld, int k, int memspace)
@@ -426,6 +434,7 @@ extern "C" int smg_wave_set_receivers(smg_wave* g, const int* idx, int n_rec)
         if (int rc = set_list(g, "smg_wave_set_receivers", idx, n_rec, false, g->rec, &g->n_rec)) return rc;
         g->rec_host.assign(idx, idx + n_rec);   // smg_wave_gradient groups it by vertex at its next call
         g->grouped = false;
+        g->lin_valid = false;
         return SMG_OK;
     });
 }

@@ -60,12 +60,8 @@ int wave_adjoint_check_operands(const char* who, int op, int nV, int nF, int k, 
     return SMG_OK;
 }
 
-}  // namespace smg
-
-namespace {
-
 // the blocks of a gradient call; they grow with the largest shape seen and are kept.  The receivers are grouped by vertex where the list has changed
-int ensure_adjoint(smg_wave* g, int n_steps, bool backward, bool observed, bool grad_signal)
+int wave_ensure_adjoint(smg_wave* g, int n_steps, bool backward, bool observed, bool grad_signal)
 {
     const size_t nk = (size_t)g->nV * g->k, ent = (size_t)n_steps * g->n_rec, ek = ent * g->k;
     HIPCHK(hipStreamSynchronize(g->stream));
@@ -100,47 +96,12 @@ int ensure_adjoint(smg_wave* g, int n_steps, bool backward, bool observed, bool 
     return SMG_OK;
 }
 
-int gradient_impl(smg_wave* g, int n_steps, const double* signal, const double* observed, const smg_solve_opts* opts, double* misfit, double* grad_speed, int ld,
-                  double* grad_u0, double* grad_v0, int ld0, double* grad_signal, double* traces, int* cycles, int* n_done)
+// the backward pass: what smg_wave_gradient and smg_wave_gauss_newton run alike
+int wave_backward(smg_wave* g, const char* who, int n_steps, const double* rho, const smg_solve_opts* opts, bool grad_signal, int* cycles)
 {
-    const char* who = "smg_wave_gradient";
-    if (n_done) *n_done = 0;
-    if (int rc = wave_check_steps(who, g, n_steps)) return rc;
-    if (g->n_rec == 0) return fail(SMG_ERR_INVALID, "%s: no receivers: call smg_wave_set_receivers first", who);
-    if (int rc = wave_check_signal(who, g, n_steps, signal)) return rc;
     const int n = g->nV, k = g->k, N = n_steps, ns = g->n_src, nr = g->n_rec;
-    if ((long long)N * nr * k > INT_MAX) return fail(SMG_ERR_INVALID, "%s: %d steps of %d receivers and %d columns exceed the index range", who, N, nr, k);
-    const size_t nk = (size_t)n * k, D = sizeof(double), row_s = (size_t)ns * k, row_r = (size_t)nr * k, ent = (size_t)N * nr, ek = ent * k;
-    if (observed)
-        for (size_t j = 0; j < ek; j++)
-            if (!std::isfinite(observed[j]))
-                return fail(SMG_ERR_INVALID, "%s: observed is not finite at step %d, receiver %d, column %d", who, (int)(j / row_r), (int)(j % row_r) / k,
-                            (int)(j % row_r) % k);
-    if ((grad_speed && ld < n) || ((grad_u0 || grad_v0) && ld0 < n)) return fail(SMG_ERR_INVALID, "%s: a leading dimension is too small", who);
-    if (grad_signal && !signal) return fail(SMG_ERR_INVALID, "%s: grad_signal without a signal", who);
-    const bool backward = grad_speed || grad_u0 || grad_v0 || grad_signal;
-    DeviceScope dsc(g->device);
+    const size_t nk = (size_t)n * k, D = sizeof(double), row_s = (size_t)ns * k, row_r = (size_t)nr * k;
     hipStream_t st = g->stream;
-    if (int rc = ensure_adjoint(g, N, backward, observed != nullptr, grad_signal != nullptr)) return rc;
-
-    // the forward half: smg_wave_step's loop, the traces recorded on the device, e_n kept
-    int done = 0;
-    const int rcf = wave_forward(g, who, N, signal, opts, nullptr, traces, true, cycles, &done, backward ? g->H.p : nullptr);
-    if (n_done) *n_done = done;
-    if (rcf != SMG_OK || done < N) return rcf;
-
-    // the residuals and the misfit
-    double *rho = g->rho.p, *sq = rho + ek, *obs = observed ? rho + 2 * ek : nullptr;
-    if (observed) HIPCHK(hipMemcpyAsync(obs, observed, ek * D, hipMemcpyHostToDevice, st));
-    HIPCHK(launch_wave_adj_residual(k, (long long)ent, g->trace.p, obs, rho, sq, st));
-    for (int c = 0; c < k; c++) HIPCHK(launch_fixed_sum(sq + (size_t)c * ent, (int)ent, g->apart.p, g->ared.p + c, st));
-    std::vector<double> J((size_t)k);
-    HIPCHK(hipMemcpyAsync(J.data(), g->ared.p, (size_t)k * D, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int c = 0; misfit && c < k; c++) misfit[c] = 0.5 * J[(size_t)c];
-    if (!backward) return SMG_OK;
-
-    // the backward pass
     g->rhs_valid = false;   // B and rsq hold the adjoint right-hand side from here on
     for (DevBuf<double>* b : {&g->P, &g->Q, &g->Y, &g->G}) HIPCHK(hipMemsetAsync(b->p, 0, nk * D, st));
     if (grad_signal) HIPCHK(hipMemsetAsync(g->gs.p, 0, ((size_t)N + 1) * row_s * D, st));
@@ -164,8 +125,60 @@ int gradient_impl(smg_wave* g, int n_steps, const double* signal, const double* 
         HIPCHK(launch_wave_adj_advance(n, k, g->mt.p, g->s2.p, dt, g->q2, g->Y.p, n, g->H.p + (size_t)t * nk, g->P.p, g->Q.p, g->G.p, n, st));
         if (grad_signal) HIPCHK(launch_wave_adj_signal(n, k, ns, g->src.p, g->a, g->Y.p, n, g->gs.p + (size_t)t * row_s, g->gs.p + ((size_t)t + 1) * row_s, st));
         if (t >= 1) HIPCHK(launch_wave_adj_inject(n, k, g->n_grp, g->grp_v.p, g->grp_ptr.p, g->grp_slot.p, rho + (size_t)(t - 1) * row_r, g->P.p, n, st));
-        if (cycles) cycles[N + (N - 1 - t)] = e;
+        if (cycles) cycles[N - 1 - t] = e;
     }
+    return SMG_OK;
+}
+
+}  // namespace smg
+
+namespace {
+
+int gradient_impl(smg_wave* g, int n_steps, const double* signal, const double* observed, const smg_solve_opts* opts, double* misfit, double* grad_speed, int ld,
+                  double* grad_u0, double* grad_v0, int ld0, double* grad_signal, double* traces, int* cycles, int* n_done)
+{
+    const char* who = "smg_wave_gradient";
+    if (n_done) *n_done = 0;
+    if (int rc = wave_check_steps(who, g, n_steps)) return rc;
+    if (g->n_rec == 0) return fail(SMG_ERR_INVALID, "%s: no receivers: call smg_wave_set_receivers first", who);
+    if (int rc = wave_check_signal(who, g, n_steps, signal)) return rc;
+    const int n = g->nV, k = g->k, N = n_steps, ns = g->n_src, nr = g->n_rec;
+    if ((long long)N * nr * k > INT_MAX) return fail(SMG_ERR_INVALID, "%s: %d steps of %d receivers and %d columns exceed the index range", who, N, nr, k);
+    const size_t D = sizeof(double), row_s = (size_t)ns * k, row_r = (size_t)nr * k, ent = (size_t)N * nr, ek = ent * k;
+    if (observed)
+        for (size_t j = 0; j < ek; j++)
+            if (!std::isfinite(observed[j]))
+                return fail(SMG_ERR_INVALID, "%s: observed is not finite at step %d, receiver %d, column %d", who, (int)(j / row_r), (int)(j % row_r) / k,
+                            (int)(j % row_r) % k);
+    if ((grad_speed && ld < n) || ((grad_u0 || grad_v0) && ld0 < n)) return fail(SMG_ERR_INVALID, "%s: a leading dimension is too small", who);
+    if (grad_signal && !signal) return fail(SMG_ERR_INVALID, "%s: grad_signal without a signal", who);
+    const bool backward = grad_speed || grad_u0 || grad_v0 || grad_signal;
+    DeviceScope dsc(g->device);
+    hipStream_t st = g->stream;
+    // a call with a backward pass regrows and overwrites the history: smg_wave_gauss_newton's linearisation point is this call's once it has
+    // completed and none where it has not; a call without one leaves both
+    if (backward) g->lin_valid = false;
+    if (int rc = wave_ensure_adjoint(g, N, backward, observed != nullptr, grad_signal != nullptr)) return rc;
+
+    // the forward half: smg_wave_step's loop, the traces recorded on the device, e_n kept
+    int done = 0;
+    const int rcf = wave_forward(g, who, g->S, &g->cur, nullptr, N, signal, opts, nullptr, traces, true, cycles, &done, backward ? g->H.p : nullptr);
+    if (n_done) *n_done = done;
+    if (rcf != SMG_OK || done < N) return rcf;
+
+    // the residuals and the misfit
+    double *rho = g->rho.p, *sq = rho + ek, *obs = observed ? rho + 2 * ek : nullptr;
+    if (observed) HIPCHK(hipMemcpyAsync(obs, observed, ek * D, hipMemcpyHostToDevice, st));
+    HIPCHK(launch_wave_adj_residual(k, (long long)ent, g->trace.p, obs, rho, sq, st));
+    for (int c = 0; c < k; c++) HIPCHK(launch_fixed_sum(sq + (size_t)c * ent, (int)ent, g->apart.p, g->ared.p + c, st));
+    std::vector<double> J((size_t)k);
+    HIPCHK(hipMemcpyAsync(J.data(), g->ared.p, (size_t)k * D, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int c = 0; misfit && c < k; c++) misfit[c] = 0.5 * J[(size_t)c];
+    if (!backward) return SMG_OK;
+
+    // the backward pass
+    if (int rc = wave_backward(g, who, N, rho, opts, grad_signal != nullptr, cycles ? cycles + N : nullptr)) return rc;
     if (grad_speed) {
         HIPCHK(launch_wave_adj_scale(n, k, g->fac.p, g->G.p, n, g->G.p, n, st));
         HIPCHK(copy_columns(grad_speed, ld, g->G.p, n, n, k, hipMemcpyDeviceToHost, st));
@@ -174,6 +187,8 @@ int gradient_impl(smg_wave* g, int n_steps, const double* signal, const double* 
     if (grad_v0) HIPCHK(copy_columns(grad_v0, ld0, g->Q.p, n, n, k, hipMemcpyDeviceToHost, st));
     if (grad_signal) HIPCHK(hipMemcpyAsync(grad_signal, g->gs.p, ((size_t)N + 1) * row_s * D, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    g->lin_valid = true;
+    g->lin_steps = N;
     return SMG_OK;
 }
 
@@ -189,6 +204,7 @@ int set_speed_impl(smg_wave* g, const double* speed)
     for (size_t i = 0; i < n; i++) g->mt_host[i] = speed ? g->m_host[i] / (speed[i] * speed[i]) : g->m_host[i];
     if (speed) g->speed_host.assign(speed, speed + n); else g->speed_host.clear();
     g->fac_valid = false;
+    g->lin_valid = false;
     HIPCHK(hipStreamSynchronize(g->stream));
     HIPCHK(hipMemcpy(g->mt.p, g->mt_host.data(), n * sizeof(double), hipMemcpyHostToDevice));
     if (int rc = wave_system(g, false)) {   // back to the speed it had: the planes, and the handle's values once more, which may have been replaced in part

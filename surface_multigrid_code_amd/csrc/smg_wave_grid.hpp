@@ -1,4 +1,5 @@
-// smg_wave_grid.hpp -- the launch shapes the wave object's two kernel files share (smg_wave_device.hip, smg_wave_adjoint_device.hip): one WAVEFRONT
+// smg_wave_grid.hpp -- the launch shapes the wave object's three kernel files share (smg_wave_device.hip, smg_wave_adjoint_device.hip,
+// smg_wave_born_device.hip): one WAVEFRONT
 // per (64 consecutive vertices, column) for the vertex kernels, one lane per (list entry, column) for the list kernels.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>

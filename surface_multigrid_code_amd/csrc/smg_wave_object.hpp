@@ -1,5 +1,6 @@
 // smg_wave_object.hpp -- the wave object's state and what its two translation units share (smg_wave.cpp: create, the state, the lists, the forward
-// step; smg_wave_adjoint.cpp: smg_wave_gradient, smg_wave_set_speed; include/smg.h: smg_wave_*; DESIGN.md sections 33 and 34).
+// step; smg_wave_adjoint.cpp: smg_wave_gradient, smg_wave_set_speed; smg_wave_born.cpp: smg_wave_gauss_newton; include/smg.h: smg_wave_*; DESIGN.md
+// sections 33, 34 and 36).
 #pragma once
 #include <vector>
 
@@ -38,6 +39,10 @@ struct smg_wave : smg::MeshObject {        // handle[0]: diag(0.5 s2 mt) + a (-L
     smg::DevBuf<double> P, Q, Y, G;        // n x k each: the adjoint state, the adjoint solve's answer (the next one's warm start), sum_n y e_n
     smg::DevBuf<double> rho, apart, ared;  // the residuals, their squares (k planes) and the observed traces; the misfit's chunk sums; its k sums
     smg::DevBuf<double> gs, fac;           // the signal's gradient; the plane (-2 mt) / speed
+    // ---- smg_wave_gauss_newton (smg_wave_born.cpp): nothing below is allocated before the first product call
+    bool lin_valid = false;                // H holds the history of a completed gradient call with a backward pass: the linearisation point
+    int lin_steps = 0;                     // its steps; its columns are k (a set_state that changes k drops the point)
+    smg::DevBuf<double> T[2], fd;          // column-major n x 2k: the tangent state and the tangent step's output; n x d_cols: fac d
     ~smg_wave() { quiesce(); }
 };
 
@@ -49,15 +54,38 @@ int wave_system(smg_wave* g, bool first);
 // the checks of a stepping call, in this order: the object and its state, n_steps >= 1; then the signal: sources are set, every entry finite
 int wave_check_steps(const char* who, const smg_wave* g, int n_steps);
 int wave_check_signal(const char* who, const smg_wave* g, int n_steps, const double* signal);
-// the steps of smg_wave_step after its checks.  record: the traces are gathered on the device (g->trace) even where `traces` is nullptr; keep
-// (device, nullptr ok): n_steps blocks of n x k, block t = dt v_t - (0.5 s2) (u_t+1 - u_t) of step t, one more launch per step
-int wave_forward(smg_wave* g, const char* who, int n_steps, const double* signal, const smg_solve_opts* opts, double* energy_his, double* traces, bool record,
-                 int* cycles, int* n_done, double* keep);
+// the optional operands of a tangent (Born) run: fd = fac d (n x d_cols, d_cols 1 or k) and the kept history, n_steps blocks e_n of n x k
+struct WaveBorn {
+    const double* fd;
+    int d_cols;
+    const double* e;
+};
+// the steps of smg_wave_step after its checks, on the state blocks S[0], S[1] (n x 2k each) of which S[*cur] holds the state; a completed step
+// flips *cur.  record: the traces are gathered on the device (g->trace) even where `traces` is nullptr; keep (device, nullptr ok): n_steps
+// blocks of n x k, block t = dt v_t - (0.5 s2) (u_t+1 - u_t) of step t, one more launch per step.  born (nullptr: none): the tangent run --
+// k_wave_born adds fd e_t to the right-hand side of step t, and a right-hand side that is exactly 0.0 skips the solve with w = 0 and a cycles
+// entry of 0
+int wave_forward(smg_wave* g, const char* who, smg::DevBuf<double>* S, int* cur, const WaveBorn* born, int n_steps, const double* signal,
+                 const smg_solve_opts* opts, double* energy_his, double* traces, bool record, int* cycles, int* n_done, double* keep);
 
 // ---- smg_wave_adjoint.cpp: what smg_wave_adjoint_host and smg_debug_wave_adjoint check alike, in this order: the op and its operands, k, dt, clamped,
 // speed, sigma, the faces, then the rows and the list of a list op (sources: no vertex twice)
 int wave_adjoint_check_operands(const char* who, int op, int nV, int nF, int k, const int* F, const double* V, const double* speed, const double* sigma,
                                 int clamped, double dt, const double* x0, const double* x1, const double* x2, const double* x3, const double* x4, const int* idx,
                                 int n_idx, int n_rows, const double* out);
+
+// ---- smg_wave_adjoint.cpp, shared with smg_wave_born.cpp -----------------------------------------------------------------------------------------
+// the blocks of a gradient call; they grow with the largest shape seen and are kept.  The receivers are grouped by vertex where the list has
+// changed, the factor plane is formed where the speed has
+int wave_ensure_adjoint(smg_wave* g, int n_steps, bool backward, bool observed, bool grad_signal);
+// the backward loop of smg_wave_gradient from p = R' rho_N, q = 0, Y = 0, G = 0 over the kept history g->H: leaves (p, q) in g->P, g->Q, the
+// unscaled sum_n y e_n in g->G and, where grad_signal, the signal's gradient in g->gs.  rho: the residuals on the device, n_steps rows of
+// n_rec x k; cycles (nullptr ok): n_steps entries in the order the solves ran.  Drops the kept right-hand side
+int wave_backward(smg_wave* g, const char* who, int n_steps, const double* rho, const smg_solve_opts* opts, bool grad_signal, int* cycles);
+
+// ---- smg_wave_born.cpp: what smg_wave_born_host and smg_debug_wave_born check alike, in this order: the sizes, F and out; the operands; k; d_cols;
+// clamped; the faces
+int wave_born_check_operands(const char* who, int nV, int nF, int k, int d_cols, const int* F, int clamped, const double* b, const double* e,
+                             const double* fd, const double* out);
 
 }  // namespace smg
