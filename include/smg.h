@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SMG_VERSION 552
+#define SMG_VERSION 553
 
 enum {
     SMG_OK = 0,
@@ -1591,6 +1591,13 @@ int smg_debug_geodesics(int op, int n, int nF, int k, const int *F, const int *m
 enum { SMG_ARAP_COVARIANCE = 0, SMG_ARAP_ROTATIONS = 1, SMG_ARAP_RHS = 2, SMG_ARAP_VERTEX_ENERGY = 3, SMG_ARAP_ENERGY = 4 };
 int smg_debug_arap(int op, int n, const int *rowptr, const int *col, const double *w, const double *P0, const double *P, const double *R_in,
                    double *out, int *guard_hits);
+/* The fixed-order reduction under every energy, stopping test and CFL rate (csrc/smg_fixed_sum_device.hip), handle-free and guarded like the
+ * hooks above, at a length of the caller's choosing: *out = the sum (SMG_FIXED_SUM: launch_fixed_sum) or the maximum (SMG_FIXED_MAX:
+ * launch_fixed_max; a NaN loses against a number, n NaNs give -inf) of term[0 .. n).  The chunk scratch holds exactly the launched chunk count
+ * of doubles and the result one double, each between guards; *groups (NULL ok): the chunk count that was launched.
+ * SMG_ERR_INVALID for an unknown op, n <= 0 or a NULL term / out; SMG_ERR_NO_DEVICE without a GPU. */
+enum { SMG_FIXED_SUM = 0, SMG_FIXED_MAX = 1 };
+int smg_debug_fixed_reduce(int op, int n, const double *term, double *out, int *groups, int *guard_bad);
 
 /* One launcher of the membrane step (csrc/smg_membrane_device.hip), handle-free and guarded like the hooks above.  V0: the rest pose, P: a pose,
  * both nV x 3 row-major; per-face arrays are planes (entry e of face f at [e nF + f]); in / out are concatenations in the order given:

@@ -126,6 +126,7 @@ def load():
         "smg_geodesics_device_bytes": (C.c_longlong, [vp]),
         "smg_geodesics_solve": (i, [vp, i, ip, ip, i, C.POINTER(SolveOptsC), C.POINTER(SolveOptsC), vp, i, ip]),
         "smg_debug_arap": (i, [i, i, ip, ip, dp, dp, dp, dp, dp, ip]),
+        "smg_debug_fixed_reduce": (i, [i, i, dp, dp, ip, ip]),
         "smg_arap_create": (i, [vp, dp, i, ip, i, ip, i, C.POINTER(vp)]),
         "smg_arap_destroy": (None, [vp]),
         "smg_arap_set_solver": (i, [vp, i]),

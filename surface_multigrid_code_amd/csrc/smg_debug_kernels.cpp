@@ -1,5 +1,5 @@
 // smg_debug_kernels.cpp -- handle-free test hooks of the LOBPCG and PCG block kernels (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine,
-// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow), of the Hodge kernels (smg_debug_hodge), of the earth mover's kernels (smg_debug_emd), of the surface-fluid kernels (smg_debug_fluid), of the reaction-diffusion kernels (smg_debug_rd), of the wave-equation kernels (smg_debug_wave) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
+// smg_debug_eig_residual, smg_debug_krylov), of the geodesics kernels (smg_debug_geodesics), of the ARAP kernels (smg_debug_arap), of the fixed-order reduction (smg_debug_fixed_reduce), of the membrane kernels (smg_debug_membrane, smg_debug_membrane_material), of the parameterization kernels (smg_debug_param), of the projective-dynamics kernels (smg_debug_pd), of the denoising kernels (smg_debug_denoise), of the stylization kernels (smg_debug_stylize), of the morphing kernels (smg_debug_morph), of the flow kernels (smg_debug_flow), of the Hodge kernels (smg_debug_hodge), of the earth mover's kernels (smg_debug_emd), of the surface-fluid kernels (smg_debug_fluid), of the reaction-diffusion kernels (smg_debug_rd), of the wave-equation kernels (smg_debug_wave) and of the union kernels (smg_debug_union).  Each hook uploads host arrays to scratch device buffers, calls the launcher of smg_device.hpp once
 // on a private stream, and copies the results back.  Every device buffer sits between two guard regions filled with a sentinel byte; a guard that
 // changed is reported, so a stray write past either end of an output is seen by the caller.
 #include <hip/hip_runtime_api.h>
@@ -383,6 +383,28 @@ extern "C" int smg_debug_arap(int op, int n, const int* rowptr, const int* col, 
         int bad = 0;
         HIPCHK(X.finish(&bad));
         if (guard_hits) *guard_hits = bad;
+        return SMG_OK;
+    });
+}
+
+extern "C" int smg_debug_fixed_reduce(int op, int n, const double* term, double* out, int* groups, int* guard_bad)
+{
+    return guarded("smg_debug_fixed_reduce", [&]() -> int {
+        if ((op != SMG_FIXED_SUM && op != SMG_FIXED_MAX) || n <= 0 || !term || !out) return fail(SMG_ERR_INVALID, "smg_debug_fixed_reduce: bad arguments");
+        if (int rc = need_device("smg_debug_fixed_reduce")) return rc;
+        Scratch X;
+        HIPCHK(X.init());
+        const int g = fixed_sum_groups(n);
+        double *dterm = nullptr, *dpart = nullptr, *dout = nullptr;
+        HIPCHK(X.add(term, nullptr, (size_t)n * sizeof(double), &dterm));
+        HIPCHK(X.add(nullptr, nullptr, (size_t)g * sizeof(double), &dpart));      // exactly the chunks: one more written shows in the guard
+        HIPCHK(X.add(nullptr, out, sizeof(double), &dout));
+        if (op == SMG_FIXED_SUM) HIPCHK(launch_fixed_sum(dterm, n, dpart, dout, X.stream()));
+        else HIPCHK(launch_fixed_max(dterm, n, dpart, dout, X.stream()));
+        int bad = 0;
+        HIPCHK(X.finish(&bad));
+        if (groups) *groups = g;
+        if (guard_bad) *guard_bad = bad;
         return SMG_OK;
     });
 }

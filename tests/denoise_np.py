@@ -49,6 +49,18 @@ def square2():
     return V, np.array([[0, 1, 2], [0, 2, 3]], dtype=np.int32)
 
 
+def edge_shapes():
+    """label -> (V, F), the awkward shapes a launcher is held on: strips with one row more or fewer than a wave (63 / 64 / 65 faces) and than a
+    256-thread block (strip(n) has n faces and n + 2 vertices: 253 / 254 / 255 put the vertices, 255 / 256 / 257 the faces around 256), a fan
+    whose hub has 65 corners and 65 neighbours, and two meshes smaller than any block"""
+    out = {"strip%d" % n: strip(n) for n in (63, 64, 65, 253, 254, 255, 256, 257)}
+    out.update(fan65=fan(65), tetrahedron=tetrahedron(), square=square2())
+    return out
+
+
+EDGE_SHAPES = ["strip63", "strip64", "strip65", "strip253", "strip254", "strip255", "strip256", "strip257", "fan65", "tetrahedron", "square"]
+
+
 def mirrored_triple():
     """three faces: face 0 shares one vertex with face 1 and one with face 2, which is face 1 mirrored in the plane x = 0 (corner by corner):
     A_1 = A_2 and |c_0 - c_1| = |c_0 - c_2| to the bit"""

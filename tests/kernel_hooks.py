@@ -1,5 +1,5 @@
 """numpy wrappers of the kernel test hooks (include/smg.h: the handle-free smg_debug_eig_gram, smg_debug_eig_combine, smg_debug_eig_residual,
-smg_debug_krylov, smg_debug_union; on a handle smg_debug_cycle_f32, smg_debug_convert_f32; read-only, which kernel variants run: smg_debug_wgs_launches,
+smg_debug_krylov, smg_debug_union, smg_debug_fixed_reduce; on a handle smg_debug_cycle_f32, smg_debug_convert_f32; read-only, which kernel variants run: smg_debug_wgs_launches,
 smg_debug_wgs_level_plan, smg_debug_deep_launches, smg_debug_gs_colour_wpb) and the rounding-error bounds the tests hold them to.
 
 Every wrapper asserts that the hook succeeded and that no guard region around a device buffer changed (no write out of place)."""
@@ -114,6 +114,21 @@ def krylov(L, op, vecs, s=None, restart=None, e=None, tol=0.0, done=0):
     assert groups.value == kry_groups(n, k)
     ctrl = dict(sumsq=cd[0], r0=cd[1], n_his=ci[0], done=ci[1], status=ci[2])
     return vecs, s, (None if rs is None else rs.value), ctrl
+
+
+FIXED_OPS = dict(SUM=0, MAX=1)
+
+
+def fixed_reduce(L, op, term):
+    """(launch_fixed_sum's or launch_fixed_max's result over term, the chunk count launched) through smg_debug_fixed_reduce; the chunk scratch
+    holds exactly that many doubles and the result one, each between guards"""
+    term = _c(term).reshape(-1)
+    out = sentinel(1)
+    groups, bad = C.c_int(-1), C.c_int(-1)
+    rc = L.smg_debug_fixed_reduce(FIXED_OPS[op], term.size, _p(term), _p(out), C.byref(groups), C.byref(bad))
+    assert rc == 0, L.smg_last_error()
+    assert bad.value == 0, "a guard region around a device buffer was overwritten"
+    return out[0], groups.value
 
 
 UNION_OPS = dict(SUMSQ_DECIDE=0, RESTORE=1, COARSE=2)

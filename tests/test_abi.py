@@ -69,8 +69,8 @@ def test_compute_fails_loudly_without_gpu(smg_mod):
 
 def _kernel_hook_calls(L, n=4, m=2, nb=1, op=0, k=2):
     """one call of each handle-free kernel hook (include/smg.h: smg_debug_eig_gram, smg_debug_eig_combine, smg_debug_eig_residual,
-    smg_debug_krylov, and the three ops of smg_debug_union on a well-formed two-member problem) on arrays large enough for the largest legal
-    shape among the arguments"""
+    smg_debug_krylov, smg_debug_fixed_reduce (sum for an even op, maximum for an odd one), and the three ops of smg_debug_union on a well-formed
+    two-member problem) on arrays large enough for the largest legal shape among the arguments"""
     dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
     big = max(n, 1) * max(m, 1, k) * 3
     D = [np.zeros(big * max(m, 1) * 6) for _ in range(8)]
@@ -84,6 +84,7 @@ def _kernel_hook_calls(L, n=4, m=2, nb=1, op=0, k=2):
         "combine": L.smg_debug_eig_combine(n, m, nb, d[0], d[1], d[2], 1, 0, d[3], d[4], d[5], d[6], C.byref(bad)),
         "residual": L.smg_debug_eig_residual(n, m, d[0], d[1], d[2], d[3], 1, 0, d[4], d[5], f[0], f[1], d[6], C.byref(gi), C.byref(bad)),
         "krylov": L.smg_debug_krylov(op, n, k, d[0], d[1], d[2], d[3], f[0], d[4], C.byref(rs), 0.0, 0, cd, ci, C.byref(gi), C.byref(bad)),
+        "fixed_reduce": L.smg_debug_fixed_reduce(op % 2, n, d[0], d[1], C.byref(gi), C.byref(bad)),
         **{"union%d" % uop: _union_hook_call(L, uop) for uop in range(3)},
     }
 
@@ -107,7 +108,7 @@ def test_kernel_hooks_refuse_bad_shapes(smg_mod):
     """SMG_ERR_INVALID before any device work: n < 1, m outside 1..64, nb outside 1..3, an unknown Krylov op, k < 1; the fp32 cycle's hooks:
     no handle, an unknown op, a missing array, a handle without a precomputed system; the union hook: what its launchers cannot take"""
     L = smg_mod._lib.load()
-    hooks = dict(n=["gram", "combine", "residual", "krylov"], m=["gram", "combine", "residual"], nb=["gram", "combine"], op=["krylov"],
+    hooks = dict(n=["gram", "combine", "residual", "krylov", "fixed_reduce"], m=["gram", "combine", "residual"], nb=["gram", "combine"], op=["krylov"],
                  k=["krylov"])
     for arg, bad_values in (("n", (0, -3)), ("m", (0, 65)), ("nb", (0, 4)), ("op", (-1, 6)), ("k", (0,))):
         for v in bad_values:

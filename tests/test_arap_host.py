@@ -53,10 +53,22 @@ class ArapRest:
     def __init__(self, L, P0):
         L = sp.csr_matrix(L)
         L.sort_indices()
-        self.n = L.shape[0]
-        self.rowptr = np.ascontiguousarray(L.indptr, dtype=np.int32)
-        self.col = np.ascontiguousarray(L.indices, dtype=np.int32)
-        self.w = np.ascontiguousarray(L.data, dtype=np.float64)
+        self._set(L.indptr, L.indices, L.data, P0)
+        self.L = L
+
+    @classmethod
+    def from_csr(cls, rowptr, col, w, P0):
+        """the rest data of a hand-made CSR, entries in the order given (rows may be empty, unsorted, or hold their diagonal anywhere)"""
+        A = cls.__new__(cls)
+        A._set(rowptr, col, w, P0)
+        A.L = None
+        return A
+
+    def _set(self, rowptr, col, w, P0):
+        self.n = len(rowptr) - 1
+        self.rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+        self.col = np.ascontiguousarray(col, dtype=np.int32)
+        self.w = np.ascontiguousarray(w, dtype=np.float64)
         self.P0 = np.ascontiguousarray(P0, dtype=np.float64)
         row = np.repeat(np.arange(self.n), np.diff(self.rowptr))
         q = np.nonzero(self.col != row)[0]
@@ -64,7 +76,6 @@ class ArapRest:
         rank = np.arange(q.size) - np.searchsorted(r, np.arange(self.n))[r]
         self.slots = [(r[rank == p], q[rank == p]) for p in range(int(rank.max()) + 1)]
         self.deg = np.bincount(r, minlength=self.n)
-        self.L = L
 
     def scale(self):
         """s = sqrt(sum_i (sum_j |w_ij| |e_ij|)^2): |b|_F <= s for every set of rotations"""

@@ -4,14 +4,17 @@ The host reference is tests/test_arap_host.py -- the same method with LAPACK SVD
 kernels are held launcher by launcher (smg_debug_arap, guarded buffers) to the restatement's expressions: covariance, right-hand side and
 energy terms bit for bit, the rotations to the perturbation bound of the polar factor.
 
-Measured on an MI355X (DESIGN.md section 19): rotations max err * gap / eps = 68.7 (bound 256), |R^T R - I| <= 9 eps (bound 32);
+Measured on an MI355X: rotations max err * gap / eps = 68.7 (bound 256; 63.4 on the edge shapes of
+denoise_np.edge_shapes(), 4 to 259 rows and one row of 65 entries), |R^T R - I| <= 9 eps (bound 32);
 end to end against the restatement: positions <= 1.11e-12 diagonals, energies <= 1.29e-12 relative (bound E2E_BOUND = 1e-9)."""
 import math
 
 import numpy as np
 import pytest
 
+from denoise_np import EDGE_SHAPES, edge_shapes, mean_edge
 from oracle import mesh_np as M
+from pd_np import fixed_sum
 from test_arap_host import (ARAP_COVARIANCE, ARAP_ENERGY, ARAP_RHS, ARAP_ROTATIONS, ARAP_VERTEX_ENERGY, ArapNp, ArapRest, arap_hook, bbox_diag,
                             covariance, flat_square, load_mesh, rhs, roll_onto_cylinder, rotation_matrix, rotations_np, twist, vertex_energy)
 from test_gpu_parity import smg  # noqa: F401  (fixture)
@@ -49,25 +52,36 @@ def hook(smg, op, A, P, R_in, shape):
 
 
 # ---- kernels, launcher by launcher ----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", KERNEL_MESHES)
-def test_covariance_rhs_energy_bitwise(smg, kernel_cases, name):
-    A, Ps = kernel_cases[name]
+def check_bitwise(smg, A, Ps, label):
+    """covariance, right-hand side and energy terms at the poses Ps bit for bit against the restatement; the reduced energy is the fixed
+    sum of the DEVICE's terms in its own order, the same on a second call, and a sum (the fsum bound).  Returns the device's outputs of the
+    last pose."""
     n = A.n
-    print(name, "n = %d, max degree %d" % (n, A.deg.max()))
+    print(label, "n = %d, max degree %d" % (n, A.deg.max()))
     for P in Ps:
         S = covariance(A, P)
-        assert np.array_equal(hook(smg, ARAP_COVARIANCE, A, P, None, 9 * n).reshape(n, 3, 3), S)
+        Sd = hook(smg, ARAP_COVARIANCE, A, P, None, 9 * n).reshape(n, 3, 3)
+        assert np.array_equal(Sd, S)
         R, _, _ = rotations_np(S)
         b = hook(smg, ARAP_RHS, A, None, R, 3 * n).reshape(3, n).T
         assert np.array_equal(b, rhs(A, R))
         terms = vertex_energy(A, P, R)
-        assert np.array_equal(hook(smg, ARAP_VERTEX_ENERGY, A, P, R, n), terms)
+        td = hook(smg, ARAP_VERTEX_ENERGY, A, P, R, n)
+        assert np.array_equal(td, terms)
         E1 = hook(smg, ARAP_ENERGY, A, P, R, 1)[0]
         E2 = hook(smg, ARAP_ENERGY, A, P, R, 1)[0]
         exact = math.fsum(terms)
         print("  reduced energy %.17g, |E - fsum| = %.2e (bound %.2e)" % (E1, abs(E1 - exact), 2 * n * EPS * np.abs(terms).sum()))
         assert E1 == E2
+        assert E1 == fixed_sum(td)                                                   # the fixed sum in its own order
         assert abs(E1 - exact) <= 2 * n * EPS * np.abs(terms).sum()
+    return Sd, b, td, E1
+
+
+@pytest.mark.parametrize("name", KERNEL_MESHES)
+def test_covariance_rhs_energy_bitwise(smg, kernel_cases, name):
+    A, Ps = kernel_cases[name]
+    check_bitwise(smg, A, Ps, name)
 
 
 def check_rotations(smg, A, P, label, expect_reflections):
@@ -109,6 +123,77 @@ def test_rotations_degenerate_inputs(smg):
     _, gap, _ = rotations_np(covariance(A, P))
     assert gap.min() >= GAP_MIN
     check_rotations(smg, A, P, "flat square on a cylinder", True)
+
+
+# ---- the same launchers on the edge shapes: fewer rows than a block, rows around a wave and a block, one row of 65 entries ---------------------
+@pytest.fixture(scope="module")
+def edge_cases():
+    """per edge shape: the rest data and two poses -- P1 a rigid image plus 0.05 mean edges of noise, P2 the rest pose stretched by
+    (1.3, 0.8, 1.0) plus 0.2 mean edges of noise (default_rng(7) per shape, P1 drawn first)"""
+    out = {}
+    Rg, tg = rotation_matrix([1.0, 2.0, -0.5], 1.1), np.array([0.3, -0.2, 0.7])
+    for name, (V, F) in edge_shapes().items():
+        rng = np.random.default_rng(7)
+        h = mean_edge(V, F)
+        P1 = (V @ Rg.T + tg) + 0.05 * h * rng.standard_normal(V.shape)
+        P2 = V * np.array([1.3, 0.8, 1.0]) + 0.2 * h * rng.standard_normal(V.shape)
+        out[name] = (ArapRest(M.cotmatrix(V, F), V), [np.ascontiguousarray(P1), np.ascontiguousarray(P2)])
+    return out
+
+
+@pytest.mark.parametrize("name", EDGE_SHAPES)
+def test_covariance_rhs_energy_bitwise_on_edge_shapes(smg, edge_cases, name):
+    A, Ps = edge_cases[name]
+    check_bitwise(smg, A, Ps, name)
+
+
+@pytest.mark.parametrize("name", EDGE_SHAPES)
+def test_rotations_against_lapack_on_edge_shapes(smg, edge_cases, name):
+    """the cotangent weights on a boundary are negative: reflections (d < 0) occur on every open shape at both poses, on the closed tetrahedron
+    at neither; no vertex has a gap below GAP_MIN (the smallest is 1.2e-2, on the fan), so none is left out"""
+    A, Ps = edge_cases[name]
+    for label, P in zip(("P1", "P2"), Ps):
+        _, gap, _ = rotations_np(covariance(A, P))
+        assert gap.min() >= GAP_MIN
+        check_rotations(smg, A, P, "%s %s" % (name, label), name != "tetrahedron")
+
+
+def test_hand_made_rows(smg):
+    """a CSR no mesh gives, through the hook's rowptr / col: row 0 is empty, row 1 holds only its diagonal, row 2 stores its diagonal last, row 3
+    first, row 4 in the middle, row 5 not at all.  Rows 0 and 1 have no neighbours: S = 0, R = I, b = 0 and an energy term of 0, exactly."""
+    rng = np.random.default_rng(11)
+    rows = [[], [1], [4, 0, 2], [3, 5, 1, 0], [2, 4, 5], [0, 3]]
+    rowptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    col = np.array([j for r in rows for j in r], dtype=np.int32)
+    n = len(rows)
+    P0 = rng.uniform(-1, 1, (n, 3))
+    A = ArapRest.from_csr(rowptr, col, rng.uniform(0.5, 1.5, col.size), P0)
+    assert list(A.deg) == [0, 0, 2, 3, 2, 2]
+    P = np.ascontiguousarray((P0 @ rotation_matrix([1.0, 2.0, -0.5], 1.1).T + 0.3) + 0.05 * rng.standard_normal((n, 3)))
+
+    def call(op, R_in, shape):
+        out = np.full(shape, np.nan)
+        rc, bad = arap_hook(smg._lib.load(), op, A, None if op == ARAP_RHS else P, None if R_in is None else np.ascontiguousarray(R_in.reshape(-1)),
+                            out, rowptr=rowptr, col=col)
+        assert rc == 0 and bad == 0, (rc, bad)
+        return out
+
+    S = covariance(A, P)
+    Sd = call(ARAP_COVARIANCE, None, 9 * n).reshape(n, 3, 3)
+    assert np.array_equal(Sd, S) and not Sd[:2].any() and np.all(np.abs(Sd[2:]).max(axis=(1, 2)) > 0)
+    Rn, gap, _ = rotations_np(S)
+    assert gap[2:].min() >= GAP_MIN
+    Rd = call(ARAP_ROTATIONS, None, 9 * n).reshape(n, 3, 3)
+    assert np.array_equal(Rd[:2], np.tile(np.eye(3), (2, 1, 1)))
+    err = np.linalg.norm((Rd - Rn).reshape(n, 9), axis=1)
+    print("hand-made rows: max err * gap / eps = %.1f" % (err[2:] * gap[2:] / EPS).max())
+    assert np.all(err[2:] <= ROT_BOUND * EPS / gap[2:]) and np.all(np.linalg.det(Rd) > 0)
+    assert np.abs(np.einsum("nji,njk->nik", Rd, Rd) - np.eye(3)).max() <= 32 * EPS
+    b = call(ARAP_RHS, Rn, 3 * n).reshape(3, n).T
+    assert np.array_equal(b, rhs(A, Rn)) and not b[:2].any() and np.all(np.abs(b[2:]).max(axis=1) > 0)
+    td = call(ARAP_VERTEX_ENERGY, Rn, n)
+    assert np.array_equal(td, vertex_energy(A, P, Rn)) and not td[:2].any() and np.all(td[2:] > 0)
+    assert call(ARAP_ENERGY, Rn, 1)[0] == fixed_sum(td)
 
 
 # ---- end to end -----------------------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import denoise_np as DN
 from oracle import mesh_np as M
 from test_geodesics_host import (GEO_BASIS, GEO_DIVERGENCE, GEO_SCATTER, GEO_SHIFT, INVALID, corner_lists, geo_hook, grad_basis, great_circle,
                                  heat_geodesics_np, icosphere, indicator, neg_divergence, shift)
@@ -103,6 +104,113 @@ def test_shift_kernel(smg):
         assert np.array_equal(out[:n], shift(phi, sets))
         assert np.all(out[n:] == -9.0)
         assert out[4, 0] == 0.0 and out[776, 3] == 0.0
+
+
+# ---- the same launchers on the edge shapes: rows around a wave and a block, a 65-long corner list, meshes smaller than a block ------------------
+@pytest.fixture(scope="module")
+def edge_shapes():
+    return DN.edge_shapes()
+
+
+@pytest.mark.parametrize("name", DN.EDGE_SHAPES)
+def test_basis_kernel_on_edge_shapes(smg, edge_shapes, name):
+    L = smg._lib.load()
+    V, F = edge_shapes[name]
+    W, Af = np.full(9 * F.shape[0], np.nan), np.full(F.shape[0], np.nan)
+    rc, bad = geo_hook(L, GEO_BASIS, V.shape[0], 1, F=F, inp=np.ascontiguousarray(V), W=W, Af=Af)
+    assert rc == 0 and bad == 0
+    Wn, An = grad_basis(V, F)
+    assert np.array_equal(W.reshape(-1, 3, 3), Wn) and np.array_equal(Af, An)
+
+
+def divergence_columns(V, F, seed):
+    """n x 3: column 0 all zero (X = 0 everywhere); column 1 random but 0 on the three vertices of a few faces (|grad u| == 0 on those alone:
+    the nrm > 0 branch diverges inside a wave) and one value on the vertices of another (a gradient of rounding noise); column 2 random"""
+    n, nF = V.shape[0], F.shape[0]
+    U = np.asfortranarray(np.random.default_rng(seed).uniform(-1, 1, (n, 3)))
+    U[:, 0] = 0.0
+    flat = [0, nF // 2] if nF > 4 else [0]
+    if nF > 8:
+        U[F[nF - 1], 1] = 0.37
+    U[F[flat].ravel(), 1] = 0.0
+    return U, flat
+
+
+@pytest.mark.parametrize("name", DN.EDGE_SHAPES)
+def test_divergence_kernel_on_edge_shapes(smg, edge_shapes, name):
+    L = smg._lib.load()
+    V, F = edge_shapes[name]
+    n, nF = V.shape[0], F.shape[0]
+    W, Af = grad_basis(V, F)
+    m_ptr, m_idx = corner_lists(F, n)
+    U3, flat = divergence_columns(V, F, nF)
+    u = U3[F, 1]                                                 # the partly flat column: exactly those faces have no gradient, the others do
+    g = u[:, 0, None] * W[:, 0] + u[:, 1, None] * W[:, 1] + u[:, 2, None] * W[:, 2]
+    zero = np.nonzero(np.sqrt(np.sum(g * g, axis=1)) == 0.0)[0]
+    assert set(flat) <= set(zero) <= set(flat) | {nF - 1} and zero.size < nF    # (the face with one value: noise, or it rounds to nothing)
+    blocks = [U3[:, [c]] for c in range(3)] + [U3]               # k = 1 (each kind of column alone) and k = 3
+    if name == "tetrahedron":
+        blocks.append(np.tile(U3, (1, 22))[:, :64])             # k = 64 on n = 4
+    print(name, "n = %d, nF = %d, longest corner list %d, faces without a gradient in column 1: %s" % (n, nF, np.diff(m_ptr).max(), zero))
+    for U in blocks:
+        U = np.asfortranarray(U)
+        k = U.shape[1]
+        ref = neg_divergence(F, W, Af, m_ptr, m_idx, U)
+        for ld in (n, n + 3):
+            out = np.full((ld, k), -9.0, order="F")
+            rc, bad = geo_hook(L, GEO_DIVERGENCE, n, k, F=F, m_ptr=m_ptr, m_idx=m_idx, inp=U, W=np.ascontiguousarray(W.ravel()), Af=Af, out=out, ld_out=ld)
+            assert rc == 0 and bad == 0
+            assert np.array_equal(out[:n], ref), (k, ld)
+            assert np.all(out[n:] == -9.0)                       # the pad rows of a padded block keep what they held
+            if k >= 3:
+                assert np.all(out[:n, 0] == 0.0) and np.any(out[:n, 1] != 0.0)
+
+
+def source_sets(n, k, seed):
+    """k source sets on n vertices: one of 300 entries and one of 513 (more than one pass of a 256-thread block), a repeated source, the first
+    and the last vertex, singletons"""
+    rng = np.random.default_rng(seed)
+    pick = lambda m: [int(v) for v in (rng.choice(n, m, replace=False) if m <= n else rng.integers(0, n, m))]   # noqa: E731
+    sets = [[n - 1], pick(300), [0, n - 1, 0], pick(513), [n // 2, n // 2]]
+    sets += [[int(rng.integers(n))] for _ in range(k - len(sets))]
+    sets[k - 1] = [n - 1, 0]                                     # the last column, in the second block of k_geo_source_mean
+    ptr = np.zeros(k + 1, np.int32)
+    ptr[1:] = np.cumsum([len(s) for s in sets])
+    return sets, ptr, np.concatenate([np.array(s, np.int32) for s in sets])
+
+
+# n = 4: g / n decides the column; n k is no multiple of 256 in any case; k = 65 and 130: k_geo_source_mean's second and third block
+SCATTER_SHIFT_CASES = [(4, 65), (4, 130), (777, 65), (1001, 130)]
+
+
+@pytest.mark.parametrize("n,k", SCATTER_SHIFT_CASES)
+def test_scatter_kernel_many_columns_and_long_lists(smg, n, k):
+    L = smg._lib.load()
+    assert (n * k) % 256 != 0
+    sets, ptr, src = source_sets(n, k, n + k)
+    for ld in (n, n + 7):
+        out = np.full((ld, k), 7.0, order="F")
+        rc, bad = geo_hook(L, GEO_SCATTER, n, k, src_ptr=ptr, src=src, inp=np.zeros(1), out=out, ld_out=ld)
+        assert rc == 0 and bad == 0
+        assert np.array_equal(out[:n], indicator(n, sets))
+        assert np.all(out[n:] == 7.0)
+    if n > 513:
+        assert out[:n, 1].sum() == 300 and out[:n, 3].sum() == 513
+
+
+@pytest.mark.parametrize("n,k", SCATTER_SHIFT_CASES)
+def test_shift_kernel_many_columns_and_long_lists(smg, n, k):
+    L = smg._lib.load()
+    sets, ptr, src = source_sets(n, k, n + k)
+    phi = np.asfortranarray(np.random.default_rng(k).uniform(-3, 3, (n, k)))
+    ref = shift(phi, sets)
+    for ld in (n, n + 5):
+        out = np.full((ld, k), -9.0, order="F")
+        rc, bad = geo_hook(L, GEO_SHIFT, n, k, src_ptr=ptr, src=src, inp=phi, out=out, ld_out=ld)
+        assert rc == 0 and bad == 0
+        assert np.array_equal(out[:n], ref)
+        assert np.all(out[n:] == -9.0)
+        assert out[n - 1, 0] == 0.0 and out[n // 2, 4] == 0.0     # one source, and one source twice: the mean is the value itself
 
 
 # ---- end to end against the restatement ---------------------------------------------------------------------------------------------------

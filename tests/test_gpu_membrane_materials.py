@@ -19,6 +19,8 @@ import pytest
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
+from denoise_np import edge_shapes
+from test_gpu_membrane import check_sums
 from test_gpu_parity import smg  # noqa: F401  (fixture)
 from membrane_materials_np import (MATERIAL_NAMES, PURE, SLACK, STVK, TENSION_FIELD, WRINKLED, MaterialNp, fan_mesh, fan_pose, hook_material,
                                    infer_branch, relative_errors, strip_mesh, strip_pose)
@@ -210,6 +212,15 @@ def test_sums_are_bitwise_the_documented_ones(smg, ogre, mat):
     mv = np.repeat(p["mass_scale"] * mass0, 3)
     b_np = -((mv * (qdot - qdot0) + p["dt"] * g_np) + p["dt"] * fext)
     assert np.array_equal(o[:3 * nV], g_np) and np.array_equal(o[3 * nV:], b_np)
+
+
+@pytest.mark.parametrize("name", ["fan65", "strip255"])
+@pytest.mark.parametrize("mat", MATERIALS)
+def test_sums_on_edge_shapes(smg, mat, name):
+    """the summing launchers are shared by the three materials: the same sums from these materials' face outputs on the fan (a 65-long block
+    list and corner list) and on a strip with 257 vertices and 255 faces, at rest and perturbed"""
+    V, F = edge_shapes()[name]
+    check_sums(smg, "%s %s" % (name, MATERIAL_NAMES[mat]), V, F, MaterialNp(V, F, mat), [V, perturbed_pose(V, F)], mat=mat, restatement=False)
 
 
 # ---- 5: one Newton system -----------------------------------------------------------------------------------------------------------------------------
